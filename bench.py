@@ -12,9 +12,20 @@ checked against).
     python bench.py --gpus 1 --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Weak scaling: the population has 64 * N individuals, rank r owns [64r, 64r+64); value = 64 * N * K / T.
-Rank 0 prints ONE JSON line.  Beside the contract's fields it carries
+Weak scaling: the population has 64 * N individuals, rank r owns [64r, 64r+64); value = 64 * N * K / T, T the time of
+exactly K timed steps.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the
+headline fields (metric, value, unit, higher_is_better, dtype, ms_per_step and the workload's description).
 
+    --dump-outputs DIR   after the timed steps, the fitness values of the last one (what a caller of the step receives) as
+                         DIR/fitness_values.npy, float64; the inputs are seeded, so two builds can be compared value by value
+    --full               everything else below as well (about half a minute on one MI355X); --no-extras / --no-cpu-baseline
+                         leave parts of it out
+
+With --full the line also carries
+
+  timed_windows     the K-step window repeated until >= 50 ms have been timed: min / median / max window
+  value_host_lists / value_fresh_inputs   the same steps with the parameter values as host lists, and with two device
+                    matrices taking turns
   roofline          per instantiation of the gate-pass kernel (HIP events around every launch, measured in extra
                     profiled steps AFTER the timed region), and ``microbench``: single-gate sweeps at n = 24 and 26
   config3           BASELINE.json configs[2] at this N: n = 24, P = 256 in total (strong scaling), per-rank times
@@ -747,10 +758,18 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)  # (200 steps of 85 us: a timed region of 17 ms; 20 steps made it 1.7 ms, a tenth of which one host hiccup takes)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline measurement (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: repeated windows, host-list and fresh-input steps, per-kernel roofline, the other "
+                         "configurations, calling patterns and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the fitness values of the last timed step to DIR/fitness_values.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: the headline, its variants and the roofline only (profiling runs)")
     ap.add_argument("--only", default=None, help="profiling runs: just one row of the deep block (" + ", ".join(DEEP_ROWS) + ")")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.only in ("trajectory", "layer_search", "config5_sweep"):
         torch.cuda.set_device(0)
         block = (trajectory_block(ising_operator(N_QUBITS, 2020), search_precision=os.environ.get("QSV_BENCH_SEARCH_PRECISION")) if args.only == "trajectory" else
@@ -797,7 +816,6 @@ def main() -> None:
     lo, hi = shard_bounds(len(circuits), world, rank)
     operator = ising_operator(N_QUBITS, 2020)
     evaluator = OperatorCircuitEvaluator(operator, device=local_rank)
-    device = evaluator.statevector_device
 
     # The populations, circuits and plans built so far are long-lived: out of the garbage collector's way (what a
     # long-running service does after start-up), so that a full collection inside a timed region of a few milliseconds
@@ -842,9 +860,6 @@ def main() -> None:
         step()
     prewarm_steps += 5
     # ---- timed region: exactly K steps (no profiling events inside), barrier + synchronize on both sides, MAX over ranks.
-    # A window of K steps of this workload lasts K * 60-90 us: with the driver's K = 20 a single host hiccup is a tenth
-    # of it.  So the K-step window is REPEATED until at least 50 ms have been timed (every window bracketed the same way;
-    # the count is rank 0's, agreed between the ranks) and the line reports the MEDIAN window; `steps` stays K.
     def window():
         fence()
         t0 = time.perf_counter()
@@ -858,15 +873,78 @@ def main() -> None:
             dt = float(t.item())
         return dt, out
 
-    first, values = window()
+    elapsed, values = window()
+    if args.dump_outputs and rank == 0:
+        out_dir = Path(args.dump_outputs)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        np.save(out_dir / "fitness_values.npy", np.asarray(values, dtype=np.float64))
+    if args.full:
+        full_run(args, world, rank, local_rank, comm_device, population, circuits, params, operator, evaluator, host_matrix,
+                 param_matrix, feed, step, fence, window, elapsed, values, prewarm_steps)
+    elif rank == 0:
+        print(json.dumps(headline(args, world, elapsed, prewarm_steps, operator)), flush=True)
+
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def headline(args, world: int, elapsed: float, prewarm_steps: int, operator) -> dict:
+    """The fields of the result line that describe the K timed steps."""
+    total_evals = POP_PER_GPU * world * args.steps
+    return {
+        "metric": "circuit-evals/sec (EVQE population) at n qubits; achieved HBM GB/s vs roofline",
+        "value": total_evals / elapsed,
+        "unit": "circuit-evals/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "prewarm": {"seconds": PREWARM_S, "untimed_steps": prewarm_steps,
+                    "why": "GPU clocks reach steady state only after tens of ms of load; the timed K steps follow"},
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "inputs": ("circuit structures registered (plans in the device arena) and the population's parameter values resident "
+                   "in HBM before the timed region (a float64 matrix in device memory, one row per individual: "
+                   "qsv_eval_push_device); results to the host") if os.environ.get("QSV_BENCH_HOST_LISTS") != "1" else
+                  "parameter values as host lists (QSV_BENCH_HOST_LISTS=1)",
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {
+            "workload": f"{N_QUBITS}-qubit EVQE population={POP_PER_GPU} per GPU, {N_LAYERS} layers, random Ising "
+            f"Hamiltonian ({len(operator)} terms), fp64 (BASELINE.json configs[1])",
+            "n_qubits": N_QUBITS,
+            "population_per_gpu": POP_PER_GPU,
+            "layers": N_LAYERS,
+            "pauli_terms": len(operator),
+            "parallelism": (f"population sharded over {world} GPU(s); fitness values exchanged through a table in shared host memory the "
+                            "kernels store into (one node; RCCL all-gather: fallback and first-step check)") if world > 1 else "1 GPU",
+            "path": "library defaults (DESIGN.md 4.2 / 5): register splitting with up to five cut keys, one launch per push "
+                    "where both virtual circuits are one tile, factorised Ising expectation, multiplexed gates, chain "
+                    "stream, end of a batch read off the pinned result buffer, a repeated batch keeps its layout",
+        },
+    }
+
+
+def full_run(args, world, rank, local_rank, comm_device, population, circuits, params, operator, evaluator, host_matrix,
+             param_matrix, feed, step, fence, window, elapsed, values, prewarm_steps) -> None:
+    """--full: every measurement beside the headline, after its K timed steps, on the same handle; rank 0 prints the line."""
+    from queasars_amd.distributed import evaluate_population_sharded
+
+    device = evaluator.statevector_device
+    # A window of K steps of this workload lasts K * 60-90 us: with K = 20 a single host hiccup is a tenth of it.  So the
+    # K-step window is REPEATED until at least 50 ms have been timed (every window bracketed the same way; the count is rank
+    # 0's, agreed between the ranks) and `timed_windows` reports the MEDIAN window beside the headline's one.
     # (QSV_BENCH_WINDOWS caps the count: profiling runs, where every launch is traced, set it to 1)
+    first = elapsed
     most = max(1, int(os.environ.get("QSV_BENCH_WINDOWS", 256)))
     n_windows = 1 + agreed_count(min(most - 1, int(0.05 / max(first, 1e-6))), world, comm_device)
     windows = [first]
     for _ in range(n_windows - 1):
-        dt, values = window()
+        dt, _ = window()
         windows.append(dt)
-    elapsed = sorted(windows)[len(windows) // 2]
+    median = sorted(windows)[len(windows) // 2]
     # ... and the same K-step windows with the parameter values as host lists (list[list[float]], the reference's argument
     # type: packed into pinned memory by the host and fetched over PCIe by the kernels, all inside the step)
     host_windows = []
@@ -922,7 +1000,6 @@ def main() -> None:
         config3_deep = config3_block(world, rank, local_rank, steps=3, layers=8)
 
     if rank == 0:
-        total_evals = POP_PER_GPU * world * args.steps
         dominant = max(kernels, key=lambda k: k["launches"] * k["avg_launch_us"]) if kernels else None
         roofline = None
         if dominant is not None:
@@ -965,51 +1042,28 @@ def main() -> None:
                 "region.  traffic = 2 x FETCH_SIZE + WRITE_SIZE per launch from separate rocprofv3 --pmc passes of this "
                 "command (profiles/, see traffic_source), gfx950 correction of MI355X_MICROARCH.md",
             }
-        result = {
-            "metric": "circuit-evals/sec (EVQE population) at n qubits; achieved HBM GB/s vs roofline",
-            "value": total_evals / elapsed,
-            "unit": "circuit-evals/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "prewarm": {"seconds": PREWARM_S, "untimed_steps": prewarm_steps,
-                        "why": "GPU clocks reach steady state only after tens of ms of load; the timed K steps follow"},
+        total_evals = POP_PER_GPU * world * args.steps
+        result = headline(args, world, elapsed, prewarm_steps, operator)
+        result.update({
             "timed_windows": {"count": len(windows), "steps_each": args.steps, "reported": "median",
-                              "ms_min": min(windows) * 1e3, "ms_median": elapsed * 1e3, "ms_max": max(windows) * 1e3,
-                              "why": "K steps of this workload last a millisecond or two: the K-step window is repeated until "
-                                     ">= 50 ms have been timed and the median window is the one reported"},
-            "ms_per_step": elapsed / args.steps * 1e3,
+                              "ms_min": min(windows) * 1e3, "ms_median": median * 1e3, "ms_max": max(windows) * 1e3,
+                              "value_median_window": total_evals / median,
+                              "why": "K steps of this workload last a millisecond or two: the headline's K-step window (the "
+                                     "first) is repeated until >= 50 ms have been timed; the median window is reported here"},
             "value_host_lists": (total_evals / elapsed_host) if elapsed_host else None,
             "ms_per_step_host_lists": (elapsed_host / args.steps * 1e3) if elapsed_host else None,
             "host_lists_results_identical": inputs_agree,
             "value_fresh_inputs": (total_evals / elapsed_fresh) if elapsed_fresh else None,
             "ms_per_step_fresh_inputs": (elapsed_fresh / args.steps * 1e3) if elapsed_fresh else None,
-            "inputs": ("`value`: circuit structures registered (plans in the device arena) and the population's parameter values "
-                       "resident in HBM before the timed region (a float64 matrix in device memory, one row per individual: "
-                       "qsv_eval_push_device); results to the host.  `value_host_lists`: the same steps with the parameter "
-                       "values as Python lists of floats, packed by the host and read over PCIe inside every step (what "
-                       "rounds 1-2 and BENCH_r02 reported as `value`); host_lists_results_identical: the two gave the same bits") if elapsed_host else
-                      "parameter values as host lists (QSV_BENCH_HOST_LISTS=1)",
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {
-                "workload": f"{N_QUBITS}-qubit EVQE population={POP_PER_GPU} per GPU, {N_LAYERS} layers, random Ising "
-                f"Hamiltonian ({len(operator)} terms), fp64 (BASELINE.json configs[1])",
-                "n_qubits": N_QUBITS,
-                "population_per_gpu": POP_PER_GPU,
-                "layers": N_LAYERS,
-                "pauli_terms": len(operator),
-                "parallelism": (f"population sharded over {world} GPU(s); fitness values exchanged through a table in shared host memory the "
-                                "kernels store into (one node; RCCL all-gather: fallback and first-step check)") if world > 1 else "1 GPU",
-                "path": "library defaults (DESIGN.md 4.2 / 5): register splitting with up to five cut keys, one launch per push "
-                        "where both virtual circuits are one tile, factorised Ising expectation, multiplexed gates, chain "
-                        "stream, end of a batch read off the pinned result buffer, a repeated batch keeps its layout",
-            },
             "roofline": roofline,
-        }
+        })
+        if elapsed_host:
+            result["inputs"] = (
+                "`value`: circuit structures registered (plans in the device arena) and the population's parameter values "
+                "resident in HBM before the timed region (a float64 matrix in device memory, one row per individual: "
+                "qsv_eval_push_device); results to the host.  `value_host_lists`: the same steps with the parameter "
+                "values as Python lists of floats, packed by the host and read over PCIe inside every step (what "
+                "rounds 1-2 and BENCH_r02 reported as `value`); host_lists_results_identical: the two gave the same bits")
         if config3 is not None:
             result["config3"] = config3
             result["config3_deep"] = config3_deep
@@ -1042,10 +1096,6 @@ def main() -> None:
             err = float(np.abs(np.asarray(values[: len(ref_values)]) - np.asarray(ref_values)).max())
             result["max_abs_diff_vs_cpu_oracle"] = err
         print(json.dumps(result), flush=True)
-
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -73,7 +73,7 @@ def main():
         env = dict(os.environ, QSV_BENCH_QUBITS=n, QSV_BENCH_POP=pop)
         if name != "base":
             env["QSV_LIBRARY"] = str(lib_of(name))
-        res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--no-extras", "--no-cpu-baseline", "--steps", "10", "--warmup", "3"],
+        res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--no-extras", "--no-cpu-baseline", "--steps", "10", "--warmup", "3"],
                              env=env, capture_output=True, text=True)
         if res.returncode != 0:
             print(name, "FAILED", res.stderr[-400:])

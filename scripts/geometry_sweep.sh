@@ -1,12 +1,13 @@
 #!/bin/bash
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out
+out=${BENCH_OUT:-bench_out}  # (where the runs' lines and logs go)
+mkdir -p "$out"
 run() {
   label=$1; shift
-  env "$@" timeout -k 10 100 python bench.py --no-extras --no-cpu-baseline --steps 10 --warmup 3 > gpurun_out/geo_$label.json 2> gpurun_out/geo_$label.err || { echo "$label failed"; tail -3 gpurun_out/geo_$label.err; return 1; }
+  env "$@" timeout -k 10 100 python bench.py --full --no-extras --no-cpu-baseline --steps 10 --warmup 3 > "$out/geo_$label.json" 2> "$out/geo_$label.err" || { echo "$label failed"; tail -3 "$out/geo_$label.err"; return 1; }
   python - <<PY
 import json
-d=json.load(open("gpurun_out/geo_$label.json"))
+d=json.load(open("$out/geo_$label.json"))
 print("$label", round(d["value"]), "evals/s", [(round(k["avg_launch_us"],1), k["launches"]) for k in d["roofline"]["kernels"]])
 PY
 }

@@ -1,5 +1,5 @@
 """Golden vectors for two small host-side pieces next to the hot path, produced BY THE REFERENCE ITSELF (both modules are
-plain Python / NumPy and import in the build container from /root/reference):
+plain Python / NumPy and import from a checkout of it named by QUEASARS_REFERENCE, or as an installed package):
 
 * ``SPSATerminationChecker.termination_check`` (queasars/utility/spsa_termination.py:46-94): what it answers, call by call,
   along sequences of (evaluations so far, function value, accepted) -- converging, noisy, with rejected steps, with a budget,
@@ -10,13 +10,15 @@ plain Python / NumPy and import in the build container from /root/reference):
     python tests/golden/make_host_golden.py        # writes tests/golden/spsa_termination_reference.json
 """
 import json
+import os
 import sys
 from pathlib import Path
 from random import Random
 
 import numpy as np
 
-sys.path.insert(0, "/root/reference")
+if os.environ.get("QUEASARS_REFERENCE"):  # a checkout of the reference project; otherwise its installed package
+    sys.path.insert(0, os.environ["QUEASARS_REFERENCE"])
 from queasars.utility.random import new_random_seed  # noqa: E402
 from queasars.utility.spsa_termination import SPSATerminationChecker  # noqa: E402
 

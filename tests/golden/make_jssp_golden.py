@@ -1,5 +1,6 @@
 """Golden vectors for the JSSP datatypes, produced BY THE REFERENCE ITSELF: its problem-instance, random-instance and
-serialization modules are plain Python (no Qiskit) and import in the build container from /root/reference.
+serialization modules are plain Python (no Qiskit) and import from a checkout of it named by QUEASARS_REFERENCE, or
+as an installed package.
 
     python tests/golden/make_jssp_golden.py        # writes tests/golden/jssp_reference.json
 
@@ -10,11 +11,13 @@ text ``json.dumps(..., indent=2)`` gives), and a handful of random schedules of 
 The tests (tests/test_jssp.py) hold this repository's generator, validity rules, encoder and decoder to these vectors; the
 reference is not needed to run them."""
 import json
+import os
 import sys
 from pathlib import Path
 from random import Random
 
-sys.path.insert(0, "/root/reference")
+if os.environ.get("QUEASARS_REFERENCE"):  # a checkout of the reference project; otherwise its installed package
+    sys.path.insert(0, os.environ["QUEASARS_REFERENCE"])
 from queasars.job_shop_scheduling.problem_instances import JobShopSchedulingResult, ScheduledOperation, UnscheduledOperation  # noqa: E402
 from queasars.job_shop_scheduling.random_problem_instances import random_job_shop_scheduling_instance  # noqa: E402
 from queasars.job_shop_scheduling.serialization import JSSPJSONDecoder, JSSPJSONEncoder  # noqa: E402

@@ -418,7 +418,7 @@ class TestSharedDeviceScratch:
         from queasars_amd.circuit_evaluation.circuit_evaluation import StatevectorDevice, _make_gone
 
         dev = object.__new__(StatevectorDevice)  # no GPU here: only the bookkeeping is exercised
-        dev._dead, dev._watched, dev._handle, dev._lib = [], {}, None, None
+        dev._dead, dev._dead_states, dev._watched, dev._handle, dev._lib = [], [], {}, None, None
         dev._gone = _make_gone(dev._dead, dev._watched)
         dev._serial, dev._n_qubits, dev._last_batch, dev._reg_lock = ("test", 1), 3, None, threading.Lock()
         return dev
