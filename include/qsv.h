@@ -169,6 +169,25 @@ typedef struct qsv_circuit_cost_t {
 int qsv_circuit_cost(qsv_t* h, int circuit_id, qsv_circuit_cost_t* out);
 
 /*
+ * How a registered circuit is planned, read back as it is (tests and coverage claims: which form of split evaluation a
+ * circuit took).  Computes nothing: route and n_keys are qsv_circuit_cost's; the rest is the circuit's split form, all
+ * zero when it has none.  Side x is the side the split block calls X (its states are the outer index of the split
+ * sampler's draw: index = deposit(x, mask_x) | deposit(y, mask_y)).
+ */
+typedef struct qsv_circuit_form_t {
+    int32_t route;           /* QSV_ROUTE_*, as qsv_circuit_cost */
+    int32_t n_keys;          /* as qsv_circuit_cost */
+    int32_t n_virtual[2];    /* virtual qubits of side x, side y (0 if not split) */
+    int32_t amps_per_thread; /* of the side plans: 8 (the sides_r3 form) or the handle's own 16 */
+    int32_t halves;          /* three-key thirteen-qubit sides on two workgroups each (kEvalHalves) */
+    int32_t outer[2];        /* log2 of the tiles a side sweeps: qubits of side x, side y outside its tile */
+    int32_t one_launch;      /* the split form may take the one-launch route (both sides one pass, kEvalFused) */
+    int32_t split_sampled;   /* qsv_sample_* draw it from its two side tables */
+    uint32_t mask_x, mask_y; /* qubits of side x, side y (without the keys) */
+} qsv_circuit_form_t;
+int qsv_circuit_form(qsv_t* h, int circuit_id, qsv_circuit_form_t* out);
+
+/*
  * Expectation values real(<psi_i|H|psi_i>) of n_evals (circuit, parameter vector) pairs, |psi_i> prepared from
  * |0..0>.  params holds the vectors back to back, vector i at params[param_offsets[i] .. param_offsets[i+1]).
  * Replaces `estimator.run(pubs, precision=0).result()` + `real(res.data.evs)` (circuit_evaluation.py:210-215).
@@ -318,7 +337,7 @@ int qsv_sample_cvar_batch(qsv_t* h, int n_evals, const int* circuit_ids, const i
  * distribution that equals the exact one (reference: queasars/circuit_evaluation/expectation_calculation.py:14-32, :55-69),
  * including the loop's stopping rule numpy.isclose(gathered, alpha) and, for states of equal value, the index order a stable
  * sort leaves them in.  Needs a diagonal operator on the handle, 0 < alpha <= 1 and at most 28 qubits; deterministic.
- * (For alpha = 1 this is the expectation value qsv_eval_circuits computes.)  Circuits that have a split form are read from
+ * (For alpha = 1 -- numpy.isclose, as the reference tests it -- this is the expectation value qsv_eval_circuits computes.)  Circuits that have a split form are read from
  * their two side tables, the others from the probabilities their last gate pass writes.
  */
 int qsv_exact_cvar_batch(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,

@@ -100,6 +100,23 @@ class QsvCircuitCost(C.Structure):
     ]
 
 
+class QsvCircuitForm(C.Structure):
+    """``qsv_circuit_form_t`` of include/qsv.h."""
+
+    _fields_ = [
+        ("route", C.c_int32),
+        ("n_keys", C.c_int32),
+        ("n_virtual", C.c_int32 * 2),
+        ("amps_per_thread", C.c_int32),
+        ("halves", C.c_int32),
+        ("outer", C.c_int32 * 2),
+        ("one_launch", C.c_int32),
+        ("split_sampled", C.c_int32),
+        ("mask_x", C.c_uint32),
+        ("mask_y", C.c_uint32),
+    ]
+
+
 ROUTE_NAMES = ("one tile", "split, one launch", "split", "gate passes")
 
 assert C.sizeof(QsvOp) == 40
@@ -123,6 +140,7 @@ SIGNATURES = {
     "qsv_circuit_create_on_prefix": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
     "qsv_circuits_create_on_prefixes": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
     "qsv_circuit_cost": (C.c_int, [_P, C.c_int, C.POINTER(QsvCircuitCost)]),
+    "qsv_circuit_form": (C.c_int, [_P, C.c_int, C.POINTER(QsvCircuitForm)]),
     "qsv_eval_circuits": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     "qsv_eval_coalesced": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_double, C.POINTER(C.c_double)]),
     "qsv_eval_begin": (C.c_int, [_P, C.c_int, _P, _P]),

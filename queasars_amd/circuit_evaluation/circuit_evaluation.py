@@ -443,6 +443,18 @@ class StatevectorDevice:
         return {"route": _lib.ROUTE_NAMES[cost.route], "n_keys": cost.n_keys, "n_passes": cost.n_passes,
                 "on_kept_state": bool(cost.on_kept_state), "microseconds": cost.microseconds}
 
+    def circuit_form(self, circuit: CircuitIR) -> dict:
+        """How ``circuit`` is planned on this device (``qsv_circuit_form``): route and n_keys as :meth:`circuit_cost` (the
+        route as its QSV_ROUTE_* number), and its split form -- virtual qubits, amplitudes per thread, half sides, swept
+        tiles and qubit masks of side x and side y, whether it may take the one-launch route and whether the sampler
+        draws it from its side tables.  Reads, computes nothing."""
+        form = _lib.QsvCircuitForm()
+        self._check(self._lib.qsv_circuit_form(self._handle, self.circuit_id(circuit), C.byref(form)))
+        return {"route": form.route, "n_keys": form.n_keys, "n_virtual": tuple(form.n_virtual),
+                "amps_per_thread": form.amps_per_thread, "halves": bool(form.halves), "outer": tuple(form.outer),
+                "one_launch": bool(form.one_launch), "split_sampled": bool(form.split_sampled), "mask_x": form.mask_x,
+                "mask_y": form.mask_y}
+
     def _watch(self, circuit: CircuitIR, cid: int) -> None:
         """Note the device-side plan ``cid`` for destruction once ``circuit`` is garbage collected.  (A plain weak
         reference with a callback, kept alive in a dict: ``weakref.finalize`` cost 1.4 us per circuit -- 90 us of the

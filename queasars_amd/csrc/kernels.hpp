@@ -46,8 +46,8 @@ constexpr int kSideMaxOwnBits = 16;  // ... and a side's own qubits (launch_fact
 // the next kSplitLoopBits a thread's own bits (it walks their 32 combinations itself), the rest the chunk number.  Per
 // circuit: which side each of them belongs to, as ready-made pieces of the two table indices.
 //   [0] number of keys K  [1] index bits of side X's table (without the keys)  [2] of side Y's
-//   [3] bit 0: X is side B (else A); bits 8..: LX, how many of the thread's own bits belong to side X (0 .. 2: X is the
-//       side with fewer of them)
+//   [3] (kSplitFlags) bit 0 (kSplitSwapXY): X is side B (else A); bits 8..: LX, how many of the thread's own bits belong to
+//       side X (0 .. 2: X is the side with fewer of them)
 //   [4 .. 9)    thread's own bit b (X's bits first, then Y's): its bit in the table index of the side it belongs to
 //   [9 .. 14)   ... and its value in the full index (1 << position)
 //   [14] the qubits of side X as a mask of the full index  [15] of side Y (the split sampler deposits table indices there)
@@ -63,6 +63,7 @@ constexpr uint32_t kNoSideDiag = 0xffffffffu;
 constexpr uint32_t kSplitLoopCols = 4, kSplitLoopPos = 9, kSplitMaskX = 14, kSplitMaskY = 15, kSplitLaneTable = 16, kSplitWaveTable = 144,
                    kSplitChunkLow = 160, kSplitChunkHigh = 416, kSplitSideDiag = 672, kSplitBlockWords = 674;
 constexpr int kSplitLoopBits = 5, kSplitMaxLoopX = 2;
+constexpr uint32_t kSplitFlags = 3, kSplitSwapXY = 1u;
 
 enum PassMode : uint32_t {
     kModeSynthFirst = 1u,  // pass 0 synthesises |0..0> instead of reading the state

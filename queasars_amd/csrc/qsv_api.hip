@@ -627,7 +627,7 @@ int build_circuit(qsv_t* h, int n_ops, const qsv_op* ops, int n_params, bool fol
                     blk[0] = uint32_t(sc.n_keys);
                     blk[1] = uint32_t(sc.n_side[sx]);
                     blk[2] = uint32_t(sc.n_side[1 - sx]);
-                    blk[3] = (swap_xy ? 1u : 0u) | uint32_t(loop_x) << 8;
+                    blk[kSplitFlags] = (swap_xy ? kSplitSwapXY : 0u) | uint32_t(loop_x) << 8;
                     blk[kSplitMaskX] = uint32_t(sc.mask[sx]);
                     blk[kSplitMaskY] = uint32_t(sc.mask[1 - sx]);
                     blk[kSplitSideDiag] = blk[kSplitSideDiag + 1] = kNoSideDiag;  // (upload_plans names the tables)
@@ -1434,7 +1434,13 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
             if (!h->d_factor_big_count.ptr) {
                 const size_t cbytes = factor_big_slot_counters() * sizeof(uint32_t) * size_t(h->side_slots);
                 if ((rc3 = ensure(h, h->d_factor_big_count, cbytes))) return rc3;
+                // Zeroed, and waited for, before anything else is enqueued: the counters of EVERY slot are cleared here, and the
+                // next push's chain -- on the other lane's stream, which does not wait for this one -- adds to those of its own
+                // slots.  Left to run in stream order, a clear that came late (its stream still busy with this chain's virtual
+                // circuits) reset counters that other chain had begun to add to: its evaluations of four and five keys were
+                // combined from incomplete partial sums, or not at all -- a wrong value in the first batch of a handle.
                 QSV_HIP(h, hipMemsetAsync(h->d_factor_big_count.ptr, 0, cbytes, ws(h)));
+                QSV_HIP(h, hipStreamSynchronize(ws(h)));
             }
         }
         a.evals = batch_evals(h) + first;
@@ -2563,6 +2569,44 @@ int qsv_circuit_cost(qsv_t* h, int circuit_id, qsv_circuit_cost_t* out) {
     return QSV_OK;
 }
 
+// The sampling entry points (and the exact CVaR) take a circuit's split form up to this many keys: the split sampler and the
+// exact CVaR read the product of the two side tables, which they do up to three keys (batch_layout's max_keys).
+constexpr int kSampledSplitMaxKeys = 3;
+bool sampled_from_sides(const qsv_t* h, const Circuit& c) {
+    return h->split_sampling && c.split.ok && c.split.n_keys <= kSampledSplitMaxKeys;
+}
+
+int qsv_circuit_form(qsv_t* h, int circuit_id, qsv_circuit_form_t* out) {
+    if (!h) return QSV_E_ARG;
+    if (!out) return fail(h, QSV_E_ARG, "out is null");
+    qsv_circuit_cost_t cost;
+    int rc = qsv_circuit_cost(h, circuit_id, &cost);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(h->mu);
+    auto it = h->circuits.find(circuit_id);
+    if (it == h->circuits.end()) return fail(h, QSV_E_ARG, "unknown circuit id");
+    const Circuit& c = it->second;
+    *out = qsv_circuit_form_t{};
+    out->route = cost.route;
+    out->n_keys = cost.n_keys;
+    const SplitInfo& sp = c.split;
+    if (!sp.ok) return QSV_OK;
+    // (the side plans are indexed as find_split left them; the split block names which of them is X)
+    const uint32_t* blk = c.plan.words.data() + sp.off_block;
+    const int sx = (blk[kSplitFlags] & kSplitSwapXY) ? 1 : 0;
+    for (int xy = 0; xy < 2; ++xy) {
+        out->n_virtual[xy] = sp.n_virtual[xy == 0 ? sx : 1 - sx];
+        out->outer[xy] = sp.outer[xy == 0 ? sx : 1 - sx];
+    }
+    out->amps_per_thread = 1 << sp.side_r;
+    out->halves = sp.fused && sp.halves ? 1 : 0;
+    out->one_launch = sp.fused ? 1 : 0;
+    out->split_sampled = sampled_from_sides(h, c) && c.prefix_id < 0 ? 1 : 0;  // (kept states are not sampled)
+    out->mask_x = blk[kSplitMaskX];
+    out->mask_y = blk[kSplitMaskY];
+    return QSV_OK;
+}
+
 int qsv_eval_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
                       double* out) {
     if (!h) return QSV_E_ARG;
@@ -3022,7 +3066,7 @@ static int sample_batch_locked(qsv_t* h, const std::vector<Circuit*>& circs, con
         if (np[i]) std::memcpy(packed.data() + cur, params + param_offsets[i], size_t(np[i]) * sizeof(double));
     h->prof = qsv_profile{};
     // circuits that have a split form are sampled from their two side tables: no state, no 2^n probabilities
-    int rc = batch_layout(h, circs, np, h->split_sampling);
+    int rc = batch_layout(h, circs, np, h->split_sampling, kSampledSplitMaxKeys);
     if (rc) return rc;
     const size_t n_split = order_split_first(h, 0, n_evals), n_plain = n_evals - n_split;
     const uint64_t dim = uint64_t(1) << h->n;
@@ -3122,6 +3166,17 @@ static int exact_cvar_locked(qsv_t* h, const std::vector<Circuit*>& circs, const
     if (!(h->has_diag_part && h->diagonal))
         return fail(h, QSV_E_STATE, "the exact CVaR needs a diagonal operator (call qsv_set_operator with I/Z terms only)");
     if (h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "the exact CVaR is available up to 28 qubits");
+    std::vector<int64_t> np(n_evals);
+    size_t total = 0;
+    for (size_t i = 0; i < n_evals; ++i) {
+        np[i] = param_offsets[i + 1] - param_offsets[i];
+        if (np[i] < 0) return fail(h, QSV_E_ARG, "param_offsets must be non-decreasing");
+        total += size_t(np[i]);
+    }
+    // alpha = 1 (numpy.isclose(alpha, 1), the reference's test): the reference takes the plain mean of the values there
+    // (expectation_calculation.py:55-69), not its accumulation loop, whose stopping rule leaves out the last 1e-5 of the mass
+    // (5e-4 of an Ising value at 20 qubits): the expectation value, as qsv_eval_circuits computes it
+    if (std::fabs(alpha - 1.0) <= 1e-8 + 1e-5) return eval_all(h, circs, param_offsets, params, out_cvar);
     const uint64_t dim = uint64_t(1) << h->n;
     int rc;
     if (!h->order_valid) {
@@ -3130,19 +3185,12 @@ static int exact_cvar_locked(qsv_t* h, const std::vector<Circuit*>& circs, const
                                         static_cast<double*>(h->d_sorted.ptr), h->stream));
         h->order_valid = true;
     }
-    std::vector<int64_t> np(n_evals);
     std::vector<double> packed;
-    size_t total = 0;
-    for (size_t i = 0; i < n_evals; ++i) {
-        np[i] = param_offsets[i + 1] - param_offsets[i];
-        if (np[i] < 0) return fail(h, QSV_E_ARG, "param_offsets must be non-decreasing");
-        total += size_t(np[i]);
-    }
     packed.resize(total + 1);
     for (size_t i = 0, cur = 0; i < n_evals; cur += size_t(np[i]), ++i)
         if (np[i]) std::memcpy(packed.data() + cur, params + param_offsets[i], size_t(np[i]) * sizeof(double));
     h->prof = qsv_profile{};
-    if ((rc = batch_layout(h, circs, np, h->split_sampling))) return rc;
+    if ((rc = batch_layout(h, circs, np, h->split_sampling, kSampledSplitMaxKeys))) return rc;
     const size_t n_split = order_split_first(h, 0, n_evals), n_plain = n_evals - n_split;
     const size_t G = size_t(h->group), SG = size_t(std::max(1, h->side_slots));
     {

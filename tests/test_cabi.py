@@ -40,6 +40,12 @@ def test_struct_layouts_match_the_header():
         assert getattr(_lib.QsvOp, field).offset == offset
     assert C.sizeof(_lib.QsvPlanConfig) == 20
     assert C.sizeof(_lib.QsvProfile) == 5 * 8 + 4 * 8 + 8 + 6 * 24  # six per-kernel arrays of three
+    assert C.sizeof(_lib.QsvCircuitCost) == 24
+    # qsv_circuit_form_t: ten int32 (two pairs) and two uint32, no padding
+    assert C.sizeof(_lib.QsvCircuitForm) == 48
+    for field, offset in (("route", 0), ("n_keys", 4), ("n_virtual", 8), ("amps_per_thread", 16), ("halves", 20), ("outer", 24),
+                          ("one_launch", 32), ("split_sampled", 36), ("mask_x", 40), ("mask_y", 44)):
+        assert getattr(_lib.QsvCircuitForm, field).offset == offset, field
 
 
 def test_argument_errors_without_a_device():
@@ -53,6 +59,8 @@ def test_argument_errors_without_a_device():
     handle = C.c_void_p()
     assert lib.qsv_create(0, 0, 0, None, C.byref(handle)) == _lib.QSV_E_ARG
     assert lib.qsv_create(4, 9, 0, None, C.byref(handle)) == _lib.QSV_E_ARG
+    form = _lib.QsvCircuitForm()
+    assert lib.qsv_circuit_form(None, 0, C.byref(form)) == _lib.QSV_E_ARG
 
 
 def test_no_cpu_fallback():

@@ -223,19 +223,31 @@ def test_sample_single_and_foreign_stream():
 
 
 def test_config3_n24_population_against_the_c_oracle(c_oracle):
-    """n = 24, L = 4, the 300-term Ising operator of default_rng(2024): individuals 0, 1, 100 and 255 of the
-    256-individual population (seed 0) directly against the plain-C oracle, |dE| <= 1e-10."""
+    """n = 24, L = 4, the 300-term Ising operator of default_rng(2024): about 24 of the 256 individuals of the population
+    (seed 0) -- individuals 0 and 255 and, round robin, the first ones of every (route, cut keys) the library takes them by
+    (circuit_costs) -- directly against the plain-C oracle, |dE| <= 1e-10."""
     n = 24
     _, circuits, params = helpers.population_circuits(n, 4, 256, seed=0)
-    pick = [0, 1, 100, 255]
-    cs, ps = [circuits[i] for i in pick], [params[i] for i in pick]
     op = helpers.random_ising_operator(n, seed=2024)
     assert len(op) == 300
-    got = np.asarray(OperatorCircuitEvaluator(op).evaluate_circuits(cs, ps))
+    ev = OperatorCircuitEvaluator(op)
+    got = np.asarray(ev.evaluate_circuits(circuits, params))
+    by_form = {}
+    for i, cost in enumerate(ev.circuit_costs(circuits)):
+        by_form.setdefault((cost["route"], cost["n_keys"]), []).append(i)
+    pick = [0, 255]
+    queues = [list(v) for _, v in sorted(by_form.items())]
+    while len(pick) < 24 and any(queues):
+        for q in queues:
+            while q and q[0] in pick:
+                q.pop(0)
+            if q and len(pick) < 24:
+                pick.append(q.pop(0))
+    assert len(by_form) >= 2 and len(pick) == 24, sorted(by_form)
     table = c_oracle.diagonal_table(op)
     scratch = np.zeros(2 << n)
-    ref = np.asarray([c_oracle.evaluate(c, p, op, table, scratch) for c, p in zip(cs, ps)])
-    assert np.abs(got - ref).max() < EXP_TOL
+    ref = np.asarray([c_oracle.evaluate(circuits[i], params[i], op, table, scratch) for i in pick])
+    assert np.abs(got[pick] - ref).max() < EXP_TOL, sorted(by_form)
 
 
 # ---- (i) BASELINE config 5: general 500-term operator, fp64 and fp32 ----------------------------------------------
@@ -499,15 +511,20 @@ def _split_device(n, split, **kwargs):
             os.environ["QSV_SPLIT"] = old
 
 
-def _keys_like_the_library(circuit, n):
-    """Number of keys of the split form the library finds (it tries virtual circuits of at most a tile, then a tile + 2 and
-    + 4 qubits), -1 if there is none."""
-    tile = 12 if n < 21 else 13
-    for extra in (0, 2, 4):
-        k = _split_keys(circuit, min(tile + extra, n - 1))
-        if k >= 0:
-            return k
-    return -1
+def _keys_by_the_library(circuits, n, device=None):
+    """Cut keys of the split form the library planned each circuit in, -1 for a circuit it does not split: qsv_circuit_form on
+    ``device`` (its options, circuits registered under the Ising operator it is given here) or on a device of its own with
+    the default options.  Under a quadratic operator every split form -- up to five keys -- takes a split route."""
+    own = device is None
+    dev = StatevectorDevice(n) if own else device
+    try:
+        ev = OperatorCircuitEvaluator(helpers.random_ising_operator(n, seed=1), statevector_device=dev)
+        ev.circuit_costs(circuits)  # (registers them, several at once)
+        forms = [dev.circuit_form(c) for c in circuits]
+    finally:
+        if own:
+            dev.close()
+    return [f["n_keys"] if f["route"] in (1, 2) else -1 for f in forms]
 
 
 def _split_keys(circuit, max_side):
@@ -526,7 +543,7 @@ def test_split_evaluations_agree_with_the_pass_path(n, layers, count):
     a tile, and for circuits that cannot be split at all (deeper ones), mixed in one batch."""
     _, circuits, params = helpers.population_circuits(n, layers, count, seed=40 + n)
     op = helpers.random_ising_operator(n, seed=n)
-    keys = [_keys_like_the_library(c, n) for c in circuits]
+    keys = _keys_by_the_library(circuits, n)
     # the population exercises keys, and key-less or unsplit circuits (or, since four and five keys are taken, those)
     assert max(keys) >= 1 and (min(keys) <= 0 or max(keys) >= 4), keys
     split = OperatorCircuitEvaluator(op, statevector_device=_split_device(n, True)).evaluate_circuits(circuits, params)
@@ -643,7 +660,7 @@ def test_split_results_do_not_depend_on_the_batch(c_oracle):
     n = 20
     _, shallow, ps = helpers.population_circuits(n, 4, 12, seed=7)
     _, deep, pd = helpers.population_circuits(n, 9, 3, seed=8)
-    assert all(_keys_like_the_library(c, n) < 0 for c in deep)
+    assert all(k < 0 for k in _keys_by_the_library(deep, n))
     op = helpers.random_ising_operator(n, seed=3)
     ev = OperatorCircuitEvaluator(op)
     alone = [ev.evaluate_circuits([c], [p])[0] for c, p in zip(shallow, ps)]
@@ -664,7 +681,7 @@ def test_one_launch_route_of_split_evaluations(c_oracle):
     that read a stale line would show as a repetition that differs."""
     n = 20
     _, circuits, params = helpers.population_circuits(n, 4, 64, seed=0)
-    keys = [_keys_like_the_library(c, n) for c in circuits]
+    keys = _keys_by_the_library(circuits, n)
     assert max(keys) >= 2 and min(keys) == 0
     op = helpers.random_ising_operator(n, seed=2020)
     ev = OperatorCircuitEvaluator(op)
@@ -729,7 +746,7 @@ def test_sides_of_eight_amplitudes_per_thread_and_half_sides(c_oracle, layers):
     want = wide.evaluate_circuits(circuits, params)
     assert np.abs(np.asarray(got) - np.asarray(want)).max() < EXP_TOL
     assert got != want  # (the two forms add in different orders: were they the same bits, the option would not be doing anything)
-    keys = [_keys_like_the_library(c, n) for c in circuits]
+    keys = _keys_by_the_library(circuits, n)
     assert 3 in keys
     table = c_oracle.diagonal_table(op)
     scratch = np.zeros(2 << n)
@@ -746,7 +763,7 @@ def test_sides_of_eight_amplitudes_per_thread_and_half_sides(c_oracle, layers):
         # a push too large for one launch with the sides' states in LDS (128 evaluations, two of them with half sides): the half-sided
         # ones get a launch of their own beside the others' -- the same bits as in pushes of 64
         _, many_c, many_p = helpers.population_circuits(n, layers, 128, seed=0)
-        many_keys = [_keys_like_the_library(c, n) for c in many_c]
+        many_keys = _keys_by_the_library(many_c, n)
         assert many_keys.count(3) >= 1 and len(many_c) == 128
         together = ev.evaluate_circuits(many_c, many_p)
         assert together == ev.evaluate_circuits(many_c[:64], many_p[:64]) + ev.evaluate_circuits(many_c[64:], many_p[64:])
@@ -770,6 +787,23 @@ def test_sides_of_eight_amplitudes_per_thread_and_half_sides(c_oracle, layers):
     plain = OperatorCircuitEvaluator(general)
     plain.statevector_device.set_option("split", 0)
     assert np.abs(np.asarray(split) - np.asarray(plain.evaluate_circuits(sub_c, sub_p))).max() < EXP_TOL
+    plain.statevector_device.close()
+    # the split sampler on the same plans: every shot is the exact draw of its uniform number in the sampler's order of states
+    # (tests/sampler_draws.py), up to rounding at a boundary, and its value is D[state]
+    from sampler_draws import DELTA_FP64, DrawCheck, plain_order, shot_uniform, split_order
+
+    dev = ev.statevector_device
+    dev.set_operator(op)
+    forms = [dev.circuit_form(c) for c in sub_c]
+    assert any(f["split_sampled"] and f["amps_per_thread"] == 8 for f in forms), forms
+    shots = 4096
+    states, values = dev.sample_batch(sub_c, sub_p, shots, seed=29, with_values=True)
+    for i, f in enumerate(forms):
+        probs = np.abs(c_oracle.simulate(sub_c[i], sub_p[i])) ** 2
+        order = split_order(f["mask_x"], f["mask_y"]) if f["split_sampled"] else plain_order(n)
+        rep = DrawCheck(probs, order, DELTA_FP64).report(shot_uniform(29, i, np.arange(shots)), states[i])
+        assert rep["rejected"] == 0 and rep["differ_fraction"] <= 0.01, (i, f, rep)
+        assert np.abs(values[i] - table[states[i].astype(np.int64)]).max() <= 1e-12 * float(np.abs(op.coeffs).sum()), i
 
 
 def test_sides_tables_of_d_survive_their_buffer_filling_up():
@@ -900,8 +934,7 @@ def _sampler_device(n, split_sample, **kwargs):
 def _one_circuit_per_key_count(n, layers, count, seed, tile=12):
     _, circuits, params = helpers.population_circuits(n, layers, count, seed=seed)
     chosen = {}
-    for c, p in zip(circuits, params):
-        k = _keys_like_the_library(c, n)
+    for c, p, k in zip(circuits, params, _keys_by_the_library(circuits, n)):
         if k >= 0:  # (unsplittable circuits are the old sampler's, tested elsewhere)
             chosen.setdefault(k, (c, p))
     return chosen
@@ -980,10 +1013,10 @@ def test_split_sampler_on_large_registers(n, dtype, count):
     per evaluation): the split sampler touches 2^(n/2)-sized tables only; fp32 side tables at n = 18."""
     shots = 4096
     _, circuits, params = helpers.population_circuits(n, 3 if n == 28 else 4, count, seed=n)
-    assert any(_keys_like_the_library(c, n) >= 0 for c in circuits)
     op = helpers.random_ising_operator(n, seed=1)
     exact = np.asarray(OperatorCircuitEvaluator(op, dtype=dtype).evaluate_circuits(circuits, params))
     dev = _sampler_device(n, True, dtype=dtype)
+    assert any(k >= 0 for k in _keys_by_the_library(circuits, n, dev))
     dev.set_operator(op)
     _, values = dev.sample_batch(circuits, params, shots, seed=11, with_values=True)
     mean = values.mean(axis=1)
@@ -1035,7 +1068,7 @@ def test_factorised_expectation_agrees_with_the_contraction_and_the_pass_path(n,
     factorised expectation, the contraction kernel and the ordinary multi-pass path agree within 1e-10; an operator with
     terms of weight three and four is not quadratic and still agrees (it takes the contraction kernel either way)."""
     _, circuits, params = helpers.population_circuits(n, layers, count, seed=70 + n)
-    keys = [_keys_like_the_library(c, n) for c in circuits]
+    keys = _keys_by_the_library(circuits, n)
     assert max(keys) >= (1 if n < 25 else 0), keys  # (n = 25: sides of 12 and 13 qubits, the largest tables)
     for kind in ("quadratic", "fields", "cubic"):
         op = _diagonal_operator(n, seed=n, kind=kind)
@@ -1147,7 +1180,7 @@ def test_general_operators_on_split_circuits(n, layers, count, n_terms):
     _, circuits, params = helpers.population_circuits(n, layers, count, seed=90 + n)
     _, deep, pd = helpers.population_circuits(n, 9, 2, seed=91 + n) if n <= 20 else (None, [], [])
     circuits, params = deep[:1] + circuits + deep[1:], pd[:1] + params + pd[1:]
-    keys = [_keys_like_the_library(c, n) for c in circuits]
+    keys = _keys_by_the_library(circuits, n)
     assert max(keys) >= 1 or n >= 24, keys
     op = helpers.random_pauli_operator(n, n_terms, seed=n)
     factor = OperatorCircuitEvaluator(op, statevector_device=_factor_device(n, True)).evaluate_circuits(circuits, params)
@@ -1173,10 +1206,10 @@ def test_split_evaluations_on_the_largest_registers(n, count):
     contraction kernel (1e-10) for the whole population; the ordinary multi-pass path (a 1 / 4 GiB state per evaluation)
     for two of its circuits; sample means of the split sampler within 6 sigma."""
     _, circuits, params = helpers.population_circuits(n, 4, count, seed=n)
-    keys = [_keys_like_the_library(c, n) for c in circuits]
-    assert sum(k >= 0 for k in keys) >= count // 2 and max(keys) >= 1, keys
     op = helpers.random_ising_operator(n, seed=2)
     factor_dev = _factor_device(n, True)
+    keys = _keys_by_the_library(circuits, n, factor_dev)
+    assert sum(k >= 0 for k in keys) >= count // 2 and max(keys) >= 1, keys
     factor = OperatorCircuitEvaluator(op, statevector_device=factor_dev).evaluate_circuits(circuits, params)
     contract = OperatorCircuitEvaluator(op, statevector_device=_factor_device(n, False)).evaluate_circuits(circuits, params)
     scale = max(1.0, float(np.abs(op.coeffs).sum()) / 50.0)
