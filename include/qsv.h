@@ -343,6 +343,33 @@ int qsv_sample_cvar_batch(qsv_t* h, int n_evals, const int* circuit_ids, const i
 int qsv_exact_cvar_batch(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
                          double alpha, double* out_cvar);
 
+/* ---- several observables per evaluation ---------------------------------------------------------- */
+
+/*
+ * OBSERVABLE SETS.  The reference evaluates every aux operator at the best individual and returns the values as
+ * result.aux_operators_evaluated (reference: queasars/minimum_eigensolvers/base/evolving_ansatz_minimum_eigensolver.py:177-199,
+ * :461-476); an EstimatorV2 pub may hold an array of observables.  A set holds M observables
+ *     O_m = sum over k in [term_offsets[m], term_offsets[m+1]) of (coeff_re[k] + i coeff_im[k]) P_k
+ * (Pauli conventions as qsv_set_operator; an observable without terms is 0; duplicate strings are allowed, within an
+ * observable or across observables).  Its distinct strings are grouped by x mask once, on the device.  At most 65536
+ * observables, 65536 distinct strings and 2^24 terms; a term acting on a qubit >= n_qubits, n_observables < 1 or a larger
+ * set is QSV_E_ARG.  Sets live until qsv_observables_destroy or the handle.
+ *
+ * qsv_eval_observables: out[e * n_observables + m] = real(<psi_e| O_m |psi_e>) for n_evals (circuit, parameter vector)
+ * pairs laid out as in qsv_eval_circuits, psi_e prepared as qsv_eval_circuits prepares it (from |0..0>, or from the kept state
+ * of a circuit registered on one).  Independent of the handle's operator: none needs to be set, no table is rebuilt and no
+ * plan invalidated, and qsv_eval_* results after the call are bitwise those before it.  Deterministic: a value depends only on
+ * the set, the circuit, its parameters and the handle configuration, never on the batch.  Each evaluation takes one route,
+ * fixed by its circuit and the handle: a split form of at most three keys on a handle with side tables runs its two virtual
+ * circuits and takes every string's value from the two side tables; everything else runs its gate passes into a state slot,
+ * whose strings' values come from one Walsh-Hadamard sweep of the state per x-mask group.
+ */
+int qsv_observables_create(qsv_t* h, int n_observables, const int64_t* term_offsets, const uint64_t* x_mask,
+                           const uint64_t* z_mask, const double* coeff_re, const double* coeff_im, int* out_set_id);
+int qsv_observables_destroy(qsv_t* h, int set_id);
+int qsv_eval_observables(qsv_t* h, int set_id, int n_evals, const int* circuit_ids, const int64_t* param_offsets,
+                         const double* params, double* out);
+
 /* ---- sharded populations on one node ------------------------------------------------------------- */
 
 /*

@@ -160,6 +160,9 @@ SIGNATURES = {
     "qsv_sample_batch": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, C.c_uint64, _P, _P]),
     "qsv_sample_cvar_batch": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, C.c_uint64, C.c_double, _P]),
     "qsv_exact_cvar_batch": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_double, _P]),
+    "qsv_observables_create": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.POINTER(C.c_int)]),
+    "qsv_observables_destroy": (C.c_int, [_P, C.c_int]),
+    "qsv_eval_observables": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "qsv_set_option": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "qsv_fitness_table_wait": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int]),
     "qsv_set_profiling": (C.c_int, [_P, C.c_int]),

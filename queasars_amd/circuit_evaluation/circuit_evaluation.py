@@ -26,6 +26,7 @@ import os
 import threading
 import uuid
 import weakref
+from collections import OrderedDict
 from itertools import count
 from abc import ABC, abstractmethod
 from typing import Optional, Sequence
@@ -255,6 +256,7 @@ class StatevectorDevice:
         self._gone = _make_gone(self._dead, self._watched)  # (holds the two containers, not the device)
         # held across "set the operator, then evaluate" by evaluators that share this device
         self.operator_lock = threading.RLock()
+        self._observable_sets: "OrderedDict[tuple, int]" = OrderedDict()  # (observable_values; gone with the handle)
 
     # -- plumbing -------------------------------------------------------------------------------
     def __reduce__(self):
@@ -270,6 +272,7 @@ class StatevectorDevice:
         handle, self._handle = getattr(self, "_handle", None), None
         if handle:
             getattr(self, "_watched", {}).clear()
+            getattr(self, "_observable_sets", {}).clear()
             self._lib.qsv_destroy(handle)
 
     def _check(self, rc: int) -> None:
@@ -793,6 +796,67 @@ class StatevectorDevice:
                                                    float(alpha), _lib.as_ptr(out)))
         return out.tolist()
 
+    # -- several observables ---------------------------------------------------------------------
+    MAX_OBSERVABLE_SETS = 16
+
+    def _observable_set(self, operators: Sequence[PauliOperator]) -> int:
+        """Device-side set of ``operators`` (``qsv_observables_create``), cached by content; the least recently used sets
+        beyond :attr:`MAX_OBSERVABLE_SETS` are destroyed."""
+        for op in operators:
+            if not isinstance(op, PauliOperator):
+                raise ValueError("every observable must be a PauliOperator")
+            if op.num_qubits != self._n_qubits:
+                raise ValueError(f"an observable acts on {op.num_qubits} qubits, the device was created for {self._n_qubits}")
+        key = tuple((op.num_qubits, op.x_mask.tobytes(), op.z_mask.tobytes(), op.coeffs.tobytes()) for op in operators)
+        sets = self._observable_sets
+        hit = sets.get(key)
+        if hit is not None:
+            sets.move_to_end(key)
+            return hit
+        offsets = np.zeros(len(operators) + 1, dtype=np.int64)
+        np.cumsum([len(op) for op in operators], out=offsets[1:])
+        pad = [np.zeros(1, dtype=np.uint64)]
+        x = np.ascontiguousarray(np.concatenate([np.asarray(op.x_mask, dtype=np.uint64) for op in operators] + pad))
+        z = np.ascontiguousarray(np.concatenate([np.asarray(op.z_mask, dtype=np.uint64) for op in operators] + pad))
+        coeffs = np.concatenate([op.coeffs for op in operators] + [np.zeros(1, dtype=complex)])
+        cre = np.ascontiguousarray(coeffs.real, dtype=np.float64)
+        cim = np.ascontiguousarray(coeffs.imag, dtype=np.float64)
+        out = C.c_int(0)
+        self._check(self._lib.qsv_observables_create(self._handle, len(operators), _lib.as_ptr(offsets), _lib.as_ptr(x),
+                                                     _lib.as_ptr(z), _lib.as_ptr(cre), _lib.as_ptr(cim), C.byref(out)))
+        sets[key] = out.value
+        while len(sets) > self.MAX_OBSERVABLE_SETS:
+            _, old = sets.popitem(last=False)
+            self._check(self._lib.qsv_observables_destroy(self._handle, old))
+        return out.value
+
+    def observable_values(
+        self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]], operators: Sequence[PauliOperator]
+    ) -> np.ndarray:
+        """``real(<psi_i|O_m|psi_i>)`` for every (circuit, parameter vector) pair i and operator m, a ``(len(circuits),
+        len(operators))`` array (``qsv_eval_observables``).  Does not use or change the operator set on the device."""
+        n = len(circuits)
+        if len(parameter_values) != n:
+            raise ValueError("circuits and parameter_values must have the same length")
+        operators = list(operators)
+        if not operators:
+            raise ValueError("at least one observable is needed")
+        set_id = self._observable_set(operators)
+        if n == 0:
+            return np.zeros((0, len(operators)), dtype=np.float64)
+        ids, need, _ = self._batch_metadata(circuits)
+        counts = np.fromiter(map(len, parameter_values), dtype=np.int64, count=n)
+        if (counts < need).any():
+            i = int(np.argmax(counts < need))
+            raise ValueError(f"circuit {i} needs {int(need[i])} parameter values, got {int(counts[i])}")
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(counts, out=offsets[1:])
+        flat = _pack_slice(parameter_values, 0, n, int(offsets[-1])) if offsets[-1] else np.zeros(1)
+        out = np.empty((n, len(operators)), dtype=np.float64)
+        self._check(self._lib.qsv_eval_observables(self._handle, set_id, n, _lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat),
+                                                    _lib.as_ptr(out)))
+        return out
+
     # -- measurement support ----------------------------------------------------------------------
     def set_option(self, name: str, value: int) -> None:
         """Switches of the handle (``qsv_set_option``): "split", "factor", "split_sampling" (0 / 1), "streams" (1 .. 4).
@@ -947,6 +1011,19 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
                 values = self._evaluate_device_matrix(circuits, matrix)
             else:
                 values = self._device.expectation_values(circuits, parameter_values)
+        if self._precision > 0:
+            values = values + self._rng.normal(0.0, self._precision, size=values.shape)
+        return values.tolist()
+
+    def evaluate_observables(
+        self, circuits: list[CircuitIR], parameter_values: list[list[float]], operators: Sequence[PauliOperator]
+    ) -> list[list[float]]:
+        """``real(<psi_i|O_m|psi_i>)`` of every circuit (behind this evaluator's initial state) and observable, one row per
+        circuit (:meth:`StatevectorDevice.observable_values`); with ``estimator_precision > 0`` each value gets its own Gaussian
+        noise, as in :meth:`evaluate_circuits`.  The evaluator's own operator is neither used nor changed."""
+        if self._initial_state_circuit is not None:
+            circuits = [self._with_initial_state(c) for c in circuits]
+        values = self._device.observable_values(circuits, parameter_values, operators)
         if self._precision > 0:
             values = values + self._rng.normal(0.0, self._precision, size=values.shape)
         return values.tolist()
@@ -1113,6 +1190,18 @@ def _cvar_of_samples(values: np.ndarray, alpha: float) -> float:
     return total / mass
 
 
+def _diagonal_values(operator: PauliOperator, states: np.ndarray) -> np.ndarray:
+    """The diagonal operator's value on every sampled basis state, sum_k Re(c_k) (-1)^popcount(state & z_k) (what
+    ``_evaluate_sparsepauli`` computes per measured state, reference: expectation_calculation.py:64-66)."""
+    out = np.zeros(states.shape, dtype=np.float64)
+    for z, c in zip(np.asarray(operator.z_mask, dtype=np.uint64), operator.coeffs.real):
+        v = states & z
+        for shift in (32, 16, 8, 4, 2, 1):
+            v = v ^ (v >> np.uint64(shift))
+        out += np.where((v & np.uint64(1)) != 0, -c, c)
+    return out
+
+
 def _cvar_of_sample_matrix(values: np.ndarray, alpha: float) -> list[float]:
     """:func:`_cvar_of_samples` for every row of ``values`` (one row of ``shots`` sample values per circuit) at once: one
     sort of the whole matrix instead of one NumPy call chain per circuit (5 us each: as much as the device took to
@@ -1190,6 +1279,42 @@ class OperatorSamplerCircuitEvaluator(BaseCircuitEvaluator):
                 return self._device.sample_cvar_batch([c for c, _ in pairs], [p for _, p in pairs], self._shots, seed, self._alpha)
             _, values = self._device.sample_batch([c for c, _ in pairs], [p for _, p in pairs], self._shots, seed, with_values=True)
         return _cvar_of_sample_matrix(values, self._alpha)
+
+    def evaluate_observables(
+        self, circuits: list[CircuitIR], parameter_values: list[list[float]], operators: Sequence[PauliOperator]
+    ) -> list[list[float]]:
+        """CVaR_alpha of every (diagonal) operator per circuit, one row per circuit: what an aux evaluator of the reference --
+        a sampler evaluator with this one's shots and alpha -- returns.  The samples are drawn once per circuit and valued on
+        the host for each operator; ``sampler_shots=None`` takes the exact distribution (alpha = 1: the expectation value,
+        :meth:`StatevectorDevice.observable_values`).  The operator set on the device is left as it was.  With shots the call
+        draws one seed from this evaluator's own generator, as :meth:`evaluate_circuits` does (the reference's aux evaluators
+        sample with their own sampler); nothing else's random stream is touched."""
+        operators = list(operators)
+        for op in operators:
+            if not isinstance(op, PauliOperator) or not op.is_diagonal():
+                raise ValueError("The sampler branch needs a diagonal (I/Z only) operator!")
+            if op.num_qubits != self.n_qubits:
+                raise ValueError(f"an observable acts on {op.num_qubits} qubits, the evaluator on {self.n_qubits}")
+        pairs = [(self._composed.get(c), p) for c, p in zip(circuits, parameter_values) if c is not None and p is not None]
+        circs, values = [c for c, _ in pairs], [p for _, p in pairs]
+        if self._shots is None:
+            if np.isclose(self._alpha, 1):
+                return self._device.observable_values(circs, values, operators).tolist()
+            columns = []
+            with self._device.operator_lock:
+                previous = self._device._operator
+                try:
+                    for op in operators:
+                        self._device.set_operator(op)
+                        columns.append(self._device.exact_cvar_batch(circs, values, self._alpha))
+                finally:
+                    if previous is not None:
+                        self._device.set_operator(previous)
+            return np.asarray(columns, dtype=np.float64).reshape(len(operators), len(circs)).T.tolist()
+        seed = int(self._rng.integers(0, 2**63 - 1))
+        states, _ = self._device.sample_batch(circs, values, self._shots, seed)
+        columns = [_cvar_of_sample_matrix(_diagonal_values(op, states), self._alpha) for op in operators]
+        return np.asarray(columns, dtype=np.float64).reshape(len(operators), len(circs)).T.tolist()
 
     @property
     def n_qubits(self) -> int:

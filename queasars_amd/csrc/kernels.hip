@@ -2012,6 +2012,173 @@ hipError_t launch_pauli_combine(const double* partials, uint32_t per_slot, const
     return hipGetLastError();
 }
 
+// ---- observable sets (kernels.hpp: launch_pauli_terms) -------------------------------------------------------------
+// Length-1024 Walsh-Hadamard transform of the values l = j * 64 + lane (v[j] in lane `lane`), in place: the four bits of j in
+// registers, the six lane bits across lanes.  A fixed order of every sum.
+constexpr int kObsPerLane = (1 << kObsBlockBits) / 64;
+__device__ __forceinline__ void obs_wht(double (&v)[kObsPerLane]) {
+#pragma unroll
+    for (int s = 1; s < kObsPerLane; s <<= 1)
+#pragma unroll
+        for (int j = 0; j < kObsPerLane; ++j)
+            if (!(j & s)) {
+                const double a = v[j], b = v[j | s];
+                v[j] = a + b;
+                v[j | s] = a - b;
+            }
+    const int lane = int(threadIdx.x & 63u);
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1)
+#pragma unroll
+        for (int j = 0; j < kObsPerLane; ++j) {
+            const double other = __shfl_xor(v[j], s);
+            v[j] = (lane & s) ? other - v[j] : v[j] + other;
+        }
+}
+
+// One wave per workgroup: row blockIdx.y (a chunk of one group's strings), state slot blockIdx.z, blocks h = blockIdx.x,
+// blockIdx.x + gridDim.x, ... of the row's index space.  Lane `lane` owns strings lane, lane + 64, ... of the chunk.
+template <typename real>
+__global__ void __launch_bounds__(64) pauli_terms_kernel(const cx<real>* __restrict__ states, uint64_t state_stride, int n_qubits,
+                                                         const ObsRow* __restrict__ rows, const ObsTerm* __restrict__ terms,
+                                                         uint32_t n_terms, double* __restrict__ partials) {
+    constexpr int B = 1 << kObsBlockBits, Q = int(kObsChunk / 64);
+    __shared__ double w_re[B], w_im[B];
+    const ObsRow row = rows[blockIdx.y];
+    const uint32_t lane = threadIdx.x;
+    const cx<real>* __restrict__ st = states + uint64_t(blockIdx.z) * state_stride;
+    const bool diag = row.x == 0;
+    const int bits = diag ? n_qubits : n_qubits - 1;
+    const uint64_t n_index = uint64_t(1) << bits;
+    const uint64_t n_blocks = bits > kObsBlockBits ? uint64_t(1) << (bits - kObsBlockBits) : 1;
+    const bool want_re = row.parts & 1u, want_im = row.parts & 2u;
+    const uint64_t low_mask = (uint64_t(1) << row.pivot) - 1;
+    uint32_t z_lo[Q], z_hi[Q];
+    bool odd[Q];
+    double acc[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const uint32_t k = uint32_t(q) * 64u + lane;
+        ObsTerm t{0, 0, 0, 0.0};
+        if (k < row.count) t = terms[row.first + k];
+        z_lo[q] = uint32_t(t.zp) & uint32_t(B - 1);
+        z_hi[q] = uint32_t(t.zp >> kObsBlockBits);
+        odd[q] = t.odd != 0;
+        acc[q] = 0.0;
+    }
+    for (uint64_t hb = blockIdx.x; hb < n_blocks; hb += gridDim.x) {
+        double re[kObsPerLane], im[kObsPerLane];
+#pragma unroll
+        for (int j = 0; j < kObsPerLane; ++j) {
+            const uint64_t p = (hb << kObsBlockBits) | uint64_t(j * 64 + int(lane));
+            double r = 0.0, m = 0.0;
+            if (p < n_index) {
+                if (diag) {
+                    const cx<real> a = st[p];
+                    r = double(a.re) * double(a.re) + double(a.im) * double(a.im);
+                } else {
+                    const uint64_t i = ((p & ~low_mask) << 1) | (p & low_mask);  // bit `pivot` of i is 0
+                    const cx<real> a = st[i], b = st[i ^ row.x];
+                    r = double(a.re) * double(b.re) + double(a.im) * double(b.im);
+                    m = double(a.re) * double(b.im) - double(a.im) * double(b.re);
+                }
+            }
+            re[j] = r;
+            im[j] = m;
+        }
+        if (want_re) {
+            obs_wht(re);
+#pragma unroll
+            for (int j = 0; j < kObsPerLane; ++j) w_re[j * 64 + int(lane)] = re[j];
+        }
+        if (want_im) {
+            obs_wht(im);
+#pragma unroll
+            for (int j = 0; j < kObsPerLane; ++j) w_im[j * 64 + int(lane)] = im[j];
+        }
+        __syncthreads();
+        const uint32_t h32 = uint32_t(hb);
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const double w = odd[q] ? w_im[z_lo[q]] : w_re[z_lo[q]];
+            acc[q] += (uint32_t(__builtin_popcount(h32 & z_hi[q])) & 1u) ? -w : w;
+        }
+        __syncthreads();  // (the next block overwrites the transforms)
+    }
+    double* out = partials + (size_t(blockIdx.z) * gridDim.x + blockIdx.x) * n_terms + row.first;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const uint32_t k = uint32_t(q) * 64u + lane;
+        if (k < row.count) out[k] = acc[q];
+    }
+}
+
+hipError_t launch_pauli_terms(int dtype, const void* states, uint64_t state_stride, int n_qubits, int n_slots, int n_rows,
+                              const ObsRow* rows, const ObsTerm* terms, uint32_t n_terms, int nb, double* partials,
+                              hipStream_t stream) {
+    if (n_slots <= 0 || n_rows <= 0) return hipSuccess;
+    const dim3 grid{unsigned(nb), unsigned(n_rows), unsigned(n_slots)};
+    if (dtype == 0)
+        hipLaunchKernelGGL(pauli_terms_kernel<double>, grid, dim3(64), 0, stream, static_cast<const cx<double>*>(states),
+                           state_stride, n_qubits, rows, terms, n_terms, partials);
+    else
+        hipLaunchKernelGGL(pauli_terms_kernel<float>, grid, dim3(64), 0, stream, static_cast<const cx<float>*>(states),
+                           state_stride, n_qubits, rows, terms, n_terms, partials);
+    return hipGetLastError();
+}
+
+// 64 strings per workgroup (lane = string), its four waves take the partial sums b = wave (mod 4), four independent running sums
+// each (latency: a single chain over nb loads was 108 us for 64 states x 211 strings x nb = 256); fixed order throughout.
+__global__ void __launch_bounds__(256) pauli_terms_reduce_kernel(const double* __restrict__ partials, uint32_t nb, uint32_t n_terms,
+                                                                 const ObsTerm* __restrict__ terms, double* __restrict__ values) {
+    __shared__ double part[4][64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t k = blockIdx.x * 64u + lane;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    if (k < n_terms) {
+        const double* p = partials + size_t(blockIdx.y) * nb * n_terms + k;
+        uint32_t b = wave;
+        for (; b + 12 < nb; b += 16) {
+            acc[0] += p[size_t(b) * n_terms];
+            acc[1] += p[size_t(b + 4) * n_terms];
+            acc[2] += p[size_t(b + 8) * n_terms];
+            acc[3] += p[size_t(b + 12) * n_terms];
+        }
+        for (uint32_t q = 0; b < nb; b += 4, ++q) acc[q] += p[size_t(b) * n_terms];
+    }
+    part[wave][lane] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+    __syncthreads();
+    if (wave == 0 && k < n_terms)
+        values[size_t(blockIdx.y) * n_terms + k] = terms[k].scale * (((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane]);
+}
+
+hipError_t launch_pauli_terms_reduce(const double* partials, int nb, uint32_t n_terms, const ObsTerm* terms, int n_evals,
+                                     double* values, hipStream_t stream) {
+    if (n_evals <= 0 || n_terms == 0) return hipSuccess;
+    hipLaunchKernelGGL(pauli_terms_reduce_kernel, dim3((n_terms + 63u) / 64u, unsigned(n_evals)), dim3(256), 0, stream, partials,
+                       uint32_t(nb), n_terms, terms, values);
+    return hipGetLastError();
+}
+
+__global__ void __launch_bounds__(256) observables_combine_kernel(const double* __restrict__ values, uint32_t n_terms, uint32_t n_obs,
+                                                                  const int64_t* __restrict__ offsets, const uint32_t* __restrict__ term_of,
+                                                                  const double* __restrict__ coef, double* __restrict__ out) {
+    const uint32_t m = blockIdx.x * 256u + threadIdx.x;
+    if (m >= n_obs) return;
+    const double* v = values + size_t(blockIdx.y) * n_terms;
+    double acc = 0.0;
+    for (int64_t j = offsets[m]; j < offsets[m + 1]; ++j) acc = fma(coef[j], v[term_of[j]], acc);
+    out[size_t(blockIdx.y) * n_obs + m] = acc;
+}
+
+hipError_t launch_observables_combine(const double* values, uint32_t n_terms, int n_evals, uint32_t n_obs, const int64_t* offsets,
+                                      const uint32_t* term_of, const double* coef, double* out, hipStream_t stream) {
+    if (n_evals <= 0) return hipSuccess;
+    hipLaunchKernelGGL(observables_combine_kernel, dim3((n_obs + 255u) / 256u, unsigned(n_evals)), dim3(256), 0, stream, values, n_terms,
+                       n_obs, offsets, term_of, coef, out);
+    return hipGetLastError();
+}
+
 // ---- state read-out ------------------------------------------------------------------------------------
 template <typename real>
 __global__ void __launch_bounds__(256) probabilities_kernel(const cx<real>* __restrict__ st_all, uint64_t dim,
@@ -3674,30 +3841,36 @@ __device__ __forceinline__ void factor_term_side(const cx<real>* __restrict__ ta
     *out_im = acc_im;
 }
 
+// <P> of the Pauli string (x, z) of the full index from the two side tables (every lane of the wave gets it)
+template <typename real, int J>
+__device__ __forceinline__ double factor_term_value(const cx<real>* __restrict__ X, const cx<real>* __restrict__ Y, const uint32_t (&bits)[2],
+                                                    const uint32_t (&mask)[2], uint32_t x, uint32_t z, cx<real>* stage) {
+    constexpr uint32_t NQ = J * J;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t fx = extract_bits(x, mask[0]), zx = extract_bits(z, mask[0]);
+    const uint32_t fy = extract_bits(x, mask[1]), zy = extract_bits(z, mask[1]);
+    double ar, ai, br, bi;
+    factor_term_side<real, J>(X, bits[0], fx, zx, stage, &ar, &ai);
+    factor_term_side<real, J>(Y, bits[1], fy, zy, stage, &br, &bi);
+    // sum over the entries of A[j'j] B[j'j] (complex), then the power of i of the string's Y factors
+    double sr = lane < NQ ? fma(ar, br, -ai * bi) : 0.0, si = lane < NQ ? fma(ar, bi, ai * br) : 0.0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sr += __shfl_xor(sr, off);
+        si += __shfl_xor(si, off);
+    }
+    const uint32_t ny = uint32_t(__builtin_popcount(x & z)) & 3u;
+    return ny == 0 ? sr : ny == 1 ? -si : ny == 2 ? -sr : si;  // Re(i^ny (sr + i si))
+}
+
 template <typename real, int J>
 __device__ double factor_terms_body(const cx<real>* __restrict__ X, const cx<real>* __restrict__ Y, const uint32_t (&bits)[2],
                                     const uint32_t (&mask)[2], const FactorTerm* __restrict__ terms, uint32_t n_terms,
                                     uint32_t first, uint32_t step, cx<real>* stage) {
-    constexpr uint32_t NQ = J * J;
-    const uint32_t lane = threadIdx.x & 63u;
     double total = 0.0;
     for (uint32_t k = first; k < n_terms; k += step) {
         const FactorTerm t = terms[k];
-        const uint32_t fx = extract_bits(t.x, mask[0]), zx = extract_bits(t.z, mask[0]);
-        const uint32_t fy = extract_bits(t.x, mask[1]), zy = extract_bits(t.z, mask[1]);
-        double ar, ai, br, bi;
-        factor_term_side<real, J>(X, bits[0], fx, zx, stage, &ar, &ai);
-        factor_term_side<real, J>(Y, bits[1], fy, zy, stage, &br, &bi);
-        // sum over the entries of A[j'j] B[j'j] (complex), then the power of i of the string's Y factors
-        double sr = lane < NQ ? fma(ar, br, -ai * bi) : 0.0, si = lane < NQ ? fma(ar, bi, ai * br) : 0.0;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            sr += __shfl_xor(sr, off);
-            si += __shfl_xor(si, off);
-        }
-        const uint32_t ny = uint32_t(__builtin_popcount(t.x & t.z)) & 3u;
-        const double value = ny == 0 ? sr : ny == 1 ? -si : ny == 2 ? -sr : si;  // Re(i^ny (sr + i si))
-        total = fma(t.coeff, value, total);
+        total = fma(t.coeff, factor_term_value<real, J>(X, Y, bits, mask, t.x, t.z, stage), total);
     }
     return total;
 }
@@ -3742,6 +3915,51 @@ hipError_t launch_factor_terms(int dtype, unsigned n_evals, const FactorTerm* te
     else
         hipLaunchKernelGGL(factor_terms_kernel<float>, grid, dim3(256), 0, stream, a.plan, a.evals,
                            static_cast<const cx<float>*>(a.wtab), a.wtab_stride, terms, n_terms, partials);
+    return hipGetLastError();
+}
+
+// One wave per (string, split evaluation): the string's value goes to its own slot, values[blockIdx.y * n_terms + k].
+template <typename real>
+__global__ void __launch_bounds__(256, 2) split_term_values_kernel(const uint32_t* __restrict__ plan_arena, const EvalDesc* __restrict__ evals,
+                                                                   const cx<real>* __restrict__ sides, uint64_t side_stride,
+                                                                   const FactorTerm* __restrict__ terms, uint32_t n_terms,
+                                                                   double* __restrict__ values) {
+    __shared__ cx<real> stage_all[4 * 2 * 9 * 64];
+    const EvalDesc ev = evals[blockIdx.y];
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t k = blockIdx.x * 4u + wave;
+    if (!(ev.flags & kEvalSide) || k >= n_terms) return;
+    const uint32_t* sp = plan_arena + ev.split_base;
+    const uint32_t n_keys = sp[0];
+    const bool swap = sp[3] & 1u;
+    const uint32_t bits[2] = {sp[1], sp[2]}, mask[2] = {sp[kSplitMaskX], sp[kSplitMaskY]};
+    const cx<real>* ta = sides + uint64_t(ev.state_slot) * side_stride;
+    const cx<real>* X = ta + (swap ? side_stride >> 1 : 0);
+    const cx<real>* Y = ta + (swap ? 0 : side_stride >> 1);
+    cx<real>* stage = stage_all + size_t(wave) * 2 * 9 * 64;
+    const FactorTerm t = terms[k];
+    double value;
+    if (n_keys == 0)
+        value = factor_term_value<real, 1>(X, Y, bits, mask, t.x, t.z, stage);
+    else if (n_keys == 1)
+        value = factor_term_value<real, 2>(X, Y, bits, mask, t.x, t.z, stage);
+    else if (n_keys == 2)
+        value = factor_term_value<real, 4>(X, Y, bits, mask, t.x, t.z, stage);
+    else
+        value = factor_term_value<real, 8>(X, Y, bits, mask, t.x, t.z, stage);
+    if ((threadIdx.x & 63u) == 0) values[size_t(blockIdx.y) * n_terms + k] = value;
+}
+
+hipError_t launch_split_term_values(int dtype, unsigned n_evals, const FactorTerm* terms, uint32_t n_terms, double* values,
+                                    hipStream_t stream, const PassArgs& a) {
+    if (n_evals == 0 || n_terms == 0) return hipSuccess;
+    const dim3 grid((n_terms + 3u) / 4u, n_evals);
+    if (dtype == 0)
+        hipLaunchKernelGGL(split_term_values_kernel<double>, grid, dim3(256), 0, stream, a.plan, a.evals,
+                           static_cast<const cx<double>*>(a.wtab), a.wtab_stride, terms, n_terms, values);
+    else
+        hipLaunchKernelGGL(split_term_values_kernel<float>, grid, dim3(256), 0, stream, a.plan, a.evals,
+                           static_cast<const cx<float>*>(a.wtab), a.wtab_stride, terms, n_terms, values);
     return hipGetLastError();
 }
 

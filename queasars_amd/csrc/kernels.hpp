@@ -272,6 +272,46 @@ hipError_t launch_pauli_combine(const double* partials, uint32_t per_slot, const
                                 uint32_t diag_per_eval, int n_slots, const EvalDesc* evals, double* out,
                                 hipStream_t stream);
 
+// ---- observable sets (qsv.h: qsv_observables_create / qsv_eval_observables) ------------------------------------------------
+// The distinct Pauli strings of a set, grouped by x mask (x = 0: the diagonal group), one value <P_k> per string and state.
+// State route (pauli_terms_kernel): for a group with pivot P (highest bit of x), pair p in [0, 2^(n-1)), i = p with a 0
+// inserted at bit P, j = i ^ x, c_p = conj(a_i) a_j and z' = z without bit P,
+//     <X^x Z^z> = +-2 sum_p (-1)^popcount(p & z') (Re or Im of c_p);
+// with p = (h << kObsBlockBits) | l the inner sum over l, for every low part of z' at once, is the Walsh-Hadamard transform W_h
+// of block h: each wave transforms one block (in registers and across lanes), puts W_h in LDS, and every string of the row
+// adds (-1)^popcount(h & z'_hi) W_h[z'_lo].  The diagonal group: the same over the 2^n values |a_i|^2.  One read of the state
+// per group, ~2 kObsBlockBits adds per pair, one pick per string and block.  A row is a chunk of at most kObsChunk strings of
+// one group; each chunk reads the state again.
+constexpr int kObsBlockBits = 10;
+constexpr uint32_t kObsChunk = 512;  // (eight strings per lane of the row's wave)
+struct ObsRow {
+    uint64_t x;      // x mask of the group (0: diagonal)
+    uint32_t first;  // first string of the chunk in the string array
+    uint32_t count;
+    uint32_t pivot;  // highest set bit of x
+    uint32_t parts;  // bit 0: a string of the chunk reads Re c_p (or |a_i|^2), bit 1: one reads Im c_p
+};
+struct ObsTerm {
+    uint64_t zp;   // z without the pivot bit (diagonal group: z)
+    uint32_t odd;  // odd number of Y factors: the string reads Im c_p
+    uint32_t pad;
+    double scale;  // 2 (-1)^floor(ny / 2), or 1 in the diagonal group
+};
+// partials[(slot * nb + b) * n_terms + k]: workgroup b's share of string k on state slot s (grid nb x n_rows x n_slots)
+hipError_t launch_pauli_terms(int dtype, const void* states, uint64_t state_stride, int n_qubits, int n_slots, int n_rows,
+                              const ObsRow* rows, const ObsTerm* terms, uint32_t n_terms, int nb, double* partials,
+                              hipStream_t stream);
+// values[e * n_terms + k] = terms[k].scale * (sum over b < nb of the partials, in order of b)
+hipError_t launch_pauli_terms_reduce(const double* partials, int nb, uint32_t n_terms, const ObsTerm* terms, int n_evals,
+                                     double* values, hipStream_t stream);
+// Split route: values[e * n_terms + k] = <P_k> of split evaluation e from its two side tables (factor_terms_kernel's value of
+// a string before its coefficient: one wave per string, no sum across waves).  PassArgs as launch_factor_terms.
+hipError_t launch_split_term_values(int dtype, unsigned n_evals, const FactorTerm* terms, uint32_t n_terms, double* values,
+                                    hipStream_t stream, const PassArgs& args);
+// out[e * n_obs + m] = sum over j in [offsets[m], offsets[m + 1]) of coef[j] * values[e * n_terms + term_of[j]], in order of j
+hipError_t launch_observables_combine(const double* values, uint32_t n_terms, int n_evals, uint32_t n_obs, const int64_t* offsets,
+                                      const uint32_t* term_of, const double* coef, double* out, hipStream_t stream);
+
 // For each of n_slots probability vectors (slot s at probs + s * dim, need not be normalised) draw `shots` basis
 // states; evaluation (first_eval + s) gets its own random stream and writes out[(first_eval + s) * shots ..].
 // chunk_sums: scratch of n_slots * sample_chunk_count(dim) doubles.  With diag != null, out_values receives D[state].

@@ -88,6 +88,16 @@ struct DeviceBuffer {
     size_t bytes = 0;
 };
 
+// An observable set (qsv_observables_create): its distinct Pauli strings as pauli_terms_kernel and split_term_values_kernel
+// read them, and each observable as a list of (string, real coefficient) in the caller's order (kernels.hpp)
+struct ObservableSet {
+    uint32_t n_obs = 0;
+    uint32_t n_terms = 0;  // distinct strings
+    int n_rows = 0;
+    int nb = 1;            // workgroups per row and state of pauli_terms_kernel
+    DeviceBuffer d_rows, d_terms, d_split_terms, d_offsets, d_term_of, d_coef;
+};
+
 }  // namespace
 
 // Persistent host threads for scheduling many circuit structures at once (a generation of EVQE brings up to a
@@ -240,6 +250,11 @@ struct qsv_handle {
     std::vector<uint32_t> prefix_free; // recycled slots
     size_t prefix_used = 0;            // slots handed out so far (below capacity)
     std::unordered_map<std::string, int> inline_cache;
+    // observable sets (qsv_observables_create) and the scratch of qsv_eval_observables: per-workgroup partial sums of the
+    // strings' values, and the values
+    std::unordered_map<int, ObservableSet> obs_sets;
+    int next_obs_id = 1;
+    DeviceBuffer d_obs_partials, d_obs_values;
     std::unique_ptr<WorkerPool> pool;  // created on first use (qsv_circuits_create, qsv_eval_batch)
     std::mutex pool_mu;
 
@@ -1980,6 +1995,118 @@ int run_single_to_state(qsv_t* h, int circuit_id, const double* params, int n_pa
     return rc;
 }
 
+// ---- observable sets ---------------------------------------------------------------------------------------------------
+// Largest set qsv_observables_create accepts, and the scratch one launch group of qsv_eval_observables may use for the partial
+// sums of its strings (the group is made smaller to stay inside it)
+constexpr uint32_t kMaxObsStrings = 1u << 16, kMaxObservables = 1u << 16;
+constexpr int64_t kMaxObsEntries = int64_t(1) << 24;
+constexpr size_t kObsScratchBytes = size_t(64) << 20;
+
+void free_observable_set(ObservableSet& s) {
+    for (DeviceBuffer* b : {&s.d_rows, &s.d_terms, &s.d_split_terms, &s.d_offsets, &s.d_term_of, &s.d_coef})
+        if (b->ptr) (void)hipFree(b->ptr);
+    s = ObservableSet{};
+}
+
+int upload_bytes(qsv_t* h, DeviceBuffer& b, const void* src, size_t bytes) {
+    int rc = ensure(h, b, bytes);
+    if (rc) return rc;
+    if (bytes) QSV_HIP(h, hipMemcpy(b.ptr, src, bytes, hipMemcpyHostToDevice));
+    return QSV_OK;
+}
+
+// A split evaluation takes the split route when its circuit has a split form of at most three keys and the handle has side tables
+// (factor_terms_path without the operator); everything else takes the state route.  Depends on the circuit and the handle only.
+bool observables_split_route(const qsv_t* h, const Circuit& c) {
+    return h->factor_enabled && h->d_side.ptr != nullptr && h->n <= 32 && c.split.ok && c.split.n_keys <= 3 && c.prefix_id < 0;
+}
+
+// qsv_eval_observables with the lock held and the arguments checked.  The evaluations run reordered -- split route first, then
+// the ordinary state route, then circuits on kept states (a launch group holds one kind) --, each launch group's values land in
+// the pinned result buffer at its positions, and the host puts the rows back in the caller's order.
+int eval_observables_locked(qsv_t* h, const ObservableSet& set, const std::vector<Circuit*>& in_circs, const int64_t* param_offsets,
+                            const double* params, double* out) {
+    const size_t n_evals = in_circs.size();
+    std::vector<size_t> order;
+    order.reserve(n_evals);
+    for (int kind = 0; kind < 3; ++kind)
+        for (size_t i = 0; i < n_evals; ++i) {
+            const Circuit& c = *in_circs[i];
+            const int k = observables_split_route(h, c) ? 0 : (c.prefix_id >= 0 ? 2 : 1);
+            if (k == kind) order.push_back(i);
+        }
+    std::vector<Circuit*> circs(n_evals);
+    std::vector<int64_t> np(n_evals);
+    size_t total = 0, n_split = 0, n_plain = 0;
+    for (size_t j = 0; j < n_evals; ++j) {
+        circs[j] = in_circs[order[j]];
+        np[j] = param_offsets[order[j] + 1] - param_offsets[order[j]];
+        total += size_t(np[j]);
+        if (observables_split_route(h, *circs[j])) ++n_split;
+        else if (circs[j]->prefix_id < 0) ++n_plain;
+    }
+    std::vector<double> packed(total + 1);
+    for (size_t j = 0, cur = 0; j < n_evals; cur += size_t(np[j]), ++j)
+        if (np[j]) std::memcpy(packed.data() + cur, params + param_offsets[order[j]], size_t(np[j]) * sizeof(double));
+    h->prof = qsv_profile{};
+    int rc = batch_layout(h, circs, np, h->factor_enabled && h->d_side.ptr != nullptr && h->n <= 32, 3);
+    if (rc) return rc;
+    const size_t T = set.n_terms, M = set.n_obs;
+    const size_t per_state = std::max<size_t>(1, T * size_t(set.nb)) * sizeof(double);
+    const size_t G = std::max<size_t>(1, std::min(size_t(h->group), kObsScratchBytes / per_state));
+    const size_t SG = std::max<size_t>(1, std::min(size_t(std::max(1, h->side_slots)), kObsScratchBytes / (std::max<size_t>(1, T) * 8)));
+    // launch groups: [0, n_split) by SG, then the ordinary ones and the kept-state ones by G; a group's slots start at 0
+    std::vector<std::pair<size_t, size_t>> groups;
+    for (size_t g0 = 0; g0 < n_split; g0 += SG) groups.emplace_back(g0, std::min(SG, n_split - g0));
+    for (size_t g0 = n_split; g0 < n_split + n_plain; g0 += G) groups.emplace_back(g0, std::min(G, n_split + n_plain - g0));
+    for (size_t g0 = n_split + n_plain; g0 < n_evals; g0 += G) groups.emplace_back(g0, std::min(G, n_evals - g0));
+    {
+        EvalDesc* hd = static_cast<EvalDesc*>(h->h_batch);
+        for (const auto& g : groups)
+            for (size_t j = g.first; j < g.first + g.second; ++j) {
+                hd[j].state_slot = uint32_t(j - g.first);
+                if (h->batch.split_any) hd[n_evals + j].state_slot = uint32_t(j - g.first);
+            }
+    }
+    if ((rc = ensure(h, h->d_obs_partials, G * per_state))) return rc;
+    if ((rc = ensure(h, h->d_obs_values, std::max(G, n_split ? std::min(SG, n_split) : size_t(1)) * std::max<size_t>(1, T) * 8))) return rc;
+    if ((rc = ensure(h, h->d_partials, std::max<size_t>(1, n_evals) * partials_per_state(h) * sizeof(double)))) return rc;
+    if ((rc = ensure_host_out(h, n_evals * M))) return rc;
+    double* values = static_cast<double*>(h->d_obs_values.ptr);
+    double* partials = static_cast<double*>(h->d_obs_partials.ptr);
+    const auto* offsets = static_cast<const int64_t*>(set.d_offsets.ptr);
+    const auto* term_of = static_cast<const uint32_t*>(set.d_term_of.ptr);
+    const auto* coef = static_cast<const double*>(set.d_coef.ptr);
+    rc = batch_ship(h, 0, n_evals, packed.data(), n_split);
+    for (const auto& g : groups) {
+        if (rc) break;
+        const size_t g0 = g.first, gc = g.second;
+        if (g0 < n_split) {
+            if ((rc = run_group(h, circs, g0, gc, kModeSynthFirst | kModeFinalStore | kModeSidesOnly))) break;
+            PassArgs a{};
+            a.plan = static_cast<const uint32_t*>(h->d_arena.ptr);
+            a.evals = batch_evals(h) + g0;
+            a.wtab = h->d_side.ptr;
+            a.wtab_stride = h->side_stride;
+            QSV_HIP(h, launch_split_term_values(h->dtype, unsigned(gc), static_cast<const FactorTerm*>(set.d_split_terms.ptr),
+                                                uint32_t(T), values, ws(h), a));
+        } else {
+            if ((rc = run_group(h, circs, g0, gc, kModeSynthFirst | kModeFinalStore))) break;
+            QSV_HIP(h, launch_pauli_terms(h->dtype, h->d_states.ptr, uint64_t(1) << h->n, h->n, int(gc), set.n_rows,
+                                          static_cast<const ObsRow*>(set.d_rows.ptr), static_cast<const ObsTerm*>(set.d_terms.ptr),
+                                          uint32_t(T), set.nb, partials, ws(h)));
+            QSV_HIP(h, launch_pauli_terms_reduce(partials, set.nb, uint32_t(T), static_cast<const ObsTerm*>(set.d_terms.ptr), int(gc),
+                                                 values, ws(h)));
+        }
+        QSV_HIP(h, launch_observables_combine(values, uint32_t(T), int(gc), uint32_t(M), offsets, term_of, coef, h->h_out + g0 * M, ws(h)));
+    }
+    h->batch.circs.clear();
+    if (rc) return rc;
+    QSV_HIP(h, hipStreamSynchronize(ws(h)));
+    for (size_t j = 0; j < n_evals; ++j) std::memcpy(out + order[j] * M, h->h_out + j * M, M * sizeof(double));
+    return QSV_OK;
+}
+
 
 }  // namespace
 
@@ -2140,8 +2267,10 @@ void qsv_destroy(qsv_t* h) {
     }
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     for (DeviceBuffer* b : {&h->d_z, &h->d_cre, &h->d_diag, &h->d_order, &h->d_sorted, &h->d_term_partials, &h->d_groups, &h->d_term_odd, &h->d_arena,
-                            &h->d_states, &h->d_wtab, &h->d_side, &h->d_factor, &h->d_factor_count, &h->d_factor_big, &h->d_factor_big_count, &h->d_quad, &h->d_fterms, &h->d_fpart, &h->d_batch, &h->d_mats, &h->d_partials, &h->d_out, &h->d_scratch, &h->d_prefix, &h->d_sdiag})
+                            &h->d_states, &h->d_wtab, &h->d_side, &h->d_factor, &h->d_factor_count, &h->d_factor_big, &h->d_factor_big_count, &h->d_quad, &h->d_fterms, &h->d_fpart, &h->d_batch, &h->d_mats, &h->d_partials, &h->d_out, &h->d_scratch, &h->d_prefix, &h->d_sdiag,
+                            &h->d_obs_partials, &h->d_obs_values})
         if (b->ptr) (void)hipFree(b->ptr);
+    for (auto& kv : h->obs_sets) free_observable_set(kv.second);
     if (h->h_batch) (void)hipHostFree(h->h_batch);
     if (h->d_ship) (void)hipFree(h->d_ship);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
@@ -3289,6 +3418,114 @@ int qsv_exact_cvar_batch(qsv_t* h, int n_evals, const int* circuit_ids, const in
     }
     static const double dummy = 0.0;
     return exact_cvar_locked(h, circs, param_offsets, params ? params : &dummy, alpha, out_cvar);
+}
+
+int qsv_observables_create(qsv_t* h, int n_observables, const int64_t* term_offsets, const uint64_t* x_mask, const uint64_t* z_mask,
+                           const double* coeff_re, const double* coeff_im, int* out_set_id) {
+    if (!h) return QSV_E_ARG;
+    (void)coeff_im;  // <P_k> is real for every Pauli string: real(<O_m>) only needs the real parts (as qsv_set_operator)
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (n_observables < 1 || uint32_t(n_observables) > kMaxObservables || !term_offsets || !out_set_id)
+        return fail(h, QSV_E_ARG, "an observable set needs 1 .. 65536 observables, their term offsets and an output");
+    const int64_t first = term_offsets[0], n_entries = term_offsets[n_observables] - first;
+    if (first < 0) return fail(h, QSV_E_ARG, "term offsets must not be negative");
+    for (int m = 0; m < n_observables; ++m)
+        if (term_offsets[m + 1] < term_offsets[m]) return fail(h, QSV_E_ARG, "term offsets must be non-decreasing");
+    if (n_entries > kMaxObsEntries) return fail(h, QSV_E_ARG, "an observable set holds at most 2^24 terms");
+    if (n_entries > 0 && (!x_mask || !z_mask || !coeff_re)) return fail(h, QSV_E_ARG, "term arrays are null");
+    const uint64_t limit = h->n >= 64 ? ~uint64_t(0) : (uint64_t(1) << h->n) - 1;
+    for (int64_t k = first; k < first + n_entries; ++k)
+        if ((x_mask[k] | z_mask[k]) & ~limit) return fail(h, QSV_E_ARG, "Pauli term acts on a qubit >= n_qubits");
+    // the distinct strings, ordered by (x, z): the diagonal group first, then the groups by x mask
+    std::vector<std::pair<uint64_t, uint64_t>> strings;
+    strings.reserve(size_t(n_entries));
+    for (int64_t k = first; k < first + n_entries; ++k) strings.emplace_back(x_mask[k], z_mask[k]);
+    std::sort(strings.begin(), strings.end());
+    strings.erase(std::unique(strings.begin(), strings.end()), strings.end());
+    if (strings.size() > kMaxObsStrings) return fail(h, QSV_E_ARG, "an observable set holds at most 65536 distinct Pauli strings");
+    const uint32_t T = uint32_t(strings.size());
+    std::vector<ObsTerm> terms(T);
+    std::vector<FactorTerm> split_terms(T);
+    std::vector<ObsRow> rows;
+    for (uint32_t k = 0; k < T; ++k) {
+        const uint64_t x = strings[k].first, z = strings[k].second;
+        const uint32_t pivot = x ? uint32_t(63 - __builtin_clzll(x)) : 0u;
+        const int ny = __builtin_popcountll(x & z);
+        const uint64_t low = (uint64_t(1) << pivot) - 1;
+        terms[k].zp = x ? ((z >> (pivot + 1)) << pivot) | (z & low) : z;
+        terms[k].odd = uint32_t(ny & 1);
+        terms[k].pad = 0;
+        terms[k].scale = x ? (((ny >> 1) & 1) ? -2.0 : 2.0) : 1.0;  // (-1)^{floor(ny/2)}, both halves of each pair
+        split_terms[k] = FactorTerm{uint32_t(x), uint32_t(z), 1.0};
+        if (rows.empty() || rows.back().x != x || rows.back().count == kObsChunk) rows.push_back(ObsRow{x, k, 0, pivot, 0});
+        rows.back().count += 1;
+        rows.back().parts |= (ny & 1) ? 2u : 1u;
+    }
+    std::vector<int64_t> offsets(size_t(n_observables) + 1);
+    std::vector<uint32_t> term_of(static_cast<size_t>(n_entries));
+    std::vector<double> coef(static_cast<size_t>(n_entries));
+    for (int m = 0; m <= n_observables; ++m) offsets[size_t(m)] = term_offsets[m] - first;
+    for (int64_t k = 0; k < n_entries; ++k) {
+        const auto at = std::lower_bound(strings.begin(), strings.end(), std::make_pair(x_mask[first + k], z_mask[first + k]));
+        term_of[size_t(k)] = uint32_t(at - strings.begin());
+        coef[size_t(k)] = coeff_re[first + k];
+    }
+    QSV_HIP(h, hipSetDevice(h->device));
+    ObservableSet s;
+    s.n_obs = uint32_t(n_observables);
+    s.n_terms = T;
+    s.n_rows = int(rows.size());
+    // workgroups (one wave each) per row and state: up to 2048 per state in all, each sweeping at least four blocks of the
+    // diagonal group -- a function of the set and the register only, so that the partial sums of a string are laid out, and
+    // added, the same way in every batch (measured shapes: DESIGN 4.6)
+    const uint64_t blocks = h->n > kObsBlockBits ? uint64_t(1) << (h->n - kObsBlockBits) : 1;
+    s.nb = int(std::max<uint64_t>(1, std::min<uint64_t>(blocks / 4, 2048 / std::max<uint64_t>(1, rows.size()))));
+    int rc;
+    if ((rc = upload_bytes(h, s.d_rows, rows.data(), rows.size() * sizeof(ObsRow))) ||
+        (rc = upload_bytes(h, s.d_terms, terms.data(), terms.size() * sizeof(ObsTerm))) ||
+        (rc = upload_bytes(h, s.d_split_terms, split_terms.data(), split_terms.size() * sizeof(FactorTerm))) ||
+        (rc = upload_bytes(h, s.d_offsets, offsets.data(), offsets.size() * sizeof(int64_t))) ||
+        (rc = upload_bytes(h, s.d_term_of, term_of.data(), term_of.size() * sizeof(uint32_t))) ||
+        (rc = upload_bytes(h, s.d_coef, coef.data(), coef.size() * sizeof(double)))) {
+        free_observable_set(s);
+        return rc;
+    }
+    const int id = h->next_obs_id++;
+    h->obs_sets.emplace(id, std::move(s));
+    *out_set_id = id;
+    return QSV_OK;
+}
+
+int qsv_observables_destroy(qsv_t* h, int set_id) {
+    if (!h) return QSV_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    auto it = h->obs_sets.find(set_id);
+    if (it == h->obs_sets.end()) return fail(h, QSV_E_ARG, "unknown observable set " + std::to_string(set_id));
+    QSV_HIP(h, hipSetDevice(h->device));
+    QSV_HIP(h, sync_streams(h));
+    free_observable_set(it->second);
+    h->obs_sets.erase(it);
+    return QSV_OK;
+}
+
+int qsv_eval_observables(qsv_t* h, int set_id, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
+                         double* out) {
+    if (!h) return QSV_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets || !out))) return fail(h, QSV_E_ARG, "bad arguments");
+    auto set = h->obs_sets.find(set_id);
+    if (set == h->obs_sets.end()) return fail(h, QSV_E_ARG, "unknown observable set " + std::to_string(set_id));
+    std::vector<Circuit*> circs(size_t(n_evals), nullptr);
+    for (int i = 0; i < n_evals; ++i) {
+        auto it = h->circuits.find(circuit_ids[i]);
+        if (it == h->circuits.end()) return fail(h, QSV_E_ARG, "unknown circuit id " + std::to_string(circuit_ids[i]));
+        circs[size_t(i)] = &it->second;
+        if (param_offsets[i + 1] < param_offsets[i]) return fail(h, QSV_E_ARG, "param_offsets must be non-decreasing");
+    }
+    if (n_evals == 0) return QSV_OK;
+    QSV_HIP(h, hipSetDevice(h->device));
+    static const double dummy = 0.0;
+    return eval_observables_locked(h, set->second, circs, param_offsets, params ? params : &dummy, out);
 }
 
 int qsv_sample(qsv_t* h, int circuit_id, const double* params, int n_params, int shots, uint64_t seed,

@@ -29,7 +29,7 @@ import os
 from dataclasses import dataclass, field
 from random import Random
 from statistics import mean, median
-from typing import Callable, Optional, Sequence
+from typing import Any, Callable, Optional, Sequence, Union
 
 import numpy as np
 
@@ -454,6 +454,8 @@ class EVQEResult:
     best_expectation_values: list[float] = field(default_factory=list)
     median_expectation_values: list[float] = field(default_factory=list)
     mean_expectation_values: list[float] = field(default_factory=list)
+    # the aux operators' values at the best individual, a list or dict as they were given (None: none were given)
+    aux_operators_evaluated: Optional[Union[list[float], dict[Any, float]]] = None
 
 
 # ---- the solver -----------------------------------------------------------------------------------------------
@@ -712,17 +714,29 @@ class EVQEMinimumEigensolver:
         return EVQEPopulation(tuple(selected), population.species_representatives, None, None)
 
     # -- main loop ------------------------------------------------------------------------------------------
-    def compute_minimum_eigenvalue(self, evaluator, search_evaluator=None) -> EVQEResult:
+    def compute_minimum_eigenvalue(self, evaluator, search_evaluator=None, aux_operators=None) -> EVQEResult:
         """``search_evaluator``: a second evaluator of the SAME operator for the parameter searches alone -- a single-precision
         handle: the points a search compares differ by far more than 1e-6 (the reference's own tests run their searches on an
         estimator with precision 0.05, test/minimum_eigensolvers/evqe/solver.py:20-27), a layer search on kept states is bound
         by the bytes of the state, and fp32 halves them (bench.py layer_search: 227 k against 160 k evaluations per second at
         seven layers, 170 k against 107 k at eight).  Every individual's FITNESS, what selection and the result see, comes from
-        ``evaluator``."""
+        ``evaluator``.
+
+        ``aux_operators``: a list or dict of PauliOperator, evaluated once after the run at the best individual by
+        ``evaluator.evaluate_observables`` (reference: evolving_ansatz_minimum_eigensolver.py:177-199, :461-476); the values go
+        to ``result.aux_operators_evaluated`` in the same shape.  They use no random stream of the solver and are not counted
+        in ``circuit_evaluations``.  (A sampling evaluator draws its samples with its own generator, after the run, as the
+        reference's aux sampler evaluators do.)  In a sharded run every rank evaluates them itself."""
         cfg = self.configuration
         searcher = evaluator if search_evaluator is None else search_evaluator
         if searcher.n_qubits != evaluator.n_qubits:
             raise ValueError("the search evaluator must be over the same register")
+        if aux_operators is not None:
+            if not callable(getattr(evaluator, "evaluate_observables", None)):
+                raise ValueError("aux_operators need an evaluator with evaluate_observables (an operator evaluator)")
+            for op in (aux_operators.values() if isinstance(aux_operators, dict) else aux_operators):
+                if op.num_qubits != evaluator.n_qubits:
+                    raise ValueError(f"an aux operator acts on {op.num_qubits} qubits, the evaluator on {evaluator.n_qubits}")
         if cfg.termination_criterion is not None:
             cfg.termination_criterion.reset_state()
         population = EVQEPopulation.random_population(
@@ -786,4 +800,16 @@ class EVQEMinimumEigensolver:
             population = self._layer_removal(population)
         if evaluations and evaluations[-1] == 0 and len(evaluations) > 1:
             evaluations.pop()
+        if aux_operators is not None:
+            result.aux_operators_evaluated = self._evaluate_aux_operators(evaluator, result.best_individual, aux_operators)
         return result
+
+    def _evaluate_aux_operators(self, evaluator, individual: EVQEIndividual, aux_operators):
+        """The aux operators' values at ``individual``, one call of ``evaluator.evaluate_observables``."""
+        names = list(aux_operators) if isinstance(aux_operators, dict) else None
+        operators = [aux_operators[k] for k in names] if names is not None else list(aux_operators)
+        if not operators:
+            return {} if names is not None else []
+        circuit = individual.get_parameterized_quantum_circuit(shared=self.share_circuits)
+        values = [float(v) for v in evaluator.evaluate_observables([circuit], [list(individual.parameter_values)], operators)[0]]
+        return dict(zip(names, values)) if names is not None else values

@@ -117,15 +117,18 @@ class GpuEstimator(_EstimatorBase):
         """dtype / device / seed, for ``configured_primitives.evaluator_for``."""
         return {"dtype": self._dtype, "device": self._device_index, "seed": self._seed}
 
+    def _device(self, n_qubits: int) -> StatevectorDevice:
+        dev = self._devices.get(n_qubits)
+        if dev is None:
+            dev = StatevectorDevice(n_qubits, dtype=self._dtype, device=self._device_index)
+            self._devices[n_qubits] = dev
+        return dev
+
     def _evaluator(self, operator: PauliOperator) -> OperatorCircuitEvaluator:
         key = _operator_key(operator)
         hit = self._evaluators.get(key)
         if hit is None:
-            dev = self._devices.get(operator.num_qubits)
-            if dev is None:
-                dev = StatevectorDevice(operator.num_qubits, dtype=self._dtype, device=self._device_index)
-                self._devices[operator.num_qubits] = dev
-            hit = OperatorCircuitEvaluator(operator, statevector_device=dev)
+            hit = OperatorCircuitEvaluator(operator, statevector_device=self._device(operator.num_qubits))
             self._evaluators[key] = hit
             while len(self._evaluators) > self._max_operators:
                 self._evaluators.popitem(last=False)
@@ -134,23 +137,107 @@ class GpuEstimator(_EstimatorBase):
         return hit
 
     def run(self, pubs: Iterable[Sequence[Any]], *, precision: Optional[float] = None) -> _Job:
+        """A pub is (circuit, observables[, parameter values[, precision]]): observables one observable or a (nested) list or
+        object array of them, parameter values one vector or an array of shape (..., n_params); ``evs`` has their broadcast
+        shape (:func:`pub_broadcast`).  A pub's own precision overrides ``precision``."""
         pubs = [tuple(pub) for pub in pubs]
-        out: list[Optional[float]] = [None] * len(pubs)
+        out: list[Any] = [None] * len(pubs)
         by_operator: dict[tuple, list[int]] = {}
-        operators = []
+        operators: dict[int, PauliOperator] = {}
         for i, pub in enumerate(pubs):
-            operators.append(self._convert.operator(pub[1]))
-            by_operator.setdefault(_operator_key(operators[-1]), []).append(i)
+            values = pub[2] if len(pub) > 2 else None
+            if _is_observable_array(pub[1]) or (values is not None and np.ndim(values) > 1):
+                out[i] = self._run_array_pub(pub[0], pub[1], values)
+                continue
+            operators[i] = self._convert.operator(pub[1])
+            by_operator.setdefault(_operator_key(operators[i]), []).append(i)
         for indices in by_operator.values():  # one batched call per distinct operator
             evaluator = self._evaluator(operators[indices[0]])
             circuits = [self._convert.circuit(pubs[i][0]) for i in indices]
             values = [list(np.ravel(pubs[i][2])) if len(pubs[i]) > 2 and pubs[i][2] is not None else [] for i in indices]
             for i, value in zip(indices, evaluator.evaluate_circuits(circuits, values)):
                 out[i] = value
-        if precision:
-            out = [v + float(self._rng.normal(0.0, precision)) for v in out]
-        return _Job([SimpleNamespace(data=SimpleNamespace(evs=np.asarray(v)), metadata={"target_precision": precision or 0.0})
-                     for v in out])
+        results = []
+        for pub, v in zip(pubs, out):
+            p = pub[3] if len(pub) > 3 and pub[3] is not None else precision
+            if p:
+                v = v + float(self._rng.normal(0.0, p)) if np.ndim(v) == 0 else v + self._rng.normal(0.0, p, size=np.shape(v))
+            results.append(SimpleNamespace(data=SimpleNamespace(evs=np.asarray(v)), metadata={"target_precision": p or 0.0}))
+        return _Job(results)
+
+    def _run_array_pub(self, circuit: Any, observables: Any, values: Any) -> np.ndarray:
+        """One pub with an array of observables and / or of parameter vectors: ONE observable_values call over its distinct
+        bindings and distinct observables, spread to the broadcast shape (:func:`pub_layout`)."""
+        circuit = self._convert.circuit(circuit)
+        layout = pub_layout(observables, values)
+        ops, keys, observable_of = [], {}, []
+        for o in layout.observables:
+            op = self._convert.operator(o)
+            key = _operator_key(op)
+            if key not in keys:
+                keys[key] = len(ops)
+                ops.append(op)
+            observable_of.append(keys[key])
+        dev = self._device(circuit.num_qubits)
+        table = dev.observable_values([circuit] * len(layout.rows), [list(r) for r in layout.rows], ops)
+        return table[layout.binding_index, np.asarray(observable_of, dtype=np.intp)[layout.observable_index]]
+
+
+def pub_layout(observables: Any, values: Any) -> SimpleNamespace:
+    """The shape logic of an EstimatorV2 pub (circuit, observables, parameter values), without a device:
+      shape             of ``evs`` (:func:`pub_broadcast`)
+      observables       the observables in C order of their array (one observable: an array of shape ())
+      rows              the distinct parameter vectors, one per row (no values, or vectors of no parameters: one empty row;
+                        an empty array of bindings: none)
+      binding_index     (shape ``shape``) the row of ``rows`` each entry of ``evs`` is evaluated with
+      observable_index  (shape ``shape``) the position in ``observables`` of each entry's observable"""
+    obs = _observable_array(observables)
+    vals = np.zeros(0) if values is None else np.asarray(values, dtype=np.float64)
+    if vals.ndim == 0:
+        vals = vals.reshape(1)
+    shape = pub_broadcast(obs.shape, vals.shape)
+    bindings = vals.shape[:-1]
+    rows = vals.reshape(int(np.prod(bindings, dtype=np.int64)), vals.shape[-1])
+    if rows.shape[0] and rows.shape[1]:
+        rows, inverse = np.unique(rows, axis=0, return_inverse=True)
+    elif rows.shape[0]:  # bindings of no parameters: all the same empty vector
+        rows, inverse = rows[:1], np.zeros(rows.shape[0], dtype=np.intp)
+    else:
+        inverse = np.zeros(0, dtype=np.intp)
+    b, o = np.broadcast_arrays(np.reshape(inverse, bindings), np.arange(obs.size, dtype=np.intp).reshape(obs.shape))
+    return SimpleNamespace(shape=shape, observables=list(obs.flat), rows=rows, binding_index=b, observable_index=o)
+
+
+def pub_broadcast(observables_shape: Sequence[int], values_shape: Sequence[int]) -> tuple:
+    """Shape of ``evs`` for an EstimatorV2 pub (as Qiskit defines it): the NumPy broadcast of the observables' shape and the
+    bindings' shape, i.e. the parameter values' shape without its last axis (the parameters of one binding)."""
+    bindings = tuple(values_shape)[:-1]
+    try:
+        return tuple(np.broadcast_shapes(tuple(observables_shape), bindings))
+    except ValueError as exc:
+        raise ValueError(f"observables of shape {tuple(observables_shape)} and parameter values of shape {tuple(values_shape)} "
+                         "do not broadcast") from exc
+
+
+def _is_observable_array(observables: Any) -> bool:
+    return isinstance(observables, (list, tuple, np.ndarray))
+
+
+def _observable_array(observables: Any) -> np.ndarray:
+    """A (nested) list / tuple / object array of observables as an object array of that shape (one observable: shape ())."""
+    if isinstance(observables, np.ndarray):
+        return observables.astype(object) if observables.dtype != object else observables
+    if not isinstance(observables, (list, tuple)):
+        leaf = np.empty((), dtype=object)
+        leaf[()] = observables
+        return leaf
+    items = [_observable_array(o) for o in observables]
+    if len({item.shape for item in items}) > 1:
+        raise ValueError("a nested list of observables must be rectangular")
+    out = np.empty((len(items),) + (items[0].shape if items else ()), dtype=object)
+    for k, item in enumerate(items):
+        out[k, ...] = item
+    return out
 
 
 class _BitArray:
