@@ -146,6 +146,18 @@ def _pack_slice(vectors: Sequence[Sequence[float]], first: int, last: int, total
     return out
 
 
+def _pack_batch(vectors: Sequence[Sequence[float]], need: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """(parameter offsets, packed values) of a batch whose evaluation i takes at least ``need[i]`` values."""
+    n = len(need)
+    counts = np.fromiter(map(len, vectors), dtype=np.int64, count=n)
+    if (counts < need).any():
+        i = int(np.argmax(counts < need))
+        raise ValueError(f"circuit {i} needs {int(need[i])} parameter values, got {int(counts[i])}")
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    return offsets, _pack_slice(vectors, 0, n, int(offsets[-1])) if offsets[-1] else np.zeros(1)
+
+
 def _pack_doubles(vectors: Sequence[Sequence[float]], total: int) -> np.ndarray:
     """Parameter vectors back to back as one float64 array.  ``array.fromlist`` is the fastest way CPython offers to
     turn lists of floats into doubles (about 15 ns per value, 40% less than ``np.fromiter`` over a chain)."""
@@ -411,14 +423,8 @@ class StatevectorDevice:
             raise ValueError("a kept state of a circuit that itself continues a kept state is not supported")
         self._register_many([c for c in circuits if self._serial not in c._registered])
         ids = np.fromiter((self.circuit_id(c) for c in circuits), dtype=np.int32, count=n)
-        need = [c.num_parameters for c in circuits]
-        counts = np.fromiter(map(len, parameter_values), dtype=np.int64, count=n)
-        for i in range(n):
-            if counts[i] < need[i]:
-                raise ValueError(f"circuit {i} needs {need[i]} parameter values, got {int(counts[i])}")
-        offsets = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum(counts, out=offsets[1:])
-        flat = _pack_slice(parameter_values, 0, n, int(offsets[-1])) if offsets[-1] else np.zeros(1)
+        # (not _batch_metadata: these circuits are run once, and its cache stays the optimiser's batch)
+        offsets, flat = _pack_batch(parameter_values, np.fromiter((c.num_parameters for c in circuits), dtype=np.int64, count=n))
         out = np.zeros(n, dtype=np.int32)
         with self._reg_lock:
             self._reap()
@@ -498,6 +504,12 @@ class StatevectorDevice:
         total = int(need.sum())  # parameter values the batch takes
         self._last_batch = ((CircuitIR.edits_of_registered, *map(id, circuits)), list(circuits), ids, need, total)
         return ids, need, total
+
+    def _batch_arguments(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]]) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(circuit ids, parameter offsets, packed values) of a non-empty batch, as the library's batch entry points take
+        them (the caller has checked that the two sequences have the same length)."""
+        ids, need, _ = self._batch_metadata(circuits)
+        return (ids, *_pack_batch(parameter_values, need))
 
     def results_seen(self) -> None:
         """The caller has seen every result of the last batch that ended without waiting (``qsv_eval_results_seen``): the next
@@ -727,14 +739,7 @@ class StatevectorDevice:
         values = np.empty((n, int(shots)), dtype=np.float64) if with_values else None
         if n == 0 or shots == 0:
             return states, values
-        ids, need, _ = self._batch_metadata(circuits)
-        counts = np.fromiter(map(len, parameter_values), dtype=np.int64, count=n)
-        if (counts < need).any():
-            i = int(np.argmax(counts < need))
-            raise ValueError(f"circuit {i} needs {int(need[i])} parameter values, got {int(counts[i])}")
-        offsets = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum(counts, out=offsets[1:])
-        flat = _pack_slice(parameter_values, 0, n, int(offsets[-1])) if offsets[-1] else np.zeros(1)
+        ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
         self._check(
             self._lib.qsv_sample_batch(
                 self._handle, n, _lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat), int(shots),
@@ -757,14 +762,7 @@ class StatevectorDevice:
             raise ValueError("circuits and parameter_values must have the same length")
         if n == 0:
             return []
-        ids, need, _ = self._batch_metadata(circuits)
-        counts = np.fromiter(map(len, parameter_values), dtype=np.int64, count=n)
-        if (counts < need).any():
-            i = int(np.argmax(counts < need))
-            raise ValueError(f"circuit {i} needs {int(need[i])} parameter values, got {int(counts[i])}")
-        offsets = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum(counts, out=offsets[1:])
-        flat = _pack_slice(parameter_values, 0, n, int(offsets[-1])) if offsets[-1] else np.zeros(1)
+        ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
         out = np.empty(n, dtype=np.float64)
         self._check(
             self._lib.qsv_sample_cvar_batch(
@@ -783,14 +781,7 @@ class StatevectorDevice:
             raise ValueError("circuits and parameter_values must have the same length")
         if n == 0:
             return []
-        ids, need, _ = self._batch_metadata(circuits)
-        counts = np.fromiter(map(len, parameter_values), dtype=np.int64, count=n)
-        if (counts < need).any():
-            i = int(np.argmax(counts < need))
-            raise ValueError(f"circuit {i} needs {int(need[i])} parameter values, got {int(counts[i])}")
-        offsets = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum(counts, out=offsets[1:])
-        flat = _pack_slice(parameter_values, 0, n, int(offsets[-1])) if offsets[-1] else np.zeros(1)
+        ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
         out = np.empty(n, dtype=np.float64)
         self._check(self._lib.qsv_exact_cvar_batch(self._handle, n, _lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat),
                                                    float(alpha), _lib.as_ptr(out)))
@@ -844,14 +835,7 @@ class StatevectorDevice:
         set_id = self._observable_set(operators)
         if n == 0:
             return np.zeros((0, len(operators)), dtype=np.float64)
-        ids, need, _ = self._batch_metadata(circuits)
-        counts = np.fromiter(map(len, parameter_values), dtype=np.int64, count=n)
-        if (counts < need).any():
-            i = int(np.argmax(counts < need))
-            raise ValueError(f"circuit {i} needs {int(need[i])} parameter values, got {int(counts[i])}")
-        offsets = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum(counts, out=offsets[1:])
-        flat = _pack_slice(parameter_values, 0, n, int(offsets[-1])) if offsets[-1] else np.zeros(1)
+        ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
         out = np.empty((n, len(operators)), dtype=np.float64)
         self._check(self._lib.qsv_eval_observables(self._handle, set_id, n, _lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat),
                                                     _lib.as_ptr(out)))

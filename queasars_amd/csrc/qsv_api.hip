@@ -967,13 +967,21 @@ size_t mat_doubles_of(const qsv_t* h, const Circuit& c, bool split, int side) {
                               c.split.outer[side], c.split.stats[side].n_passes);
 }
 
-// allow_split: the caller only wants <D> of the final states (fused diagonal expectation), so a circuit that has a
-// split form (split.hpp) may run as its two virtual circuits + the contraction kernel.
-// max_keys: split forms with more cut keys than the caller's kernels take (four and five keys: the factorised expectation
-// under a quadratic operator only) are not used; such a circuit runs its ordinary plan.
-int batch_layout(qsv_t* h, const std::vector<Circuit*>& circs, const std::vector<int64_t>& n_params, bool allow_split = false,
-                 int max_keys = 3) {
-    auto splits = [&](const Circuit* c) { return allow_split && c->split.ok && c->split.n_keys <= max_keys; };
+// Whether a circuit runs as the two virtual circuits of its split form (split.hpp) in a call of one kind (split_rule):
+// `allow` -- what the virtual circuits leave is all the caller needs of the final state --, and no more cut keys than the
+// caller's kernels take (four and five keys: the factorised expectation under a quadratic operator only).  Otherwise the
+// circuit runs its ordinary plan.  (A circuit on a kept state has no split form: its plan is unfolded.)
+struct SplitRule {
+    bool allow = false;
+    int max_keys = 3;
+    bool takes(const Circuit& c) const { return allow && c.split.ok && c.split.n_keys <= max_keys && c.prefix_id < 0; }
+    size_t count(const std::vector<Circuit*>& circs) const {
+        return size_t(std::count_if(circs.begin(), circs.end(), [&](const Circuit* c) { return takes(*c); }));
+    }
+};
+
+int batch_layout(qsv_t* h, const std::vector<Circuit*>& circs, const std::vector<int64_t>& n_params, SplitRule rule = {}) {
+    auto splits = [&](const Circuit* c) { return rule.takes(*c); };
     qsv_handle::Batch& b = h->batch;
     const size_t n_evals = circs.size();
     int rc;
@@ -1161,6 +1169,24 @@ bool factor_terms_path(const qsv_t* h) { return h->factor_enabled && !h->diagona
 
 // Split evaluations flagged kEvalFused are finished by the launch that runs their virtual circuits (quadratic operator).
 bool fused_route(const qsv_t* h) { return factor_path(h) && h->d_factor_count.ptr != nullptr && h->fused_factor; }
+
+// The kinds of call that may run circuits split, and what each needs of the final states: the expectation value under the
+// operator set now (eval_begin; qsv_circuit_cost also asks before an operator is set), samples or the exact CVaR (read from the
+// product of the two side tables, up to three keys), the values of an observable set's Pauli strings (the side tables, at most
+// 32 qubits).
+enum class SplitUse { Expectation, Sampling, Observables };
+
+SplitRule split_rule(const qsv_t* h, SplitUse use) {
+    switch (use) {
+    case SplitUse::Expectation:
+        return {h->n_terms == 0 || h->diagonal || factor_terms_path(h), (h->n_terms == 0 || factor_path(h)) ? kMaxSplitKeys : 3};
+    case SplitUse::Sampling:
+        return {h->split_sampling, 3};
+    case SplitUse::Observables:
+        break;
+    }
+    return {h->factor_enabled && h->d_side.ptr != nullptr && h->n <= 32, 3};
+}
 
 // Workgroups of a one-launch evaluation that do not leave at once: one per side, two for a half side (kernels.hpp kEvalHalves).
 size_t working_workgroups(const SplitInfo& sp) {
@@ -1548,7 +1574,7 @@ int eval_begin(qsv_t* h, const std::vector<Circuit*>& circs, const std::vector<i
         QSV_HIP(h, hipEventCreate(&h->batch.ev1));
         QSV_HIP(h, hipEventRecord(h->batch.ev0, h->stream));
     }
-    if ((rc = batch_layout(h, circs, n_params, h->diagonal || factor_terms_path(h), factor_path(h) ? kMaxSplitKeys : 3))) return rc;
+    if ((rc = batch_layout(h, circs, n_params, split_rule(h, SplitUse::Expectation)))) return rc;
     if (factor_terms_path(h) && h->batch.split_any &&
         (rc = ensure(h, h->d_fpart, std::max<size_t>(1, n_evals) * kFactorTermWaves * sizeof(double))))
         return rc;
@@ -1956,42 +1982,111 @@ void eval_close(qsv_t* h) {
     h->work = nullptr;
 }
 
-// One-shot evaluation: begin + one push + end.
-int eval_all(qsv_t* h, const std::vector<Circuit*>& circs, const int64_t* param_offsets, const double* params,
-             double* out) {
-    if (circs.empty()) return QSV_OK;
-    std::vector<int64_t> np(circs.size());
-    for (size_t i = 0; i < circs.size(); ++i) np[i] = param_offsets[i + 1] - param_offsets[i];
-    int rc = eval_begin(h, circs, np);
-    // the caller's vectors may have gaps between them: pack what each evaluation declared
-    std::vector<double> packed;
-    if (!rc) {
-        size_t total = 0;
-        for (int64_t v : np) total += size_t(v);
-        packed.resize(total + 1);
-        size_t cur = 0;
-        for (size_t i = 0; i < circs.size(); ++i) {
-            if (np[i]) std::memcpy(packed.data() + cur, params + param_offsets[i], size_t(np[i]) * sizeof(double));
-            cur += size_t(np[i]);
-        }
-        rc = eval_push(h, 0, circs.size(), packed.data());
+// where a batch without parameter values reads them from
+const double kNoValues[1] = {0.0};
+
+// A batch as the entry points take it: its circuits, each evaluation's parameter count, and the values packed back to back
+// (the caller's vectors may have gaps between them).
+struct BatchArgs {
+    std::vector<Circuit*> circs;
+    std::vector<int64_t> n_params;
+    std::vector<double> values;
+};
+
+// Looks up circuit_ids[0, n) and packs what each evaluation's param_offsets declare (params == nullptr: an empty array;
+// param_offsets == nullptr: the ids only, for a call that runs nothing).  kept_refusal: circuits on kept states are refused
+// with this message.
+int resolve_batch(qsv_t* h, size_t n, const int* circuit_ids, const int64_t* param_offsets, const double* params, BatchArgs& out,
+                  const char* kept_refusal = nullptr) {
+    out.circs.assign(n, nullptr);
+    out.n_params.assign(n, 0);
+    size_t total = 0;
+    for (size_t i = 0; i < n; ++i) {
+        auto it = h->circuits.find(circuit_ids[i]);
+        if (it == h->circuits.end()) return fail(h, QSV_E_ARG, "unknown circuit id " + std::to_string(circuit_ids[i]));
+        if (kept_refusal && it->second.prefix_id >= 0) return fail(h, QSV_E_UNSUPPORTED, kept_refusal);
+        out.circs[i] = &it->second;
+        if (!param_offsets) continue;
+        out.n_params[i] = param_offsets[i + 1] - param_offsets[i];
+        if (out.n_params[i] < 0) return fail(h, QSV_E_ARG, "param_offsets must be non-decreasing");
+        total += size_t(out.n_params[i]);
     }
+    out.values.assign(total + 1, 0.0);
+    for (size_t i = 0, cur = 0; params && i < n; cur += size_t(out.n_params[i]), ++i)
+        if (out.n_params[i]) std::memcpy(out.values.data() + cur, params + param_offsets[i], size_t(out.n_params[i]) * sizeof(double));
+    return QSV_OK;
+}
+
+// One-shot evaluation: begin + one push + end.
+int eval_all(qsv_t* h, const BatchArgs& args, double* out) {
+    if (args.circs.empty()) return QSV_OK;
+    int rc = eval_begin(h, args.circs, args.n_params);
+    if (!rc) rc = eval_push(h, 0, args.circs.size(), args.values.data());
     if (!rc) rc = eval_end(h, out);
     eval_close(h);
     return rc;
 }
 
-// Prepare the final state of one circuit in slot 0 (used by statevector / probabilities / sample).
-int run_single_to_state(qsv_t* h, int circuit_id, const double* params, int n_params) {
-    auto it = h->circuits.find(circuit_id);
-    if (it == h->circuits.end()) return fail(h, QSV_E_ARG, "unknown circuit id");
-    std::vector<Circuit*> cc{&it->second};
+// How run_to_states runs a batch: which circuits run split, the launch groups of split evaluations (side-table slots) and
+// of the others (state slots), whether the pass kernel prepares every evaluation itself (one-tile registers) or the split
+// ones only, and the run_group mode of each kind.
+struct StateRun {
+    SplitRule rule;
+    size_t split_group, state_group;
+    bool prepare_in_pass;
+    uint32_t split_mode, state_mode;
+};
+
+// Runs a batch into state slots, for the entry points that need more of the final states than the expectation value: split
+// evaluations first (order_split_first), in launch groups of their own, then the ordinary ones, then -- in groups of their
+// own, which run_group requires -- those on kept states.  An evaluation's slot is its position in its launch group.  After
+// each group, on_split / on_state(first, count) launches the caller's consumer of positions [first, first + count);
+// batch.eval_at maps positions back to evaluations, also after the return.
+using GroupFn = std::function<int(size_t, size_t)>;
+int run_to_states(qsv_t* h, const BatchArgs& args, const StateRun& run, const GroupFn& on_split, const GroupFn& on_state) {
+    struct Release {
+        qsv_t* h;
+        ~Release() { h->batch.circs.clear(); }
+    } release{h};
+    const size_t n = args.circs.size();
     h->prof = qsv_profile{};
-    int rc = batch_layout(h, cc, std::vector<int64_t>{int64_t(n_params)});
-    if (!rc) rc = batch_ship(h, 0, 1, params);
-    if (!rc) rc = ensure(h, h->d_partials, size_t(partials_per_state(h)) * sizeof(double));
-    if (!rc) rc = run_group(h, cc, 0, 1, kModeSynthFirst | kModeFinalStore);
-    h->batch.circs.clear();
+    int rc = batch_layout(h, args.circs, args.n_params, run.rule);
+    if (rc) return rc;
+    size_t n_cont = 0;
+    const size_t n_split = order_split_first(h, 0, n, &n_cont);
+    std::vector<std::pair<size_t, size_t>> groups;
+    auto cut = [&](size_t lo, size_t hi, size_t size) {
+        for (size_t g0 = lo; g0 < hi; g0 += size) groups.emplace_back(g0, std::min(size, hi - g0));
+    };
+    cut(0, n_split, run.split_group);
+    cut(n_split, n - n_cont, run.state_group);
+    cut(n - n_cont, n, run.state_group);
+    EvalDesc* hd = static_cast<EvalDesc*>(h->h_batch);
+    for (const auto& g : groups)
+        for (size_t j = g.first; j < g.first + g.second; ++j) {
+            hd[j].state_slot = uint32_t(j - g.first);
+            if (h->batch.split_any) hd[n + j].state_slot = uint32_t(j - g.first);
+        }
+    if ((rc = ensure(h, h->d_partials, std::max<size_t>(1, n) * partials_per_state(h) * sizeof(double)))) return rc;
+    if ((rc = batch_ship(h, 0, n, args.values.data(), run.prepare_in_pass ? n : n_split))) return rc;
+    for (const auto& g : groups) {
+        const bool split = g.first < n_split;
+        if ((rc = run_group(h, args.circs, g.first, g.second, split ? run.split_mode : run.state_mode))) return rc;
+        const GroupFn& consume = split ? on_split : on_state;
+        if (consume && (rc = consume(g.first, g.second))) return rc;
+    }
+    return QSV_OK;
+}
+
+// The final state of one circuit in slot 0 (statevector / probabilities).
+int run_single_to_state(qsv_t* h, int circuit_id, const double* params, int n_params) {
+    const int64_t offsets[2] = {0, std::max(0, n_params)};
+    BatchArgs args;
+    int rc = resolve_batch(h, 1, &circuit_id, offsets, params, args);
+    if (!rc && n_params < 0)  // (a count, not offsets: refused as batch_layout refuses too few values)
+        rc = fail(h, QSV_E_ARG, "circuit needs " + std::to_string(args.circs[0]->n_params) + " parameter values, got " +
+                                    std::to_string(n_params));
+    if (!rc) rc = run_to_states(h, args, StateRun{SplitRule{}, 1, 1, false, 0, kModeSynthFirst | kModeFinalStore}, {}, {});
     return rc;
 }
 
@@ -2015,95 +2110,51 @@ int upload_bytes(qsv_t* h, DeviceBuffer& b, const void* src, size_t bytes) {
     return QSV_OK;
 }
 
-// A split evaluation takes the split route when its circuit has a split form of at most three keys and the handle has side tables
-// (factor_terms_path without the operator); everything else takes the state route.  Depends on the circuit and the handle only.
-bool observables_split_route(const qsv_t* h, const Circuit& c) {
-    return h->factor_enabled && h->d_side.ptr != nullptr && h->n <= 32 && c.split.ok && c.split.n_keys <= 3 && c.prefix_id < 0;
-}
-
-// qsv_eval_observables with the lock held and the arguments checked.  The evaluations run reordered -- split route first, then
-// the ordinary state route, then circuits on kept states (a launch group holds one kind) --, each launch group's values land in
-// the pinned result buffer at its positions, and the host puts the rows back in the caller's order.
-int eval_observables_locked(qsv_t* h, const ObservableSet& set, const std::vector<Circuit*>& in_circs, const int64_t* param_offsets,
-                            const double* params, double* out) {
-    const size_t n_evals = in_circs.size();
-    std::vector<size_t> order;
-    order.reserve(n_evals);
-    for (int kind = 0; kind < 3; ++kind)
-        for (size_t i = 0; i < n_evals; ++i) {
-            const Circuit& c = *in_circs[i];
-            const int k = observables_split_route(h, c) ? 0 : (c.prefix_id >= 0 ? 2 : 1);
-            if (k == kind) order.push_back(i);
-        }
-    std::vector<Circuit*> circs(n_evals);
-    std::vector<int64_t> np(n_evals);
-    size_t total = 0, n_split = 0, n_plain = 0;
-    for (size_t j = 0; j < n_evals; ++j) {
-        circs[j] = in_circs[order[j]];
-        np[j] = param_offsets[order[j] + 1] - param_offsets[order[j]];
-        total += size_t(np[j]);
-        if (observables_split_route(h, *circs[j])) ++n_split;
-        else if (circs[j]->prefix_id < 0) ++n_plain;
-    }
-    std::vector<double> packed(total + 1);
-    for (size_t j = 0, cur = 0; j < n_evals; cur += size_t(np[j]), ++j)
-        if (np[j]) std::memcpy(packed.data() + cur, params + param_offsets[order[j]], size_t(np[j]) * sizeof(double));
-    h->prof = qsv_profile{};
-    int rc = batch_layout(h, circs, np, h->factor_enabled && h->d_side.ptr != nullptr && h->n <= 32, 3);
-    if (rc) return rc;
+// qsv_eval_observables with the lock held and the arguments checked.  An evaluation takes the split route when split_rule
+// lets its circuit run split (the side tables); everything else takes the state route.  Each launch group's values land in the
+// pinned result buffer at its positions, and the host puts the rows back in the caller's order.
+int eval_observables_locked(qsv_t* h, const ObservableSet& set, const BatchArgs& args, double* out) {
+    const size_t n_evals = args.circs.size();
+    const SplitRule rule = split_rule(h, SplitUse::Observables);
+    const size_t n_split = rule.count(args.circs);
     const size_t T = set.n_terms, M = set.n_obs;
     const size_t per_state = std::max<size_t>(1, T * size_t(set.nb)) * sizeof(double);
     const size_t G = std::max<size_t>(1, std::min(size_t(h->group), kObsScratchBytes / per_state));
     const size_t SG = std::max<size_t>(1, std::min(size_t(std::max(1, h->side_slots)), kObsScratchBytes / (std::max<size_t>(1, T) * 8)));
-    // launch groups: [0, n_split) by SG, then the ordinary ones and the kept-state ones by G; a group's slots start at 0
-    std::vector<std::pair<size_t, size_t>> groups;
-    for (size_t g0 = 0; g0 < n_split; g0 += SG) groups.emplace_back(g0, std::min(SG, n_split - g0));
-    for (size_t g0 = n_split; g0 < n_split + n_plain; g0 += G) groups.emplace_back(g0, std::min(G, n_split + n_plain - g0));
-    for (size_t g0 = n_split + n_plain; g0 < n_evals; g0 += G) groups.emplace_back(g0, std::min(G, n_evals - g0));
-    {
-        EvalDesc* hd = static_cast<EvalDesc*>(h->h_batch);
-        for (const auto& g : groups)
-            for (size_t j = g.first; j < g.first + g.second; ++j) {
-                hd[j].state_slot = uint32_t(j - g.first);
-                if (h->batch.split_any) hd[n_evals + j].state_slot = uint32_t(j - g.first);
-            }
-    }
+    int rc;
     if ((rc = ensure(h, h->d_obs_partials, G * per_state))) return rc;
     if ((rc = ensure(h, h->d_obs_values, std::max(G, n_split ? std::min(SG, n_split) : size_t(1)) * std::max<size_t>(1, T) * 8))) return rc;
-    if ((rc = ensure(h, h->d_partials, std::max<size_t>(1, n_evals) * partials_per_state(h) * sizeof(double)))) return rc;
     if ((rc = ensure_host_out(h, n_evals * M))) return rc;
     double* values = static_cast<double*>(h->d_obs_values.ptr);
     double* partials = static_cast<double*>(h->d_obs_partials.ptr);
-    const auto* offsets = static_cast<const int64_t*>(set.d_offsets.ptr);
-    const auto* term_of = static_cast<const uint32_t*>(set.d_term_of.ptr);
-    const auto* coef = static_cast<const double*>(set.d_coef.ptr);
-    rc = batch_ship(h, 0, n_evals, packed.data(), n_split);
-    for (const auto& g : groups) {
-        if (rc) break;
-        const size_t g0 = g.first, gc = g.second;
-        if (g0 < n_split) {
-            if ((rc = run_group(h, circs, g0, gc, kModeSynthFirst | kModeFinalStore | kModeSidesOnly))) break;
-            PassArgs a{};
-            a.plan = static_cast<const uint32_t*>(h->d_arena.ptr);
-            a.evals = batch_evals(h) + g0;
-            a.wtab = h->d_side.ptr;
-            a.wtab_stride = h->side_stride;
-            QSV_HIP(h, launch_split_term_values(h->dtype, unsigned(gc), static_cast<const FactorTerm*>(set.d_split_terms.ptr),
-                                                uint32_t(T), values, ws(h), a));
-        } else {
-            if ((rc = run_group(h, circs, g0, gc, kModeSynthFirst | kModeFinalStore))) break;
-            QSV_HIP(h, launch_pauli_terms(h->dtype, h->d_states.ptr, uint64_t(1) << h->n, h->n, int(gc), set.n_rows,
-                                          static_cast<const ObsRow*>(set.d_rows.ptr), static_cast<const ObsTerm*>(set.d_terms.ptr),
-                                          uint32_t(T), set.nb, partials, ws(h)));
-            QSV_HIP(h, launch_pauli_terms_reduce(partials, set.nb, uint32_t(T), static_cast<const ObsTerm*>(set.d_terms.ptr), int(gc),
-                                                 values, ws(h)));
-        }
-        QSV_HIP(h, launch_observables_combine(values, uint32_t(T), int(gc), uint32_t(M), offsets, term_of, coef, h->h_out + g0 * M, ws(h)));
-    }
-    h->batch.circs.clear();
-    if (rc) return rc;
-    QSV_HIP(h, hipStreamSynchronize(ws(h)));
-    for (size_t j = 0; j < n_evals; ++j) std::memcpy(out + order[j] * M, h->h_out + j * M, M * sizeof(double));
+    auto combine = [&](size_t g0, size_t gc) -> int {
+        QSV_HIP(h, launch_observables_combine(values, uint32_t(T), int(gc), uint32_t(M), static_cast<const int64_t*>(set.d_offsets.ptr),
+                                              static_cast<const uint32_t*>(set.d_term_of.ptr), static_cast<const double*>(set.d_coef.ptr),
+                                              h->h_out + g0 * M, h->stream));
+        return QSV_OK;
+    };
+    auto on_split = [&](size_t g0, size_t gc) -> int {
+        PassArgs a{};
+        a.plan = static_cast<const uint32_t*>(h->d_arena.ptr);
+        a.evals = batch_evals(h) + g0;
+        a.wtab = h->d_side.ptr;
+        a.wtab_stride = h->side_stride;
+        QSV_HIP(h, launch_split_term_values(h->dtype, unsigned(gc), static_cast<const FactorTerm*>(set.d_split_terms.ptr),
+                                            uint32_t(T), values, h->stream, a));
+        return combine(g0, gc);
+    };
+    auto on_state = [&](size_t g0, size_t gc) -> int {
+        QSV_HIP(h, launch_pauli_terms(h->dtype, h->d_states.ptr, uint64_t(1) << h->n, h->n, int(gc), set.n_rows,
+                                      static_cast<const ObsRow*>(set.d_rows.ptr), static_cast<const ObsTerm*>(set.d_terms.ptr),
+                                      uint32_t(T), set.nb, partials, h->stream));
+        QSV_HIP(h, launch_pauli_terms_reduce(partials, set.nb, uint32_t(T), static_cast<const ObsTerm*>(set.d_terms.ptr), int(gc),
+                                             values, h->stream));
+        return combine(g0, gc);
+    };
+    const StateRun run{rule, SG, G, false, kModeSynthFirst | kModeFinalStore | kModeSidesOnly, kModeSynthFirst | kModeFinalStore};
+    if ((rc = run_to_states(h, args, run, on_split, on_state))) return rc;
+    QSV_HIP(h, hipStreamSynchronize(h->stream));
+    for (size_t j = 0; j < n_evals; ++j) std::memcpy(out + size_t(h->batch.eval_at[j]) * M, h->h_out + j * M, M * sizeof(double));
     return QSV_OK;
 }
 
@@ -2484,21 +2535,9 @@ int qsv_prefix_create(qsv_t* h, int n_states, const int* circuit_ids, const int6
     if (n_states == 0) return QSV_OK;
     QSV_HIP(h, hipSetDevice(h->device));
     const size_t n = size_t(n_states);
-    std::vector<Circuit*> circs(n, nullptr);
-    std::vector<int64_t> np(n);
-    size_t total = 0;
-    for (size_t i = 0; i < n; ++i) {
-        auto it = h->circuits.find(circuit_ids[i]);
-        if (it == h->circuits.end()) return fail(h, QSV_E_ARG, "unknown circuit id " + std::to_string(circuit_ids[i]));
-        if (it->second.prefix_id >= 0) return fail(h, QSV_E_UNSUPPORTED, "a kept state of a circuit that itself continues a kept state");
-        circs[i] = &it->second;
-        np[i] = param_offsets[i + 1] - param_offsets[i];
-        if (np[i] < 0) return fail(h, QSV_E_ARG, "param_offsets must be non-decreasing");
-        total += size_t(np[i]);
-    }
-    std::vector<double> packed(total + 1, 0.0);
-    for (size_t i = 0, cur = 0; i < n; cur += size_t(np[i]), ++i)
-        if (np[i]) std::memcpy(packed.data() + cur, params + param_offsets[i], size_t(np[i]) * sizeof(double));
+    BatchArgs args;
+    int rc = resolve_batch(h, n, circuit_ids, param_offsets, params, args, "a kept state of a circuit that itself continues a kept state");
+    if (rc) return rc;
     // room for n more states
     const size_t state_bytes = (size_t(1) << h->n) * h->amp_bytes;
     const size_t fresh_needed = n > h->prefix_free.size() ? n - h->prefix_free.size() : 0;
@@ -2530,47 +2569,36 @@ int qsv_prefix_create(qsv_t* h, int n_states, const int* circuit_ids, const int6
         h->d_prefix.bytes = cap * state_bytes;
         h->prefix_slots = cap;
     }
+    // (kept slots are taken once the batch is laid out and run: a batch refused before that leaves them as they were)
+    std::vector<uint32_t> slots;
+    auto give_back = [&]() {
+        if (slots.empty()) return;
+        for (uint32_t sl : slots) h->prefix_free.push_back(sl);
+        (void)sync_streams(h);  // (copies into them may still be queued)
+    };
     // the circuits run their ordinary plans (a state is wanted, not an expectation value), a launch group at a time, on the
     // handle's stream; each final state is copied from its slot of the group to its kept slot
-    h->prof = qsv_profile{};
-    int rc = batch_layout(h, circs, np);
-    if (rc) return rc;
-    const size_t G = size_t(h->group);
-    {
-        EvalDesc* hd = static_cast<EvalDesc*>(h->h_batch);
-        for (size_t j = 0; j < n; ++j) hd[j].state_slot = uint32_t(j % G);
-    }
-    if (!rc) rc = ensure(h, h->d_partials, std::max<size_t>(1, n) * partials_per_state(h) * sizeof(double));
-    if (!rc) rc = batch_ship(h, 0, n, packed.data());
-    std::vector<uint32_t> slots(n);
-    for (size_t i = 0; i < n; ++i) {
-        if (!h->prefix_free.empty()) {
-            slots[i] = h->prefix_free.back();
-            h->prefix_free.pop_back();
-        } else {
-            slots[i] = uint32_t(h->prefix_used++);
+    auto keep = [&](size_t g0, size_t gc) -> int {
+        for (size_t i = slots.size(); i < n; ++i) {
+            if (!h->prefix_free.empty()) {
+                slots.push_back(h->prefix_free.back());
+                h->prefix_free.pop_back();
+            } else {
+                slots.push_back(uint32_t(h->prefix_used++));
+            }
         }
-    }
-    auto give_back = [&]() {
-        for (uint32_t sl : slots) h->prefix_free.push_back(sl);
-        h->batch.circs.clear();
-        (void)sync_streams(h);
-    };
-    for (size_t g0 = 0; !rc && g0 < n; g0 += G) {
-        const size_t gc = std::min(G, n - g0);
-        rc = run_group(h, circs, g0, gc, kModeSynthFirst | kModeFinalStore);
-        for (size_t i = g0; !rc && i < g0 + gc; ++i) {
-            hipError_t e = hipMemcpyAsync(static_cast<char*>(h->d_prefix.ptr) + size_t(slots[i]) * state_bytes,
-                                          static_cast<const char*>(h->d_states.ptr) + (i % G) * state_bytes, state_bytes,
+        for (size_t j = g0; j < g0 + gc; ++j) {
+            hipError_t e = hipMemcpyAsync(static_cast<char*>(h->d_prefix.ptr) + size_t(slots[h->batch.eval_at[j]]) * state_bytes,
+                                          static_cast<const char*>(h->d_states.ptr) + (j - g0) * state_bytes, state_bytes,
                                           hipMemcpyDeviceToDevice, h->stream);
-            if (e != hipSuccess) rc = fail(h, QSV_E_DEVICE, std::string("hipMemcpyAsync(kept state): ") + hipGetErrorString(e));
+            if (e != hipSuccess) return fail(h, QSV_E_DEVICE, std::string("hipMemcpyAsync(kept state): ") + hipGetErrorString(e));
         }
-    }
-    if (rc) {
+        return QSV_OK;
+    };
+    if ((rc = run_to_states(h, args, StateRun{SplitRule{}, 1, size_t(h->group), false, 0, kModeSynthFirst | kModeFinalStore}, {}, keep))) {
         give_back();
         return rc;
     }
-    h->batch.circs.clear();
     // (the staging buffers this batch's preparation read are free again, and whatever stream continues a kept state finds it)
     hipError_t e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) {
@@ -2654,11 +2682,9 @@ int qsv_circuit_cost(qsv_t* h, int circuit_id, qsv_circuit_cost_t* out) {
     if (it == h->circuits.end()) return fail(h, QSV_E_ARG, "unknown circuit id");
     Circuit& c = it->second;
     *out = qsv_circuit_cost_t{};
-    // which way an expectation value of this circuit goes under the operator set now (eval_begin's rules)
-    const bool allow_split = h->n_terms == 0 || h->diagonal || factor_terms_path(h);
-    const int max_keys = (h->n_terms == 0 || factor_path(h)) ? kMaxSplitKeys : 3;
+    // which way an expectation value of this circuit goes under the operator set now
     const double scale = std::ldexp(1.0, h->n - 20) * (h->dtype == QSV_F64 ? 1.0 : 0.5);
-    if (c.split.ok && allow_split && c.split.n_keys <= max_keys) {
+    if (split_rule(h, SplitUse::Expectation).takes(c)) {
         const SplitInfo& sp = c.split;
         const bool one_launch = sp.fused && h->fused_factor && (h->n_terms == 0 || factor_path(h));
         out->route = one_launch ? QSV_ROUTE_SPLIT_ONE_LAUNCH : QSV_ROUTE_SPLIT;
@@ -2698,13 +2724,6 @@ int qsv_circuit_cost(qsv_t* h, int circuit_id, qsv_circuit_cost_t* out) {
     return QSV_OK;
 }
 
-// The sampling entry points (and the exact CVaR) take a circuit's split form up to this many keys: the split sampler and the
-// exact CVaR read the product of the two side tables, which they do up to three keys (batch_layout's max_keys).
-constexpr int kSampledSplitMaxKeys = 3;
-bool sampled_from_sides(const qsv_t* h, const Circuit& c) {
-    return h->split_sampling && c.split.ok && c.split.n_keys <= kSampledSplitMaxKeys;
-}
-
 int qsv_circuit_form(qsv_t* h, int circuit_id, qsv_circuit_form_t* out) {
     if (!h) return QSV_E_ARG;
     if (!out) return fail(h, QSV_E_ARG, "out is null");
@@ -2730,7 +2749,7 @@ int qsv_circuit_form(qsv_t* h, int circuit_id, qsv_circuit_form_t* out) {
     out->amps_per_thread = 1 << sp.side_r;
     out->halves = sp.fused && sp.halves ? 1 : 0;
     out->one_launch = sp.fused ? 1 : 0;
-    out->split_sampled = sampled_from_sides(h, c) && c.prefix_id < 0 ? 1 : 0;  // (kept states are not sampled)
+    out->split_sampled = split_rule(h, SplitUse::Sampling).takes(c) ? 1 : 0;
     out->mask_x = blk[kSplitMaskX];
     out->mask_y = blk[kSplitMaskY];
     return QSV_OK;
@@ -2743,15 +2762,9 @@ int qsv_eval_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int64
     if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets || !out)))
         return fail(h, QSV_E_ARG, "bad arguments");
     QSV_HIP(h, hipSetDevice(h->device));
-    std::vector<Circuit*> circs(size_t(n_evals), nullptr);
-    for (int i = 0; i < n_evals; ++i) {
-        auto it = h->circuits.find(circuit_ids[i]);
-        if (it == h->circuits.end()) return fail(h, QSV_E_ARG, "unknown circuit id " + std::to_string(circuit_ids[i]));
-        circs[size_t(i)] = &it->second;
-        if (param_offsets[i + 1] < param_offsets[i]) return fail(h, QSV_E_ARG, "param_offsets must be non-decreasing");
-    }
-    static const double dummy = 0.0;
-    return eval_all(h, circs, param_offsets, params ? params : &dummy, out);
+    BatchArgs args;
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args);
+    return rc ? rc : eval_all(h, args, out);
 }
 
 // Collect the requests of concurrent callers for a moment, evaluate them as ONE batch, hand every caller its value.
@@ -2785,9 +2798,7 @@ static void coalesce_lead(qsv_t* h, std::unique_lock<std::mutex>& lock, double w
     lock.unlock();
     {
         std::lock_guard<std::mutex> hl(h->mu);
-        std::vector<Circuit*> circs;
-        std::vector<int64_t> offsets{0};
-        std::vector<double> params;
+        BatchArgs args;  // (each request is checked on its own: a bad one fails alone)
         std::vector<qsv_handle::CoalesceRequest*> valid;
         for (auto* r : batch) {
             auto it = h->circuits.find(r->circuit_id);
@@ -2797,16 +2808,16 @@ static void coalesce_lead(qsv_t* h, std::unique_lock<std::mutex>& lock, double w
                                                  : "circuit needs " + std::to_string(it->second.n_params) + " parameter values";
                 continue;
             }
-            circs.push_back(&it->second);
-            params.insert(params.end(), r->params, r->params + r->n_params);
-            offsets.push_back(int64_t(params.size()));
+            args.circs.push_back(&it->second);
+            args.n_params.push_back(r->n_params);
+            args.values.insert(args.values.end(), r->params, r->params + r->n_params);
             valid.push_back(r);
         }
         if (!valid.empty()) {
             std::vector<double> values(valid.size(), 0.0);
-            params.push_back(0.0);
+            args.values.push_back(0.0);
             int rc = hipSetDevice(h->device) == hipSuccess ? QSV_OK : QSV_E_DEVICE;
-            if (!rc) rc = eval_all(h, circs, offsets.data(), params.data(), values.data());
+            if (!rc) rc = eval_all(h, args, values.data());
             const std::string err = rc ? g_handle_error : std::string();
             for (size_t i = 0; i < valid.size(); ++i) {
                 valid[i]->rc = rc;
@@ -2893,16 +2904,13 @@ int qsv_eval_begin(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t*
             return QSV_OK;
         }
     }
-    std::vector<Circuit*> circs(size_t(n_evals), nullptr);
-    std::vector<int64_t> np(size_t(n_evals), 0);
-    for (int i = 0; i < n_evals; ++i) {
-        auto it = h->circuits.find(circuit_ids[i]);
-        if (it == h->circuits.end()) return fail(h, QSV_E_ARG, "unknown circuit id " + std::to_string(circuit_ids[i]));
-        circs[size_t(i)] = &it->second;
+    BatchArgs args;
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, nullptr, nullptr, args);
+    if (rc) return rc;
+    for (int i = 0; i < n_evals; ++i)
         if (param_counts[i] < 0) return fail(h, QSV_E_ARG, "negative parameter count");
-        np[size_t(i)] = param_counts[i];
-    }
-    int rc = eval_begin(h, circs, np);
+    args.n_params.assign(param_counts, param_counts + n_evals);
+    rc = eval_begin(h, args.circs, args.n_params);
     if (rc) {
         eval_close(h);
         return rc;
@@ -2917,8 +2925,7 @@ int qsv_eval_push(qsv_t* h, int first, int count, const double* values) {
     if (!h) return QSV_E_ARG;
     if (!h->batch.open) return fail(h, QSV_E_STATE, "no open batch (call qsv_eval_begin first)");
     if (first < 0 || count < 0) return fail(h, QSV_E_ARG, "bad arguments");
-    static const double dummy = 0.0;
-    return eval_push(h, size_t(first), size_t(count), values ? values : &dummy);
+    return eval_push(h, size_t(first), size_t(count), values ? values : kNoValues);
 }
 
 int qsv_eval_push_device(qsv_t* h, int first, int count, const double* device_values, void* ready_event) {
@@ -2939,8 +2946,7 @@ int qsv_eval_push_device(qsv_t* h, int first, int count, const double* device_va
         QSV_HIP(h, hipStreamWaitEvent(h->stream, static_cast<hipEvent_t>(ready_event), 0));
         for (hipStream_t st : h->side_streams) QSV_HIP(h, hipStreamWaitEvent(st, static_cast<hipEvent_t>(ready_event), 0));
     }
-    static const double dummy = 0.0;
-    return eval_push(h, size_t(first), size_t(count), &dummy, device_values);
+    return eval_push(h, size_t(first), size_t(count), kNoValues, device_values);
 }
 
 int qsv_eval_staging(qsv_t* h, int first, int count, double** values) {
@@ -3128,10 +3134,9 @@ int qsv_eval_batch(qsv_t* h, int n_evals, const int64_t* op_offsets, const qsv_o
             if (pending[size_t(i)] >= 0) ids[size_t(i)] = fresh_id[size_t(pending[size_t(i)])];
     }
     // pass 3: only now, with every registration done, take pointers into the circuit table
-    std::vector<Circuit*> circs(size_t(n_evals), nullptr);
-    for (int i = 0; i < n_evals; ++i) circs[size_t(i)] = &h->circuits.find(ids[size_t(i)])->second;
-    static const double dummy = 0.0;
-    return eval_all(h, circs, param_offsets, params ? params : &dummy, out);
+    BatchArgs args;
+    int rc = resolve_batch(h, size_t(n_evals), ids.data(), param_offsets, params, args);
+    return rc ? rc : eval_all(h, args, out);
 }
 
 int qsv_statevector(qsv_t* h, int circuit_id, const double* params, int n_params, double* out_re_im) {
@@ -3139,8 +3144,7 @@ int qsv_statevector(qsv_t* h, int circuit_id, const double* params, int n_params
     std::lock_guard<std::mutex> lock(h->mu);
     if (!out_re_im) return fail(h, QSV_E_ARG, "out is null");
     QSV_HIP(h, hipSetDevice(h->device));
-    static const double dummy = 0.0;
-    int rc = run_single_to_state(h, circuit_id, params ? params : &dummy, n_params);
+    int rc = run_single_to_state(h, circuit_id, params, n_params);
     if (rc) return rc;
     const uint64_t dim = uint64_t(1) << h->n;
     if (h->dtype == QSV_F64) {
@@ -3159,8 +3163,7 @@ int qsv_probabilities(qsv_t* h, int circuit_id, const double* params, int n_para
     std::lock_guard<std::mutex> lock(h->mu);
     if (!out_probs) return fail(h, QSV_E_ARG, "out is null");
     QSV_HIP(h, hipSetDevice(h->device));
-    static const double dummy = 0.0;
-    int rc = run_single_to_state(h, circuit_id, params ? params : &dummy, n_params);
+    int rc = run_single_to_state(h, circuit_id, params, n_params);
     if (rc) return rc;
     const uint64_t dim = uint64_t(1) << h->n;
     if ((rc = ensure(h, h->d_scratch, dim * 8))) return rc;
@@ -3170,44 +3173,22 @@ int qsv_probabilities(qsv_t* h, int circuit_id, const double* params, int n_para
     return QSV_OK;
 }
 
+static const char* const kNotSampled = "circuits on kept states are not sampled (qsv_eval_* only)";
+
 // Sampler branch for a whole batch: run the circuits group by group, turn each resident state into probabilities,
 // draw `shots` samples per evaluation on the device and (for a diagonal operator) gather each sample's value D[state].
 // out_cvar != null: the samples and their values stay on the device, only CVaR_alpha per evaluation comes back.
-static int sample_batch_locked(qsv_t* h, const std::vector<Circuit*>& circs, const int64_t* param_offsets,
-                               const double* params, int shots, uint64_t seed, uint64_t* out_states,
+static int sample_batch_locked(qsv_t* h, const BatchArgs& args, int shots, uint64_t seed, uint64_t* out_states,
                                double* out_values, double alpha = 1.0, double* out_cvar = nullptr) {
-    const size_t n_evals = circs.size();
+    const size_t n_evals = args.circs.size();
     if (n_evals == 0 || shots == 0) return QSV_OK;
-    for (const Circuit* c : circs)
-        if (c->prefix_id >= 0) return fail(h, QSV_E_UNSUPPORTED, "circuits on kept states are not sampled (qsv_eval_* only)");
     if ((out_values || out_cvar) && !(h->has_diag_part && h->diagonal))
         return fail(h, QSV_E_STATE, "sample values need a diagonal operator (call qsv_set_operator with I/Z terms only)");
-    std::vector<int64_t> np(n_evals);
-    std::vector<double> packed;
-    size_t total = 0;
-    for (size_t i = 0; i < n_evals; ++i) {
-        np[i] = param_offsets[i + 1] - param_offsets[i];
-        if (np[i] < 0) return fail(h, QSV_E_ARG, "param_offsets must be non-decreasing");
-        total += size_t(np[i]);
-    }
-    packed.resize(total + 1);
-    for (size_t i = 0, cur = 0; i < n_evals; cur += size_t(np[i]), ++i)
-        if (np[i]) std::memcpy(packed.data() + cur, params + param_offsets[i], size_t(np[i]) * sizeof(double));
-    h->prof = qsv_profile{};
     // circuits that have a split form are sampled from their two side tables: no state, no 2^n probabilities
-    int rc = batch_layout(h, circs, np, h->split_sampling, kSampledSplitMaxKeys);
-    if (rc) return rc;
-    const size_t n_split = order_split_first(h, 0, n_evals), n_plain = n_evals - n_split;
+    const SplitRule rule = split_rule(h, SplitUse::Sampling);
+    const size_t n_split = rule.count(args.circs), n_plain = n_evals - n_split;
     const uint64_t dim = uint64_t(1) << h->n;
     const size_t G = size_t(h->group), SG = size_t(std::max(1, h->side_slots));
-    {
-        EvalDesc* hd = static_cast<EvalDesc*>(h->h_batch);
-        for (size_t j = 0; j < n_evals; ++j) {
-            const uint32_t slot = uint32_t(j < n_split ? j % SG : (j - n_split) % G);
-            hd[j].state_slot = slot;
-            if (h->batch.split_any) hd[n_evals + j].state_slot = slot;
-        }
-    }
     // device scratch: probabilities and chunk sums of a group of ordinary evaluations | tables of a group of split
     // ones | (device-side CVaR) the samples
     const size_t probs_bytes = n_plain ? G * dim * 8 : 0, sums_bytes = n_plain ? G * size_t(sample_chunk_count(dim)) * 8 : 0;
@@ -3215,8 +3196,8 @@ static int sample_batch_locked(qsv_t* h, const std::vector<Circuit*>& circs, con
     const size_t split_bytes = n_split ? std::min(SG, n_split) * split_sample_slot_doubles(h->geo.k + kSideExtraBits) * 8 : 0;
     const size_t out_bytes = n_evals * size_t(shots) * 8;
     const size_t dev_samples_off = ((split_off + split_bytes + 63) / 64) * 64;
+    int rc;
     if ((rc = ensure(h, h->d_scratch, dev_samples_off + (out_cvar ? 2 * out_bytes : 0)))) return rc;
-    if ((rc = ensure(h, h->d_partials, std::max<size_t>(1, n_evals) * partials_per_state(h) * sizeof(double)))) return rc;
     if (out_cvar && (rc = ensure_host_out(h, n_evals))) return rc;
     // samples (and their operator values) are written by the kernel straight into pinned host memory: no copy operations
     if (!out_cvar && h->h_samples_bytes < 2 * out_bytes) {
@@ -3243,11 +3224,8 @@ static int sample_batch_locked(qsv_t* h, const std::vector<Circuit*>& circs, con
     // probabilities, not the state
     const bool fuse = h->geo.blocks_per_state == 1;
     const bool probs_in_pass = h->n <= 28;
-    rc = batch_ship(h, 0, n_evals, packed.data(), fuse ? n_evals : n_split);
-    // the split evaluations (they lead the descriptors), a group of side-table slots at a time
-    for (size_t g0 = 0; !rc && g0 < n_split; g0 += SG) {
-        const size_t gc = std::min(SG, n_split - g0);
-        if ((rc = run_group(h, circs, g0, gc, kModeSynthFirst | kModeFinalStore | kModeSidesOnly))) break;
+    // the split evaluations, a group of side-table slots at a time
+    auto on_split = [&](size_t g0, size_t gc) -> int {
         PassArgs a{};
         a.plan = static_cast<const uint32_t*>(h->d_arena.ptr);
         a.evals = batch_evals(h) + g0;
@@ -3256,24 +3234,24 @@ static int sample_batch_locked(qsv_t* h, const std::vector<Circuit*>& circs, con
         QSV_HIP(h, launch_split_tables(h->dtype, h->geo.k + kSideExtraBits, unsigned(gc), split_scratch, h->stream, a));
         uint32_t table_doubles = 64;  // the largest Gram table of the group (whichever side the contraction calls Y)
         for (size_t i = 0; i < gc; ++i) {
-            const SplitInfo& sp = circs[h->batch.eval_at[g0 + i]]->split;
+            const SplitInfo& sp = args.circs[h->batch.eval_at[g0 + i]]->split;
             for (int side = 0; side < 2; ++side)
                 table_doubles = std::max(table_doubles, uint32_t(1) << (2 * sp.n_keys + std::max(0, sp.n_virtual[side] - sp.n_keys - 6)));
         }
         QSV_HIP(h, launch_split_sample(h->dtype, h->geo.k + kSideExtraBits, unsigned(gc), split_scratch, shots, seed, diag, d_states, d_values,
                                        h->stream, a, table_doubles));
-    }
-    const uint32_t mode = kModeSynthFirst | (probs_in_pass ? kModeFinalProbs : kModeFinalStore) | (fuse ? kModeFusedPrepare : 0u);
-    for (size_t g0 = n_split; !rc && g0 < n_evals; g0 += G) {
-        const size_t gc = std::min(G, n_evals - g0);
-        if ((rc = run_group(h, circs, g0, gc, mode))) break;
+        return QSV_OK;
+    };
+    auto on_state = [&](size_t g0, size_t gc) -> int {
         if (!probs_in_pass) QSV_HIP(h, launch_probabilities(h->dtype, h->d_states.ptr, dim, int(gc), probs, h->stream));
         QSV_HIP(h, launch_sample(probs, dim, int(gc), sums, shots, seed, uint32_t(g0), diag, d_states, d_values, h->stream,
                                  n_split ? batch_evals(h) + g0 : nullptr));
-    }
-    if (!rc && out_cvar) QSV_HIP(h, launch_cvar(d_values, int(n_evals), shots, alpha, h->h_out, h->stream));
-    h->batch.circs.clear();
-    if (rc) return rc;
+        return QSV_OK;
+    };
+    const StateRun run{rule, SG, G, fuse, kModeSynthFirst | kModeFinalStore | kModeSidesOnly,
+                       kModeSynthFirst | (probs_in_pass ? kModeFinalProbs : kModeFinalStore) | (fuse ? kModeFusedPrepare : 0u)};
+    if ((rc = run_to_states(h, args, run, on_split, on_state))) return rc;
+    if (out_cvar) QSV_HIP(h, launch_cvar(d_values, int(n_evals), shots, alpha, h->h_out, h->stream));
     QSV_HIP(h, hipStreamSynchronize(h->stream));
     if (out_cvar) {
         std::memcpy(out_cvar, h->h_out, n_evals * sizeof(double));
@@ -3286,26 +3264,16 @@ static int sample_batch_locked(qsv_t* h, const std::vector<Circuit*>& circs, con
 
 // Exact-probability CVaR for a whole batch: the circuits group by group as in the sampler branch (split circuits as their
 // two virtual circuits, the others with the probabilities written by their last gate pass), then launch_cvar_exact.
-static int exact_cvar_locked(qsv_t* h, const std::vector<Circuit*>& circs, const int64_t* param_offsets, const double* params,
-                             double alpha, double* out_cvar) {
-    const size_t n_evals = circs.size();
+static int exact_cvar_locked(qsv_t* h, const BatchArgs& args, double alpha, double* out_cvar) {
+    const size_t n_evals = args.circs.size();
     if (n_evals == 0) return QSV_OK;
-    for (const Circuit* c : circs)
-        if (c->prefix_id >= 0) return fail(h, QSV_E_UNSUPPORTED, "circuits on kept states are not sampled (qsv_eval_* only)");
     if (!(h->has_diag_part && h->diagonal))
         return fail(h, QSV_E_STATE, "the exact CVaR needs a diagonal operator (call qsv_set_operator with I/Z terms only)");
     if (h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "the exact CVaR is available up to 28 qubits");
-    std::vector<int64_t> np(n_evals);
-    size_t total = 0;
-    for (size_t i = 0; i < n_evals; ++i) {
-        np[i] = param_offsets[i + 1] - param_offsets[i];
-        if (np[i] < 0) return fail(h, QSV_E_ARG, "param_offsets must be non-decreasing");
-        total += size_t(np[i]);
-    }
     // alpha = 1 (numpy.isclose(alpha, 1), the reference's test): the reference takes the plain mean of the values there
     // (expectation_calculation.py:55-69), not its accumulation loop, whose stopping rule leaves out the last 1e-5 of the mass
     // (5e-4 of an Ising value at 20 qubits): the expectation value, as qsv_eval_circuits computes it
-    if (std::fabs(alpha - 1.0) <= 1e-8 + 1e-5) return eval_all(h, circs, param_offsets, params, out_cvar);
+    if (std::fabs(alpha - 1.0) <= 1e-8 + 1e-5) return eval_all(h, args, out_cvar);
     const uint64_t dim = uint64_t(1) << h->n;
     int rc;
     if (!h->order_valid) {
@@ -3314,54 +3282,33 @@ static int exact_cvar_locked(qsv_t* h, const std::vector<Circuit*>& circs, const
                                         static_cast<double*>(h->d_sorted.ptr), h->stream));
         h->order_valid = true;
     }
-    std::vector<double> packed;
-    packed.resize(total + 1);
-    for (size_t i = 0, cur = 0; i < n_evals; cur += size_t(np[i]), ++i)
-        if (np[i]) std::memcpy(packed.data() + cur, params + param_offsets[i], size_t(np[i]) * sizeof(double));
-    h->prof = qsv_profile{};
-    if ((rc = batch_layout(h, circs, np, h->split_sampling, kSampledSplitMaxKeys))) return rc;
-    const size_t n_split = order_split_first(h, 0, n_evals), n_plain = n_evals - n_split;
+    const SplitRule rule = split_rule(h, SplitUse::Sampling);
+    const size_t n_split = rule.count(args.circs), n_plain = n_evals - n_split;
     const size_t G = size_t(h->group), SG = size_t(std::max(1, h->side_slots));
-    {
-        EvalDesc* hd = static_cast<EvalDesc*>(h->h_batch);
-        for (size_t j = 0; j < n_evals; ++j) {
-            const uint32_t slot = uint32_t(j < n_split ? j % SG : (j - n_split) % G);
-            hd[j].state_slot = slot;
-            if (h->batch.split_any) hd[n_evals + j].state_slot = slot;
-        }
-    }
     const uint32_t n_chunks = cvar_exact_chunks(dim);
     const size_t probs_bytes = n_plain ? G * dim * 8 : 0;
     const size_t chunk_off = ((probs_bytes + 63) / 64) * 64;
     const size_t chunk_bytes = 2 * std::max(G, std::min(SG, std::max<size_t>(1, n_split))) * size_t(n_chunks) * 8;
     if ((rc = ensure(h, h->d_scratch, chunk_off + chunk_bytes))) return rc;
-    if ((rc = ensure(h, h->d_partials, std::max<size_t>(1, n_evals) * partials_per_state(h) * sizeof(double)))) return rc;
     if ((rc = ensure_host_out(h, n_evals))) return rc;
     double* probs = static_cast<double*>(h->d_scratch.ptr);
     double* chunk_scratch = reinterpret_cast<double*>(static_cast<char*>(h->d_scratch.ptr) + chunk_off);
     const bool fuse = h->geo.blocks_per_state == 1;
-    rc = batch_ship(h, 0, n_evals, packed.data(), fuse ? n_evals : n_split);
-    PassArgs a{};
-    a.plan = static_cast<const uint32_t*>(h->d_arena.ptr);
-    a.wtab = h->d_side.ptr;
-    a.wtab_stride = h->side_stride;
     const uint32_t* order = static_cast<const uint32_t*>(h->d_order.ptr);
     const double* sorted = static_cast<const double*>(h->d_sorted.ptr);
-    for (size_t g0 = 0; !rc && g0 < n_split; g0 += SG) {
-        const size_t gc = std::min(SG, n_split - g0);
-        if ((rc = run_group(h, circs, g0, gc, kModeSynthFirst | kModeFinalStore | kModeSidesOnly))) break;
+    // (split evaluations and the others alike: the kernel reads each one's side tables or probabilities by its descriptor)
+    auto consume = [&](size_t g0, size_t gc) -> int {
+        PassArgs a{};  // (here: the batch's layout may have moved the plan arena)
+        a.plan = static_cast<const uint32_t*>(h->d_arena.ptr);
+        a.wtab = h->d_side.ptr;
+        a.wtab_stride = h->side_stride;
         a.evals = batch_evals(h) + g0;
         QSV_HIP(h, launch_cvar_exact(h->dtype, probs, dim, unsigned(gc), order, sorted, alpha, chunk_scratch, h->h_out, h->stream, a));
-    }
-    const uint32_t mode = kModeSynthFirst | kModeFinalProbs | (fuse ? kModeFusedPrepare : 0u);
-    for (size_t g0 = n_split; !rc && g0 < n_evals; g0 += G) {
-        const size_t gc = std::min(G, n_evals - g0);
-        if ((rc = run_group(h, circs, g0, gc, mode))) break;
-        a.evals = batch_evals(h) + g0;
-        QSV_HIP(h, launch_cvar_exact(h->dtype, probs, dim, unsigned(gc), order, sorted, alpha, chunk_scratch, h->h_out, h->stream, a));
-    }
-    h->batch.circs.clear();
-    if (rc) return rc;
+        return QSV_OK;
+    };
+    const StateRun run{rule, SG, G, fuse, kModeSynthFirst | kModeFinalStore | kModeSidesOnly,
+                       kModeSynthFirst | kModeFinalProbs | (fuse ? kModeFusedPrepare : 0u)};
+    if ((rc = run_to_states(h, args, run, consume, consume))) return rc;
     QSV_HIP(h, hipStreamSynchronize(h->stream));
     std::memcpy(out_cvar, h->h_out, n_evals * sizeof(double));
     return QSV_OK;
@@ -3374,14 +3321,9 @@ int qsv_sample_batch(qsv_t* h, int n_evals, const int* circuit_ids, const int64_
     if (n_evals < 0 || shots < 0 || (n_evals > 0 && shots > 0 && (!circuit_ids || !param_offsets || !out_states)))
         return fail(h, QSV_E_ARG, "bad arguments");
     QSV_HIP(h, hipSetDevice(h->device));
-    std::vector<Circuit*> circs(size_t(n_evals), nullptr);
-    for (int i = 0; i < n_evals; ++i) {
-        auto it = h->circuits.find(circuit_ids[i]);
-        if (it == h->circuits.end()) return fail(h, QSV_E_ARG, "unknown circuit id " + std::to_string(circuit_ids[i]));
-        circs[size_t(i)] = &it->second;
-    }
-    static const double dummy = 0.0;
-    return sample_batch_locked(h, circs, param_offsets, params ? params : &dummy, shots, seed, out_states, out_values);
+    BatchArgs args;  // (no shots: only the ids are looked at)
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, shots ? param_offsets : nullptr, params, args, shots ? kNotSampled : nullptr);
+    return rc ? rc : sample_batch_locked(h, args, shots, seed, out_states, out_values);
 }
 
 int qsv_sample_cvar_batch(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
@@ -3393,14 +3335,9 @@ int qsv_sample_cvar_batch(qsv_t* h, int n_evals, const int* circuit_ids, const i
     if (!(alpha > 0.0) || alpha > 1.0) return fail(h, QSV_E_ARG, "alpha must be in (0, 1]");
     if (shots > kCvarMaxShots) return fail(h, QSV_E_ARG, "the device-side CVaR sorts at most 4096 samples per evaluation");
     QSV_HIP(h, hipSetDevice(h->device));
-    std::vector<Circuit*> circs(size_t(n_evals), nullptr);
-    for (int i = 0; i < n_evals; ++i) {
-        auto it = h->circuits.find(circuit_ids[i]);
-        if (it == h->circuits.end()) return fail(h, QSV_E_ARG, "unknown circuit id " + std::to_string(circuit_ids[i]));
-        circs[size_t(i)] = &it->second;
-    }
-    static const double dummy = 0.0;
-    return sample_batch_locked(h, circs, param_offsets, params ? params : &dummy, shots, seed, nullptr, nullptr, alpha, out_cvar);
+    BatchArgs args;
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args, kNotSampled);
+    return rc ? rc : sample_batch_locked(h, args, shots, seed, nullptr, nullptr, alpha, out_cvar);
 }
 
 int qsv_exact_cvar_batch(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
@@ -3410,14 +3347,9 @@ int qsv_exact_cvar_batch(qsv_t* h, int n_evals, const int* circuit_ids, const in
     if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets || !out_cvar))) return fail(h, QSV_E_ARG, "bad arguments");
     if (!(alpha > 0.0) || alpha > 1.0) return fail(h, QSV_E_ARG, "alpha must be in (0, 1]");
     QSV_HIP(h, hipSetDevice(h->device));
-    std::vector<Circuit*> circs(size_t(n_evals), nullptr);
-    for (int i = 0; i < n_evals; ++i) {
-        auto it = h->circuits.find(circuit_ids[i]);
-        if (it == h->circuits.end()) return fail(h, QSV_E_ARG, "unknown circuit id " + std::to_string(circuit_ids[i]));
-        circs[size_t(i)] = &it->second;
-    }
-    static const double dummy = 0.0;
-    return exact_cvar_locked(h, circs, param_offsets, params ? params : &dummy, alpha, out_cvar);
+    BatchArgs args;
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args, kNotSampled);
+    return rc ? rc : exact_cvar_locked(h, args, alpha, out_cvar);
 }
 
 int qsv_observables_create(qsv_t* h, int n_observables, const int64_t* term_offsets, const uint64_t* x_mask, const uint64_t* z_mask,
@@ -3515,17 +3447,11 @@ int qsv_eval_observables(qsv_t* h, int set_id, int n_evals, const int* circuit_i
     if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets || !out))) return fail(h, QSV_E_ARG, "bad arguments");
     auto set = h->obs_sets.find(set_id);
     if (set == h->obs_sets.end()) return fail(h, QSV_E_ARG, "unknown observable set " + std::to_string(set_id));
-    std::vector<Circuit*> circs(size_t(n_evals), nullptr);
-    for (int i = 0; i < n_evals; ++i) {
-        auto it = h->circuits.find(circuit_ids[i]);
-        if (it == h->circuits.end()) return fail(h, QSV_E_ARG, "unknown circuit id " + std::to_string(circuit_ids[i]));
-        circs[size_t(i)] = &it->second;
-        if (param_offsets[i + 1] < param_offsets[i]) return fail(h, QSV_E_ARG, "param_offsets must be non-decreasing");
-    }
-    if (n_evals == 0) return QSV_OK;
+    BatchArgs args;
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args);
+    if (rc || n_evals == 0) return rc;
     QSV_HIP(h, hipSetDevice(h->device));
-    static const double dummy = 0.0;
-    return eval_observables_locked(h, set->second, circs, param_offsets, params ? params : &dummy, out);
+    return eval_observables_locked(h, set->second, args, out);
 }
 
 int qsv_sample(qsv_t* h, int circuit_id, const double* params, int n_params, int shots, uint64_t seed,
@@ -3534,12 +3460,10 @@ int qsv_sample(qsv_t* h, int circuit_id, const double* params, int n_params, int
     std::lock_guard<std::mutex> lock(h->mu);
     if (shots < 0 || n_params < 0 || (shots > 0 && !out_states)) return fail(h, QSV_E_ARG, "bad arguments");
     QSV_HIP(h, hipSetDevice(h->device));
-    auto it = h->circuits.find(circuit_id);
-    if (it == h->circuits.end()) return fail(h, QSV_E_ARG, "unknown circuit id");
-    std::vector<Circuit*> circs{&it->second};
     const int64_t offsets[2] = {0, n_params};
-    static const double dummy = 0.0;
-    return sample_batch_locked(h, circs, offsets, params ? params : &dummy, shots, seed, out_states, nullptr);
+    BatchArgs args;
+    int rc = resolve_batch(h, 1, &circuit_id, offsets, params, args, shots ? kNotSampled : nullptr);
+    return rc ? rc : sample_batch_locked(h, args, shots, seed, out_states, nullptr);
 }
 
 int qsv_fitness_table_wait(const volatile uint64_t* own, int count, volatile int64_t* done, int stride, int world, int rank,
@@ -3642,8 +3566,7 @@ static int bench_ops_locked(qsv_t* h, int n_ops, const qsv_op* ops, int reps, do
     Circuit& c = h->circuits.find(id)->second;
     auto cleanup = [&]() { h->circuits.erase(id); };
     std::vector<Circuit*> cc{&c};
-    static const double dummy = 0.0;
-    if ((rc = batch_layout(h, cc, std::vector<int64_t>{0})) || (rc = batch_ship(h, 0, 1, &dummy))) {
+    if ((rc = batch_layout(h, cc, std::vector<int64_t>{0})) || (rc = batch_ship(h, 0, 1, kNoValues))) {
         h->batch.circs.clear();
         cleanup();
         return rc;

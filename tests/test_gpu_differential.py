@@ -25,6 +25,7 @@ import helpers
 from oracle import statevector_oracle as so
 from queasars_amd import _lib
 from queasars_amd.circuit_evaluation import OperatorCircuitEvaluator, StatevectorDevice
+from queasars_amd.evqe import EVQEPopulation
 from queasars_amd.ir import PauliOperator
 from sampler_draws import DELTA_FP32, DELTA_FP64, DrawCheck, plain_order, shot_uniform, split_order
 from test_gpu_configs import _diagonal_operator
@@ -141,7 +142,9 @@ def _device(case, dtype, monkeypatch, variant="defaults", split=True):
         monkeypatch.setenv(*ENVIRONMENT[variant])
     elif variant == "push_plan":
         monkeypatch.setenv("QSV_PUSH_PLAN", ",".join(str(s) for s in case["plan"]))
-    dev = StatevectorDevice(case["n"], dtype=dtype)
+    elif variant == "group=3":  # (launch groups of three state slots and of eight side-table slots: a batch spans many)
+        monkeypatch.setenv("QSV_SIDE_SLOTS", "8")
+    dev = StatevectorDevice(case["n"], dtype=dtype, group=3 if variant == "group=3" else 0)
     if variant in OPTIONS:
         dev.set_option(*OPTIONS[variant])
     if not split:
@@ -340,12 +343,13 @@ def test_the_matrix_covers_every_form(monkeypatch):
 
 
 @pytest.mark.parametrize("n,dtype,variant", [(14, "fp64", "defaults"), (14, "fp32", "defaults"), (17, "fp64", "defaults"),
-                                             (20, "fp64", "defaults"), (20, "fp64", "QSV_NO_HALF_SIDES")])
+                                             (20, "fp64", "defaults"), (20, "fp64", "QSV_NO_HALF_SIDES"), (14, "fp64", "group=3")])
 def test_exact_draws_of_both_samplers(n, dtype, variant, c_oracle, monkeypatch):
     """Both samplers in one mixed, shuffled batch: split-sampled circuits (zero to three keys; at n = 20 the sides_r3 plans,
     half sides, and with QSV_NO_HALF_SIDES the swept ones) and plain-sampled ones (four and five keys, unsplittable), two
     seeds of 4096 shots.  Every shot is accepted against the exact CDF in its sampler's order; in fp64 at most 1 % differ
-    from the exact draw; values are D[state] within 1e-12 sum |c|."""
+    from the exact draw; values are D[state] within 1e-12 sum |c|.  With group=3 the batch spans many launch groups of
+    both kinds, and every consumer of final states is held to the same bits as with one group (_check_many_groups)."""
     blocks = [(4, 24, 2 * n), (6, 12, 2 * n + 1), (9, 3, 2 * n + 2)]
     if n == 20:
         blocks = [(4, 16, 0), (5, 16, 0), (6, 8, 0), (9, 3, 8)]
@@ -379,9 +383,42 @@ def test_exact_draws_of_both_samplers(n, dtype, variant, c_oracle, monkeypatch):
             total += sum(r["shots"] for r in reports)
             differ += sum(r["differ"] for r in reports)
         print(f"\nn = {n} {dtype} {variant}: {differ} of {total} shots differ from the exact draw ({sorted(split_keys)} keys split-sampled)")
+        if variant == "group=3":
+            _check_many_groups(dev, dtype, op, circuits, params, monkeypatch)
     finally:
         dev.close()
         plain.close()
+
+
+def _check_many_groups(dev, dtype, op, circuits, params, monkeypatch):
+    """Every consumer of final states on batches that span many launch groups of ``dev`` (three state slots, eight side-table
+    slots), bit for bit: both samplers against a device whose launch groups hold the whole batch (a draw depends on the
+    evaluation's index in its batch); the exact CVaR, kept states and the observables (split, plain and kept-state
+    evaluations in one batch) against the same calls one evaluation at a time."""
+    n = dev.n_qubits
+    monkeypatch.delenv("QSV_SIDE_SLOTS")
+    whole = StatevectorDevice(n, dtype=dtype)
+    try:
+        whole.set_operator(op)
+        grouped, one = (d.sample_batch(circuits, params, 256, 5, with_values=True) for d in (dev, whole))
+        assert np.array_equal(grouped[0], one[0]) and np.array_equal(grouped[1], one[1])
+        assert dev.sample_cvar_batch(circuits, params, 256, 5, 0.5) == whole.sample_cvar_batch(circuits, params, 256, 5, 0.5)
+        exact = dev.exact_cvar_batch(circuits, params, 0.5)
+        assert exact == [dev.exact_cvar_batch([c], [p], 0.5)[0] for c, p in zip(circuits, params)]
+        population = EVQEPopulation.random_population(n, 3, 7, True, 1)
+        pairs = [ind.get_layer_search_circuits(2) for ind in population.individuals]
+        values = [list(ind.get_layer_parameter_values(2)) for ind in population.individuals]
+        together = dev.keep_states([front for front, _ in pairs], [[] for _ in pairs])
+        alone = [dev.keep_states([front], [[]])[0] for front, _ in pairs]
+        kept = [rest.continue_from(state) for (_, rest), state in zip(pairs, together)]
+        for (_, rest), state, c, v in zip(pairs, alone, kept, values):
+            assert np.array_equal(dev.statevector(c, v), dev.statevector(rest.continue_from(state), v))
+        ops = [op, helpers.random_pauli_operator(n, 12, seed=3)]
+        got = dev.observable_values(circuits + kept, params + values, ops)
+        for i, (c, p) in enumerate(zip(circuits + kept, params + values)):
+            assert np.array_equal(got[i], dev.observable_values([c], [p], ops)[0]), i
+    finally:
+        whole.close()
 
 
 def test_exact_cvar_at_alpha_one_is_the_expectation_value(c_oracle):
