@@ -343,6 +343,38 @@ int qsv_sample_cvar_batch(qsv_t* h, int n_evals, const int* circuit_ids, const i
 int qsv_exact_cvar_batch(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
                          double alpha, double* out_cvar);
 
+/*
+ * Both of the above with the parameter values READ FROM and the results LEFT IN device memory (this handle's GPU), queued on the
+ * handle's stream (qsv_set_stream) without waiting: the evaluation step of an optimiser that lives on the device
+ * (evqe/device_search.py with a sampler evaluator; with qsv_spsa_step an iteration is two chains of launches and the host waits for
+ * neither).  Replaces, like they do, measure_quasi_distributions + get_expectation_with_operator of the reference's
+ * OperatorSamplerCircuitEvaluator.evaluate_circuits (circuit_evaluation.py:94-161, expectation_calculation.py:14-69).
+ *   device_values  row-major matrix of n_evals rows of `width` doubles: evaluation e takes the first n_params of row e, exactly as
+ *                  qsv_eval_push_device documents (rows wider than 1024: prepared without the LDS copy, same remark).  They must
+ *                  stay unchanged until the call's work is complete.  `ready_event` as in qsv_eval_push_device.
+ *   shots > 0      device_out[e] = what qsv_sample_cvar_batch computes for the same circuits, values, shots, seed and alpha, bit
+ *                  for bit (evaluation e draws from the stream of (seed, e)); shots <= 4096.
+ *   shots == 0     device_out[e] = what qsv_exact_cvar_batch computes, bit for bit, including alpha = 1 (numpy.isclose): the
+ *                  expectation value.  At most 28 qubits.
+ *   device_active  may be NULL: every evaluation runs.  Otherwise entry e / active_stride (uint8) decides evaluation e: 0 = its
+ *                  workgroups return at once in every kernel of the call and device_out[e] is left untouched (stride 2 with
+ *                  qsv_spsa_step's own `active` array: a stopped run's plus / minus pair costs nothing and its values are not
+ *                  read).  The values of the evaluations that run do not depend on the mask, bit for bit.  The mask is read by
+ *                  the kernels, in stream order: what was written to it on the handle's stream before the call is what they see.
+ *                  (alpha = 1 with shots == 0: switched-off evaluations still run, only their results are withheld.)
+ * Returns without waiting: the results are complete once the work enqueued so far on the handle's stream is.  The next call on
+ * the handle that needs the staging or scratch buffers waits for unfinished work first, as after qsv_eval_end(h, NULL) -- except
+ * a qsv_cvar_device call with the same circuit_ids, width and kind (shots > 0 or not) as the one before it and nothing else in
+ * between: it reuses that call's layout and neither writes a staging buffer nor waits, so the iterations of a search follow each
+ * other on the stream.  A call allocates only if its scratch has to grow (more evaluations x shots than any call before) or its
+ * batch is laid out afresh; it waits for the handle's streams before it frees anything.
+ * Errors as the host forms: no diagonal operator QSV_E_STATE; shots > 4096, alpha outside (0, 1], a pointer that is not this
+ * device's memory QSV_E_ARG; more than 28 qubits with shots == 0, and circuits on kept states, QSV_E_UNSUPPORTED.
+ */
+int qsv_cvar_device(qsv_t* h, int n_evals, const int* circuit_ids, int width, const double* device_values, void* ready_event,
+                    int shots /* 0: the exact distribution */, uint64_t seed, double alpha,
+                    const uint8_t* device_active /* may be NULL */, int active_stride, double* device_out);
+
 /* ---- several observables per evaluation ---------------------------------------------------------- */
 
 /*

@@ -787,6 +787,46 @@ class StatevectorDevice:
                                                    float(alpha), _lib.as_ptr(out)))
         return out.tolist()
 
+    def cvar_of_device_parameters(
+        self,
+        circuits: Sequence[CircuitIR],
+        matrix_ptr: int,
+        width: int,
+        event: int,
+        shots: int,
+        seed: int,
+        alpha: float,
+        out_ptr: int,
+        active_ptr: int = 0,
+        active_stride: int = 1,
+    ) -> None:
+        """:meth:`sample_cvar_batch` (``shots > 0``) or :meth:`exact_cvar_batch` (``shots == 0``) for parameter values that
+        live in device memory -- a row-major ``len(circuits) x width`` matrix of doubles at ``matrix_ptr``, circuit i taking
+        the first ``num_parameters`` values of row i -- with the results left in device memory at ``out_ptr``
+        (``len(circuits)`` doubles) and nothing waited for (``qsv_cvar_device``): the same numbers, bit for bit.  ``event``: a
+        ``hipEvent_t`` (as an integer) after which the matrix is complete, 0 when it already is or was written on the
+        handle's stream.  ``active_ptr``: 0, or ``uint8`` flags in device memory, entry ``i // active_stride`` deciding
+        circuit i: 0 = not evaluated, its entry of the output left as it is."""
+        n = len(circuits)
+        if n == 0:
+            return
+        if width < 0 or (width > 0 and not matrix_ptr) or not out_ptr:
+            raise ValueError("matrix_ptr / width / out_ptr do not describe a matrix and its results")
+        if shots < 0 or shots > self.MAX_CVAR_SHOTS:
+            raise ValueError(f"the device-side CVaR takes 0 (the exact distribution) to {self.MAX_CVAR_SHOTS} shots")
+        if not 0 < alpha <= 1:
+            raise ValueError("alpha must be in the range (0, 1]!")
+        if active_ptr and active_stride < 1:
+            raise ValueError("active_stride must be at least 1")
+        ids, _need, _total = self._batch_metadata(circuits)
+        self._check(
+            self._lib.qsv_cvar_device(
+                self._handle, n, _lib.as_ptr(ids), int(width), C.c_void_p(matrix_ptr) if width else None,
+                C.c_void_p(event) if event else None, int(shots), C.c_uint64(seed & (2**64 - 1)), float(alpha),
+                C.c_void_p(active_ptr) if active_ptr else None, int(active_stride), C.c_void_p(out_ptr),
+            )
+        )
+
     # -- several observables ---------------------------------------------------------------------
     MAX_OBSERVABLE_SETS = 16
 
@@ -927,6 +967,51 @@ def _check_initial_state(initial_state_circuit: Optional[CircuitIR], n_qubits: i
         )
 
 
+def _device_matrix_arguments(evaluator, circuits, matrix, ready: bool):
+    """What the device-resident methods of both evaluators check and work out about a parameter matrix: returns
+    ``(pointer, width, event, remember)`` -- where the matrix is, its row length, a ``hipEvent_t`` after which it is complete
+    (0: it already is) and a callable, to be called once the library call has been made, that notes the matrix as seen (it also
+    keeps the event alive until then).  ``evaluator`` keeps
+    ``_last_matrix`` and names its device (``_device.device_index``)."""
+    import torch
+
+    # (the matrix this evaluator read last, untouched by any torch operation since -- same storage owner, same version
+    # counter, same place and shape: an optimiser's population evaluated again, a benchmark's resident input -- is as
+    # complete as it was then, and as well-formed)
+    base = matrix._base
+    owner = base if base is not None else matrix
+    shape = matrix.shape
+    stamp = (matrix._version, matrix.data_ptr(), shape[0], shape[1] if len(shape) == 2 else -1)
+    last = evaluator._last_matrix
+    seen = last is not None and last[0]() is owner and last[1] == stamp
+    if not seen:
+        if matrix.dim() != 2 or matrix.dtype != torch.float64 or not matrix.is_contiguous():
+            raise ValueError("a device-resident parameter matrix must be a contiguous 2-D float64 tensor")
+        if matrix.device.index != evaluator._device.device_index:
+            raise ValueError("the parameter matrix lives on another device than the evaluator")
+    if shape[0] != len(circuits):
+        raise ValueError("circuits and parameter_values must have the same length")
+    if _has_none(circuits):
+        raise ValueError("a device-resident parameter matrix cannot skip circuits (None entries)")
+    event, marker = 0, None
+    if seen:
+        ready = True
+    stream = None if ready else torch.cuda.current_stream(matrix.device)
+    if stream is not None and not stream.query():
+        # (whatever produces the matrix was queued on the tensor's current stream and has not finished: the handle's
+        # streams wait for it.  An idle stream -- the usual case -- costs one query instead of an event and four waits.)
+        # (an event of this call's own: evaluators are shared by threads, whose tensors may come from different streams)
+        marker = torch.cuda.Event()
+        marker.record(stream)
+        event = marker.cuda_event
+
+    def remember(_marker=marker):  # (holds the event until the call that waits for it has been made)
+        if not seen:
+            evaluator._last_matrix = (weakref.ref(owner), stamp)
+
+    return stamp[1], stamp[3], event, remember
+
+
 class OperatorCircuitEvaluator(BaseCircuitEvaluator):
     """Exact expectation values of ``operator`` on the GPU (estimator branch of the reference).
 
@@ -1013,40 +1098,9 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         return values.tolist()
 
     def _evaluate_device_matrix(self, circuits, matrix, ready: bool = False, out_device_pointer: int = 0) -> Optional[np.ndarray]:
-        import torch
-
-        # (the matrix this evaluator read last, untouched by any torch operation since -- same storage owner, same version
-        # counter, same place and shape: an optimiser's population evaluated again, a benchmark's resident input -- is as
-        # complete as it was then, and as well-formed)
-        base = matrix._base
-        owner = base if base is not None else matrix
-        shape = matrix.shape
-        stamp = (matrix._version, matrix.data_ptr(), shape[0], shape[1] if len(shape) == 2 else -1)
-        last = self._last_matrix
-        seen = last is not None and last[0]() is owner and last[1] == stamp
-        if not seen:
-            if matrix.dim() != 2 or matrix.dtype != torch.float64 or not matrix.is_contiguous():
-                raise ValueError("a device-resident parameter matrix must be a contiguous 2-D float64 tensor")
-            if matrix.device.index != self._device.device_index:
-                raise ValueError("the parameter matrix lives on another device than the evaluator")
-        if shape[0] != len(circuits):
-            raise ValueError("circuits and parameter_values must have the same length")
-        if _has_none(circuits):
-            raise ValueError("a device-resident parameter matrix cannot skip circuits (None entries)")
-        event = 0
-        if seen:
-            ready = True
-        stream = None if ready else torch.cuda.current_stream(matrix.device)
-        if stream is not None and not stream.query():
-            # (whatever produces the matrix was queued on the tensor's current stream and has not finished: the handle's
-            # streams wait for it.  An idle stream -- the usual case -- costs one query instead of an event and four waits.)
-            # (an event of this call's own: evaluators are shared by threads, whose tensors may come from different streams)
-            marker = torch.cuda.Event()
-            marker.record(stream)
-            event = marker.cuda_event
-        out = self._device.expectation_values_of_device_parameters(circuits, stamp[1], stamp[3], event, out_device_pointer)
-        if not seen:
-            self._last_matrix = (weakref.ref(owner), stamp)
+        pointer, width, event, remember = _device_matrix_arguments(self, circuits, matrix, ready)
+        out = self._device.expectation_values_of_device_parameters(circuits, pointer, width, event, out_device_pointer)
+        remember()
         return out
 
     def evaluate_device_parameters(self, circuits: list[CircuitIR], matrix, ready: bool = False) -> np.ndarray:
@@ -1083,6 +1137,10 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
                 self._device.set_operator(self._operator)
             self._device._register_many([c for c in circuits if self._device._serial not in c._registered])
             return [self._device.circuit_cost(c) for c in circuits]
+
+    #: what ``device_resident_search=None`` of the solver's configuration means for this evaluator (evqe/solver.py): searches of
+    #: enough runs go to the device
+    device_resident_search_by_default = True
 
     def device_resident_search_possible(self) -> bool:
         """Can an optimiser keep its points and values in this evaluator's device memory (:meth:`evaluate_device_to_device`)?
@@ -1242,10 +1300,74 @@ class OperatorSamplerCircuitEvaluator(BaseCircuitEvaluator):
         with self._device.operator_lock:
             self._device.set_operator(operator)
         self._composed = _ComposedCircuits(initial_state_circuit)
+        self._last_matrix = None     # (_device_matrix_arguments)
+        self._composed_lists = None  # (evaluate_device_to_device: the last list of circuits behind the initial state)
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["_last_matrix"] = None  # (a weak reference to a tensor does not travel)
+        state["_composed_lists"] = None
+        return state
 
     @property
     def statevector_device(self) -> StatevectorDevice:
         return self._device
+
+    #: what ``device_resident_search=None`` of the solver's configuration means for this evaluator (evqe/solver.py): the host
+    #: driver, as before the device search could take it -- ``True`` opts in
+    device_resident_search_by_default = False
+
+    def device_resident_search_possible(self) -> bool:
+        """Can an optimiser keep its points and values in this evaluator's device memory (:meth:`evaluate_device_to_device`)?
+        With the exact distribution (``sampler_shots=None``) or up to ``StatevectorDevice.MAX_CVAR_SHOTS`` shots: beyond that
+        the host sorts the sample values."""
+        if self._shots is not None and self._shots > StatevectorDevice.MAX_CVAR_SHOTS:
+            return False
+        try:
+            import torch
+        except ImportError:
+            return False
+        return torch.cuda.is_available()
+
+    def evaluate_device_to_device(self, circuits: list[CircuitIR], matrix, out, active=None, active_stride: int = 1) -> None:
+        """Parameter values from a device matrix (one row per circuit), this evaluator's values -- what
+        :meth:`evaluate_circuits` returns for the same points, bit for bit -- into the device tensor ``out``
+        (``len(circuits)`` doubles), nothing waited for and nothing copied (``qsv_cvar_device``).  All tensors belong to the
+        stream the evaluator's handle launches on (``StatevectorDevice.set_stream``): work queued there before the call is
+        seen, work queued after it sees the values.  With shots the call draws one seed from the evaluator's own generator
+        exactly as :meth:`evaluate_circuits` does, so two evaluators built with the same seed, one called through each method,
+        stay in step call after call.  ``active``: None, or a ``uint8`` / bool device tensor whose entry
+        ``i // active_stride`` decides circuit i -- 0: not evaluated, ``out[i]`` left as it is (a stopped run of a lock-step
+        search); the other values do not depend on it.  ``circuits`` should be the same list object call after call."""
+        import torch
+
+        if self._shots is not None and self._shots > StatevectorDevice.MAX_CVAR_SHOTS:
+            raise ValueError(f"more than {StatevectorDevice.MAX_CVAR_SHOTS} shots are sorted on the host: use evaluate_circuits")
+        if self._initial_state_circuit is not None:
+            kept = self._composed_lists
+            if kept is None or kept[0] is not circuits:
+                kept = self._composed_lists = (circuits, [self._composed.get(c) for c in circuits])
+            circuits = kept[1]
+        pointer, width, event, remember = _device_matrix_arguments(self, circuits, matrix, ready=True)
+        n = len(circuits)
+        if out.dtype != torch.float64 or out.numel() < n or not out.is_contiguous() or out.device != matrix.device:
+            raise ValueError("the output must be a contiguous float64 tensor of len(circuits) entries on the matrix's device")
+        active_ptr = 0
+        if active is not None:
+            if active_stride < 1:
+                raise ValueError("active_stride must be at least 1")
+            if (active.dtype not in (torch.uint8, torch.bool) or not active.is_contiguous() or active.device != matrix.device
+                    or active.numel() * active_stride < n):
+                raise ValueError("the mask must be a contiguous uint8 or bool tensor on the matrix's device that covers every circuit")
+            active_ptr = active.data_ptr()
+        seed = int(self._rng.integers(0, 2**63 - 1))
+        with self._device.operator_lock:
+            if self._device._operator is not self._operator:
+                self._device.set_operator(self._operator)
+            # (sampler_shots=None with alpha = 1 is the expectation value, as in evaluate_circuits: the library takes that route)
+            self._device.cvar_of_device_parameters(circuits, pointer, width, event, self._shots or 0, seed, self._alpha,
+                                                   out.data_ptr(), active_ptr, active_stride)
+        remember()
 
     def evaluate_circuits(self, circuits: list[CircuitIR], parameter_values: list[list[float]]) -> list[float]:
         """Samples every circuit on the device, gathers each sample's operator value from the device-resident diagonal

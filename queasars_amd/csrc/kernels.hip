@@ -357,6 +357,8 @@ struct PassScalars {
     const void* prefix_states;
     uint32_t dephase;
     const double* side_diag;
+    const uint8_t* active;  // kModeMasked: PassArgs::active
+    uint32_t active_stride;
 };
 
 // XMODE selects how a tile is transposed through LDS:
@@ -749,6 +751,24 @@ __global__ void __launch_bounds__(512, (Occupancy<R, XMODE, FIRST, FUSED>::waves
     const bool tile_major = !FIRST && (a.mode & kModeTileMajor);
     const uint32_t block_x = tile_major ? blockIdx.y : blockIdx.x, grid_x = tile_major ? gridDim.y : gridDim.x;
     const uint32_t block_y = tile_major ? blockIdx.x : blockIdx.y;
+    // kModeMasked (qsv_cvar_device): a workgroup of an evaluation the caller's mask switches off leaves here, in front of the
+    // preparation, every barrier and every hand-off; all it does is the device copy of its descriptor where this launch makes it
+    // (the kernels that follow find their evaluation by it).  A block of its own in front of everything else, so that nothing it
+    // uses is alive in the code behind it.  The flag was written by an earlier launch on this stream and is one per evaluation:
+    // every workgroup of the evaluation, both sides of a split one, takes the same branch.  The one-launch route, whose half
+    // sides trade rows through memory, is never launched masked -- the sampler path runs its virtual circuits without it,
+    // kModeSidesOnly -- and its instantiation does not carry the check.
+    if constexpr (!FUSED) {
+        if (__builtin_expect(a.mode & kModeMasked, 0)) {
+            const size_t slot = size_t(block_y) + size_t(blockIdx.z) * a.region_stride;
+            const bool prepares = FIRST && (a.mode & kModeFusedPrepare);
+            const EvalDesc* d = (prepares ? a.host_evals : evals) + slot;
+            if (!(d->flags & kEvalNull) && masked_out(a.active, a.active_stride, d->out_index)) {
+                if (prepares && threadIdx.x == 0 && block_x == 0) a.evals_out[slot] = *d;
+                return;
+            }
+        }
+    }
     EvalDesc ev;
     const double* mats_base = mats_all;
     bool prepared_here = false;
@@ -1426,7 +1446,7 @@ static hipError_t launch_pass_t(dim3 grid, int threads, size_t lds_bytes, hipStr
     const PassScalars sc{args.state_stride, args.wtab_stride, args.pass_index, args.mode, args.tiles_per_block,
                          args.partial_chunks, args.region_stride, args.host_evals, args.evals_out, args.host_params,
                          args.mats_out, args.result_out, args.quad, args.factor_scratch, args.factor_counters, args.n_full,
-                         args.prefix_states, args.dephase, args.side_diag};
+                         args.prefix_states, args.dephase, args.side_diag, args.active.flags, args.active.stride};
     cx<real>* st = reinterpret_cast<cx<real>*>(args.states);
     const bool first = args.pass_index == 0 && (args.mode & kModeSynthFirst);
     if constexpr (R == 4 || R == 3) {
@@ -1484,7 +1504,7 @@ static hipError_t pass_dispatch(int op, int dtype, int r, int xmode, dim3 grid, 
     const PassScalars sc{args->state_stride, args->wtab_stride, args->pass_index, args->mode, args->tiles_per_block,
                          args->partial_chunks, args->region_stride, args->host_evals, args->evals_out, args->host_params,
                          args->mats_out, args->result_out, args->quad, args->factor_scratch, args->factor_counters, args->n_full,
-                          args->prefix_states, args->dephase, args->side_diag};
+                          args->prefix_states, args->dephase, args->side_diag, args->active.flags, args->active.stride};
     if (args->pass_index == 0 && (args->mode & kModeSynthFirst))
         hipLaunchKernelGGL((pass_kernel<double, QSV_PROBE_R, 2, true>), grid, dim3(threads), lds_bytes, stream, args->plan,
                            args->mats, args->evals, reinterpret_cast<cx<double>*>(args->states),
@@ -1527,19 +1547,24 @@ __global__ void __launch_bounds__(256) prepare_kernel(const uint32_t* __restrict
                                                       const EvalDesc* __restrict__ host_evals,
                                                       EvalDesc* __restrict__ evals,
                                                       const double* __restrict__ params, double* __restrict__ mats,
-                                                      uint32_t region_stride, uint32_t float_mats) {
+                                                      uint32_t region_stride, uint32_t float_mats, const uint8_t* __restrict__ active,
+                                                      uint32_t active_stride) {
     __shared__ double scratch[kPrepScratchDoubles];
     const size_t slot = size_t(blockIdx.x) + size_t(blockIdx.y) * region_stride;
     const EvalDesc ev = host_evals[slot];
     if (threadIdx.x == 0) evals[slot] = ev;
     if (ev.flags & kEvalNull) return;
+    // (the caller's mask, kernels.hpp ActiveMask: behind the device copy of the descriptor, which later kernels find their
+    // evaluation by; uniform over the workgroup, in front of prepare_eval's first barrier)
+    if (masked_out(active, active_stride, ev.out_index)) return;
     prepare_eval(plan, ev, params, mats, scratch, float_mats != 0);
 }
 
 hipError_t launch_prepare(const uint32_t* plan, const EvalDesc* host_evals, EvalDesc* evals, const double* params,
-                          double* mats, int n_evals, hipStream_t stream, int n_regions, uint32_t region_stride, int dtype) {
+                          double* mats, int n_evals, hipStream_t stream, int n_regions, uint32_t region_stride, int dtype,
+                          ActiveMask active) {
     hipLaunchKernelGGL(prepare_kernel, dim3(n_evals, n_regions), dim3(256), 0, stream, plan, host_evals, evals, params,
-                       mats, region_stride, uint32_t(dtype != 0));
+                       mats, region_stride, uint32_t(dtype != 0), active.flags, active.stride);
     return hipGetLastError();
 }
 
@@ -2210,7 +2235,11 @@ __global__ void __launch_bounds__(256) state_to_f64_kernel(const cx<real>* __res
 constexpr uint32_t kSampleChunk = 64;
 
 __global__ void __launch_bounds__(256) chunk_sums_kernel(const double* __restrict__ probs_all, uint64_t dim,
-                                                         double* __restrict__ sums_all, uint32_t n_chunks) {
+                                                         double* __restrict__ sums_all, uint32_t n_chunks, uint32_t first_eval,
+                                                         const EvalDesc* __restrict__ evals, const uint8_t* __restrict__ active,
+                                                         uint32_t active_stride) {
+    // (the caller's mask: uniform over the workgroup, no barrier in this kernel)
+    if (active && masked_out(active, active_stride, evals ? evals[blockIdx.y].out_index : first_eval + blockIdx.y)) return;
     const double* __restrict__ probs = probs_all + uint64_t(blockIdx.y) * dim;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (uint32_t chunk = blockIdx.x * 4 + wave; chunk < n_chunks; chunk += gridDim.x * 4) {
@@ -2223,8 +2252,12 @@ __global__ void __launch_bounds__(256) chunk_sums_kernel(const double* __restric
 }
 
 // in-place inclusive scan of `n` chunk sums by one workgroup per slot (n <= 2^20: a few microseconds)
-__global__ void __launch_bounds__(256) scan_sums_kernel(double* __restrict__ sums_all, uint32_t n) {
+__global__ void __launch_bounds__(256) scan_sums_kernel(double* __restrict__ sums_all, uint32_t n, uint32_t first_eval,
+                                                        const EvalDesc* __restrict__ evals, const uint8_t* __restrict__ active,
+                                                        uint32_t active_stride) {
     __shared__ double part[256];
+    // (the caller's mask: uniform over the workgroup, in front of the first barrier)
+    if (active && masked_out(active, active_stride, evals ? evals[blockIdx.x].out_index : first_eval + blockIdx.x)) return;
     double* __restrict__ sums = sums_all + size_t(blockIdx.x) * n;
     const uint32_t per = (n + 255) / 256;
     const uint32_t lo = min(n, threadIdx.x * per), hi = min(n, lo + per);
@@ -2268,10 +2301,12 @@ __global__ void __launch_bounds__(256) sample_kernel(const double* __restrict__ 
                                                      const double* __restrict__ scanned_all, uint32_t n_chunks,
                                                      int shots, uint64_t seed, uint32_t first_eval,
                                                      const double* __restrict__ diag, uint64_t* __restrict__ out,
-                                                     double* __restrict__ out_values, const EvalDesc* __restrict__ evals) {
+                                                     double* __restrict__ out_values, const EvalDesc* __restrict__ evals,
+                                                     const uint8_t* __restrict__ active, uint32_t active_stride) {
     const int shot = blockIdx.x * blockDim.x + threadIdx.x;
     if (shot >= shots) return;
     const uint32_t slot = blockIdx.y, eval = evals ? evals[slot].out_index : first_eval + slot;
+    if (masked_out(active, active_stride, eval)) return;  // (the caller's mask: this slot's sums were never formed)
     const double* __restrict__ probs = probs_all + uint64_t(slot) * dim;
     const double* __restrict__ scanned = scanned_all + size_t(slot) * n_chunks;
     const double total = scanned[n_chunks - 1];
@@ -2299,13 +2334,15 @@ __global__ void __launch_bounds__(256) sample_kernel(const double* __restrict__ 
 
 hipError_t launch_sample(const double* probs, uint64_t dim, int n_slots, double* chunk_sums, int shots, uint64_t seed,
                          uint32_t first_eval, const double* diag, uint64_t* out, double* out_values,
-                         hipStream_t stream, const EvalDesc* evals) {
+                         hipStream_t stream, const EvalDesc* evals, ActiveMask active) {
     const uint32_t n_chunks = uint32_t((dim + kSampleChunk - 1) / kSampleChunk);
     const uint32_t sum_blocks = (n_chunks + 3) / 4 < 4096 ? (n_chunks + 3) / 4 : 4096;
-    hipLaunchKernelGGL(chunk_sums_kernel, dim3(sum_blocks, n_slots), dim3(256), 0, stream, probs, dim, chunk_sums, n_chunks);
-    hipLaunchKernelGGL(scan_sums_kernel, dim3(n_slots), dim3(256), 0, stream, chunk_sums, n_chunks);
+    hipLaunchKernelGGL(chunk_sums_kernel, dim3(sum_blocks, n_slots), dim3(256), 0, stream, probs, dim, chunk_sums, n_chunks,
+                       first_eval, evals, active.flags, active.stride);
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(n_slots), dim3(256), 0, stream, chunk_sums, n_chunks, first_eval, evals, active.flags,
+                       active.stride);
     hipLaunchKernelGGL(sample_kernel, dim3((shots + 255) / 256, n_slots), dim3(256), 0, stream, probs, dim, chunk_sums,
-                       n_chunks, shots, seed, first_eval, diag, out, out_values, evals);
+                       n_chunks, shots, seed, first_eval, diag, out, out_values, evals, active.flags, active.stride);
     return hipGetLastError();
 }
 
@@ -2314,8 +2351,11 @@ uint32_t sample_chunk_count(uint64_t dim) { return uint32_t((dim + kSampleChunk 
 // CVaR of one evaluation's sample values per workgroup (expectation_calculation.py:27-40 restated for equally weighted
 // samples): sort ascending, take probability mass alpha from the low end.
 __global__ void __launch_bounds__(1024) cvar_kernel(const double* __restrict__ values, int shots, int padded, double alpha,
-                                                   double* __restrict__ out) {
+                                                   double* __restrict__ out, const uint8_t* __restrict__ active, uint32_t active_stride) {
     extern __shared__ double sorted[];
+    // (the caller's mask: the evaluation drew no samples and out[blockIdx.x] keeps what it holds; uniform over the workgroup, in
+    // front of the first barrier)
+    if (masked_out(active, active_stride, blockIdx.x)) return;
     const double* v = values + size_t(blockIdx.x) * size_t(shots);
     for (int i = threadIdx.x; i < padded; i += blockDim.x) sorted[i] = i < shots ? v[i] : __builtin_huge_val();
     __syncthreads();
@@ -2357,7 +2397,8 @@ __global__ void __launch_bounds__(1024) cvar_kernel(const double* __restrict__ v
     }
 }
 
-hipError_t launch_cvar(const double* values, int n_evals, int shots, double alpha, double* out, hipStream_t stream) {
+hipError_t launch_cvar(const double* values, int n_evals, int shots, double alpha, double* out, hipStream_t stream,
+                       ActiveMask active) {
     if (shots < 1 || shots > kCvarMaxShots || !(alpha > 0.0) || alpha > 1.0) return hipErrorInvalidValue;
     int padded = 256;  // (at least one value per thread: the reduction tree reuses the buffer)
     while (padded < shots) padded <<= 1;
@@ -2365,7 +2406,19 @@ hipError_t launch_cvar(const double* values, int n_evals, int shots, double alph
     // 55 barrier-separated steps, and four values per thread and step made each of them longer)
     const int threads = padded < 1024 ? padded : 1024;
     hipLaunchKernelGGL(cvar_kernel, dim3(n_evals), dim3(threads), size_t(padded) * sizeof(double), stream, values, shots, padded,
-                       alpha, out);
+                       alpha, out, active.flags, active.stride);
+    return hipGetLastError();
+}
+
+__global__ void __launch_bounds__(256) masked_copy_kernel(const double* __restrict__ src, double* __restrict__ dst, int n,
+                                                          const uint8_t* __restrict__ active, uint32_t active_stride) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n && !masked_out(active, active_stride, uint32_t(e))) dst[e] = src[e];
+}
+
+hipError_t launch_masked_copy(const double* src, double* dst, int n, ActiveMask active, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(masked_copy_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, src, dst, n, active.flags, active.stride);
     return hipGetLastError();
 }
 
@@ -2502,10 +2555,12 @@ constexpr unsigned kSplitGramParts = 4;  // workgroups per evaluation
 template <typename real>
 __global__ void __launch_bounds__(256, 2) split_gram_kernel(const uint32_t* __restrict__ plan_arena, const EvalDesc* __restrict__ evals,
                                                             const cx<real>* __restrict__ sides, uint64_t side_stride,
-                                                            double* __restrict__ scratch, uint32_t slot_doubles, uint32_t cum_doubles) {
+                                                            double* __restrict__ scratch, uint32_t slot_doubles, uint32_t cum_doubles,
+                                                            const uint8_t* __restrict__ active, uint32_t active_stride) {
     __shared__ cx<real> stage[4 * 9 * 64];
     const EvalDesc ev = evals[blockIdx.y];
     if (!(ev.flags & kEvalSide)) return;
+    if (masked_out(active, active_stride, ev.out_index)) return;  // (the caller's mask: uniform, in front of the first barrier)
     const uint32_t* sp = plan_arena + ev.split_base;
     const uint32_t n_keys = sp[0], bits_y = sp[2];
     const bool swap = sp[3] & 1u;
@@ -2579,10 +2634,12 @@ __device__ void split_marginal_body(const cx<real>* __restrict__ X, uint32_t bit
 template <typename real>
 __global__ void __launch_bounds__(256, 2) split_marginal_kernel(const uint32_t* __restrict__ plan_arena, const EvalDesc* __restrict__ evals,
                                                                 const cx<real>* __restrict__ sides, uint64_t side_stride,
-                                                                double* __restrict__ scratch, uint32_t slot_doubles, uint32_t cum_doubles) {
+                                                                double* __restrict__ scratch, uint32_t slot_doubles, uint32_t cum_doubles,
+                                                                const uint8_t* __restrict__ active, uint32_t active_stride) {
     __shared__ double lds[256];
     const EvalDesc ev = evals[blockIdx.x];
     if (!(ev.flags & kEvalSide)) return;
+    if (masked_out(active, active_stride, ev.out_index)) return;  // (the caller's mask: uniform, in front of the first barrier)
     const uint32_t* sp = plan_arena + ev.split_base;
     const uint32_t n_keys = sp[0], bits_x = sp[1], bits_y = sp[2];
     const bool swap = sp[3] & 1u;
@@ -2769,10 +2826,12 @@ __global__ void __launch_bounds__(256, 8) split_sample_kernel(const uint32_t* __
                                                               const double* __restrict__ scratch, uint32_t slot_doubles,
                                                               uint32_t cum_doubles, uint32_t lds_doubles, int shots, uint64_t seed,
                                                               const double* __restrict__ diag, uint64_t* __restrict__ out,
-                                                              double* __restrict__ out_values) {
+                                                              double* __restrict__ out_values, const uint8_t* __restrict__ active,
+                                                              uint32_t active_stride) {
     extern __shared__ __align__(16) double split_lds[];
     const EvalDesc ev = evals[blockIdx.y];
     if (!(ev.flags & kEvalSide)) return;
+    if (masked_out(active, active_stride, ev.out_index)) return;  // (the caller's mask: uniform, in front of the first barrier)
     const uint32_t* sp = plan_arena + ev.split_base;
     const uint32_t n_keys = sp[0], bits_x = sp[1], bits_y = sp[2];
     const bool swap = sp[3] & 1u;
@@ -2798,14 +2857,14 @@ hipError_t launch_split_tables(int dtype, int side_bits, unsigned n_evals, doubl
     const dim3 gram_grid(kSplitGramParts, n_evals);
     if (dtype == 0) {
         hipLaunchKernelGGL(split_gram_kernel<double>, gram_grid, dim3(256), 0, stream, a.plan, a.evals,
-                           static_cast<const cx<double>*>(a.wtab), a.wtab_stride, scratch, slot, cum);
+                           static_cast<const cx<double>*>(a.wtab), a.wtab_stride, scratch, slot, cum, a.active.flags, a.active.stride);
         hipLaunchKernelGGL(split_marginal_kernel<double>, dim3(n_evals), dim3(256), 0, stream, a.plan, a.evals,
-                           static_cast<const cx<double>*>(a.wtab), a.wtab_stride, scratch, slot, cum);
+                           static_cast<const cx<double>*>(a.wtab), a.wtab_stride, scratch, slot, cum, a.active.flags, a.active.stride);
     } else {
         hipLaunchKernelGGL(split_gram_kernel<float>, gram_grid, dim3(256), 0, stream, a.plan, a.evals,
-                           static_cast<const cx<float>*>(a.wtab), a.wtab_stride, scratch, slot, cum);
+                           static_cast<const cx<float>*>(a.wtab), a.wtab_stride, scratch, slot, cum, a.active.flags, a.active.stride);
         hipLaunchKernelGGL(split_marginal_kernel<float>, dim3(n_evals), dim3(256), 0, stream, a.plan, a.evals,
-                           static_cast<const cx<float>*>(a.wtab), a.wtab_stride, scratch, slot, cum);
+                           static_cast<const cx<float>*>(a.wtab), a.wtab_stride, scratch, slot, cum, a.active.flags, a.active.stride);
     }
     return hipGetLastError();
 }
@@ -2822,10 +2881,12 @@ hipError_t launch_split_sample(int dtype, int side_bits, unsigned n_evals, const
     const dim3 grid(unsigned((shots + kSplitSampleShotsPerBlock - 1) / kSplitSampleShotsPerBlock), n_evals);
     if (dtype == 0)
         hipLaunchKernelGGL(split_sample_kernel<double>, grid, dim3(256), lds, stream, a.plan, a.evals,
-                           static_cast<const cx<double>*>(a.wtab), a.wtab_stride, scratch, slot, cum, lds_doubles, shots, seed, diag, out, out_values);
+                           static_cast<const cx<double>*>(a.wtab), a.wtab_stride, scratch, slot, cum, lds_doubles, shots, seed, diag, out, out_values,
+                           a.active.flags, a.active.stride);
     else
         hipLaunchKernelGGL(split_sample_kernel<float>, grid, dim3(256), lds, stream, a.plan, a.evals,
-                           static_cast<const cx<float>*>(a.wtab), a.wtab_stride, scratch, slot, cum, lds_doubles, shots, seed, diag, out, out_values);
+                           static_cast<const cx<float>*>(a.wtab), a.wtab_stride, scratch, slot, cum, lds_doubles, shots, seed, diag, out, out_values,
+                           a.active.flags, a.active.stride);
     return hipGetLastError();
 }
 
@@ -4016,9 +4077,11 @@ __global__ void __launch_bounds__(256) cvar_exact_chunks_kernel(const uint32_t* 
                                                                 const double* __restrict__ probs_all, uint64_t dim,
                                                                 const cx<real>* __restrict__ sides, uint64_t side_stride,
                                                                 const uint32_t* __restrict__ order, const double* __restrict__ sorted,
-                                                                uint32_t n_chunks, double* __restrict__ scratch) {
+                                                                uint32_t n_chunks, double* __restrict__ scratch,
+                                                                const uint8_t* __restrict__ active, uint32_t active_stride) {
     __shared__ double red[4];
     const EvalDesc ev = evals[blockIdx.y];
+    if (masked_out(active, active_stride, ev.out_index)) return;  // (the caller's mask: uniform, in front of the block sums)
     const ExactSource<real> src = exact_source<real>(plan_arena, ev, blockIdx.y, probs_all, dim, sides, side_stride);
     const uint64_t base = uint64_t(blockIdx.x) * kCvarChunk;
     double m = 0.0, w = 0.0;
@@ -4047,12 +4110,15 @@ __global__ void __launch_bounds__(256) cvar_exact_finish_kernel(const uint32_t* 
                                                                 const cx<real>* __restrict__ sides, uint64_t side_stride,
                                                                 const uint32_t* __restrict__ order, const double* __restrict__ sorted,
                                                                 uint32_t n_chunks, const double* __restrict__ scratch, double alpha,
-                                                                double* __restrict__ out) {
+                                                                double* __restrict__ out, const uint8_t* __restrict__ active,
+                                                                uint32_t active_stride) {
     __shared__ double sh_a[256], sh_b[256];
     __shared__ uint32_t sh_i[256];
     __shared__ double pick[4];
     __shared__ uint32_t pick_i[2];
     const EvalDesc ev = evals[blockIdx.x];
+    // (the caller's mask: no chunk sums were formed and out[ev.out_index] keeps what it holds; uniform, in front of the first barrier)
+    if (masked_out(active, active_stride, ev.out_index)) return;
     const uint32_t t = threadIdx.x;
     const double* mass = scratch + (size_t(blockIdx.x) * 2 + 0) * n_chunks;
     const double* wsum = scratch + (size_t(blockIdx.x) * 2 + 1) * n_chunks;
@@ -4197,14 +4263,18 @@ hipError_t launch_cvar_exact(int dtype, const double* probs, uint64_t dim, unsig
     const uint32_t n_chunks = cvar_exact_chunks(dim);
     if (dtype == 0) {
         hipLaunchKernelGGL(cvar_exact_chunks_kernel<double>, dim3(n_chunks, n_evals), dim3(256), 0, stream, a.plan, a.evals, probs, dim,
-                           static_cast<const cx<double>*>(a.wtab), a.wtab_stride, order, sorted_values, n_chunks, chunk_scratch);
+                           static_cast<const cx<double>*>(a.wtab), a.wtab_stride, order, sorted_values, n_chunks, chunk_scratch,
+                           a.active.flags, a.active.stride);
         hipLaunchKernelGGL(cvar_exact_finish_kernel<double>, dim3(n_evals), dim3(256), 0, stream, a.plan, a.evals, probs, dim,
-                           static_cast<const cx<double>*>(a.wtab), a.wtab_stride, order, sorted_values, n_chunks, chunk_scratch, alpha, out);
+                           static_cast<const cx<double>*>(a.wtab), a.wtab_stride, order, sorted_values, n_chunks, chunk_scratch, alpha, out,
+                           a.active.flags, a.active.stride);
     } else {
         hipLaunchKernelGGL(cvar_exact_chunks_kernel<float>, dim3(n_chunks, n_evals), dim3(256), 0, stream, a.plan, a.evals, probs, dim,
-                           static_cast<const cx<float>*>(a.wtab), a.wtab_stride, order, sorted_values, n_chunks, chunk_scratch);
+                           static_cast<const cx<float>*>(a.wtab), a.wtab_stride, order, sorted_values, n_chunks, chunk_scratch,
+                           a.active.flags, a.active.stride);
         hipLaunchKernelGGL(cvar_exact_finish_kernel<float>, dim3(n_evals), dim3(256), 0, stream, a.plan, a.evals, probs, dim,
-                           static_cast<const cx<float>*>(a.wtab), a.wtab_stride, order, sorted_values, n_chunks, chunk_scratch, alpha, out);
+                           static_cast<const cx<float>*>(a.wtab), a.wtab_stride, order, sorted_values, n_chunks, chunk_scratch, alpha, out,
+                           a.active.flags, a.active.stride);
     }
     return hipGetLastError();
 }

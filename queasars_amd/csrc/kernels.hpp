@@ -87,7 +87,22 @@ enum PassMode : uint32_t {
                              // meet in the memory-side cache); measurement knob QSV_TILE_MAJOR
     kModeFusedPrepare = 8u,  // (pass 0 only) every workgroup first does prepare_kernel's work for its evaluation, reading
                              // the descriptor from host_evals (PassArgs below); no prepare launch ran for these evaluations
+    kModeMasked = 2048u,     // (qsv_cvar_device only) PassArgs::active is given: the workgroups of an evaluation whose entry is 0
+                             // leave at once (masked_out below); without the bit a launch executes what it did before the mask existed
 };
+// The optional mask of a device-resident CVaR call (qsv.h: qsv_cvar_device): entry e / stride decides evaluation e (its out_index,
+// the caller's numbering), 0 = skipped.  flags == nullptr: every evaluation runs.  The flags are written by an EARLIER launch on
+// the same stream and are the same for every workgroup of an evaluation in every kernel of a call, so all of them take the same
+// branch; each kernel asks before its first barrier or hand-off.
+struct ActiveMask {
+    const uint8_t* flags = nullptr;
+    uint32_t stride = 1;
+};
+#if defined(__HIPCC__)
+__device__ __forceinline__ bool masked_out(const uint8_t* flags, uint32_t stride, uint32_t eval) {
+    return flags != nullptr && flags[eval / stride] == 0;
+}
+#endif
 
 struct PassArgs {
     const uint32_t* plan;  // plan arena
@@ -121,6 +136,7 @@ struct PassArgs {
     const void* prefix_states;  // kEvalPrefix: kept states, slot s at s * state_stride amplitudes (may be null otherwise)
     uint32_t dephase;           // (measurement knob QSV_DEPHASE) odd workgroups of a later pass sleep this many s_sleep(127) first
     const double* side_diag;    // the sides' own values of D (split block word kSplitSideDiag; may be null when no block names one)
+    ActiveMask active;          // kModeMasked (and the sampler path's own kernels, which take a null pointer as "no mask")
 };
 // LDS bytes the fused factor tail of a pass launch needs (up to eight waves form a side's Gram matrices)
 constexpr size_t kFusedFactorLdsBytes = 8 * (18 * 64 + 64) * sizeof(double) + 64;
@@ -194,7 +210,8 @@ inline __host__ __device__ size_t tile_info_offset(uint32_t n_real, uint32_t n_q
 // n_regions = 2: also descriptors [region_stride + i] (the second descriptors of split evaluations).
 // dtype != 0 (single precision): the gate matrices are left as floats (kernels.hip prepare_eval, float_mats).
 hipError_t launch_prepare(const uint32_t* plan, const EvalDesc* host_evals, EvalDesc* evals, const double* params,
-                          double* mats, int n_evals, hipStream_t stream, int n_regions = 1, uint32_t region_stride = 0, int dtype = 0);
+                          double* mats, int n_evals, hipStream_t stream, int n_regions = 1, uint32_t region_stride = 0, int dtype = 0,
+                          ActiveMask active = {});  // (active: evaluations it switches off get their device descriptor, nothing else)
 
 // Split evaluations (split.hpp): <psi|D|psi> with psi[i] = sum_kappa A_kappa[a(i)] B_kappa[b(i)] formed on the fly from
 // the two side tables; grid and partial-sum layout as the pass kernel's fused last pass (PassArgs: plan, evals, wtab,
@@ -316,9 +333,10 @@ hipError_t launch_observables_combine(const double* values, uint32_t n_terms, in
 // states; evaluation (first_eval + s) gets its own random stream and writes out[(first_eval + s) * shots ..].
 // chunk_sums: scratch of n_slots * sample_chunk_count(dim) doubles.  With diag != null, out_values receives D[state].
 // evals != null: slot s belongs to evaluation evals[s].out_index instead (a batch that put its split evaluations first).
+// active: slots of evaluations it switches off are left alone by all three kernels (nothing read, nothing written).
 hipError_t launch_sample(const double* probs, uint64_t dim, int n_slots, double* chunk_sums, int shots, uint64_t seed,
                          uint32_t first_eval, const double* diag, uint64_t* out, double* out_values,
-                         hipStream_t stream, const EvalDesc* evals = nullptr);
+                         hipStream_t stream, const EvalDesc* evals = nullptr, ActiveMask active = {});
 uint32_t sample_chunk_count(uint64_t dim);
 
 // Sampling a split evaluation (split.hpp) WITHOUT forming its 2^n probabilities.  With psi(x, y) = sum_j X_j[x] Y_j[y]
@@ -331,6 +349,7 @@ uint32_t sample_chunk_count(uint64_t dim);
 // launch_sample's (x-major), so the same seed gives different -- equally distributed -- samples.
 // PassArgs: plan, evals (device descriptors of the group, side A region), wtab / wtab_stride (side tables).
 // scratch: n_evals * split_sample_slot_doubles(side_bits) doubles, side_bits = the most qubits a virtual circuit may have.
+// PassArgs::active (may be empty): evaluations it switches off are skipped by all three kernels.
 size_t split_sample_slot_doubles(int side_bits);
 hipError_t launch_split_tables(int dtype, int side_bits, unsigned n_evals, double* scratch, hipStream_t stream, const PassArgs& args);
 hipError_t launch_split_sample(int dtype, int side_bits, unsigned n_evals, const double* scratch, int shots, uint64_t seed,
@@ -340,7 +359,12 @@ hipError_t launch_split_sample(int dtype, int side_bits, unsigned n_evals, const
 // out[first_eval + e] = CVaR_alpha of values[e * shots .. (e + 1) * shots) for e < n_evals (shots <= kCvarMaxShots):
 // bitonic sort in LDS, fixed-order sum of the lowest alpha * shots values (the boundary value weighted fractionally).
 constexpr int kCvarMaxShots = 4096;
-hipError_t launch_cvar(const double* values, int n_evals, int shots, double alpha, double* out, hipStream_t stream);
+// active: out[e] of an evaluation it switches off is left untouched.
+hipError_t launch_cvar(const double* values, int n_evals, int shots, double alpha, double* out, hipStream_t stream,
+                       ActiveMask active = {});
+
+// dst[e] = src[e] for the evaluations e < n the mask leaves on (qsv_cvar_device's alpha = 1, whose values the expectation routes form)
+hipError_t launch_masked_copy(const double* src, double* dst, int n, ActiveMask active, hipStream_t stream);
 
 // ---- exact-probability CVaR (the sampler branch without sampling noise) ---------------------------------------------------
 // order[j] = the basis state of rank j when the states are sorted by their value under the diagonal operator (ties in index
@@ -354,7 +378,8 @@ hipError_t sort_states_by_value(const double* values, uint64_t dim, uint32_t* or
 // circuit (|sum_j X_j[x(i)] Y_j[y(i)]|^2, formed per state; at most three keys).  Two launches: sums per chunk of
 // kCvarChunk ranks (mass and mass x value; fixed order), then per evaluation the chunk in which the mass is reached and
 // the rank inside it.  PassArgs: plan, evals (the group's device descriptors), wtab / wtab_stride (side tables).
-// chunk_scratch: 2 * n_evals * cvar_exact_chunks(dim) doubles.  out[evals[e].out_index] receives the result.
+// chunk_scratch: 2 * n_evals * cvar_exact_chunks(dim) doubles.  out[evals[e].out_index] receives the result (PassArgs::active:
+// not for an evaluation it switches off, whose workgroups leave both kernels at once).
 constexpr uint32_t kCvarChunk = 4096;
 inline uint32_t cvar_exact_chunks(uint64_t dim) { return uint32_t((dim + kCvarChunk - 1) / kCvarChunk); }
 hipError_t launch_cvar_exact(int dtype, const double* probs, uint64_t dim, unsigned n_evals, const uint32_t* order,

@@ -351,6 +351,19 @@ struct qsv_handle {
                                              // where evaluation 0's values would be -- descriptors index it like the staging buffer
     } batch;
     std::unique_lock<std::mutex> batch_lock;  // held from begin to end
+    // qsv_cvar_device: its device_active for the duration of the call (run_group and batch_ship hand it to their launches) ...
+    ActiveMask mask;
+    const void* cvar_checked[3] = {nullptr, nullptr, nullptr};  // its values / output / mask pointers last found to be this device's memory
+    // ... and the layout its last call left in the staging buffer (descriptors ordered and slotted, batch.eval_at / split /
+    // param_base): valid while `epoch` is the handle's, for a call with the same circuits, row width and kind
+    struct CvarSnap {
+        uint64_t epoch = 0;
+        std::vector<int> ids;
+        int width = -1;
+        bool sampled = false;
+        size_t n_split = 0;
+        std::vector<std::pair<size_t, size_t>> groups;
+    } cvar_snap;
 
     // profiling
     bool profiling = false;
@@ -1128,7 +1141,7 @@ int batch_ship(qsv_t* h, size_t first, size_t count, const double* values, size_
     if (count > n_fused)
         QSV_HIP(h, launch_prepare(static_cast<const uint32_t*>(h->d_arena.ptr), host_evals + first + n_fused,
                                   static_cast<EvalDesc*>(h->d_batch.ptr) + first + n_fused, ship_params,
-                                  static_cast<double*>(h->d_mats.ptr), int(count - n_fused), ws(h), 1, 0, h->dtype));
+                                  static_cast<double*>(h->d_mats.ptr), int(count - n_fused), ws(h), 1, 0, h->dtype, h->mask));
     return QSV_OK;
 }
 
@@ -1219,7 +1232,9 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
     }
     const bool any_split = n_split > 0;
     const size_t n_plain = count - n_split;
+    if (h->mask.flags) mode |= kModeMasked;  // (qsv_cvar_device with a mask: every launch below carries the bit and the pointer)
     PassArgs a{};
+    a.active = h->mask;
     a.plan = static_cast<const uint32_t*>(h->d_arena.ptr);
     a.mats = static_cast<const double*>(h->d_mats.ptr);
     a.evals = batch_evals(h) + first;
@@ -1991,6 +2006,9 @@ struct BatchArgs {
     std::vector<Circuit*> circs;
     std::vector<int64_t> n_params;
     std::vector<double> values;
+    // the values live in DEVICE memory instead (qsv_cvar_device): evaluation e's are row e of a row-major matrix whose row
+    // length every entry of n_params holds, as qsv_eval_push_device documents; `values` is not looked at
+    const double* device_values = nullptr;
 };
 
 // Looks up circuit_ids[0, n) and packs what each evaluation's param_offsets declare (params == nullptr: an empty array;
@@ -2042,40 +2060,107 @@ struct StateRun {
 // own, which run_group requires -- those on kept states.  An evaluation's slot is its position in its launch group.  After
 // each group, on_split / on_state(first, count) launches the caller's consumer of positions [first, first + count);
 // batch.eval_at maps positions back to evaluations, also after the return.
+//
+// Two halves, so that a caller whose batch repeats (qsv_cvar_device) lays it out once: lay_out_states writes the staging
+// buffer -- it waits for a batch that ended without waiting first, batch_layout --, run_laid_out only reads it.  Everything
+// run_laid_out enqueues goes to the handle's own stream: run_group leaves it for the second lane or the chain stream only on the
+// expectation routes (two_chains needs evaluations the launch of the virtual circuits finishes, which kModeSidesOnly has none of;
+// h->work is null outside a push).
 using GroupFn = std::function<int(size_t, size_t)>;
-int run_to_states(qsv_t* h, const BatchArgs& args, const StateRun& run, const GroupFn& on_split, const GroupFn& on_state) {
-    struct Release {
-        qsv_t* h;
-        ~Release() { h->batch.circs.clear(); }
-    } release{h};
+struct StateLayout {
+    size_t n_split = 0;
+    std::vector<std::pair<size_t, size_t>> groups;  // (first position, count) of every launch group
+};
+struct BatchRelease {  // what a batch run through these two holds: released on every exit path
+    qsv_t* h;
+    ~BatchRelease() {
+        h->batch.circs.clear();
+        h->batch.dev_params = nullptr;
+        h->batch.repeat = false;
+    }
+};
+int lay_out_states(qsv_t* h, const BatchArgs& args, const StateRun& run, StateLayout& lay) {
     const size_t n = args.circs.size();
-    h->prof = qsv_profile{};
     int rc = batch_layout(h, args.circs, args.n_params, run.rule);
     if (rc) return rc;
     size_t n_cont = 0;
-    const size_t n_split = order_split_first(h, 0, n, &n_cont);
-    std::vector<std::pair<size_t, size_t>> groups;
+    lay.n_split = order_split_first(h, 0, n, &n_cont);
+    lay.groups.clear();
     auto cut = [&](size_t lo, size_t hi, size_t size) {
-        for (size_t g0 = lo; g0 < hi; g0 += size) groups.emplace_back(g0, std::min(size, hi - g0));
+        for (size_t g0 = lo; g0 < hi; g0 += size) lay.groups.emplace_back(g0, std::min(size, hi - g0));
     };
-    cut(0, n_split, run.split_group);
-    cut(n_split, n - n_cont, run.state_group);
+    cut(0, lay.n_split, run.split_group);
+    cut(lay.n_split, n - n_cont, run.state_group);
     cut(n - n_cont, n, run.state_group);
     EvalDesc* hd = static_cast<EvalDesc*>(h->h_batch);
-    for (const auto& g : groups)
+    for (const auto& g : lay.groups)
         for (size_t j = g.first; j < g.first + g.second; ++j) {
             hd[j].state_slot = uint32_t(j - g.first);
             if (h->batch.split_any) hd[n + j].state_slot = uint32_t(j - g.first);
         }
-    if ((rc = ensure(h, h->d_partials, std::max<size_t>(1, n) * partials_per_state(h) * sizeof(double)))) return rc;
-    if ((rc = batch_ship(h, 0, n, args.values.data(), run.prepare_in_pass ? n : n_split))) return rc;
-    for (const auto& g : groups) {
-        const bool split = g.first < n_split;
+    return ensure(h, h->d_partials, std::max<size_t>(1, n) * partials_per_state(h) * sizeof(double));
+}
+int run_laid_out(qsv_t* h, const BatchArgs& args, const StateRun& run, const StateLayout& lay, const GroupFn& on_split,
+                 const GroupFn& on_state) {
+    const size_t n = args.circs.size();
+    int rc;
+    // (rows in device memory: the descriptors' offsets are e * width, so the base is the matrix itself)
+    h->batch.dev_params = args.device_values;
+    if ((rc = batch_ship(h, 0, n, args.values.data(), run.prepare_in_pass ? n : lay.n_split))) return rc;
+    for (const auto& g : lay.groups) {
+        const bool split = g.first < lay.n_split;
         if ((rc = run_group(h, args.circs, g.first, g.second, split ? run.split_mode : run.state_mode))) return rc;
         const GroupFn& consume = split ? on_split : on_state;
         if (consume && (rc = consume(g.first, g.second))) return rc;
     }
     return QSV_OK;
+}
+int run_to_states(qsv_t* h, const BatchArgs& args, const StateRun& run, const GroupFn& on_split, const GroupFn& on_state) {
+    BatchRelease release{h};
+    StateLayout lay;
+    h->prof = qsv_profile{};
+    const int rc = lay_out_states(h, args, run, lay);
+    return rc ? rc : run_laid_out(h, args, run, lay, on_split, on_state);
+}
+
+// What qsv_cvar_device has and the host forms of the sampler branch do not: the ids and row width its layout is remembered
+// by, and device memory for the results.  Such a call does not wait, so the next one that writes the staging buffer must
+// (batch_layout, async_pending) -- unless it is the same batch again, the next iteration of a search: then the layout the last
+// call left is used as it stands (handle: cvar_snap), the kernels read the descriptors from the device copy that call's kernels
+// made (batch.repeat, descs_base), and the host neither writes a staging buffer nor waits.
+struct DeviceCall {
+    const int* ids;
+    int width;
+    bool sampled;
+    double* out;
+};
+int run_states(qsv_t* h, const BatchArgs& args, const StateRun& run, const GroupFn& on_split, const GroupFn& on_state,
+               const DeviceCall* dev) {
+    if (!dev) return run_to_states(h, args, run, on_split, on_state);
+    BatchRelease release{h};
+    qsv_handle::CvarSnap& snap = h->cvar_snap;
+    const size_t n = args.circs.size();
+    StateLayout lay;
+    h->prof = qsv_profile{};
+    if (h->repeat_enabled && snap.epoch == h->epoch && snap.width == dev->width && snap.sampled == dev->sampled && snap.ids.size() == n &&
+        std::equal(snap.ids.begin(), snap.ids.end(), dev->ids)) {
+        h->batch.circs = args.circs;
+        h->batch.repeat = true;
+        lay.n_split = snap.n_split;
+        lay.groups = snap.groups;
+    } else {
+        snap.epoch = 0;
+        const int rc = lay_out_states(h, args, run, lay);
+        if (rc) return rc;
+        snap.ids.assign(dev->ids, dev->ids + n);
+        snap.width = dev->width;
+        snap.sampled = dev->sampled;
+        snap.n_split = lay.n_split;
+        snap.groups = lay.groups;
+    }
+    const int rc = run_laid_out(h, args, run, lay, on_split, on_state);
+    snap.epoch = rc ? 0 : h->epoch;
+    return rc;
 }
 
 // The final state of one circuit in slot 0 (statevector / probabilities).
@@ -3178,9 +3263,14 @@ static const char* const kNotSampled = "circuits on kept states are not sampled 
 // Sampler branch for a whole batch: run the circuits group by group, turn each resident state into probabilities,
 // draw `shots` samples per evaluation on the device and (for a diagonal operator) gather each sample's value D[state].
 // out_cvar != null: the samples and their values stay on the device, only CVaR_alpha per evaluation comes back.
+// dev != null (qsv_cvar_device): ... and goes to dev->out in device memory, and the call returns without waiting.  Which calls
+// can allocate: one whose d_scratch has to grow (more evaluations x shots, or the first call of a handle), and whatever
+// batch_layout needs for a batch it has not laid out before; ensure() waits for the handle's streams before it frees.  A search
+// that repeats one shape allocates in its first iteration only.
 static int sample_batch_locked(qsv_t* h, const BatchArgs& args, int shots, uint64_t seed, uint64_t* out_states,
-                               double* out_values, double alpha = 1.0, double* out_cvar = nullptr) {
+                               double* out_values, double alpha = 1.0, double* out_cvar = nullptr, const DeviceCall* dev = nullptr) {
     const size_t n_evals = args.circs.size();
+    if (dev) out_cvar = dev->out;
     if (n_evals == 0 || shots == 0) return QSV_OK;
     if ((out_values || out_cvar) && !(h->has_diag_part && h->diagonal))
         return fail(h, QSV_E_STATE, "sample values need a diagonal operator (call qsv_set_operator with I/Z terms only)");
@@ -3198,7 +3288,7 @@ static int sample_batch_locked(qsv_t* h, const BatchArgs& args, int shots, uint6
     const size_t dev_samples_off = ((split_off + split_bytes + 63) / 64) * 64;
     int rc;
     if ((rc = ensure(h, h->d_scratch, dev_samples_off + (out_cvar ? 2 * out_bytes : 0)))) return rc;
-    if (out_cvar && (rc = ensure_host_out(h, n_evals))) return rc;
+    if (out_cvar && !dev && (rc = ensure_host_out(h, n_evals))) return rc;
     // samples (and their operator values) are written by the kernel straight into pinned host memory: no copy operations
     if (!out_cvar && h->h_samples_bytes < 2 * out_bytes) {
         if (h->h_samples) {
@@ -3231,6 +3321,7 @@ static int sample_batch_locked(qsv_t* h, const BatchArgs& args, int shots, uint6
         a.evals = batch_evals(h) + g0;
         a.wtab = h->d_side.ptr;
         a.wtab_stride = h->side_stride;
+        a.active = h->mask;
         QSV_HIP(h, launch_split_tables(h->dtype, h->geo.k + kSideExtraBits, unsigned(gc), split_scratch, h->stream, a));
         uint32_t table_doubles = 64;  // the largest Gram table of the group (whichever side the contraction calls Y)
         for (size_t i = 0; i < gc; ++i) {
@@ -3245,13 +3336,19 @@ static int sample_batch_locked(qsv_t* h, const BatchArgs& args, int shots, uint6
     auto on_state = [&](size_t g0, size_t gc) -> int {
         if (!probs_in_pass) QSV_HIP(h, launch_probabilities(h->dtype, h->d_states.ptr, dim, int(gc), probs, h->stream));
         QSV_HIP(h, launch_sample(probs, dim, int(gc), sums, shots, seed, uint32_t(g0), diag, d_states, d_values, h->stream,
-                                 n_split ? batch_evals(h) + g0 : nullptr));
+                                 n_split ? batch_evals(h) + g0 : nullptr, h->mask));
         return QSV_OK;
     };
     const StateRun run{rule, SG, G, fuse, kModeSynthFirst | kModeFinalStore | kModeSidesOnly,
                        kModeSynthFirst | (probs_in_pass ? kModeFinalProbs : kModeFinalStore) | (fuse ? kModeFusedPrepare : 0u)};
-    if ((rc = run_to_states(h, args, run, on_split, on_state))) return rc;
-    if (out_cvar) QSV_HIP(h, launch_cvar(d_values, int(n_evals), shots, alpha, h->h_out, h->stream));
+    if ((rc = run_states(h, args, run, on_split, on_state, dev))) return rc;
+    // (evaluation e's values are at d_values[e * shots ..] in the caller's numbering -- the sample kernels address by the
+    // descriptor's out_index, or by first_eval + slot in a batch nothing reordered --, so workgroup e writes out[e])
+    if (out_cvar) QSV_HIP(h, launch_cvar(d_values, int(n_evals), shots, alpha, dev ? dev->out : h->h_out, h->stream, h->mask));
+    if (dev) {  // (everything above went to the handle's stream: complete once the work enqueued so far on it is)
+        h->async_pending = true;
+        return QSV_OK;
+    }
     QSV_HIP(h, hipStreamSynchronize(h->stream));
     if (out_cvar) {
         std::memcpy(out_cvar, h->h_out, n_evals * sizeof(double));
@@ -3264,7 +3361,11 @@ static int sample_batch_locked(qsv_t* h, const BatchArgs& args, int shots, uint6
 
 // Exact-probability CVaR for a whole batch: the circuits group by group as in the sampler branch (split circuits as their
 // two virtual circuits, the others with the probabilities written by their last gate pass), then launch_cvar_exact.
-static int exact_cvar_locked(qsv_t* h, const BatchArgs& args, double alpha, double* out_cvar) {
+// dev != null (qsv_cvar_device): the results go to dev->out in device memory and the call returns without waiting.  It can
+// allocate where sample_batch_locked can, and the first call after qsv_set_operator sorts the operator's values, which
+// allocates and waits (sort_states_by_value).
+static int expectation_to_device(qsv_t* h, const BatchArgs& args, double* device_out);
+static int exact_cvar_locked(qsv_t* h, const BatchArgs& args, double alpha, double* out_cvar, const DeviceCall* dev = nullptr) {
     const size_t n_evals = args.circs.size();
     if (n_evals == 0) return QSV_OK;
     if (!(h->has_diag_part && h->diagonal))
@@ -3273,10 +3374,14 @@ static int exact_cvar_locked(qsv_t* h, const BatchArgs& args, double alpha, doub
     // alpha = 1 (numpy.isclose(alpha, 1), the reference's test): the reference takes the plain mean of the values there
     // (expectation_calculation.py:55-69), not its accumulation loop, whose stopping rule leaves out the last 1e-5 of the mass
     // (5e-4 of an Ising value at 20 qubits): the expectation value, as qsv_eval_circuits computes it
-    if (std::fabs(alpha - 1.0) <= 1e-8 + 1e-5) return eval_all(h, args, out_cvar);
+    if (std::fabs(alpha - 1.0) <= 1e-8 + 1e-5) return dev ? expectation_to_device(h, args, dev->out) : eval_all(h, args, out_cvar);
     const uint64_t dim = uint64_t(1) << h->n;
     int rc;
     if (!h->order_valid) {
+        if (h->async_pending) {  // (it allocates: not beside a batch that ended without waiting)
+            QSV_HIP(h, sync_streams(h));
+            h->async_pending = false;
+        }
         if ((rc = ensure(h, h->d_order, dim * sizeof(uint32_t))) || (rc = ensure(h, h->d_sorted, dim * sizeof(double)))) return rc;
         QSV_HIP(h, sort_states_by_value(static_cast<const double*>(h->d_diag.ptr), dim, static_cast<uint32_t*>(h->d_order.ptr),
                                         static_cast<double*>(h->d_sorted.ptr), h->stream));
@@ -3290,7 +3395,8 @@ static int exact_cvar_locked(qsv_t* h, const BatchArgs& args, double alpha, doub
     const size_t chunk_off = ((probs_bytes + 63) / 64) * 64;
     const size_t chunk_bytes = 2 * std::max(G, std::min(SG, std::max<size_t>(1, n_split))) * size_t(n_chunks) * 8;
     if ((rc = ensure(h, h->d_scratch, chunk_off + chunk_bytes))) return rc;
-    if ((rc = ensure_host_out(h, n_evals))) return rc;
+    if (!dev && (rc = ensure_host_out(h, n_evals))) return rc;
+    double* const result = dev ? dev->out : h->h_out;  // (written at out_index, the caller's numbering: nothing to un-permute)
     double* probs = static_cast<double*>(h->d_scratch.ptr);
     double* chunk_scratch = reinterpret_cast<double*>(static_cast<char*>(h->d_scratch.ptr) + chunk_off);
     const bool fuse = h->geo.blocks_per_state == 1;
@@ -3303,15 +3409,52 @@ static int exact_cvar_locked(qsv_t* h, const BatchArgs& args, double alpha, doub
         a.wtab = h->d_side.ptr;
         a.wtab_stride = h->side_stride;
         a.evals = batch_evals(h) + g0;
-        QSV_HIP(h, launch_cvar_exact(h->dtype, probs, dim, unsigned(gc), order, sorted, alpha, chunk_scratch, h->h_out, h->stream, a));
+        a.active = h->mask;
+        QSV_HIP(h, launch_cvar_exact(h->dtype, probs, dim, unsigned(gc), order, sorted, alpha, chunk_scratch, result, h->stream, a));
         return QSV_OK;
     };
     const StateRun run{rule, SG, G, fuse, kModeSynthFirst | kModeFinalStore | kModeSidesOnly,
                        kModeSynthFirst | kModeFinalProbs | (fuse ? kModeFusedPrepare : 0u)};
-    if ((rc = run_to_states(h, args, run, consume, consume))) return rc;
+    if ((rc = run_states(h, args, run, consume, consume, dev))) return rc;
+    if (dev) {
+        h->async_pending = true;
+        return QSV_OK;
+    }
     QSV_HIP(h, hipStreamSynchronize(h->stream));
     std::memcpy(out_cvar, h->h_out, n_evals * sizeof(double));
     return QSV_OK;
+}
+
+// alpha = 1 of the exact form with values and results in device memory: the expectation values, as a batch with
+// qsv_eval_push_device and qsv_eval_set_output computes them; with a mask they go through d_scratch, and a copy kernel leaves
+// the entries of switched-off evaluations alone (those evaluations do run: the expectation routes do not know the mask).
+static int expectation_to_device(qsv_t* h, const BatchArgs& args, double* device_out) {
+    const size_t n = args.circs.size();
+    const ActiveMask mask = h->mask;
+    h->mask = ActiveMask{};
+    int rc = QSV_OK;
+    if (mask.flags) rc = ensure(h, h->d_scratch, n * sizeof(double));
+    if (!rc) rc = eval_begin(h, args.circs, args.n_params);
+    if (!rc) {
+        h->out_target = mask.flags ? static_cast<double*>(h->d_scratch.ptr) : device_out;
+        h->batch.ways = 1;  // (every push on the handle's own stream, and the ordinary evaluations of a mixed batch behind whatever
+                            // the caller queued there: qsv_eval_set_output)
+        if (h->batch.aux_plain && h->aux_stream >= 0) {
+            hipError_t e = hipEventRecord(h->ev_join, h->stream);
+            if (e == hipSuccess) e = hipStreamWaitEvent(h->side_streams[size_t(h->aux_stream)], h->ev_join, 0);
+            if (e != hipSuccess) rc = fail(h, QSV_E_DEVICE, std::string("joining the auxiliary stream: ") + hipGetErrorString(e));
+        }
+    }
+    if (!rc) rc = eval_push(h, 0, n, kNoValues, args.device_values);
+    if (!rc) rc = eval_end(h, nullptr);
+    if (!rc && h->profiling) h->async_pending = true;  // (a profiled batch waits in eval_end; harmless)
+    if (!rc && mask.flags) {
+        hipError_t e = launch_masked_copy(static_cast<const double*>(h->d_scratch.ptr), device_out, int(n), mask, h->stream);
+        if (e != hipSuccess) rc = fail(h, QSV_E_DEVICE, std::string("launch_masked_copy: ") + hipGetErrorString(e));
+    }
+    if (rc) (void)sync_streams(h);
+    eval_close(h);
+    return rc;
 }
 
 int qsv_sample_batch(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
@@ -3350,6 +3493,53 @@ int qsv_exact_cvar_batch(qsv_t* h, int n_evals, const int* circuit_ids, const in
     BatchArgs args;
     int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args, kNotSampled);
     return rc ? rc : exact_cvar_locked(h, args, alpha, out_cvar);
+}
+
+int qsv_cvar_device(qsv_t* h, int n_evals, const int* circuit_ids, int width, const double* device_values, void* ready_event,
+                    int shots, uint64_t seed, double alpha, const uint8_t* device_active, int active_stride, double* device_out) {
+    if (!h) return QSV_E_ARG;
+    if (h->batch_owner.load() == std::this_thread::get_id())
+        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_cvar_device goes between batches)");
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (n_evals < 0 || shots < 0 || width < 0 || (n_evals > 0 && (!circuit_ids || !device_out || (width > 0 && !device_values))))
+        return fail(h, QSV_E_ARG, "bad arguments");
+    if (device_active && active_stride < 1) return fail(h, QSV_E_ARG, "active_stride must be at least 1");
+    if (!(alpha > 0.0) || alpha > 1.0) return fail(h, QSV_E_ARG, "alpha must be in (0, 1]");
+    if (shots > kCvarMaxShots) return fail(h, QSV_E_ARG, "the device-side CVaR sorts at most 4096 samples per evaluation");
+    if (n_evals == 0) return QSV_OK;
+    QSV_HIP(h, hipSetDevice(h->device));
+    // (a search hands over the same three buffers call after call: each is asked about once)
+    const void* given[3] = {width > 0 ? device_values : nullptr, device_out, device_active};
+    static const char* const names[3] = {"device_values", "device_out", "device_active"};
+    for (int i = 0; i < 3; ++i) {
+        if (!given[i] || given[i] == h->cvar_checked[i]) continue;
+        hipPointerAttribute_t attr{};
+        if (hipPointerGetAttributes(&attr, given[i]) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != h->device) {
+            (void)hipGetLastError();
+            return fail(h, QSV_E_ARG, std::string(names[i]) + " is not memory of this handle's device");
+        }
+        h->cvar_checked[i] = given[i];
+    }
+    BatchArgs args;
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, nullptr, nullptr, args, kNotSampled);
+    if (rc) return rc;
+    args.n_params.assign(size_t(n_evals), int64_t(width));
+    args.device_values = width > 0 ? device_values : nullptr;
+    // (all work of the call goes to the handle's stream -- run_laid_out --, so that is the stream that waits for the values)
+    if (ready_event) QSV_HIP(h, hipStreamWaitEvent(h->stream, static_cast<hipEvent_t>(ready_event), 0));
+    struct Unmask {
+        qsv_t* h;
+        ~Unmask() { h->mask = ActiveMask{}; }
+    } unmask{h};
+    if (device_active) h->mask = ActiveMask{device_active, uint32_t(active_stride)};
+    const DeviceCall dev{circuit_ids, width, shots > 0, device_out};
+    rc = shots > 0 ? sample_batch_locked(h, args, shots, seed, nullptr, nullptr, alpha, nullptr, &dev)
+                   : exact_cvar_locked(h, args, alpha, nullptr, &dev);
+    if (rc) {  // nothing of a failed call may still be running
+        (void)sync_streams(h);
+        h->cvar_snap.epoch = 0;
+    }
+    return rc;
 }
 
 int qsv_observables_create(qsv_t* h, int n_observables, const int64_t* term_offsets, const uint64_t* x_mask, const uint64_t* z_mask,

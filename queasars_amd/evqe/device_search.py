@@ -5,7 +5,7 @@ hands them to the evaluator (packing, PCIe), waits for the 2 R values and update
 the host does its share (8.0 ms per search of 64 individuals at 20 qubits, of which the device is busy for 3).  Here the
 iterates, the pre-drawn sign vectors, the points and the function values are tensors in device memory, the evaluator reads
 the points where they are and leaves the values where the update reads them (``qsv_eval_push_device`` /
-``qsv_eval_set_output``), and everything of an iteration -- proposal, evaluation, update, the termination rule -- is queued
+``qsv_eval_set_output`` for the exact estimator, ``qsv_cvar_device`` for the sampler evaluator's CVaR), and everything of an iteration -- proposal, evaluation, update, the termination rule -- is queued
 on ONE HIP stream without the host waiting for any of it; the host looks at the device every few iterations only to see
 whether every run has stopped.
 
@@ -16,7 +16,12 @@ driver's in the last bits (tests hold the two to 1e-9 and to the same stopping i
 reference's ``SPSATerminationChecker`` (queasars/utility/spsa_termination.py:46-94) as array operations; the runs' host-side
 checker objects are not fed (nothing reads them afterwards).  Runs that have stopped stay in the batch with their updates
 masked -- taking them out would mean waiting for the device --, and are not counted: ``nfev`` is two per iteration a run
-was active, as on the host.
+was active, as on the host.  An evaluator whose ``evaluate_device_to_device`` takes a mask (the sampler evaluator) is handed
+the runs' ``active`` flags, so that the two evaluations of a stopped run cost a dispatch and nothing else.
+
+With a sampling evaluator (``sampler_shots`` given) every iteration draws one seed from the evaluator's generator, as an
+``evaluate_circuits`` call of the host driver does -- also the up to ``look_every - 1`` iterations queued after the last run
+has stopped and before the host has looked: the generator then stands further on than after the same search on the host.
 """
 
 from __future__ import annotations
@@ -28,7 +33,9 @@ _MAX_SIGN_BYTES = 256 << 20
 
 
 def supported(evaluator, jobs) -> bool:
-    """Can :func:`minimize_spsa_on_device` take these jobs?  An exact estimator on a GPU, fresh SPSA runs of one configuration."""
+    """Can :func:`minimize_spsa_on_device` take these jobs?  An evaluator that reads points from and leaves values in device
+    memory (the exact estimator; the sampler evaluator with the exact distribution or up to 4096 shots) on a GPU, fresh SPSA
+    runs of one configuration."""
     if len(jobs) < 2 or not hasattr(evaluator, "evaluate_device_to_device"):
         return False
     if not evaluator.device_resident_search_possible():
@@ -49,7 +56,9 @@ def supported(evaluator, jobs) -> bool:
 
 def minimize_spsa_on_device(evaluator, jobs, look_every: int = 8) -> None:
     """One launch per iteration for the optimiser's share (``qsv_spsa_step``: accept iteration k, propose iteration k + 1) and
-    one for the evaluation.  ``QSV_DEVICE_SEARCH_TORCH=1``: the same arithmetic as a few dozen torch operations per
+    one chain for the evaluation, which is all this function asks of the evaluator (``evaluate_device_to_device``; where that
+    method takes ``active`` it gets the runs' flags, two evaluations per entry).  The iterations queued between the last run's
+    stop and the host's next look (``look_every``) also advance a sampling evaluator's generator.  ``QSV_DEVICE_SEARCH_TORCH=1``: the same arithmetic as a few dozen torch operations per
     iteration (:func:`_minimize_with_torch_operations`; the tests hold the two against each other)."""
     import ctypes as C
     import os
@@ -88,6 +97,7 @@ def minimize_spsa_on_device(evaluator, jobs, look_every: int = 8) -> None:
     caller = torch.cuda.current_stream(device)
     stream.wait_stream(caller)
     lib, handle = dev._lib, dev._handle
+    takes_mask = _takes_mask(evaluator)
     with torch.cuda.stream(stream):
         x = torch.from_numpy(x_host).to(device)
         signs = torch.from_numpy(signs_host).to(device).to(torch.float64)
@@ -116,7 +126,10 @@ def minimize_spsa_on_device(evaluator, jobs, look_every: int = 8) -> None:
                 break
             if k > 0 and k % look_every == 0 and not bool(active.any()):
                 break
-            evaluator.evaluate_device_to_device(circuits, points, values)
+            if takes_mask:
+                evaluator.evaluate_device_to_device(circuits, points, values, active=active, active_stride=2)
+            else:
+                evaluator.evaluate_device_to_device(circuits, points, values)
         x_final = x.cpu().numpy()
         done_iterations = iterations.cpu().numpy()
     caller.wait_stream(stream)
@@ -125,6 +138,20 @@ def minimize_spsa_on_device(evaluator, jobs, look_every: int = 8) -> None:
         run.iteration = int(done_iterations[i])
         run.nfev = 2 * int(done_iterations[i])
         run.done = True
+
+
+def _takes_mask(evaluator) -> bool:
+    """Does the evaluator's ``evaluate_device_to_device`` accept the runs' ``active`` flags?  (``QSV_DEVICE_SEARCH_MASK=0``: do
+    not hand them over -- the measurement of what the mask saves.)"""
+    import inspect
+    import os
+
+    if os.environ.get("QSV_DEVICE_SEARCH_MASK") == "0":
+        return False
+    try:
+        return "active" in inspect.signature(evaluator.evaluate_device_to_device).parameters
+    except (TypeError, ValueError):
+        return False
 
 
 def _minimize_with_torch_operations(evaluator, jobs, look_every: int = 8) -> None:

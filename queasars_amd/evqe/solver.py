@@ -324,14 +324,26 @@ def _minimize_spsa_vectorised(evaluator, jobs: list) -> None:
         run.nfev = int(nfev[i])
 
 
-def _device_search_wanted(evaluator, n_runs: int, flag: Optional[bool], optimizer) -> bool:
-    """Will a search of ``n_runs`` fresh runs of ``optimizer`` keep its state on the device (_minimize_batched's rule)?"""
+def _device_search_asked_for(evaluator, n_runs: int, flag: Optional[bool]) -> bool:
+    """What the configuration's ``device_resident_search`` (``flag``) and ``QSV_DEVICE_SEARCH`` say about a search of ``n_runs``
+    runs, before anyone asks whether it can be done.  ``None`` is "where it pays" -- searches of at least
+    ``_DEVICE_SEARCH_MIN_RUNS`` runs -- for an evaluator whose ``device_resident_search_by_default`` is true (the exact
+    estimator), and the host driver for every other one (a sampling evaluator: the device search is opt-in there, so that runs
+    configured before it existed keep their numbers).  The one place that resolves the default: ``_device_search_wanted``,
+    which also decides whether layer searches embed their runs, and ``_minimize_batched`` both ask here."""
     env = os.environ.get("QSV_DEVICE_SEARCH")
-    if env == "0" or os.environ.get("QSV_SCALAR_SPSA") or not isinstance(optimizer, SPSA) or n_runs < 2:
+    if env == "0":
         return False
     if flag is None:
-        flag = n_runs >= _DEVICE_SEARCH_MIN_RUNS
-    if not (flag or env == "1"):
+        flag = bool(getattr(evaluator, "device_resident_search_by_default", False)) and n_runs >= _DEVICE_SEARCH_MIN_RUNS
+    return bool(flag) or env == "1"
+
+
+def _device_search_wanted(evaluator, n_runs: int, flag: Optional[bool], optimizer) -> bool:
+    """Will a search of ``n_runs`` fresh runs of ``optimizer`` keep its state on the device (_minimize_batched's rule)?"""
+    if os.environ.get("QSV_SCALAR_SPSA") or not isinstance(optimizer, SPSA) or n_runs < 2:
+        return False
+    if not _device_search_asked_for(evaluator, n_runs, flag):
         return False
     if not hasattr(evaluator, "evaluate_device_to_device") or not evaluator.device_resident_search_possible():
         return False
@@ -348,10 +360,7 @@ def _minimize_batched(evaluator, jobs: list, on_device: Optional[bool] = False) 
     read points from and leave values in device memory keep their whole state there (evqe/device_search.py)."""
     spsa = [] if os.environ.get("QSV_SCALAR_SPSA") else [job for job in jobs if isinstance(job[1], _SPSARun) and not job[1].done]
     if len(spsa) > 1 and len(spsa) == sum(1 for job in jobs if not job[1].done) and all(job[1].config is spsa[0][1].config for job in spsa):
-        env = os.environ.get("QSV_DEVICE_SEARCH")
-        if on_device is None:  # (the solver's default: where it pays)
-            on_device = len(spsa) >= _DEVICE_SEARCH_MIN_RUNS
-        if (on_device or env == "1") and env != "0":
+        if _device_search_asked_for(evaluator, len(spsa), on_device):
             from queasars_amd.evqe import device_search
 
             if device_search.supported(evaluator, spsa):
@@ -425,7 +434,10 @@ class EVQEMinimumEigensolverConfiguration:
     layer_removal_probability: float = 0.05
     # SPSA searches keep iterates, points and values in device memory and never wait for the GPU inside a search
     # (evqe/device_search.py; iterates agree with the host driver's to the last bits, not bit for bit; the same stopping
-    # iterations).  None: where the evaluator can do it and a search has at least 16 runs; False: never; True: whenever it can.
+    # iterations).  None: where the evaluator can do it and a search has at least 16 runs -- for an evaluator that does not
+    # sample (``device_resident_search_by_default``: the exact estimator); a sampler evaluator's searches stay with the host
+    # driver under None, as before the device search could take them, and go to the device with True (or QSV_DEVICE_SEARCH=1).
+    # False: never; True: whenever it can.
     device_resident_search: Optional[bool] = None
     # Layer searches of individuals whose circuits have no split form on the device (deep individuals: every evaluation is a few
     # passes over the 2^n state) keep the state in front of the searched layer on the device and evaluate from there
