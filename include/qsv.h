@@ -375,6 +375,67 @@ int qsv_cvar_device(qsv_t* h, int n_evals, const int* circuit_ids, int width, co
                     int shots /* 0: the exact distribution */, uint64_t seed, double alpha,
                     const uint8_t* device_active /* may be NULL */, int active_stride, double* device_out);
 
+/* ---- analytic gradients ------------------------------------------------------------------------ */
+
+/*
+ * PARAMETER-SHIFT GRADIENTS.  With the gate set id, u(theta, phi, lambda), cu3(theta, phi, lambda) the expectation value is a short
+ * trigonometric polynomial in every angle, so its derivative by a parameter is an exact linear combination of the SAME circuit's
+ * values at shifted parameter values (the reference hands its circuits to qiskit_algorithms optimisers, whose gradient-based ones
+ * fall back to finite differences there).  With
+ *     s1 = M_PI_2,  s3 = 3.0 * M_PI_2,  cp = (sqrt(2.0) + 1.0) / (4.0 * sqrt(2.0)),  cm = (sqrt(2.0) - 1.0) / (4.0 * sqrt(2.0))
+ * (doubles, formed exactly so) and E(a) the value with the parameter set to a, everything else unchanged:
+ *     two terms   every angle of u, phi and lambda of cu3:   dE/da = 0.5 * (E(a + s1) - E(a - s1))
+ *     four terms  theta of cu3 (frequencies 1/2 and 1):      dE/da = cp * (E(a + s1) - E(a - s1)) - cm * (E(a + s3) - E(a - s3))
+ *     no term     no gate reads the parameter (id gates read nothing): the derivative is 0 and nothing is evaluated
+ * in that association, every product and difference rounded on its own.  A parameter's evaluations are ordered +s1, -s1, +s3, -s3;
+ * an evaluation's are ordered by its requested parameters.  A parameter that more than one angle slot reads has no such rule
+ * (parameter values cannot shift one occurrence): its gradient is refused.
+ *
+ * qsv_gradient_describe (no handle, no device): out_n_terms[p] = 0, 2 or 4 by the rules above, -1 for a parameter more than one
+ * angle slot reads.  QSV_E_ARG for an op kind or a parameter index out of range.
+ */
+int qsv_gradient_describe(int n_ops, const qsv_op* ops, int n_params, int32_t* out_n_terms);
+
+/*
+ * Gradients of the expectation values qsv_eval_circuits computes, under the handle's operator (diagonal or general), for
+ * n_evals (circuit, parameter vector) pairs laid out as there -- circuits on kept states included.  Evaluation e is
+ * differentiated by its parameters wrt[wrt_offsets[e] .. wrt_offsets[e + 1]) in that order (wrt_offsets NULL: by every parameter,
+ * 0 .. n_params - 1); `out` receives the entries of evaluation 0, then those of evaluation 1, and so on.  out_n_shifted (may be
+ * NULL) receives the number of circuit evaluations the call ran: what an evaluation budget counts.
+ *
+ * The base points are uploaded once; a kernel expands them into the shifted rows in device memory, chunk by chunk ("gradient_chunk"
+ * rows, qsv_set_option; default 8192), each chunk runs as one batch of the qsv_eval_begin / qsv_eval_push_device /
+ * qsv_eval_set_output / qsv_eval_end driver, and a kernel combines the values.  For circuits of at most 1024 parameters every
+ * entry is, BIT FOR BIT, the combination above of what qsv_eval_circuits returns at the shifted points -- for any batch, any wrt,
+ * any chunk size and either entry point.
+ *
+ * Errors: no operator set QSV_E_STATE; a wrt index outside the circuit's parameters QSV_E_ARG; a requested parameter that more
+ * than one angle slot reads QSV_E_UNSUPPORTED, named in qsv_last_error.
+ */
+int qsv_gradient_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
+                          const int64_t* wrt_offsets /* NULL: every parameter of each circuit */, const int32_t* wrt,
+                          double* out /* host; packed back to back by the wrt counts */, int64_t* out_n_shifted /* may be NULL */);
+/*
+ * The same with the points READ FROM and the gradients LEFT IN device memory (this handle's GPU): evaluation e takes the first
+ * n_params values of row e of the row-major matrix device_values (rows of `width` doubles, `ready_event` as in
+ * qsv_eval_push_device), and row e of device_out (rows of out_width doubles) receives its entries, the rest of the row zeros;
+ * out_width smaller than an evaluation's number of entries is QSV_E_ARG.  Queued on the handle's stream (qsv_set_stream); returns
+ * without waiting, with qsv_cvar_device's contract: the gradients are complete once the work enqueued so far on that stream is,
+ * the points must stay unchanged until then, and the next call that needs the staging or scratch buffers waits first.  (A call of
+ * more than one chunk waits for each chunk but the last.)  It allocates only when its scratch has to grow (qsv_gradient_stats).
+ */
+int qsv_gradient_device(qsv_t* h, int n_evals, const int* circuit_ids, int width, const double* device_values, void* ready_event,
+                        const int64_t* wrt_offsets, const int32_t* wrt, int out_width, double* device_out, int64_t* out_n_shifted);
+/* Counters of the gradient entry points: the last call's shifted evaluations and chunks, and how often their scratch (device
+ * buffers and the pinned table) was allocated or grown since the handle was created, with its present size in device memory. */
+typedef struct qsv_gradient_stats_t {
+    int64_t n_shifted;
+    int64_t n_chunks;
+    int64_t n_allocations;
+    int64_t scratch_bytes;
+} qsv_gradient_stats_t;
+int qsv_gradient_stats(const qsv_t* h, qsv_gradient_stats_t* out);
+
 /* ---- several observables per evaluation ---------------------------------------------------------- */
 
 /*
@@ -447,6 +508,8 @@ int qsv_fitness_table_wait(const volatile uint64_t* own, int count, volatile int
  *                        keeps that batch's layout (an optimiser's next iteration)
  *   "split_sampling" 0|1 split circuits are sampled from their side tables
  *   "streams" 1..4       HIP streams the pushes of a batch cycle over (at most as many as were created with the handle)
+ *   "gradient_chunk" 0..1048576  shifted evaluations a gradient call expands and runs at a time (0: the default, 8192); the same
+ *                        bits at any value
  * Returns QSV_E_ARG for an unknown name or a value out of range.
  */
 int qsv_set_option(qsv_t* h, const char* name, int value);

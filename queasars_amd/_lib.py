@@ -117,6 +117,17 @@ class QsvCircuitForm(C.Structure):
     ]
 
 
+class QsvGradientStats(C.Structure):
+    """``qsv_gradient_stats_t`` of include/qsv.h."""
+
+    _fields_ = [
+        ("n_shifted", C.c_int64),
+        ("n_chunks", C.c_int64),
+        ("n_allocations", C.c_int64),
+        ("scratch_bytes", C.c_int64),
+    ]
+
+
 ROUTE_NAMES = ("one tile", "split, one launch", "split", "gate passes")
 
 assert C.sizeof(QsvOp) == 40
@@ -161,6 +172,10 @@ SIGNATURES = {
     "qsv_sample_cvar_batch": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, C.c_uint64, C.c_double, _P]),
     "qsv_exact_cvar_batch": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_double, _P]),
     "qsv_cvar_device": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_uint64, C.c_double, _P, C.c_int, _P]),
+    "qsv_gradient_describe": (C.c_int, [C.c_int, _P, C.c_int, _P]),
+    "qsv_gradient_circuits": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "qsv_gradient_device": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P]),
+    "qsv_gradient_stats": (C.c_int, [_P, C.POINTER(QsvGradientStats)]),
     "qsv_observables_create": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.POINTER(C.c_int)]),
     "qsv_observables_destroy": (C.c_int, [_P, C.c_int]),
     "qsv_eval_observables": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),

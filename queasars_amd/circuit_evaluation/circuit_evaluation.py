@@ -253,7 +253,8 @@ class StatevectorDevice:
         self._last_batch = None
         self._row_counts = None
         self._ids_address = None
-        self._push_evals = int(os.environ.get("QSV_PUSH_EVALS", "0"))  # measurement knob: evaluations per push
+        self.last_gradient_evaluations = 0  # circuit evaluations the last gradient call ran
+        self._push_evals =int(os.environ.get("QSV_PUSH_EVALS", "0"))  # measurement knob: evaluations per push
         self._push_plan = [int(x) for x in os.environ.get("QSV_PUSH_PLAN", "").split(",") if x]  # ... or explicit sizes
         self._operator: Optional[PauliOperator] = None
         self._reg_lock = threading.Lock()
@@ -827,6 +828,89 @@ class StatevectorDevice:
             )
         )
 
+    # -- analytic gradients -----------------------------------------------------------------------
+    def _check_gradient(self, rc: int) -> None:
+        """:meth:`_check`, with a parameter that has no shift rule (``QSV_E_UNSUPPORTED``) as a ``ValueError``."""
+        if rc == _lib.QSV_E_UNSUPPORTED:
+            raise ValueError(_lib.last_error(self._lib, self._handle))
+        self._check(rc)
+
+    @staticmethod
+    def _wrt_arguments(circuits: Sequence[CircuitIR], wrt) -> tuple[Optional[np.ndarray], Optional[np.ndarray], np.ndarray]:
+        """(wrt offsets, wrt indices, entries per circuit) of a gradient call.  ``wrt``: None (every parameter of each circuit),
+        one sequence of parameter indices for all circuits, or one sequence per circuit."""
+        n = len(circuits)
+        if wrt is None:
+            return None, None, np.fromiter((c.num_parameters for c in circuits), dtype=np.int64, count=n)
+        wrt = list(wrt)
+        if all(np.ndim(w) == 0 for w in wrt):
+            wrt = [wrt] * n
+        elif len(wrt) != n:
+            raise ValueError("wrt must be None, one list of parameter indices, or one list per circuit")
+        counts = np.fromiter((len(w) for w in wrt), dtype=np.int64, count=n)
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(counts, out=offsets[1:])
+        flat = np.zeros(max(1, int(offsets[-1])), dtype=np.int32)
+        if offsets[-1]:
+            flat[: offsets[-1]] = np.concatenate([np.asarray(w, dtype=np.int64).reshape(-1) for w in wrt])
+        return offsets, flat, counts
+
+    def gradients(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]], wrt=None) -> list[np.ndarray]:
+        """Exact gradients of :meth:`expectation_values` by parameter shift (``qsv_gradient_circuits``): one 1-D array per
+        circuit, entry j the derivative by parameter ``wrt[j]`` (``wrt``: None for every parameter, one list of indices for
+        all circuits, or one list per circuit).  Bit for bit the documented combination (include/qsv.h) of
+        :meth:`expectation_values` at the shifted points; the base points cross PCIe once, the shifted ones never exist on the
+        host.  :attr:`last_gradient_evaluations` is the number of circuit evaluations the call ran.  A requested parameter
+        that more than one angle slot reads raises ``ValueError``."""
+        n = len(circuits)
+        if len(parameter_values) != n:
+            raise ValueError("circuits and parameter_values must have the same length")
+        self.last_gradient_evaluations = 0
+        if n == 0:
+            return []
+        ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
+        wrt_offsets, wrt_flat, counts = self._wrt_arguments(circuits, wrt)
+        out = np.zeros(max(1, int(counts.sum())), dtype=np.float64)
+        n_shifted = C.c_int64(0)
+        self._check_gradient(self._lib.qsv_gradient_circuits(
+            self._handle, n, _lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat),
+            _lib.as_ptr(wrt_offsets) if wrt_offsets is not None else None, _lib.as_ptr(wrt_flat) if wrt_flat is not None else None,
+            _lib.as_ptr(out), C.byref(n_shifted)))
+        self.last_gradient_evaluations = int(n_shifted.value)
+        ends = np.cumsum(counts)
+        return [out[int(e - c): int(e)].copy() for c, e in zip(counts, ends)]
+
+    def gradients_of_device_parameters(self, circuits: Sequence[CircuitIR], matrix_ptr: int, width: int, event: int, out_ptr: int,
+                                       out_width: int, wrt=None) -> int:
+        """:meth:`gradients` for points that live in device memory -- a row-major ``len(circuits) x width`` matrix of doubles at
+        ``matrix_ptr``, circuit i taking the first ``num_parameters`` values of row i -- with the gradients left in device
+        memory: row i of the ``len(circuits) x out_width`` matrix at ``out_ptr``, zeros behind its entries
+        (``qsv_gradient_device``).  Queued on the handle's stream and not waited for.  ``event`` as in
+        :meth:`cvar_of_device_parameters`.  Returns the number of circuit evaluations queued."""
+        n = len(circuits)
+        self.last_gradient_evaluations = 0
+        if n == 0:
+            return 0
+        if width < 0 or (width > 0 and not matrix_ptr) or out_width < 0 or (out_width > 0 and not out_ptr):
+            raise ValueError("matrix_ptr / width / out_ptr / out_width do not describe a matrix and its gradients")
+        ids, _need, _total = self._batch_metadata(circuits)
+        wrt_offsets, wrt_flat, _counts = self._wrt_arguments(circuits, wrt)
+        n_shifted = C.c_int64(0)
+        self._check_gradient(self._lib.qsv_gradient_device(
+            self._handle, n, _lib.as_ptr(ids), int(width), C.c_void_p(matrix_ptr) if width else None,
+            C.c_void_p(event) if event else None, _lib.as_ptr(wrt_offsets) if wrt_offsets is not None else None,
+            _lib.as_ptr(wrt_flat) if wrt_flat is not None else None, int(out_width), C.c_void_p(out_ptr) if out_width else None,
+            C.byref(n_shifted)))
+        self.last_gradient_evaluations = int(n_shifted.value)
+        return self.last_gradient_evaluations
+
+    def gradient_stats(self) -> dict:
+        """``qsv_gradient_stats``: the last gradient call's shifted evaluations and chunks, how often the gradient scratch was
+        allocated or grown since the device was created, and its size."""
+        stats = _lib.QsvGradientStats()
+        self._check(self._lib.qsv_gradient_stats(self._handle, C.byref(stats)))
+        return {name: int(getattr(stats, name)) for name, _ in _lib.QsvGradientStats._fields_}
+
     # -- several observables ---------------------------------------------------------------------
     MAX_OBSERVABLE_SETS = 16
 
@@ -883,7 +967,8 @@ class StatevectorDevice:
 
     # -- measurement support ----------------------------------------------------------------------
     def set_option(self, name: str, value: int) -> None:
-        """Switches of the handle (``qsv_set_option``): "split", "factor", "split_sampling" (0 / 1), "streams" (1 .. 4).
+        """Switches of the handle (``qsv_set_option``): "split", "factor", "split_sampling" (0 / 1), "streams" (1 .. 4),
+        "gradient_chunk" (shifted evaluations per chunk of a gradient call, 0 = the default).
         A circuit keeps the form it was registered in; the cache of the previous batch is dropped."""
         self._check(self._lib.qsv_set_option(self._handle, name.encode(), int(value)))
         self._last_batch = None
@@ -1114,6 +1199,57 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
             if self._device._operator is not self._operator:
                 self._device.set_operator(self._operator)
             return self._evaluate_device_matrix(circuits, matrix, ready)
+
+    #: circuit evaluations the last :meth:`evaluate_gradients` / :meth:`evaluate_gradients_device_to_device` call ran
+    last_gradient_evaluations = 0
+
+    def evaluate_gradients(self, circuits: list[CircuitIR], parameter_values: list[list[float]], wrt=None) -> list[np.ndarray]:
+        """Exact gradients of :meth:`evaluate_circuits` by parameter shift on the device
+        (:meth:`StatevectorDevice.gradients`): one 1-D array per circuit, entry j the derivative by parameter ``wrt[j]`` of that
+        circuit (``wrt``: None for every parameter, one list of indices for all circuits, or one list per circuit).  The
+        initial state circuit's literal angles carry no parameters: indices are the circuit's own.
+        :attr:`last_gradient_evaluations` counts the circuit evaluations the call ran."""
+        if self._precision > 0:
+            raise ValueError("estimator_precision > 0 is emulated on the host: gradients are exact")
+        if self._initial_state_circuit is not None:
+            circuits = [self._with_initial_state(c) for c in circuits]
+        with self._device.operator_lock:
+            if self._device._operator is not self._operator:
+                self._device.set_operator(self._operator)
+            try:
+                return self._device.gradients(circuits, parameter_values, wrt)
+            finally:
+                self.last_gradient_evaluations = self._device.last_gradient_evaluations
+
+    def evaluate_gradients_device_to_device(self, circuits: list[CircuitIR], matrix, out, wrt=None) -> None:
+        """Points from a device matrix (one row per circuit), gradients into the 2-D device tensor ``out`` (one row per
+        circuit, zeros behind a circuit's entries), nothing waited for and nothing copied (``qsv_gradient_device``); tensors
+        and stream as in :meth:`evaluate_device_to_device`."""
+        import torch
+
+        if self._precision > 0:
+            raise ValueError("estimator_precision > 0 is emulated on the host")
+        if self._initial_state_circuit is not None:
+            kept = self._composed_lists
+            if kept is None or kept[0] is not circuits:
+                kept = self._composed_lists = (circuits, [self._with_initial_state(c) for c in circuits])
+            circuits = kept[1]
+        pointer, width, event, remember = _device_matrix_arguments(self, circuits, matrix, ready=True)
+        n = len(circuits)
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.dim() != 2 or out.shape[0] != n
+                or not out.is_contiguous() or out.device != matrix.device):
+            raise ValueError("the output must be a contiguous 2-D float64 tensor of len(circuits) rows on the matrix's device")
+        _offsets, _flat, counts = StatevectorDevice._wrt_arguments(circuits, wrt)
+        if n and int(counts.max()) > out.shape[1]:
+            raise ValueError(f"the output has rows of {out.shape[1]} entries, a circuit's gradient has {int(counts.max())}")
+        with self._device.operator_lock:
+            if self._device._operator is not self._operator:
+                self._device.set_operator(self._operator)
+            try:
+                self._device.gradients_of_device_parameters(circuits, pointer, width, event, out.data_ptr(), out.shape[1], wrt)
+            finally:
+                self.last_gradient_evaluations = self._device.last_gradient_evaluations
+        remember()
 
     def keep_states(self, circuits: list[CircuitIR], parameter_values: list[list[float]]) -> list[KeptState]:
         """The final states of the (circuit, parameter vector) pairs -- behind this evaluator's initial state, if it has one --

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/qsv.h"
+#include "gradient.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
 #include "split.hpp"
@@ -73,6 +74,7 @@ struct Circuit {
     bool staged = false;            // scratch flag of upload_plans (a circuit may appear several times in a batch)
     uint32_t plan_base = 0;         // word offset in the device arena
     int prefix_id = -1;             // >= 0: the circuit continues that kept state (qsv_circuit_create_on_prefix) instead of |0..0>
+    std::vector<int32_t> grad_terms;  // per parameter: shifted evaluations its derivative takes (gradient.hpp: gradient_plan)
 };
 
 // A kept state (qsv_prefix_create): one slot of the handle's prefix buffer, alive while the caller holds it or a circuit
@@ -365,6 +367,20 @@ struct qsv_handle {
         std::vector<std::pair<size_t, size_t>> groups;
     } cvar_snap;
 
+    // parameter-shift gradients (qsv_gradient_circuits / qsv_gradient_device)
+    int grad_chunk = kGradientChunkRows;  // shifted evaluations per chunk (qsv_set_option "gradient_chunk")
+    DeviceBuffer d_grad_tab;     // [GradRow x shifted][GradEntry x entries][int64 x (evaluations + 1)]
+    DeviceBuffer d_grad_rows;    // one chunk's shifted rows; grows by doubling
+    DeviceBuffer d_grad_values;  // every shifted evaluation's value
+    DeviceBuffer d_grad_base;    // host form: the base rows
+    DeviceBuffer d_grad_out;     // host form: the gradient rows
+    void* h_grad_tab = nullptr;  // pinned: what d_grad_tab is copied from
+    size_t h_grad_tab_bytes = 0;
+    hipEvent_t ev_grad = nullptr;  // that copy is complete
+    bool grad_copy_pending = false;
+    const void* grad_checked[2] = {nullptr, nullptr};  // qsv_gradient_device's values / output last found to be this device's memory
+    qsv_gradient_stats_t grad_stats{};
+
     // profiling
     bool profiling = false;
     bool stamping = false;  // per-launch events are recorded (inside qsv_eval_push of a profiled batch only)
@@ -526,6 +542,8 @@ int build_circuit(qsv_t* h, int n_ops, const qsv_op* ops, int n_params, bool fol
         }
     }
     out->n_params = n_params;
+    out->grad_terms.assign(size_t(n_params), 0);
+    (void)gradient_plan(n_ops, ops, n_params, out->grad_terms.data());
     std::vector<AngleSource> angles;
     std::vector<GateIn> gates = gates_of(ops, n_ops, &angles);
     out->n_gates = int(gates.size());
@@ -2404,7 +2422,8 @@ void qsv_destroy(qsv_t* h) {
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     for (DeviceBuffer* b : {&h->d_z, &h->d_cre, &h->d_diag, &h->d_order, &h->d_sorted, &h->d_term_partials, &h->d_groups, &h->d_term_odd, &h->d_arena,
                             &h->d_states, &h->d_wtab, &h->d_side, &h->d_factor, &h->d_factor_count, &h->d_factor_big, &h->d_factor_big_count, &h->d_quad, &h->d_fterms, &h->d_fpart, &h->d_batch, &h->d_mats, &h->d_partials, &h->d_out, &h->d_scratch, &h->d_prefix, &h->d_sdiag,
-                            &h->d_obs_partials, &h->d_obs_values})
+                            &h->d_obs_partials, &h->d_obs_values, &h->d_grad_tab, &h->d_grad_rows, &h->d_grad_values, &h->d_grad_base,
+                            &h->d_grad_out})
         if (b->ptr) (void)hipFree(b->ptr);
     for (auto& kv : h->obs_sets) free_observable_set(kv.second);
     if (h->h_batch) (void)hipHostFree(h->h_batch);
@@ -2412,6 +2431,8 @@ void qsv_destroy(qsv_t* h) {
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->h_out) (void)hipHostFree(h->h_out);
     if (h->h_samples) (void)hipHostFree(h->h_samples);
+    if (h->h_grad_tab) (void)hipHostFree(h->h_grad_tab);
+    if (h->ev_grad) (void)hipEventDestroy(h->ev_grad);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -3542,6 +3563,230 @@ int qsv_cvar_device(qsv_t* h, int n_evals, const int* circuit_ids, int width, co
     return rc;
 }
 
+// ---- parameter-shift gradients ---------------------------------------------------------------------------------------------
+
+// A device buffer that grows by doubling (the scratch matrix of the shifted rows: calls of growing size reallocate seldom).
+static int ensure_doubling(qsv_t* h, DeviceBuffer& b, size_t bytes, size_t most) {
+    if (b.bytes >= bytes && b.ptr) return QSV_OK;
+    h->grad_stats.n_allocations += 1;
+    return ensure(h, b, std::max(bytes, std::min(2 * b.bytes, most)));
+}
+static int ensure_counted(qsv_t* h, DeviceBuffer& b, size_t bytes) {
+    if (!(b.bytes >= bytes && b.ptr)) h->grad_stats.n_allocations += 1;
+    return ensure(h, b, bytes);
+}
+
+// The base rows and the output of a gradient call, both in device memory.
+struct GradCall {
+    const double* base;
+    int64_t base_stride;
+    int base_width;
+    double* out;
+    int out_width;
+};
+
+// Gradients of circs[e] at row e of call.base by the parameters wrt[wrt_offsets[e] .. wrt_offsets[e + 1]) (wrt_offsets null:
+// by every parameter) into row e of call.out: the shift tables, then chunk by chunk the expansion kernel and the shifted
+// evaluations -- one batch of the ordinary driver each, values from and results into device memory, expectation_to_device --,
+// then the combination kernel.  Everything on the handle's stream; returns without waiting for the last chunk.
+static int gradient_locked(qsv_t* h, const std::vector<Circuit*>& circs, const int* circuit_ids, const int64_t* wrt_offsets,
+                           const int32_t* wrt, const GradCall& call, int64_t* out_n_shifted) {
+    const size_t n_evals = circs.size();
+    if (h->n_terms == 0) return fail(h, QSV_E_STATE, "no operator set (call qsv_set_operator first)");
+    std::vector<GradRow> rows;
+    std::vector<GradEntry> entries;
+    std::vector<int64_t> offsets(n_evals + 1, 0);
+    const double shifts[4] = {grad_shift1(), -grad_shift1(), grad_shift3(), -grad_shift3()};
+    for (size_t e = 0; e < n_evals; ++e) {
+        const Circuit& c = *circs[e];
+        if (call.base_width < c.n_params)
+            return fail(h, QSV_E_ARG, "circuit needs " + std::to_string(c.n_params) + " parameter values, got " + std::to_string(call.base_width));
+        const int64_t first = wrt_offsets ? wrt_offsets[e] : 0, count = wrt_offsets ? wrt_offsets[e + 1] - first : int64_t(c.n_params);
+        if (count < 0) return fail(h, QSV_E_ARG, "wrt_offsets must be non-decreasing");
+        if (count > call.out_width)
+            return fail(h, QSV_E_ARG, "out_width " + std::to_string(call.out_width) + " is too small for " + std::to_string(count) + " gradient entries");
+        if (count > 0 && wrt_offsets && !wrt) return fail(h, QSV_E_ARG, "wrt is null");
+        for (int64_t j = 0; j < count; ++j) {
+            const int64_t p = wrt_offsets ? int64_t(wrt[first + j]) : j;
+            if (p < 0 || p >= c.n_params)
+                return fail(h, QSV_E_ARG, "wrt index " + std::to_string(p) + " is outside the " + std::to_string(c.n_params) +
+                                              " parameters of circuit " + std::to_string(circuit_ids[e]));
+            const int32_t t = c.grad_terms[size_t(p)];
+            if (t < 0)
+                return fail(h, QSV_E_UNSUPPORTED, "parameter " + std::to_string(p) + " of circuit " + std::to_string(circuit_ids[e]) +
+                                                      " is read by more than one angle slot: no shift rule");
+            entries.push_back(GradEntry{int64_t(rows.size()), t, 0});
+            for (int32_t k = 0; k < t; ++k) rows.push_back(GradRow{int32_t(e), int32_t(p), shifts[k]});
+        }
+        offsets[e + 1] = int64_t(entries.size());
+    }
+    const size_t T = rows.size();
+    if (out_n_shifted) *out_n_shifted = int64_t(T);
+    h->grad_stats.n_shifted = int64_t(T);
+    h->grad_stats.n_chunks = 0;
+    if (n_evals == 0 || call.out_width <= 0) return QSV_OK;
+    int rc;
+    // the three tables, back to back (each a multiple of 8 bytes), through pinned memory
+    const size_t rows_bytes = T * sizeof(GradRow), entries_bytes = entries.size() * sizeof(GradEntry),
+                 tab_bytes = rows_bytes + entries_bytes + offsets.size() * sizeof(int64_t);
+    if (h->grad_copy_pending) {  // (the pinned table is written below: the last call's copy must have read it)
+        QSV_HIP(h, hipEventSynchronize(h->ev_grad));
+        h->grad_copy_pending = false;
+    }
+    if (!h->ev_grad) QSV_HIP(h, hipEventCreateWithFlags(&h->ev_grad, hipEventDisableTiming));
+    if (h->h_grad_tab_bytes < tab_bytes) {
+        if (h->h_grad_tab) QSV_HIP(h, hipHostFree(h->h_grad_tab));
+        const size_t want = std::max(tab_bytes, 2 * h->h_grad_tab_bytes);
+        h->h_grad_tab = nullptr;
+        h->h_grad_tab_bytes = 0;
+        QSV_HIP(h, hipHostMalloc(&h->h_grad_tab, want, hipHostMallocDefault));
+        h->h_grad_tab_bytes = want;
+        h->grad_stats.n_allocations += 1;
+    }
+    if ((rc = ensure_doubling(h, h->d_grad_tab, tab_bytes, size_t(-1) / 4))) return rc;
+    if ((rc = ensure_counted(h, h->d_grad_values, std::max<size_t>(1, T) * sizeof(double)))) return rc;
+    char* ht = static_cast<char*>(h->h_grad_tab);
+    if (rows_bytes) std::memcpy(ht, rows.data(), rows_bytes);
+    if (entries_bytes) std::memcpy(ht + rows_bytes, entries.data(), entries_bytes);
+    std::memcpy(ht + rows_bytes + entries_bytes, offsets.data(), offsets.size() * sizeof(int64_t));
+    char* dt = static_cast<char*>(h->d_grad_tab.ptr);
+    QSV_HIP(h, hipMemcpyAsync(dt, ht, tab_bytes, hipMemcpyHostToDevice, h->stream));
+    QSV_HIP(h, hipEventRecord(h->ev_grad, h->stream));
+    h->grad_copy_pending = true;
+    const GradRow* d_rows = reinterpret_cast<const GradRow*>(dt);
+    const GradEntry* d_entries = reinterpret_cast<const GradEntry*>(dt + rows_bytes);
+    const int64_t* d_offsets = reinterpret_cast<const int64_t*>(dt + rows_bytes + entries_bytes);
+    double* values = static_cast<double*>(h->d_grad_values.ptr);
+
+    // the shifted rows: even width, so that every row starts on 16 bytes (an evaluation takes the first n_params of its row)
+    const int width = (std::max(call.base_width, 1) + 1) / 2 * 2;
+    const size_t chunk = size_t(std::max(1, h->grad_chunk)), row_bytes = size_t(width) * sizeof(double);
+    if (T > 0 && (rc = ensure_doubling(h, h->d_grad_rows, std::min(T, chunk) * row_bytes, chunk * row_bytes))) return rc;
+    double* matrix = static_cast<double*>(h->d_grad_rows.ptr);
+    BatchArgs args;
+    for (size_t t0 = 0; t0 < T; t0 += chunk) {
+        const size_t tc = std::min(chunk, T - t0);
+        if (t0 > 0 && h->async_pending) {  // (the chunk before this one may still be reading the rows)
+            QSV_HIP(h, sync_streams(h));
+            h->async_pending = false;
+        }
+        QSV_HIP(h, launch_gradient_expand(call.base, call.base_stride, call.base_width, d_rows + t0, int64_t(tc), matrix, width, h->stream));
+        args.circs.resize(tc);
+        for (size_t t = 0; t < tc; ++t) args.circs[t] = circs[size_t(rows[t0 + t].base_row)];
+        args.n_params.assign(tc, int64_t(width));
+        args.device_values = matrix;
+        if ((rc = expectation_to_device(h, args, values + t0))) return rc;
+        h->grad_stats.n_chunks += 1;
+    }
+    QSV_HIP(h, launch_gradient_combine(values, d_entries, d_offsets, int64_t(n_evals), call.out_width, grad_cp(), grad_cm(), call.out, h->stream));
+    return QSV_OK;
+}
+
+int qsv_gradient_describe(int n_ops, const qsv_op* ops, int n_params, int32_t* out_n_terms) {
+    if (n_ops < 0 || n_params < 0 || (n_ops > 0 && !ops) || (n_params > 0 && !out_n_terms)) return QSV_E_ARG;
+    for (int i = 0; i < n_ops; ++i) {
+        if (ops[i].kind > QSV_OP_CU3) return QSV_E_ARG;
+        if (ops[i].kind != QSV_OP_ID)
+            for (int32_t p : {ops[i].p_theta, ops[i].p_phi, ops[i].p_lambda})
+                if (p >= n_params || p < -1) return QSV_E_ARG;
+    }
+    (void)gradient_plan(n_ops, ops, n_params, out_n_terms);
+    return QSV_OK;
+}
+
+int qsv_gradient_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
+                          const int64_t* wrt_offsets, const int32_t* wrt, double* out, int64_t* out_n_shifted) {
+    if (!h) return QSV_E_ARG;
+    if (h->batch_owner.load() == std::this_thread::get_id())
+        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_gradient_circuits goes between batches)");
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets))) return fail(h, QSV_E_ARG, "bad arguments");
+    if (out_n_shifted) *out_n_shifted = 0;
+    if (n_evals == 0) return QSV_OK;
+    QSV_HIP(h, hipSetDevice(h->device));
+    BatchArgs args;
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args);
+    if (rc) return rc;
+    // the base points as one matrix, a row per evaluation; the gradient rows as wide as the longest request
+    int64_t base_width = 1, out_width = 1, total_out = 0;
+    for (int e = 0; e < n_evals; ++e) {
+        base_width = std::max(base_width, args.n_params[size_t(e)]);
+        const int64_t count = wrt_offsets ? wrt_offsets[e + 1] - wrt_offsets[e] : int64_t(args.circs[size_t(e)]->n_params);
+        if (count < 0) return fail(h, QSV_E_ARG, "wrt_offsets must be non-decreasing");
+        out_width = std::max(out_width, count);
+        total_out += count;
+        if (args.n_params[size_t(e)] < args.circs[size_t(e)]->n_params)
+            return fail(h, QSV_E_ARG, "circuit needs " + std::to_string(args.circs[size_t(e)]->n_params) + " parameter values, got " +
+                                          std::to_string(args.n_params[size_t(e)]));
+    }
+    if (total_out > 0 && !out) return fail(h, QSV_E_ARG, "out is null");
+    if (base_width > (1 << 24) || out_width > (1 << 24)) return fail(h, QSV_E_ARG, "too many parameters");
+    std::vector<double> base(size_t(n_evals) * size_t(base_width), 0.0);
+    for (size_t e = 0, cur = 0; e < size_t(n_evals); cur += size_t(args.n_params[e]), ++e)
+        if (args.n_params[e]) std::memcpy(base.data() + e * size_t(base_width), args.values.data() + cur, size_t(args.n_params[e]) * sizeof(double));
+    if ((rc = ensure_counted(h, h->d_grad_base, base.size() * sizeof(double)))) return rc;
+    if ((rc = ensure_counted(h, h->d_grad_out, size_t(n_evals) * size_t(out_width) * sizeof(double)))) return rc;
+    // (`base` outlives the copy: every path below waits for the stream before it returns)
+    QSV_HIP(h, hipMemcpyAsync(h->d_grad_base.ptr, base.data(), base.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    const GradCall call{static_cast<const double*>(h->d_grad_base.ptr), base_width, int(base_width), static_cast<double*>(h->d_grad_out.ptr),
+                        int(out_width)};
+    rc = gradient_locked(h, args.circs, circuit_ids, wrt_offsets, wrt, call, out_n_shifted);
+    if (rc) {
+        (void)sync_streams(h);
+        return rc;
+    }
+    std::vector<double> rows(size_t(n_evals) * size_t(out_width));
+    QSV_HIP(h, hipMemcpyAsync(rows.data(), h->d_grad_out.ptr, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QSV_HIP(h, sync_streams(h));
+    h->async_pending = false;
+    for (size_t e = 0, cur = 0; e < size_t(n_evals); ++e) {
+        const size_t count = size_t(wrt_offsets ? wrt_offsets[e + 1] - wrt_offsets[e] : int64_t(args.circs[e]->n_params));
+        if (count) std::memcpy(out + cur, rows.data() + e * size_t(out_width), count * sizeof(double));
+        cur += count;
+    }
+    return QSV_OK;
+}
+
+int qsv_gradient_device(qsv_t* h, int n_evals, const int* circuit_ids, int width, const double* device_values, void* ready_event,
+                        const int64_t* wrt_offsets, const int32_t* wrt, int out_width, double* device_out, int64_t* out_n_shifted) {
+    if (!h) return QSV_E_ARG;
+    if (h->batch_owner.load() == std::this_thread::get_id())
+        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_gradient_device goes between batches)");
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (n_evals < 0 || width < 0 || out_width < 0 || (n_evals > 0 && (!circuit_ids || (out_width > 0 && !device_out) || (width > 0 && !device_values))))
+        return fail(h, QSV_E_ARG, "bad arguments");
+    if (out_n_shifted) *out_n_shifted = 0;
+    if (n_evals == 0) return QSV_OK;
+    QSV_HIP(h, hipSetDevice(h->device));
+    const void* given[2] = {width > 0 ? device_values : nullptr, out_width > 0 ? device_out : nullptr};
+    static const char* const names[2] = {"device_values", "device_out"};
+    for (int i = 0; i < 2; ++i) {  // (a search hands over the same buffers call after call: each is asked about once)
+        if (!given[i] || given[i] == h->grad_checked[i]) continue;
+        hipPointerAttribute_t attr{};
+        if (hipPointerGetAttributes(&attr, given[i]) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != h->device) {
+            (void)hipGetLastError();
+            return fail(h, QSV_E_ARG, std::string(names[i]) + " is not memory of this handle's device");
+        }
+        h->grad_checked[i] = given[i];
+    }
+    BatchArgs args;
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, nullptr, nullptr, args);
+    if (rc) return rc;
+    if (ready_event) QSV_HIP(h, hipStreamWaitEvent(h->stream, static_cast<hipEvent_t>(ready_event), 0));
+    const GradCall call{device_values, int64_t(width), width, device_out, out_width};
+    rc = gradient_locked(h, args.circs, circuit_ids, wrt_offsets, wrt, call, out_n_shifted);
+    if (rc) (void)sync_streams(h);  // nothing of a failed call may still be running
+    return rc;
+}
+
+int qsv_gradient_stats(const qsv_t* h, qsv_gradient_stats_t* out) {
+    if (!h || !out) return QSV_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    *out = h->grad_stats;
+    out->scratch_bytes = int64_t(h->d_grad_tab.bytes + h->d_grad_rows.bytes + h->d_grad_values.bytes + h->d_grad_base.bytes + h->d_grad_out.bytes);
+    return QSV_OK;
+}
+
 int qsv_observables_create(qsv_t* h, int n_observables, const int64_t* term_offsets, const uint64_t* x_mask, const uint64_t* z_mask,
                            const double* coeff_re, const double* coeff_im, int* out_set_id) {
     if (!h) return QSV_E_ARG;
@@ -3724,6 +3969,9 @@ int qsv_set_option(qsv_t* h, const char* name, int value) {
     } else if (key == "streams") {
         if (value < 1 || value > h->n_lane_streams + 1) return fail(h, QSV_E_ARG, "streams must be between 1 and the number the handle was created with");
         h->n_streams = value;
+    } else if (key == "gradient_chunk") {  // shifted evaluations per chunk of a gradient call (0: the default); the same bits at any value
+        if (value < 0 || value > (1 << 20)) return fail(h, QSV_E_ARG, "gradient_chunk must be between 0 and 1048576");
+        h->grad_chunk = value ? value : kGradientChunkRows;
     } else {
         return fail(h, QSV_E_ARG, "unknown option '" + key + "'");
     }

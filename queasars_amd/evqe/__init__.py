@@ -19,6 +19,7 @@ from queasars_amd.evqe.genome import (  # noqa: F401
 from queasars_amd.evqe.solver import (  # noqa: F401,E402
     NFT,
     SPSA,
+    Adam,
     BestIndividualRelativeChangeTolerance,
     EVQEMinimumEigensolver,
     EVQEMinimumEigensolverConfiguration,

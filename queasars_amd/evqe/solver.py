@@ -218,6 +218,99 @@ class _NFTRun:
         self.done = self.nfev >= cfg.maxfev or (cfg.maxiter is not None and self.iteration >= cfg.maxiter)
 
 
+@dataclass
+class Adam:
+    """Adam (Kingma and Ba, "Adam: A Method for Stochastic Optimization", ICLR 2015, algorithm 1) on the evaluator's analytic
+    gradients (``evaluate_gradients``: parameter shift on the device).  Restated from the paper, in its notation: ``lr`` is
+    alpha.  A run stops after ``maxiter`` iterations, or when the norm of an update falls below ``tol``.  Deterministic: the
+    seed of ``new_run`` is not used.  An iteration costs the shifted evaluations of the run's free parameters (two per
+    angle, four for theta of a cu3), which is what ``nfev`` and the solver's accounting count."""
+
+    maxiter: int = 33
+    lr: float = 0.1
+    beta_1: float = 0.9
+    beta_2: float = 0.999
+    eps: float = 1e-8
+    tol: float = 0.0
+
+    #: a driver must hand these runs to ``evaluate_gradients`` (_minimize_batched)
+    needs_gradients = True
+
+    @property
+    def n_circuit_evaluations(self) -> int:
+        """Evaluations of one run when every free parameter takes two (the count depends on the searched layer:
+        :meth:`n_circuit_evaluations_for`)."""
+        return 2 * self.maxiter
+
+    def n_circuit_evaluations_for(self, n_qubits: int) -> int:
+        """Most evaluations of one layer search on ``n_qubits`` qubits, for the solver's budget: a layer has at most a rotation
+        per qubit (three angles, two evaluations each) and a controlled rotation per pair of qubits (4 + 2 + 2)."""
+        return self.maxiter * (6 * n_qubits + 8 * (n_qubits // 2))
+
+    def new_run(self, x0: Sequence[float], seed: Optional[int]) -> "_AdamRun":
+        return _AdamRun(self, x0)
+
+
+class _AdamRun:
+    """State of one Adam minimisation; the driver advances many of them in lock-step (:func:`_minimize_adam`)."""
+
+    def __init__(self, config: Adam, x0: Sequence[float]):
+        self.config = config
+        self.x = np.asarray(x0, dtype=np.float64).copy()
+        self.m = np.zeros_like(self.x)
+        self.v = np.zeros_like(self.x)
+        self.nfev = 0
+        self.iteration = 0
+        self.done = self.x.size == 0 or config.maxiter <= 0
+        self.embed = None  # (as _SPSARun.embed)
+
+    def accept_gradient(self, gradient: np.ndarray, n_evaluations: int) -> None:
+        cfg = self.config
+        g = np.asarray(gradient, dtype=np.float64)
+        self.nfev += int(n_evaluations)
+        self.iteration += 1
+        t = self.iteration
+        self.m = cfg.beta_1 * self.m + (1 - cfg.beta_1) * g
+        self.v = cfg.beta_2 * self.v + (1 - cfg.beta_2) * (g * g)
+        m_hat = self.m / (1 - cfg.beta_1**t)
+        v_hat = self.v / (1 - cfg.beta_2**t)
+        update = cfg.lr * m_hat / (np.sqrt(v_hat) + cfg.eps)
+        self.x = self.x - update
+        self.done = t >= cfg.maxiter or float(np.linalg.norm(update)) < cfg.tol
+
+
+def _require_gradients(evaluator, optimizer) -> None:
+    """An optimiser that needs gradients (:class:`Adam`) with an evaluator that has none: said before anything runs."""
+    if getattr(optimizer, "needs_gradients", False) and not callable(getattr(evaluator, "evaluate_gradients", None)):
+        raise ValueError(f"{type(optimizer).__name__} needs an evaluator with evaluate_gradients (OperatorCircuitEvaluator); "
+                         f"{type(evaluator).__name__} has none")
+
+
+def _minimize_adam(evaluator, jobs: list) -> None:
+    """:func:`_minimize_batched` for Adam runs: ONE ``evaluate_gradients`` call per iteration for all runs, each run
+    differentiated by its free parameters only (the searched layer of an embedded run).  A run's ``nfev`` counts its shifted
+    evaluations, by the circuit's shift plan; their sum is checked against what the evaluator reports."""
+    _require_gradients(evaluator, jobs[0][1].config)
+    wrt, cost = {}, {}
+    for circuit, run in jobs:
+        positions = list(range(run.x.size)) if run.embed is None else [int(p) for p in run.embed[1]]
+        terms = circuit.gradient_terms()
+        wrt[id(run)] = positions
+        cost[id(run)] = sum(max(0, terms[p]) for p in positions)
+    active = [job for job in jobs if not job[1].done]
+    while active:
+        circuits = [circuit for circuit, _ in active]
+        params = [_full_point(run, run.x).tolist() for _, run in active]
+        gradients = evaluator.evaluate_gradients(circuits, params, [wrt[id(run)] for _, run in active])
+        counted = sum(cost[id(run)] for _, run in active)
+        reported = getattr(evaluator, "last_gradient_evaluations", counted)
+        if reported != counted:
+            raise RuntimeError(f"the evaluator ran {reported} shifted evaluations, the shift plans say {counted}")
+        for (_, run), gradient in zip(active, gradients):
+            run.accept_gradient(gradient, cost[id(run)])
+        active = [job for job in active if not job[1].done]
+
+
 def _full_point(run, point: np.ndarray) -> np.ndarray:
     """The parameter vector the evaluator gets for a run's point (run.embed)."""
     if run.embed is None:
@@ -368,6 +461,11 @@ def _minimize_batched(evaluator, jobs: list, on_device: Optional[bool] = False) 
                 return
         _minimize_spsa_vectorised(evaluator, spsa)
         return
+    if jobs and all(isinstance(job[1], _AdamRun) for job in jobs):
+        _minimize_adam(evaluator, jobs)
+        return
+    if any(isinstance(job[1], _AdamRun) for job in jobs):
+        raise ValueError("Adam runs cannot share a search with runs of another optimiser")
     active = [job for job in jobs if not job[1].done]
     while active:
         circuits, params, counts = [], [], []
@@ -416,7 +514,7 @@ class BestIndividualRelativeChangeTolerance:
 class EVQEMinimumEigensolverConfiguration:
     """The solver knobs of queasars/minimum_eigensolvers/evqe/evqe.py:34-177 that do not concern primitives/executors."""
 
-    optimizer: object  # SPSA or NFT: anything with new_run(x0, seed) and n_circuit_evaluations
+    optimizer: object  # SPSA, NFT or Adam: anything with new_run(x0, seed) and n_circuit_evaluations
     population_size: int
     max_generations: Optional[int] = None
     max_circuit_evaluations: Optional[int] = None
@@ -757,7 +855,10 @@ class EVQEMinimumEigensolver:
         )
         evaluations: list[int] = [0]
         result = EVQEResult(eigenvalue=math.inf, best_individual=population.individuals[0], generations=0, circuit_evaluations=evaluations)
+        _require_gradients(searcher, cfg.optimizer)
         n_opt = cfg.optimizer.n_circuit_evaluations
+        if hasattr(cfg.optimizer, "n_circuit_evaluations_for"):  # (an optimiser whose cost depends on the register: Adam)
+            n_opt = cfg.optimizer.n_circuit_evaluations_for(evaluator.n_qubits)
 
         def budget_left(expected: int) -> bool:
             if cfg.max_circuit_evaluations is None:

@@ -235,6 +235,20 @@ class CircuitIR:
             out.append((kind, target, -1 if control == NO_CONTROL else control, theta, phi, lam))
         return out
 
+    def gradient_terms(self) -> list[int]:
+        """Per parameter, the circuit evaluations its parameter-shift derivative takes -- what ``qsv_gradient_describe``
+        (include/qsv.h) reports: 0 when no gate reads it, 2 for an angle of ``u`` and for phi / lambda of ``cu3``, 4 for theta
+        of ``cu3``, -1 when more than one angle slot reads it (no shift rule)."""
+        reads, four = [0] * self._n_parameters, [False] * self._n_parameters
+        for kind, _t, _c, _f, it, ip, il, _vt, _vp, _vl in self._rows:
+            if kind == OP_ID:
+                continue
+            for slot, p in enumerate((it, ip, il)):
+                if p >= 0:
+                    reads[p] += 1
+                    four[p] = four[p] or (slot == 0 and kind == OP_CU3)
+        return [0 if r == 0 else -1 if r > 1 else 4 if f else 2 for r, f in zip(reads, four)]
+
     def depth(self) -> int:
         """Length of the longest chain of ops that follow each other on some qubit, every op (``id`` included) counting one --
         what ``QuantumCircuit.depth()`` returns for the same op list (the reference's tests hold an individual's circuit to
