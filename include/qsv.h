@@ -375,6 +375,60 @@ int qsv_cvar_device(qsv_t* h, int n_evals, const int* circuit_ids, int width, co
                     int shots /* 0: the exact distribution */, uint64_t seed, double alpha,
                     const uint8_t* device_active /* may be NULL */, int active_stride, double* device_out);
 
+/* ---- sampled values of a host-side scoring function ------------------------------------------------ */
+
+/*
+ * VALUE CACHES.  The reference's BitstringCircuitEvaluator scores every measured state through a Python callable str -> float
+ * (reference: queasars/circuit_evaluation/circuit_evaluation.py:222-291, bitstring_evaluation.py).  The callable cannot run on the
+ * device; everything around it can.  A value cache is an open-addressing hash table basis state -> double in device memory that
+ * lives until qsv_value_cache_destroy or the handle: 2^log2_slots slots of a uint64 key (all ones: empty; state 0 is an ordinary
+ * key) and a double, home slot splitmix64(state) & (slots - 1), linear probing.  One evaluation step is two calls:
+ *
+ * qsv_sample_lookup draws, for n_evals (circuit, parameter vector) pairs laid out as in qsv_eval_circuits, exactly the samples
+ * qsv_sample_batch draws for the same handle, circuits, values, shots and seed -- they stay in device memory; no operator is
+ * needed --, looks every sample up in the table and inserts the states it does not hold.  Only those come back: the distinct
+ * never-seen states of the WHOLE batch, *out_n_missing of them at *out_missing_states, in pinned host memory that stays valid and
+ * unchanged until the finish (or the clear), in whatever order the device's atomics gave.  Same refusals as qsv_sample_batch.
+ *
+ * qsv_sample_lookup_finish takes their values, in that same order (n_values != the lookup's count: QSV_E_STATE, the lookup still
+ * waits), stores them, gathers every sample's value from the table and returns out_cvar[e] (may be NULL) = CVaR_alpha of
+ * evaluation e's values, sorted and summed on the device exactly as qsv_sample_cvar_batch does for an operator's values (so at most
+ * 4096 shots and 0 < alpha <= 1, else QSV_E_ARG), and / or out_values[e * shots + s] (may be NULL) = the value of sample s of
+ * evaluation e.  A call whose states are all known moves nothing but the results.
+ *
+ * Growth: before a lookup probes, the table is doubled (its entries rehashed) until 2 * (entries + n_evals * shots) <= slots --
+ * the worst case of every sample being new, so a probe never meets a full table.  Where that would pass 2^log2_max_slots the
+ * table is cleared first and refilled as the states come again: the scoring function is taken to be pure, so only time is lost.
+ * A single call of more than 2^(log2_max_slots - 1) samples is QSV_E_ARG, before anything is launched.  1 <= log2_slots <=
+ * log2_max_slots <= 30; 16 bytes of device memory per slot.
+ *
+ * Between a lookup and its finish only the cache's own buffers are held: other calls on the handle, lookups on other caches
+ * included, are allowed.  A second lookup on the same cache is QSV_E_STATE, and so is a finish without a lookup.
+ * qsv_value_cache_clear empties the table and cancels a lookup that was never finished (a scoring function that raised): the
+ * states such a lookup inserted have no values yet.  An unknown cache id is QSV_E_ARG.
+ */
+int qsv_value_cache_create(qsv_t* h, int log2_slots, int log2_max_slots, int* out_cache_id);
+int qsv_value_cache_destroy(qsv_t* h, int cache_id);
+int qsv_value_cache_clear(qsv_t* h, int cache_id);
+/* Counters of a cache since it was created: the states it holds and its slots now; the samples looked up, split into those whose
+ * state was already there (or was inserted by another sample of the same call) and those that created an entry; how often the
+ * table grew and how often it was cleared (at its largest size, or by qsv_value_cache_clear). */
+typedef struct qsv_value_cache_stats_t {
+    int64_t entries;
+    int64_t slots;
+    int64_t samples_looked_up;
+    int64_t hits;
+    int64_t new_entries;
+    int64_t rehashes;
+    int64_t clears;
+} qsv_value_cache_stats_t;
+int qsv_value_cache_stats(const qsv_t* h, int cache_id, qsv_value_cache_stats_t* out);
+int qsv_sample_lookup(qsv_t* h, int cache_id, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
+                      int shots, uint64_t seed, int64_t* out_n_missing, const uint64_t** out_missing_states);
+int qsv_sample_lookup_finish(qsv_t* h, int cache_id, int64_t n_values, const double* values, double alpha,
+                             double* out_cvar /* may be NULL; needs shots <= 4096 */,
+                             double* out_values /* may be NULL; n_evals * shots */);
+
 /* ---- analytic gradients ------------------------------------------------------------------------ */
 
 /*

@@ -128,6 +128,20 @@ class QsvGradientStats(C.Structure):
     ]
 
 
+class QsvValueCacheStats(C.Structure):
+    """``qsv_value_cache_stats_t`` of include/qsv.h."""
+
+    _fields_ = [
+        ("entries", C.c_int64),
+        ("slots", C.c_int64),
+        ("samples_looked_up", C.c_int64),
+        ("hits", C.c_int64),
+        ("new_entries", C.c_int64),
+        ("rehashes", C.c_int64),
+        ("clears", C.c_int64),
+    ]
+
+
 ROUTE_NAMES = ("one tile", "split, one launch", "split", "gate passes")
 
 assert C.sizeof(QsvOp) == 40
@@ -172,6 +186,12 @@ SIGNATURES = {
     "qsv_sample_cvar_batch": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, C.c_uint64, C.c_double, _P]),
     "qsv_exact_cvar_batch": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_double, _P]),
     "qsv_cvar_device": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_uint64, C.c_double, _P, C.c_int, _P]),
+    "qsv_value_cache_create": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "qsv_value_cache_destroy": (C.c_int, [_P, C.c_int]),
+    "qsv_value_cache_clear": (C.c_int, [_P, C.c_int]),
+    "qsv_value_cache_stats": (C.c_int, [_P, C.c_int, _P]),
+    "qsv_sample_lookup": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_uint64, _P, _P]),
+    "qsv_sample_lookup_finish": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_double, _P, _P]),
     "qsv_gradient_describe": (C.c_int, [C.c_int, _P, C.c_int, _P]),
     "qsv_gradient_circuits": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "qsv_gradient_device": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P]),

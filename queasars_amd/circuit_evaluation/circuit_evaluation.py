@@ -212,6 +212,92 @@ class KeptState:
             pass
 
 
+class DeviceValueCache:
+    """A table ``basis state -> float`` in a device's memory (``StatevectorDevice.value_cache``; include/qsv.h, VALUE CACHES):
+    the values of a host-side scoring function, kept where the samples are.  One step is :meth:`lookup` -- draw the samples,
+    learn which of their states the table has never seen -- and :meth:`finish` -- hand over those states' values, get the
+    CVaR (or every sample's value) back.  The samples themselves never leave the device."""
+
+    def __init__(self, owner: "StatevectorDevice", log2_slots: int = 16, log2_max_slots: int = 24):
+        self._owner = owner
+        self._id = -1
+        self._shape = None  # (evaluations, shots) of the lookup that waits for its finish
+        out = C.c_int(-1)
+        self._check(owner._lib.qsv_value_cache_create(owner._handle, int(log2_slots), int(log2_max_slots), C.byref(out)))
+        self._id = int(out.value)
+
+    def _check(self, rc: int) -> None:
+        if rc == _lib.QSV_OK:
+            return
+        msg = _lib.last_error(self._owner._lib, self._owner._handle)
+        if rc == _lib.QSV_E_ARG:
+            raise ValueError(msg)
+        if rc == _lib.QSV_E_STATE:
+            raise RuntimeError(msg)
+        raise CircuitEvaluatorException(msg)
+
+    def lookup(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]], shots: int, seed: int) -> np.ndarray:
+        """Draws the samples :meth:`StatevectorDevice.sample_batch` draws for the same arguments and returns the distinct
+        states among them (over the whole batch) that the table did not hold, in no particular order (``uint64``)."""
+        n = len(circuits)
+        if len(parameter_values) != n:
+            raise ValueError("circuits and parameter_values must have the same length")
+        owner = self._owner
+        if n and shots:
+            ids, offsets, flat = owner._batch_arguments(circuits, parameter_values)
+            arguments = (_lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat))
+        else:
+            arguments = (None, None, None)
+        n_missing, states = C.c_int64(0), C.c_void_p()
+        self._check(owner._lib.qsv_sample_lookup(owner._handle, self._id, n, *arguments, int(shots), C.c_uint64(seed & (2**64 - 1)),
+                                                 C.byref(n_missing), C.byref(states)))
+        self._shape = (n, int(shots))
+        if n_missing.value == 0:
+            return np.empty(0, dtype=np.uint64)
+        # (the library's pinned list is good until the finish; a copy is good for as long as the caller likes)
+        return np.ctypeslib.as_array(C.cast(states, C.POINTER(C.c_uint64)), shape=(int(n_missing.value),)).copy()
+
+    def finish(self, values: Sequence[float], alpha: float = 1.0, want_values: bool = False):
+        """``values[j]``: the value of state j of the last :meth:`lookup`'s result.  Returns the CVaR_alpha of every
+        evaluation's sample values (a list; at most ``StatevectorDevice.MAX_CVAR_SHOTS`` shots), or with ``want_values`` the
+        matrix ``values[i, s]`` of every sample's value instead."""
+        if self._shape is None:
+            raise RuntimeError("finish() comes after lookup()")
+        n, shots = self._shape
+        given = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        owner = self._owner
+        out = np.empty((n, shots) if want_values else n, dtype=np.float64)
+        self._check(owner._lib.qsv_sample_lookup_finish(
+            owner._handle, self._id, int(given.size), _lib.as_ptr(given) if given.size else None, float(alpha),
+            None if want_values or not out.size else _lib.as_ptr(out), _lib.as_ptr(out) if want_values and out.size else None))
+        self._shape = None
+        return out if want_values else out.tolist()
+
+    def clear(self) -> None:
+        """Forget every value, and a :meth:`lookup` that was never finished."""
+        self._shape = None
+        self._check(self._owner._lib.qsv_value_cache_clear(self._owner._handle, self._id))
+
+    def stats(self) -> dict:
+        """``entries``, ``slots``, ``samples_looked_up``, ``hits``, ``new_entries``, ``rehashes``, ``clears``."""
+        raw = _lib.QsvValueCacheStats()
+        self._check(self._owner._lib.qsv_value_cache_stats(self._owner._handle, self._id, C.byref(raw)))
+        return {name: int(getattr(raw, name)) for name, _ in raw._fields_}
+
+    def close(self) -> None:
+        """Free the table (idempotent; the device's own end frees it as well)."""
+        cid, self._id = getattr(self, "_id", -1), -1
+        owner = getattr(self, "_owner", None)
+        if cid >= 0 and owner is not None and getattr(owner, "_handle", None):
+            owner._lib.qsv_value_cache_destroy(owner._handle, cid)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover
+            pass
+
+
 class StatevectorDevice:
     """Owns one ``qsv_t`` handle: the resident state buffers, plans and operator tables of one GPU.
 
@@ -772,6 +858,11 @@ class StatevectorDevice:
             )
         )
         return out.tolist()
+
+    def value_cache(self, log2_slots: int = 16, log2_max_slots: int = 24) -> DeviceValueCache:
+        """A new :class:`DeviceValueCache` on this device: ``2**log2_slots`` slots of 16 bytes to begin with, doubled as
+        states come in, at most ``2**log2_max_slots`` (256 MB by default) -- settings, not measurements."""
+        return DeviceValueCache(self, log2_slots, log2_max_slots)
 
     def exact_cvar_batch(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]], alpha: float) -> list[float]:
         """CVaR_alpha of the (diagonal) operator under the EXACT output distribution of every (circuit, parameter vector)
@@ -1563,9 +1654,30 @@ class OperatorSamplerCircuitEvaluator(BaseCircuitEvaluator):
         return self._operator.num_qubits
 
 
+def _ascending(missing: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """A miss list in ascending state order, and the permutation that put it there (``ordered == missing[order]``)."""
+    missing = np.asarray(missing, dtype=np.uint64)
+    order = np.argsort(missing, kind="stable")
+    return missing[order], order
+
+
+def _unpermuted(ordered_values: Sequence[float], order: np.ndarray) -> np.ndarray:
+    """The values of :func:`_ascending`'s ordered states back in the miss list's own order."""
+    out = np.empty(len(order), dtype=np.float64)
+    out[order] = np.asarray(ordered_values, dtype=np.float64)
+    return out
+
+
 class BitstringCircuitEvaluator(BaseCircuitEvaluator):
     """Expectation / CVaR of a host-side bitstring scoring function over sampled measurements (reference [222-291]).
-    The scoring callable stays on the host; the GPU supplies the samples."""
+    The scoring callable stays on the host; the GPU supplies the samples.
+
+    ``device_value_cache=True`` (not in the reference) keeps the callable's values in a table in device memory for the
+    evaluator's lifetime (:class:`DeviceValueCache`): the samples stay on the device, the callable -- taken to be a pure
+    ``str -> float`` function -- is asked once per distinct state it has never scored, over the whole batch and over all
+    calls, in ascending state order, and the CVaR is taken on the device as :class:`OperatorSamplerCircuitEvaluator` takes it.
+    That CVaR adds the sample values up in another order than ``_get_expectation`` adds a distribution's, so the numbers can
+    differ in the last bits from the default path's: the default ``False`` is that path, unchanged."""
 
     def __init__(
         self,
@@ -1577,28 +1689,74 @@ class BitstringCircuitEvaluator(BaseCircuitEvaluator):
         device: int = 0,
         seed: Optional[int] = None,
         statevector_device: Optional[StatevectorDevice] = None,
+        device_value_cache: bool = False,
     ):
         _check_initial_state(
             initial_state_circuit, bitstring_evaluator.input_length, "the input length of the BitstringEvaluator"
         )
         if alpha <= 0 or 1 < alpha:
             raise ValueError("alpha must be in the range (0, 1]!")
+        if not isinstance(device_value_cache, (bool, np.bool_)):
+            raise ValueError("device_value_cache must be True or False!")
         self._bitstring_evaluator = bitstring_evaluator
         self._shots = int(sampler_shots)
         self._alpha = float(alpha)
         self._initial_state_circuit = initial_state_circuit
         self._rng = np.random.default_rng(seed)
+        self._use_value_cache = bool(device_value_cache)
+        self._value_cache: Optional[DeviceValueCache] = None  # (created by the first call that needs it)
+        self._last_scored = 0
         self._device = statevector_device or StatevectorDevice(bitstring_evaluator.input_length, dtype=dtype, device=device)
         self._composed = _ComposedCircuits(initial_state_circuit)
 
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["_value_cache"] = None  # (a cache travels empty, like _ComposedCircuits: it is refilled where it arrives)
+        return state
+
+    @property
+    def last_scored_bitstrings(self) -> int:
+        """How often the last :meth:`evaluate_circuits` call of the ``device_value_cache`` path invoked the scoring function."""
+        return self._last_scored
+
+    @property
+    def value_cache_stats(self) -> Optional[dict]:
+        """:meth:`DeviceValueCache.stats` of this evaluator's cache; None before the first call or without one."""
+        return None if self._value_cache is None else self._value_cache.stats()
+
     def evaluate_circuits(self, circuits: list[CircuitIR], parameter_values: list[list[float]]) -> list[float]:
         circuits = [None if c is None else self._composed.get(c) for c in circuits]
-        dists = measure_quasi_distributions(
-            circuits, parameter_values, self._device, self._shots, seed=int(self._rng.integers(0, 2**63 - 1))
-        )
+        seed = int(self._rng.integers(0, 2**63 - 1))
+        if self._use_value_cache:
+            return self._evaluate_through_cache(circuits, parameter_values, seed)
+        dists = measure_quasi_distributions(circuits, parameter_values, self._device, self._shots, seed=seed)
         return [
             get_expectation_with_bitstring_evaluator(d, self._bitstring_evaluator, self._alpha, self.n_qubits) for d in dists
         ]
+
+    def _evaluate_through_cache(self, circuits, parameter_values, seed: int) -> list[float]:
+        pairs = [(c, p) for c, p in zip(circuits, parameter_values) if c is not None and p is not None]
+        # (measure_quasi_distributions seeds a generator with the evaluator's draw and samples with ITS first draw)
+        seed = int(np.random.default_rng(seed).integers(0, 2**63 - 1))
+        if self._value_cache is None:
+            self._value_cache = self._device.value_cache()
+        cache = self._value_cache
+        missing = cache.lookup([c for c, _ in pairs], [p for _, p in pairs], self._shots, seed)
+        ordered, order = _ascending(missing)
+        self._last_scored = 0
+        n = self.n_qubits
+        try:
+            scores = []
+            for state in ordered.tolist():
+                self._last_scored += 1
+                scores.append(self._bitstring_evaluator.evaluate_bitstring(format(state, f"0{n}b")))
+            values = _unpermuted(scores, order)
+        except BaseException:
+            cache.clear()  # (the states the lookup inserted have no values: the next call starts from an empty table)
+            raise
+        if self._shots <= StatevectorDevice.MAX_CVAR_SHOTS:
+            return cache.finish(values, self._alpha)
+        return _cvar_of_sample_matrix(cache.finish(values, self._alpha, want_values=True), self._alpha)
 
     @property
     def n_qubits(self) -> int:

@@ -62,11 +62,13 @@ def evaluator_for(
     bitstring_evaluator: Optional[BitstringEvaluator] = None,
     alpha: float = 1.0,
     initial_state_circuit: Optional[CircuitIR] = None,
+    device_value_cache: bool = False,
 ) -> BaseCircuitEvaluator:
     """The evaluator the reference's solvers build from their configuration
     (``evolving_ansatz_minimum_eigensolver.py`` picks OperatorCircuitEvaluator for a configured estimator,
     OperatorSamplerCircuitEvaluator for a sampler + operator, BitstringCircuitEvaluator for a sampler + bitstring
-    evaluator), on the GPU backend."""
+    evaluator), on the GPU backend.  ``device_value_cache`` goes to the BitstringCircuitEvaluator (its opt-in table of
+    scored states in device memory); the other evaluators have none."""
     if (operator is None) == (bitstring_evaluator is None):
         raise ValueError("Exactly one of operator and bitstring_evaluator must be given!")
     if isinstance(configured, ConfiguredEstimatorV2):
@@ -89,6 +91,7 @@ def evaluator_for(
             bitstring_evaluator,
             alpha=alpha,
             initial_state_circuit=initial_state_circuit,
+            device_value_cache=device_value_cache,
             **options,
         )
     raise TypeError("configured must be a ConfiguredSamplerV2 or a ConfiguredEstimatorV2")

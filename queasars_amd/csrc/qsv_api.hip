@@ -19,6 +19,7 @@
 
 #include "../../include/qsv.h"
 #include "gradient.hpp"
+#include "value_cache.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
 #include "split.hpp"
@@ -167,6 +168,26 @@ private:
     std::atomic<size_t> next_{0};
     uint64_t generation_ = 0;
     bool stop_ = false;
+};
+
+// A value cache (qsv_value_cache_create): the table, what one lookup leaves for its finish -- every sample's slot and the
+// slots of the new entries, so that nothing is probed twice and nothing of the handle's scratch is held in between -- and the
+// pinned buffers the miss list and its values cross in.
+struct ValueCache {
+    int log2_slots = 0, log2_max_slots = 0;
+    uint64_t* d_keys = nullptr;
+    double* d_vals = nullptr;
+    DeviceBuffer d_sample_slot, d_miss_slots, d_counters;
+    uint64_t* h_miss = nullptr;  // pinned: the miss list's states, written by the probe kernel
+    size_t h_miss_bytes = 0;
+    double* h_values = nullptr;  // pinned: their values, read by the fill kernel
+    size_t h_values_bytes = 0;
+    uint32_t* h_counters = nullptr;  // pinned copy of d_counters
+    int64_t entries = 0;
+    bool pending = false;  // a lookup waits for its finish
+    int64_t pending_evals = 0, pending_missing = 0;
+    int pending_shots = 0;
+    int64_t samples_looked_up = 0, hits = 0, new_entries = 0, rehashes = 0, clears = 0;
 };
 
 struct qsv_handle {
@@ -380,6 +401,10 @@ struct qsv_handle {
     bool grad_copy_pending = false;
     const void* grad_checked[2] = {nullptr, nullptr};  // qsv_gradient_device's values / output last found to be this device's memory
     qsv_gradient_stats_t grad_stats{};
+
+    // device-resident value caches (qsv_value_cache_create; value_cache.hpp)
+    std::unordered_map<int, ValueCache> value_caches;
+    int next_cache_id = 1;
 
     // profiling
     bool profiling = false;
@@ -2206,6 +2231,17 @@ void free_observable_set(ObservableSet& s) {
     s = ObservableSet{};
 }
 
+void free_value_cache(ValueCache& c) {  // (the caller has waited for the handle's streams)
+    if (c.d_keys) (void)hipFree(c.d_keys);
+    if (c.d_vals) (void)hipFree(c.d_vals);
+    for (DeviceBuffer* b : {&c.d_sample_slot, &c.d_miss_slots, &c.d_counters})
+        if (b->ptr) (void)hipFree(b->ptr);
+    if (c.h_miss) (void)hipHostFree(c.h_miss);
+    if (c.h_values) (void)hipHostFree(c.h_values);
+    if (c.h_counters) (void)hipHostFree(c.h_counters);
+    c = ValueCache{};
+}
+
 int upload_bytes(qsv_t* h, DeviceBuffer& b, const void* src, size_t bytes) {
     int rc = ensure(h, b, bytes);
     if (rc) return rc;
@@ -2426,6 +2462,7 @@ void qsv_destroy(qsv_t* h) {
                             &h->d_grad_out})
         if (b->ptr) (void)hipFree(b->ptr);
     for (auto& kv : h->obs_sets) free_observable_set(kv.second);
+    for (auto& kv : h->value_caches) free_value_cache(kv.second);
     if (h->h_batch) (void)hipHostFree(h->h_batch);
     if (h->d_ship) (void)hipFree(h->d_ship);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
@@ -3288,8 +3325,11 @@ static const char* const kNotSampled = "circuits on kept states are not sampled 
 // can allocate: one whose d_scratch has to grow (more evaluations x shots, or the first call of a handle), and whatever
 // batch_layout needs for a batch it has not laid out before; ensure() waits for the handle's streams before it frees.  A search
 // that repeats one shape allocates in its first iteration only.
+// keep_states != null (qsv_sample_lookup): the samples stay in d_scratch, where the device-side CVaR keeps them, no value is
+// gathered and no operator needed; *keep_states points at them and the call returns without waiting.
 static int sample_batch_locked(qsv_t* h, const BatchArgs& args, int shots, uint64_t seed, uint64_t* out_states,
-                               double* out_values, double alpha = 1.0, double* out_cvar = nullptr, const DeviceCall* dev = nullptr) {
+                               double* out_values, double alpha = 1.0, double* out_cvar = nullptr, const DeviceCall* dev = nullptr,
+                               uint64_t** keep_states = nullptr) {
     const size_t n_evals = args.circs.size();
     if (dev) out_cvar = dev->out;
     if (n_evals == 0 || shots == 0) return QSV_OK;
@@ -3308,10 +3348,10 @@ static int sample_batch_locked(qsv_t* h, const BatchArgs& args, int shots, uint6
     const size_t out_bytes = n_evals * size_t(shots) * 8;
     const size_t dev_samples_off = ((split_off + split_bytes + 63) / 64) * 64;
     int rc;
-    if ((rc = ensure(h, h->d_scratch, dev_samples_off + (out_cvar ? 2 * out_bytes : 0)))) return rc;
+    if ((rc = ensure(h, h->d_scratch, dev_samples_off + (out_cvar ? 2 * out_bytes : keep_states ? out_bytes : 0)))) return rc;
     if (out_cvar && !dev && (rc = ensure_host_out(h, n_evals))) return rc;
     // samples (and their operator values) are written by the kernel straight into pinned host memory: no copy operations
-    if (!out_cvar && h->h_samples_bytes < 2 * out_bytes) {
+    if (!out_cvar && !keep_states && h->h_samples_bytes < 2 * out_bytes) {
         if (h->h_samples) {
             QSV_HIP(h, sync_streams(h));
             QSV_HIP(h, hipHostFree(h->h_samples));
@@ -3330,6 +3370,7 @@ static int sample_batch_locked(qsv_t* h, const BatchArgs& args, int shots, uint6
         d_states = reinterpret_cast<uint64_t*>(static_cast<char*>(h->d_scratch.ptr) + dev_samples_off);
         d_values = reinterpret_cast<double*>(static_cast<char*>(h->d_scratch.ptr) + dev_samples_off + out_bytes);
     }
+    if (keep_states) d_states = reinterpret_cast<uint64_t*>(static_cast<char*>(h->d_scratch.ptr) + dev_samples_off);
     const double* diag = d_values ? static_cast<const double*>(h->d_diag.ptr) : nullptr;
     // one-tile registers: the pass kernel prepares its evaluation itself; n <= 28: its last pass writes the
     // probabilities, not the state
@@ -3363,6 +3404,10 @@ static int sample_batch_locked(qsv_t* h, const BatchArgs& args, int shots, uint6
     const StateRun run{rule, SG, G, fuse, kModeSynthFirst | kModeFinalStore | kModeSidesOnly,
                        kModeSynthFirst | (probs_in_pass ? kModeFinalProbs : kModeFinalStore) | (fuse ? kModeFusedPrepare : 0u)};
     if ((rc = run_states(h, args, run, on_split, on_state, dev))) return rc;
+    if (keep_states) {
+        *keep_states = d_states;
+        return QSV_OK;
+    }
     // (evaluation e's values are at d_values[e * shots ..] in the caller's numbering -- the sample kernels address by the
     // descriptor's out_index, or by first_eval + slot in a batch nothing reordered --, so workgroup e writes out[e])
     if (out_cvar) QSV_HIP(h, launch_cvar(d_values, int(n_evals), shots, alpha, dev ? dev->out : h->h_out, h->stream, h->mask));
@@ -3561,6 +3606,279 @@ int qsv_cvar_device(qsv_t* h, int n_evals, const int* circuit_ids, int width, co
         h->cvar_snap.epoch = 0;
     }
     return rc;
+}
+
+// ---- device-resident value cache -------------------------------------------------------------------------------------------
+
+static int ensure_pinned(qsv_t* h, void** ptr, size_t* have, size_t bytes) {
+    if (*ptr && *have >= bytes) return QSV_OK;
+    if (*ptr) {
+        QSV_HIP(h, sync_streams(h));
+        QSV_HIP(h, hipHostFree(*ptr));
+        *ptr = nullptr;
+        *have = 0;
+    }
+    const size_t want = std::max(2 * bytes, size_t(4096));
+    QSV_HIP(h, hipHostMalloc(ptr, want, hipHostMallocDefault));
+    *have = want;
+    return QSV_OK;
+}
+
+// A table of 2^log2_slots empty slots (the keys are set on the handle's stream).
+static int cache_table_alloc(qsv_t* h, int log2_slots, uint64_t** keys, double** vals) {
+    const size_t bytes = sizeof(uint64_t) << log2_slots;
+    *keys = nullptr;
+    *vals = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(keys), bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(vals), bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(*keys, 0xFF, bytes, h->stream);
+    if (e != hipSuccess) {
+        if (*keys) (void)hipFree(*keys);
+        if (*vals) (void)hipFree(*vals);
+        *keys = nullptr;
+        *vals = nullptr;
+        return fail(h, QSV_E_DEVICE, std::string("value cache table of 2^") + std::to_string(log2_slots) + " slots: " + hipGetErrorString(e));
+    }
+    return QSV_OK;
+}
+
+static int cache_clear_locked(qsv_t* h, ValueCache& c) {
+    c.pending = false;
+    c.entries = 0;
+    c.clears += 1;
+    QSV_HIP(h, hipMemsetAsync(c.d_keys, 0xFF, sizeof(uint64_t) << c.log2_slots, h->stream));
+    return QSV_OK;
+}
+
+// The growth rule: after it 2 * (entries + n_samples) <= slots, the worst case of every sample being new, so a probe can never
+// meet a full table.  The table doubles (its entries rehashed into the new one, once, whatever the number of doublings) up to
+// 2^log2_max_slots; where the entries and the samples together would pass that, the table is cleared instead -- the scoring
+// function is pure, only time is lost.  (The caller has refused a call that cannot fit into an empty table.)
+static int cache_make_room(qsv_t* h, ValueCache& c, int64_t n_samples) {
+    bool cleared = false;
+    if (2 * (c.entries + n_samples) > (int64_t(1) << c.log2_max_slots)) {
+        cleared = true;
+        c.entries = 0;
+        c.clears += 1;
+    }
+    int target = c.log2_slots;
+    while (2 * (c.entries + n_samples) > (int64_t(1) << target)) ++target;
+    if (target == c.log2_slots) {
+        if (cleared) QSV_HIP(h, hipMemsetAsync(c.d_keys, 0xFF, sizeof(uint64_t) << c.log2_slots, h->stream));
+        return QSV_OK;
+    }
+    uint64_t* keys;
+    double* vals;
+    int rc = cache_table_alloc(h, target, &keys, &vals);
+    if (rc) return rc;
+    if (!cleared) {
+        hipError_t e = launch_cache_rehash(c.d_keys, c.d_vals, uint32_t(c.log2_slots), keys, vals, uint32_t(target),
+                                           static_cast<uint32_t*>(c.d_counters.ptr), h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) {
+            (void)hipFree(keys);
+            (void)hipFree(vals);
+            return fail(h, QSV_E_DEVICE, std::string("launch_cache_rehash: ") + hipGetErrorString(e));
+        }
+        c.rehashes += 1;
+    } else {
+        QSV_HIP(h, hipStreamSynchronize(h->stream));  // (nothing may still read the table that is freed below)
+    }
+    (void)hipFree(c.d_keys);
+    (void)hipFree(c.d_vals);
+    c.d_keys = keys;
+    c.d_vals = vals;
+    c.log2_slots = target;
+    return QSV_OK;
+}
+
+static ValueCache* find_cache(qsv_t* h, int cache_id) {
+    auto it = h->value_caches.find(cache_id);
+    if (it == h->value_caches.end()) {
+        (void)fail(h, QSV_E_ARG, "unknown value cache id " + std::to_string(cache_id));
+        return nullptr;
+    }
+    return &it->second;
+}
+
+int qsv_value_cache_create(qsv_t* h, int log2_slots, int log2_max_slots, int* out_cache_id) {
+    if (!h) return QSV_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (!out_cache_id) return fail(h, QSV_E_ARG, "out_cache_id is null");
+    if (log2_slots < 1 || log2_max_slots < log2_slots || log2_max_slots > 30)
+        return fail(h, QSV_E_ARG, "a value cache needs 1 <= log2_slots <= log2_max_slots <= 30");
+    QSV_HIP(h, hipSetDevice(h->device));
+    ValueCache c;
+    c.log2_slots = log2_slots;
+    c.log2_max_slots = log2_max_slots;
+    int rc = cache_table_alloc(h, log2_slots, &c.d_keys, &c.d_vals);
+    if (!rc) rc = ensure(h, c.d_counters, kCacheCounterWords * sizeof(uint32_t));
+    if (!rc) {
+        hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&c.h_counters), kCacheCounterWords * sizeof(uint32_t), hipHostMallocDefault);
+        if (e != hipSuccess) rc = fail(h, QSV_E_DEVICE, std::string("hipHostMalloc: ") + hipGetErrorString(e));
+    }
+    if (rc) {
+        (void)sync_streams(h);
+        free_value_cache(c);
+        return rc;
+    }
+    const int id = h->next_cache_id++;
+    h->value_caches.emplace(id, c);
+    *out_cache_id = id;
+    return QSV_OK;
+}
+
+int qsv_value_cache_destroy(qsv_t* h, int cache_id) {
+    if (!h) return QSV_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    ValueCache* c = find_cache(h, cache_id);
+    if (!c) return QSV_E_ARG;
+    QSV_HIP(h, hipSetDevice(h->device));
+    QSV_HIP(h, sync_streams(h));
+    free_value_cache(*c);
+    h->value_caches.erase(cache_id);
+    return QSV_OK;
+}
+
+int qsv_value_cache_clear(qsv_t* h, int cache_id) {
+    if (!h) return QSV_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    ValueCache* c = find_cache(h, cache_id);
+    if (!c) return QSV_E_ARG;
+    QSV_HIP(h, hipSetDevice(h->device));
+    return cache_clear_locked(h, *c);
+}
+
+int qsv_value_cache_stats(const qsv_t* h, int cache_id, qsv_value_cache_stats_t* out) {
+    if (!h || !out) return QSV_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    auto it = h->value_caches.find(cache_id);
+    if (it == h->value_caches.end()) return QSV_E_ARG;
+    const ValueCache& c = it->second;
+    out->entries = c.entries;
+    out->slots = int64_t(1) << c.log2_slots;
+    out->samples_looked_up = c.samples_looked_up;
+    out->hits = c.hits;
+    out->new_entries = c.new_entries;
+    out->rehashes = c.rehashes;
+    out->clears = c.clears;
+    return QSV_OK;
+}
+
+int qsv_sample_lookup(qsv_t* h, int cache_id, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
+                      int shots, uint64_t seed, int64_t* out_n_missing, const uint64_t** out_missing_states) {
+    if (!h) return QSV_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (n_evals < 0 || shots < 0 || !out_n_missing || !out_missing_states ||
+        (n_evals > 0 && shots > 0 && (!circuit_ids || !param_offsets)))
+        return fail(h, QSV_E_ARG, "bad arguments");
+    ValueCache* c = find_cache(h, cache_id);
+    if (!c) return QSV_E_ARG;
+    if (c->pending) return fail(h, QSV_E_STATE, "a lookup on this value cache waits for qsv_sample_lookup_finish (or qsv_value_cache_clear)");
+    const int64_t n_samples = int64_t(n_evals) * shots;
+    if (2 * n_samples > (int64_t(1) << c->log2_max_slots))  // (before anything is launched)
+        return fail(h, QSV_E_ARG, "one call's " + std::to_string(n_samples) + " samples do not fit into half of the cache's 2^" +
+                                      std::to_string(c->log2_max_slots) + " slots");
+    if (h->n >= 64) return fail(h, QSV_E_UNSUPPORTED, "value caches key on states of fewer than 64 qubits");
+    QSV_HIP(h, hipSetDevice(h->device));
+    BatchArgs args;
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, shots ? param_offsets : nullptr, params, args, shots ? kNotSampled : nullptr);
+    if (rc) return rc;
+    *out_n_missing = 0;
+    *out_missing_states = c->h_miss;
+    if (n_samples == 0) {  // (nothing is drawn, as in qsv_sample_batch; the finish has nothing to do either)
+        c->pending = true;
+        c->pending_evals = 0;
+        c->pending_shots = shots;
+        c->pending_missing = 0;
+        return QSV_OK;
+    }
+    // the cache's own buffers first (they may wait for the streams), then the draws, the growth and the probe on the stream
+    if ((rc = ensure(h, c->d_sample_slot, size_t(n_samples) * sizeof(uint32_t))) ||
+        (rc = ensure(h, c->d_miss_slots, size_t(n_samples) * sizeof(uint32_t))) ||
+        (rc = ensure_pinned(h, reinterpret_cast<void**>(&c->h_miss), &c->h_miss_bytes, size_t(n_samples) * sizeof(uint64_t))))
+        return rc;
+    uint64_t* d_states = nullptr;
+    if ((rc = sample_batch_locked(h, args, shots, seed, nullptr, nullptr, 1.0, nullptr, nullptr, &d_states))) {
+        (void)sync_streams(h);
+        return rc;
+    }
+    uint32_t* counters = static_cast<uint32_t*>(c->d_counters.ptr);
+    hipError_t e = hipMemsetAsync(counters, 0, kCacheCounterWords * sizeof(uint32_t), h->stream);
+    if (e == hipSuccess && (rc = cache_make_room(h, *c, n_samples))) {
+        (void)sync_streams(h);
+        return rc;
+    }
+    if (e == hipSuccess)
+        e = launch_cache_probe(d_states, n_samples, c->d_keys, uint32_t(c->log2_slots), static_cast<uint32_t*>(c->d_sample_slot.ptr),
+                               c->h_miss, static_cast<uint32_t*>(c->d_miss_slots.ptr), counters, h->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(c->h_counters, counters, kCacheCounterWords * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        (void)sync_streams(h);
+        return fail(h, QSV_E_DEVICE, std::string("qsv_sample_lookup: ") + hipGetErrorString(e));
+    }
+    if (c->h_counters[1] != 0) {  // (the growth rule rules it out; the table is no longer to be trusted)
+        (void)cache_clear_locked(h, *c);
+        return fail(h, QSV_E_DEVICE, "a value cache probe walked its whole table (the cache was cleared)");
+    }
+    const int64_t n_missing = int64_t(c->h_counters[0]);
+    c->entries += n_missing;
+    c->samples_looked_up += n_samples;
+    c->new_entries += n_missing;
+    c->hits += n_samples - n_missing;
+    c->pending = true;
+    c->pending_evals = n_evals;
+    c->pending_shots = shots;
+    c->pending_missing = n_missing;
+    *out_n_missing = n_missing;
+    *out_missing_states = c->h_miss;
+    return QSV_OK;
+}
+
+int qsv_sample_lookup_finish(qsv_t* h, int cache_id, int64_t n_values, const double* values, double alpha, double* out_cvar,
+                             double* out_values) {
+    if (!h) return QSV_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    ValueCache* c = find_cache(h, cache_id);
+    if (!c) return QSV_E_ARG;
+    if (!c->pending) return fail(h, QSV_E_STATE, "no lookup on this value cache waits for its values (qsv_sample_lookup comes first)");
+    if (n_values != c->pending_missing)
+        return fail(h, QSV_E_STATE, "the lookup reported " + std::to_string(c->pending_missing) + " missing states, " +
+                                        std::to_string(n_values) + " values were given");
+    if (n_values > 0 && !values) return fail(h, QSV_E_ARG, "values is null");
+    if (out_cvar && (!(alpha > 0.0) || alpha > 1.0)) return fail(h, QSV_E_ARG, "alpha must be in (0, 1]");
+    if (out_cvar && c->pending_shots > kCvarMaxShots)
+        return fail(h, QSV_E_ARG, "the device-side CVaR sorts at most 4096 samples per evaluation");
+    QSV_HIP(h, hipSetDevice(h->device));
+    const int64_t n_evals = c->pending_evals, n_samples = n_evals * c->pending_shots;
+    int rc;
+    if (h->async_pending) {  // (the scratch and the result buffer are about to be written: a batch that ended without waiting may still use them)
+        QSV_HIP(h, sync_streams(h));
+        h->async_pending = false;
+    }
+    if (n_values > 0) {
+        if ((rc = ensure_pinned(h, reinterpret_cast<void**>(&c->h_values), &c->h_values_bytes, size_t(n_values) * sizeof(double)))) return rc;
+        std::memcpy(c->h_values, values, size_t(n_values) * sizeof(double));
+        QSV_HIP(h, launch_cache_fill(c->d_vals, static_cast<const uint32_t*>(c->d_miss_slots.ptr), c->h_values, n_values, h->stream));
+    }
+    if (n_samples > 0 && (out_cvar || out_values)) {
+        // every sample's value, evaluation e's at [e * shots ..) as sample_batch_locked leaves its d_values for launch_cvar
+        if ((rc = ensure(h, h->d_scratch, size_t(n_samples) * sizeof(double)))) return rc;
+        double* d_values = static_cast<double*>(h->d_scratch.ptr);
+        QSV_HIP(h, launch_cache_gather(c->d_vals, static_cast<const uint32_t*>(c->d_sample_slot.ptr), n_samples, d_values, h->stream));
+        if (out_cvar) {
+            if ((rc = ensure_host_out(h, size_t(n_evals)))) return rc;
+            QSV_HIP(h, launch_cvar(d_values, int(n_evals), c->pending_shots, alpha, h->h_out, h->stream, ActiveMask{}));
+        }
+        if (out_values)
+            QSV_HIP(h, hipMemcpyAsync(out_values, d_values, size_t(n_samples) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    QSV_HIP(h, hipStreamSynchronize(h->stream));
+    if (out_cvar && n_samples > 0) std::memcpy(out_cvar, h->h_out, size_t(n_evals) * sizeof(double));
+    c->pending = false;
+    return QSV_OK;
 }
 
 // ---- parameter-shift gradients ---------------------------------------------------------------------------------------------
