@@ -285,6 +285,51 @@ typedef struct qsv_spsa_step_args {
     double* changes;
 } qsv_spsa_step_args;
 int qsv_spsa_step(qsv_t* h, const qsv_spsa_step_args* args);
+/*
+ * The optimiser's share of one iteration of R lock-step NFT runs (Nakanishi-Fujii-Todo sequential minimisation, Phys. Rev.
+ * Research 2, 043158: the optimiser of the reference's own test harness, test/minimum_eigensolvers/evqe/solver.py:28-36) as ONE
+ * launch on the handle's stream, for a parameter search whose state lives in device memory (evqe/device_search.py): ACCEPT
+ * iteration accept_iteration from the values measured at its points, then PROPOSE the points of iteration propose_iteration.
+ * Either half may be left out (accept / propose = 0): a search's first call only proposes, its last only accepts.  Fresh runs of
+ * one configuration move in lock-step -- which iterations evaluate the base point and where the search ends depend on no function
+ * value --, so the caller knows both iteration numbers and both forms ahead and the device keeps no counters.
+ * All pointers are device memory of the handle's GPU; x and points are row-major with rows of `width` doubles.
+ *   x         R x width.  Run r searches sizes[r] >= 1 of its row's entries: variable j is column columns[r * columns_stride + j]
+ *             (the identity for a run that owns its row; a layer's positions inside the parameter vector of a shared circuit).
+ *             The other entries of the row are never written and reach every proposed point as they are.
+ *   recycled  R doubles: the fitted minimum of the run's last accepted iteration, f at its new x, which stands in for the base
+ *             value of an iteration proposed without one.  Written by every accept; read only by an accept without the base.
+ *   accept    with j = accept_iteration % sizes[r], col = column of variable j, and k = 3 (accept_with_base) or 2 values per run:
+ *             z0 = values[3r] or recycled[r]; z1, z3 = the run's last two values (f at x[col] + pi/2 and at x[col] - pi/2);
+ *             c = 0.5 (z1 + z3); cos_part = z0 - c; sin_part = 0.5 (z3 - z1); a = hypot(cos_part, sin_part);
+ *             if a > 0: x[col] = (x[col] - atan2(sin_part, cos_part)) + pi;  recycled[r] = c - a.
+ *             Every sum and product is rounded on its own, in this order (no fused multiply-add); hypot and atan2 are the device
+ *             math library's, so the new x[col] and recycled[r] can differ from a host's in the last bits.
+ *   propose   with col as above for propose_iteration: rows k r .. k r + k - 1 of points are the run's row of x, bit for bit --
+ *             in the order base (only if propose_with_base, k = 3), plus, minus -- except that entry col is x[col] + M_PI_2 in
+ *             the plus row and x[col] - M_PI_2 in the minus row.  The values of an iteration are expected in the same order.
+ * The contents of sizes and columns are the caller's responsibility: sizes[r] in 1 .. columns_stride, columns in 0 .. width - 1.
+ * (A run whose size is outside that range is left alone, and a column outside the row moves nothing; neither is reported.)
+ * QSV_E_ARG: a null struct; null x / sizes / columns / recycled; n_runs or width < 0; columns_stride < 1; an accept without values;
+ * a propose without points; a negative iteration number on a half that is asked for; x or points not aligned to 8 bytes.
+ * n_runs == 0 or width == 0 is a successful call that launches nothing.
+ */
+typedef struct qsv_nft_step_args {
+    int32_t n_runs, width;
+    int32_t columns_stride;
+    int32_t reserved;
+    double* x;
+    const int32_t* sizes;
+    const int32_t* columns;
+    double* recycled;
+    int32_t accept, accept_with_base;
+    int64_t accept_iteration;
+    int32_t propose, propose_with_base;
+    int64_t propose_iteration;
+    const double* values;
+    double* points;
+} qsv_nft_step_args;
+int qsv_nft_step(qsv_t* h, const qsv_nft_step_args* args);
 /* How many pushes the open batch is best delivered in (1 or 2): measurement-backed advice, any number works. */
 int qsv_eval_suggested_pushes(const qsv_t* h);
 /* Launch-group size of the handle (evaluations whose states are resident at the same time). */

@@ -67,6 +67,29 @@ class QsvSpsaStepArgs(C.Structure):
     ]
 
 
+class QsvNftStepArgs(C.Structure):
+    """``qsv_nft_step_args`` of include/qsv.h (device pointers as integers)."""
+
+    _fields_ = [
+        ("n_runs", C.c_int32),
+        ("width", C.c_int32),
+        ("columns_stride", C.c_int32),
+        ("reserved", C.c_int32),
+        ("x", C.c_void_p),
+        ("sizes", C.c_void_p),
+        ("columns", C.c_void_p),
+        ("recycled", C.c_void_p),
+        ("accept", C.c_int32),
+        ("accept_with_base", C.c_int32),
+        ("accept_iteration", C.c_int64),
+        ("propose", C.c_int32),
+        ("propose_with_base", C.c_int32),
+        ("propose_iteration", C.c_int64),
+        ("values", C.c_void_p),
+        ("points", C.c_void_p),
+    ]
+
+
 class QsvProfile(C.Structure):
     _fields_ = [
         ("n_evals", C.c_uint64),
@@ -173,6 +196,7 @@ SIGNATURES = {
     "qsv_eval_staging": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P)]),
     "qsv_eval_push_device": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
     "qsv_spsa_step": (C.c_int, [_P, _P]),
+    "qsv_nft_step": (C.c_int, [_P, _P]),
     "qsv_eval_end": (C.c_int, [_P, _P]),
     "qsv_eval_set_output": (C.c_int, [_P, _P]),
     "qsv_eval_results_seen": (C.c_int, [_P]),

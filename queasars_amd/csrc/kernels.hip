@@ -1928,6 +1928,77 @@ hipError_t launch_spsa_step(const SpsaStepArgs& args, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// ---- qsv_nft_step -----------------------------------------------------------------------------------------------------------
+// The arithmetic of _NFTRun.accept / propose (queasars_amd/evqe/solver.py: sequential minimisation by a three-point sinusoid
+// fit, Nakanishi, Fujii, Todo, Phys. Rev. Research 2, 043158) for one run per workgroup.  The accept is a dozen flops on one
+// coordinate: thread 0 does it, in the host's order and with contraction off (x - atan2(..) + pi is two roundings there), and a
+// barrier publishes x to the row copies behind it.  The proposal is the kernel's traffic -- two or three rows of `width` doubles
+// written per run, the run's row of x read from cache for each --: every thread carries pairs of columns and stores them as one
+// 16-byte word.  An odd `width` leaves every other row on 8-byte alignment only, so each row finds its own first aligned column
+// and writes the column in front of it, and the one left over behind the pairs, on their own.
+__device__ __forceinline__ void nft_write_row(double* __restrict__ dst, const double* __restrict__ x, int width, int col, double shift,
+                                              int tid) {
+#pragma clang fp contract(off)
+    const int head = int((reinterpret_cast<uintptr_t>(dst) >> 3) & 1u);  // (columns in front of the first 16-byte boundary)
+    const int n_pairs = (width - head) >> 1;
+    for (int p = tid; p < n_pairs; p += 256) {
+        const int j = head + 2 * p;
+        double2 v;
+        v.x = j == col ? x[j] + shift : x[j];
+        v.y = j + 1 == col ? x[j + 1] + shift : x[j + 1];
+        *reinterpret_cast<double2*>(dst + j) = v;
+    }
+    if (tid == 0 && head) dst[0] = col == 0 ? x[0] + shift : x[0];
+    const int last = head + 2 * n_pairs;
+    if (tid == 64 && last < width) dst[last] = last == col ? x[last] + shift : x[last];
+}
+
+__global__ void __launch_bounds__(256) nft_step_kernel(const NftStepArgs a) {
+#pragma clang fp contract(off)  // (every sum below is rounded on its own, as the host's Python floats are)
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const int size = a.sizes[r];
+    if (size < 1 || size > a.columns_stride) return;  // (the caller's error, qsv.h: the run is left alone; the whole workgroup leaves)
+    double* x = a.x + size_t(r) * size_t(a.width);
+    const int* columns = a.columns + size_t(r) * size_t(a.columns_stride);
+    if (a.accept) {
+        if (tid == 0) {
+            const int col = columns[int(a.accept_iteration % size)];
+            const int k = a.accept_with_base ? 3 : 2;
+            const double* v = a.values + size_t(k) * size_t(r);
+            const double z0 = a.accept_with_base ? v[0] : a.recycled[r];
+            const double z1 = v[k - 2], z3 = v[k - 1];
+            // f(t) = c + amp cos(t - b):  z0 - c = amp cos(t0 - b),  (z3 - z1) / 2 = amp sin(t0 - b)
+            const double c = 0.5 * (z1 + z3);
+            const double cos_part = z0 - c, sin_part = 0.5 * (z3 - z1);
+            const double amp = hypot(cos_part, sin_part);
+            if (amp > 0.0 && col >= 0 && col < a.width) {
+                const double moved = x[col] - atan2(sin_part, cos_part);
+                x[col] = moved + M_PI;
+            }
+            a.recycled[r] = c - amp;
+        }
+        __syncthreads();  // (x is complete before the proposal below reads it)
+    }
+    if (a.propose) {
+        int col = columns[int(a.propose_iteration % size)];
+        if (col < 0 || col >= a.width) col = -1;  // (no such column: plain copies)
+        const int k = a.propose_with_base ? 3 : 2;
+        double* row = a.points + size_t(k) * size_t(r) * size_t(a.width);
+        if (a.propose_with_base) {
+            nft_write_row(row, x, a.width, -1, 0.0, tid);
+            row += a.width;
+        }
+        nft_write_row(row, x, a.width, col, M_PI_2, tid);
+        nft_write_row(row + a.width, x, a.width, col, -M_PI_2, tid);
+    }
+}
+
+hipError_t launch_nft_step(const NftStepArgs& args, hipStream_t stream) {
+    if (args.n_runs <= 0 || args.width <= 0) return hipSuccess;
+    hipLaunchKernelGGL(nft_step_kernel, dim3(unsigned(args.n_runs)), dim3(256), 0, stream, args);
+    return hipGetLastError();
+}
+
 hipError_t launch_reduce_partials(const double* partials, uint32_t blocks, int n_evals, double* out,
                                   hipStream_t stream, const EvalDesc* evals) {
     if (n_evals <= 0) return hipSuccess;

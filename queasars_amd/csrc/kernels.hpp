@@ -409,6 +409,25 @@ struct SpsaStepArgs {
 };
 hipError_t launch_spsa_step(const SpsaStepArgs& args, hipStream_t stream);
 
+// ---- the optimiser's share of a lock-step NFT iteration (qsv.h: qsv_nft_step) -------------------------------------------------
+// One workgroup per run: accept the iteration whose two or three values are in `values` (one coordinate of x moves to the fitted
+// sinusoid's minimum, the fitted minimum is kept in `recycled`), then write the two or three points of the next iteration.
+// Either half may be left out.  Rows of x and points need 8-byte alignment only.
+struct NftStepArgs {
+    int n_runs, width, columns_stride;
+    double* x;                    // [n_runs][width]
+    const int* sizes;             // [n_runs]: searched variables per run, 1 .. columns_stride
+    const int* columns;           // [n_runs][columns_stride]: column of x of variable j
+    double* recycled;             // [n_runs]
+    int accept, accept_with_base;
+    long long accept_iteration;
+    int propose, propose_with_base;
+    long long propose_iteration;
+    const double* values;         // [3 n_runs] (base, plus, minus per run) or [2 n_runs]
+    double* points;               // [3 n_runs][width] or [2 n_runs][width], rows in the order of the values
+};
+hipError_t launch_nft_step(const NftStepArgs& args, hipStream_t stream);
+
 hipError_t launch_probabilities(int dtype, const void* state, uint64_t dim, int n_slots, double* probs,
                                 hipStream_t stream);
 hipError_t launch_state_to_f64(int dtype, const void* state, uint64_t dim, double* out_re_im, hipStream_t stream);

@@ -3143,6 +3143,41 @@ int qsv_spsa_step(qsv_t* h, const qsv_spsa_step_args* in) {
     return QSV_OK;
 }
 
+int qsv_nft_step(qsv_t* h, const qsv_nft_step_args* in) {
+    if (!h || !in) return QSV_E_ARG;
+    // (between qsv_eval_begin and qsv_eval_end the calling thread holds the handle: it would wait for itself)
+    if (h->batch_owner.load() == std::this_thread::get_id())
+        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_nft_step goes between batches)");
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (in->n_runs < 0 || in->width < 0 || in->columns_stride < 1 || !in->x || !in->sizes || !in->columns || !in->recycled)
+        return fail(h, QSV_E_ARG, "bad arguments");
+    if (in->accept && !in->values) return fail(h, QSV_E_ARG, "an accept needs the values it fits");
+    if (in->propose && !in->points) return fail(h, QSV_E_ARG, "a proposal needs somewhere to go");
+    if ((in->accept && in->accept_iteration < 0) || (in->propose && in->propose_iteration < 0))
+        return fail(h, QSV_E_ARG, "a negative iteration number");
+    if ((reinterpret_cast<uintptr_t>(in->x) & 7u) || (reinterpret_cast<uintptr_t>(in->points) & 7u))
+        return fail(h, QSV_E_ARG, "x and points must be aligned as doubles are");
+    QSV_HIP(h, hipSetDevice(h->device));
+    NftStepArgs a{};
+    a.n_runs = in->n_runs;
+    a.width = in->width;
+    a.columns_stride = in->columns_stride;
+    a.x = in->x;
+    a.sizes = in->sizes;
+    a.columns = in->columns;
+    a.recycled = in->recycled;
+    a.accept = in->accept != 0;
+    a.accept_with_base = in->accept_with_base != 0;
+    a.accept_iteration = in->accept_iteration;
+    a.propose = in->propose != 0;
+    a.propose_with_base = in->propose_with_base != 0;
+    a.propose_iteration = in->propose_iteration;
+    a.values = in->values;
+    a.points = in->points;
+    QSV_HIP(h, launch_nft_step(a, h->stream));
+    return QSV_OK;
+}
+
 int qsv_eval_suggested_pushes(const qsv_t* h) {
     if (!h || !h->batch.open) return QSV_E_ARG;
     // Two pushes overlap the packing of the second half with the GPU work on the first -- worth it when there is GPU

@@ -22,6 +22,10 @@ the runs' ``active`` flags, so that the two evaluations of a stopped run cost a 
 With a sampling evaluator (``sampler_shots`` given) every iteration draws one seed from the evaluator's generator, as an
 ``evaluate_circuits`` call of the host driver does -- also the up to ``look_every - 1`` iterations queued after the last run
 has stopped and before the host has looked: the generator then stands further on than after the same search on the host.
+
+NFT searches (:func:`minimize_nft_on_device`, ``qsv_nft_step``) are simpler: fresh runs of one configuration move in perfect
+lock-step, the host knows every iteration's form and the last iteration before it starts (:func:`nft_schedule`), and it never
+looks at the device inside a search.
 """
 
 from __future__ import annotations
@@ -137,6 +141,134 @@ def minimize_spsa_on_device(evaluator, jobs, look_every: int = 8) -> None:
         run.x = x_final[i, where[i]].copy()
         run.iteration = int(done_iterations[i])
         run.nfev = 2 * int(done_iterations[i])
+        run.done = True
+
+
+def nft_schedule(config) -> tuple[list[bool], int]:
+    """What fresh NFT runs of ``config`` will do, known before any value is: per iteration whether the base point is evaluated
+    (three values per run) or the fitted minimum of the iteration before stands in for it (two), and the evaluations one run
+    has made when it stops.  ``_NFTRun.propose`` / ``accept`` restated without a run: the base at iteration 0 and at every
+    multiple of a positive ``reset_interval``; the stopping rule -- ``nfev >= maxfev`` or ``iteration >= maxiter`` -- is looked
+    at after an accept, so ``NFT(maxfev=40)`` runs 20 iterations and 41 evaluations.  No function value enters: every fresh
+    run of one configuration has this schedule, whatever its size.  Needs no device."""
+    flags: list[bool] = []
+    nfev = 0
+    if config.maxfev <= 0:
+        return flags, nfev
+    while True:
+        iteration = len(flags)
+        with_base = iteration == 0 or (config.reset_interval > 0 and iteration % config.reset_interval == 0)
+        flags.append(with_base)
+        nfev += 3 if with_base else 2
+        if nfev >= config.maxfev or (config.maxiter is not None and iteration + 1 >= config.maxiter):
+            return flags, nfev
+
+
+def supported_nft(evaluator, jobs) -> bool:
+    """Can :func:`minimize_nft_on_device` take these jobs?  An evaluator that reads points from and leaves values in device
+    memory, on a GPU; at least two runs, every one a fresh NFT run of one configuration object with something to search."""
+    from queasars_amd.evqe.solver import _NFTRun
+
+    if len(jobs) < 2 or not hasattr(evaluator, "evaluate_device_to_device"):
+        return False
+    if not evaluator.device_resident_search_possible():
+        return False
+    runs = [run for _, run in jobs]
+    if not all(isinstance(run, _NFTRun) for run in runs):
+        return False
+    cfg = runs[0].config
+    if any(run.config is not cfg or run.iteration != 0 or run.nfev != 0 or run.done or run.x.size < 1 for run in runs):
+        return False
+    return len(nft_schedule(cfg)[0]) > 0
+
+
+def minimize_nft_on_device(evaluator, jobs, state: dict | None = None) -> None:
+    """The lock-step NFT search of fresh runs of one configuration with its whole state in device memory: iterates, the
+    fitted minima that stand in for base values, points and function values are tensors on the stream of the evaluator's
+    handle.  The host knows the whole schedule ahead (:func:`nft_schedule`), so it queues, per iteration, one ``qsv_nft_step``
+    launch (accept iteration k - 1, propose iteration k) and one ``evaluate_device_to_device`` -- of the three-per-run circuit
+    list where the base is evaluated, of the two-per-run list and the first 2 R rows otherwise, the same two list objects
+    throughout -- and looks at the device once, at the end, for ``x`` and the fitted minima.  Nothing in the loop waits (the
+    library does where it lays a batch out afresh: when the list changes).
+
+    Given the same ``x`` and values, a proposal is bit for bit ``_NFTRun.propose``'s; an accept calls the device's ``hypot``
+    and ``atan2``, so an updated coordinate and the fitted minimum can differ from the host's in the last bits -- and in a flat
+    direction, where the fitted amplitude is rounding noise, a last bit decides an angle: whole searches are not comparable
+    with the host driver's iterate by iterate.
+
+    With a sampling evaluator every iteration draws exactly one seed from the evaluator's generator, as one
+    ``evaluate_circuits`` call of the host driver does, and nothing is queued beyond the schedule: after the search the
+    generator stands exactly where the host driver leaves it.
+
+    ``state``: a dictionary that receives the search's tensors (``x``, ``recycled``, ``points``, ``values``) before the first
+    iteration is queued -- for tests and measurements that look at an iteration from inside the evaluator."""
+    import ctypes as C
+
+    import torch
+
+    from queasars_amd import _lib
+    from queasars_amd.distributed import _chain_state
+
+    runs = [run for _, run in jobs]
+    cfg = runs[0].config
+    with_base, nfev = nft_schedule(cfg)
+    n_iter = len(with_base)
+    # (run.embed: the run's variables are entries of a longer parameter vector -- the row is that vector, `columns` says where
+    # the variables are, and the other entries travel into every point untouched)
+    where = [run.embed[1] if run.embed is not None else np.arange(run.x.size) for run in runs]
+    lengths = np.array([run.embed[0].size if run.embed is not None else run.x.size for run in runs])
+    sizes_host = np.array([run.x.size for run in runs], dtype=np.int32)
+    width, n_runs, stride = int(lengths.max()), len(runs), int(sizes_host.max())
+    x_host = np.zeros((n_runs, width))
+    columns_host = np.zeros((n_runs, stride), dtype=np.int32)
+    for i, run in enumerate(runs):
+        if run.embed is not None:
+            x_host[i, : lengths[i]] = run.embed[0]
+        x_host[i, where[i]] = run.x
+        columns_host[i, : sizes_host[i]] = where[i]
+    # (the same two list objects call after call: the evaluators key their caches on identity)
+    three = [circuit for circuit, _ in jobs for _ in (0, 1, 2)]
+    two = [circuit for circuit, _ in jobs for _ in (0, 1)]
+
+    dev = evaluator.statevector_device
+    device = torch.device("cuda", dev.device_index)
+    stream = _chain_state(evaluator, device)["stream"]  # (the stream the evaluator's handle launches on)
+    caller = torch.cuda.current_stream(device)
+    stream.wait_stream(caller)
+    lib, handle = dev._lib, dev._handle
+    with torch.cuda.stream(stream):
+        x = torch.from_numpy(x_host).to(device)
+        sizes = torch.from_numpy(sizes_host).to(device)
+        columns = torch.from_numpy(columns_host).to(device)
+        recycled = torch.zeros(n_runs, dtype=torch.float64, device=device)
+        points = torch.empty((3 * n_runs, width), dtype=torch.float64, device=device)
+        values = torch.empty(3 * n_runs, dtype=torch.float64, device=device)
+        points_two, values_two = points[: 2 * n_runs], values[: 2 * n_runs]
+        if state is not None:
+            state.update(x=x, recycled=recycled, points=points, values=values)
+        args = _lib.QsvNftStepArgs(
+            n_runs=n_runs, width=width, columns_stride=stride, reserved=0, x=x.data_ptr(), sizes=sizes.data_ptr(),
+            columns=columns.data_ptr(), recycled=recycled.data_ptr(), values=values.data_ptr(), points=points.data_ptr())
+        for k in range(n_iter + 1):
+            # accept iteration k - 1 (its values are in `values`), propose iteration k
+            args.accept, args.accept_iteration, args.accept_with_base = int(k > 0), max(k - 1, 0), int(k > 0 and with_base[k - 1])
+            args.propose, args.propose_iteration, args.propose_with_base = int(k < n_iter), k, int(k < n_iter and with_base[k])
+            dev._check(lib.qsv_nft_step(handle, C.byref(args)))
+            if k == n_iter:
+                break
+            if with_base[k]:
+                evaluator.evaluate_device_to_device(three, points, values)
+            else:
+                evaluator.evaluate_device_to_device(two, points_two, values_two)
+        x_final = x.cpu().numpy()
+        recycled_final = recycled.cpu().numpy()
+    caller.wait_stream(stream)
+    for i, run in enumerate(runs):
+        run.x = x_final[i, where[i]].copy()
+        run.iteration = n_iter
+        run.nfev = nfev
+        run._recycled = float(recycled_final[i])
+        run._needs_base = with_base[-1]
         run.done = True
 
 

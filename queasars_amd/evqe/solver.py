@@ -417,23 +417,29 @@ def _minimize_spsa_vectorised(evaluator, jobs: list) -> None:
         run.nfev = int(nfev[i])
 
 
-def _device_search_asked_for(evaluator, n_runs: int, flag: Optional[bool]) -> bool:
+def _device_search_asked_for(evaluator, n_runs: int, flag: Optional[bool], opt_in: bool = False) -> bool:
     """What the configuration's ``device_resident_search`` (``flag``) and ``QSV_DEVICE_SEARCH`` say about a search of ``n_runs``
     runs, before anyone asks whether it can be done.  ``None`` is "where it pays" -- searches of at least
     ``_DEVICE_SEARCH_MIN_RUNS`` runs -- for an evaluator whose ``device_resident_search_by_default`` is true (the exact
     estimator), and the host driver for every other one (a sampling evaluator: the device search is opt-in there, so that runs
-    configured before it existed keep their numbers).  The one place that resolves the default: ``_device_search_wanted``,
+    configured before it existed keep their numbers).  ``opt_in``: ``None`` is the host driver whatever the evaluator (NFT
+    searches, for the same reason).  The one place that resolves the default: ``_device_search_wanted``,
     which also decides whether layer searches embed their runs, and ``_minimize_batched`` both ask here."""
     env = os.environ.get("QSV_DEVICE_SEARCH")
     if env == "0":
         return False
     if flag is None:
-        flag = bool(getattr(evaluator, "device_resident_search_by_default", False)) and n_runs >= _DEVICE_SEARCH_MIN_RUNS
+        flag = (not opt_in and bool(getattr(evaluator, "device_resident_search_by_default", False))
+                and n_runs >= _DEVICE_SEARCH_MIN_RUNS)
     return bool(flag) or env == "1"
 
 
 def _device_search_wanted(evaluator, n_runs: int, flag: Optional[bool], optimizer) -> bool:
     """Will a search of ``n_runs`` fresh runs of ``optimizer`` keep its state on the device (_minimize_batched's rule)?"""
+    if isinstance(optimizer, NFT):
+        if n_runs < 2 or optimizer.maxfev <= 0 or not _device_search_asked_for(evaluator, n_runs, flag, opt_in=True):
+            return False
+        return hasattr(evaluator, "evaluate_device_to_device") and bool(evaluator.device_resident_search_possible())
     if os.environ.get("QSV_SCALAR_SPSA") or not isinstance(optimizer, SPSA) or n_runs < 2:
         return False
     if not _device_search_asked_for(evaluator, n_runs, flag):
@@ -450,7 +456,8 @@ _DEVICE_SEARCH_MIN_RUNS = 16  # (config 4 on one MI355X: searches of 25 - 64 run
 def _minimize_batched(evaluator, jobs: list, on_device: Optional[bool] = False) -> None:
     """Advance every (circuit, run) pair to completion; one evaluate_circuits call per optimiser iteration of the whole
     set (SPSA proposes two points per run and iteration, NFT two or three).  ``on_device``: SPSA runs whose evaluator can
-    read points from and leave values in device memory keep their whole state there (evqe/device_search.py)."""
+    read points from and leave values in device memory keep their whole state there (evqe/device_search.py); fresh NFT runs of
+    one configuration likewise, but only where asked for (``True`` or ``QSV_DEVICE_SEARCH=1``; ``None`` is the loop below)."""
     spsa = [] if os.environ.get("QSV_SCALAR_SPSA") else [job for job in jobs if isinstance(job[1], _SPSARun) and not job[1].done]
     if len(spsa) > 1 and len(spsa) == sum(1 for job in jobs if not job[1].done) and all(job[1].config is spsa[0][1].config for job in spsa):
         if _device_search_asked_for(evaluator, len(spsa), on_device):
@@ -467,6 +474,13 @@ def _minimize_batched(evaluator, jobs: list, on_device: Optional[bool] = False) 
     if any(isinstance(job[1], _AdamRun) for job in jobs):
         raise ValueError("Adam runs cannot share a search with runs of another optimiser")
     active = [job for job in jobs if not job[1].done]
+    if (len(active) > 1 and all(isinstance(job[1], _NFTRun) and job[1].config is active[0][1].config for job in active)
+            and _device_search_asked_for(evaluator, len(active), on_device, opt_in=True)):
+        from queasars_amd.evqe import device_search
+
+        if device_search.supported_nft(evaluator, active):
+            device_search.minimize_nft_on_device(evaluator, active)
+            return
     while active:
         circuits, params, counts = [], [], []
         for circuit, run in active:
@@ -536,6 +550,10 @@ class EVQEMinimumEigensolverConfiguration:
     # sample (``device_resident_search_by_default``: the exact estimator); a sampler evaluator's searches stay with the host
     # driver under None, as before the device search could take them, and go to the device with True (or QSV_DEVICE_SEARCH=1).
     # False: never; True: whenever it can.
+    # NFT searches have a device form too (qsv_nft_step: the whole schedule is known ahead, the host never looks at the device
+    # inside a search) and are opt-in with EVERY evaluator: None keeps them on the host driver and their numbers as they were,
+    # True (or QSV_DEVICE_SEARCH=1) sends them to the device.  Their accepts call the device's hypot / atan2, which in the flat
+    # directions these searches are full of can turn an angle by pi without changing a value.
     device_resident_search: Optional[bool] = None
     # Layer searches of individuals whose circuits have no split form on the device (deep individuals: every evaluation is a few
     # passes over the 2^n state) keep the state in front of the searched layer on the device and evaluate from there
