@@ -330,6 +330,50 @@ typedef struct qsv_nft_step_args {
     double* points;
 } qsv_nft_step_args;
 int qsv_nft_step(qsv_t* h, const qsv_nft_step_args* args);
+/*
+ * The optimiser's share of one iteration of R lock-step Adam runs (evqe/solver.py: Adam, _AdamRun.accept_gradient) as ONE launch
+ * on the handle's stream, for a search whose state lives in device memory (evqe/device_search.py: minimize_adam_on_device): the
+ * moments, the update and the stopping rule from gradients that a qsv_gradient_plan_run queued in front of it left in device
+ * memory.  It waits for nothing.  All pointers are device memory of the handle's GPU.
+ *   x         R x width, row-major.  Run r searches sizes[r] >= 1 of its row's entries: variable j is column
+ *             columns[r * columns_stride + j], as in qsv_nft_step_args.  The other entries of the row are never written.
+ *   m, v, gradient   R x grad_width, row-major: entry j of row r belongs to variable j of run r (a row of a gradient plan's output).
+ *   For every run r with active[r] != 0 and every j < sizes[r], with col the column of variable j:
+ *             g = gradient[r][j]
+ *             m = beta_1 * m + one_minus_beta_1 * g
+ *             v = beta_2 * v + one_minus_beta_2 * (g * g)
+ *             u = lr * (m / bias_1) / (sqrt(v / bias_2) + eps)
+ *             x[r][col] = x[r][col] - u
+ *             in this association, every product, quotient, square root and sum rounded on its own (no fused multiply-add; fp64
+ *             division and square root are correctly rounded): BIT FOR BIT what _AdamRun.accept_gradient computes in NumPy.
+ *             Then iterations[r] += 1; active[r] = 0 if iterations[r] >= maxiter; and, if tol > 0, active[r] = 0 also when
+ *             sqrt(sum over j of u_j * u_j) < tol, the sum taken in ascending j from 0.0, every product and sum rounded on its own.
+ *   A run with active[r] == 0 is not touched: its rows of x, m and v and its count stay as they are.
+ *   bias_1, bias_2   1 - beta_1**t and 1 - beta_2**t of THIS iteration t (1 for a run's first), and one_minus_beta_* = 1 - beta_*,
+ *             all formed by the caller: the device never calls pow, and the doubles are the ones the host driver would use.
+ * The contents of sizes and columns are the caller's responsibility: sizes[r] in 1 .. min(columns_stride, grad_width), columns in
+ * 0 .. width - 1.  (A run whose size is outside that range is left alone -- not even counted --, and a column outside the row
+ * moves nothing while its moments are still updated; neither is reported.)
+ * QSV_E_ARG: a null struct; null x / sizes / columns / m / v / gradient / active / iterations; n_runs, width or grad_width < 0;
+ * columns_stride < 1; grad_width < columns_stride (a run may search columns_stride entries: its gradient row must hold them).
+ * n_runs == 0 or width == 0 is a successful call that launches nothing.
+ */
+typedef struct qsv_adam_step_args {
+    int32_t n_runs, width;
+    int32_t columns_stride, grad_width;
+    double* x;
+    const int32_t* sizes;
+    const int32_t* columns;
+    double* m;
+    double* v;
+    const double* gradient;
+    uint8_t* active;
+    int64_t* iterations;
+    double lr, beta_1, beta_2, one_minus_beta_1, one_minus_beta_2, eps, tol;
+    double bias_1, bias_2;
+    int64_t maxiter;
+} qsv_adam_step_args;
+int qsv_adam_step(qsv_t* h, const qsv_adam_step_args* args);
 /* How many pushes the open batch is best delivered in (1 or 2): measurement-backed advice, any number works. */
 int qsv_eval_suggested_pushes(const qsv_t* h);
 /* Launch-group size of the handle (evaluations whose states are resident at the same time). */
@@ -534,6 +578,44 @@ typedef struct qsv_gradient_stats_t {
     int64_t scratch_bytes;
 } qsv_gradient_stats_t;
 int qsv_gradient_stats(const qsv_t* h, qsv_gradient_stats_t* out);
+
+/*
+ * GRADIENT PLANS: qsv_gradient_device for a caller that differentiates the SAME circuits by the SAME parameters again and again
+ * (a gradient-based optimiser's iterations).  The shift tables depend on the circuits' structure and on wrt alone, so a plan
+ * builds them once and keeps them in device memory of its own; its runs then follow each other on the handle's stream.
+ *
+ * qsv_gradient_plan_create validates exactly as qsv_gradient_device does -- same codes, same messages, QSV_E_UNSUPPORTED for a
+ * parameter more than one angle slot reads --, with `width` the row length of the points a run will read and out_width that of
+ * the gradients it will write.  It records the ids, both widths and the chunk size in force ("gradient_chunk"), uploads the
+ * tables and waits for that upload: create may block.  out_n_shifted (may be NULL): circuit evaluations ONE run queues.
+ *
+ * qsv_gradient_plan_run queues on the handle's stream what qsv_gradient_device queues for the plan's ids, wrt and widths at the
+ * points in device_values (ready_event as there), and row e of device_out receives, BIT FOR BIT, what that call writes -- for any
+ * chunk size.  Its contract is qsv_gradient_device's: complete once the work enqueued so far on the stream is, the points
+ * unchanged until then.  The ids are looked up on every run (a destroyed circuit: QSV_E_ARG); qsv_set_operator between runs is
+ * allowed.  A run of a plan with ONE chunk directly behind a run of the same plan -- nothing else on the handle in between
+ * but launches on its stream, qsv_adam_step for one -- writes no staging buffer, reuses the batch layout the run before it
+ * left and returns without the host having waited for anything.  A plan's first run, a run behind any other batch and every
+ * run of a plan with several chunks may wait where qsv_gradient_device does.
+ *
+ * qsv_gradient_plan_destroy waits for the handle's stream (a run may still read the tables) and frees them; qsv_destroy frees
+ * the plans that are left.  Unknown plan ids are QSV_E_ARG everywhere.
+ */
+int qsv_gradient_plan_create(qsv_t* h, int n_evals, const int* circuit_ids, int width, const int64_t* wrt_offsets, const int32_t* wrt,
+                             int out_width, int* out_plan_id, int64_t* out_n_shifted);
+int qsv_gradient_plan_run(qsv_t* h, int plan_id, const double* device_values, void* ready_event, double* device_out);
+int qsv_gradient_plan_destroy(qsv_t* h, int plan_id);
+/* A plan's counters: shifted evaluations and chunks of one run, runs queued so far, how often the host waited for a stream or an
+ * event inside those runs (the first run of a plan usually does; a one-chunk plan run again does not), and the bytes of its
+ * tables in device memory. */
+typedef struct qsv_gradient_plan_stats_t {
+    int64_t n_shifted;
+    int64_t n_chunks;
+    int64_t n_runs;
+    int64_t n_host_waits;
+    int64_t table_bytes;
+} qsv_gradient_plan_stats_t;
+int qsv_gradient_plan_stats(const qsv_t* h, int plan_id, qsv_gradient_plan_stats_t* out);
 
 /* ---- several observables per evaluation ---------------------------------------------------------- */
 

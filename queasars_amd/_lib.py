@@ -90,6 +90,35 @@ class QsvNftStepArgs(C.Structure):
     ]
 
 
+class QsvAdamStepArgs(C.Structure):
+    """``qsv_adam_step_args`` of include/qsv.h (device pointers as integers)."""
+
+    _fields_ = [
+        ("n_runs", C.c_int32),
+        ("width", C.c_int32),
+        ("columns_stride", C.c_int32),
+        ("grad_width", C.c_int32),
+        ("x", C.c_void_p),
+        ("sizes", C.c_void_p),
+        ("columns", C.c_void_p),
+        ("m", C.c_void_p),
+        ("v", C.c_void_p),
+        ("gradient", C.c_void_p),
+        ("active", C.c_void_p),
+        ("iterations", C.c_void_p),
+        ("lr", C.c_double),
+        ("beta_1", C.c_double),
+        ("beta_2", C.c_double),
+        ("one_minus_beta_1", C.c_double),
+        ("one_minus_beta_2", C.c_double),
+        ("eps", C.c_double),
+        ("tol", C.c_double),
+        ("bias_1", C.c_double),
+        ("bias_2", C.c_double),
+        ("maxiter", C.c_int64),
+    ]
+
+
 class QsvProfile(C.Structure):
     _fields_ = [
         ("n_evals", C.c_uint64),
@@ -151,6 +180,18 @@ class QsvGradientStats(C.Structure):
     ]
 
 
+class QsvGradientPlanStats(C.Structure):
+    """``qsv_gradient_plan_stats_t`` of include/qsv.h."""
+
+    _fields_ = [
+        ("n_shifted", C.c_int64),
+        ("n_chunks", C.c_int64),
+        ("n_runs", C.c_int64),
+        ("n_host_waits", C.c_int64),
+        ("table_bytes", C.c_int64),
+    ]
+
+
 class QsvValueCacheStats(C.Structure):
     """``qsv_value_cache_stats_t`` of include/qsv.h."""
 
@@ -197,6 +238,7 @@ SIGNATURES = {
     "qsv_eval_push_device": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
     "qsv_spsa_step": (C.c_int, [_P, _P]),
     "qsv_nft_step": (C.c_int, [_P, _P]),
+    "qsv_adam_step": (C.c_int, [_P, _P]),
     "qsv_eval_end": (C.c_int, [_P, _P]),
     "qsv_eval_set_output": (C.c_int, [_P, _P]),
     "qsv_eval_results_seen": (C.c_int, [_P]),
@@ -220,6 +262,10 @@ SIGNATURES = {
     "qsv_gradient_circuits": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "qsv_gradient_device": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P]),
     "qsv_gradient_stats": (C.c_int, [_P, C.POINTER(QsvGradientStats)]),
+    "qsv_gradient_plan_create": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "qsv_gradient_plan_run": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "qsv_gradient_plan_destroy": (C.c_int, [_P, C.c_int]),
+    "qsv_gradient_plan_stats": (C.c_int, [_P, C.c_int, C.POINTER(QsvGradientPlanStats)]),
     "qsv_observables_create": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.POINTER(C.c_int)]),
     "qsv_observables_destroy": (C.c_int, [_P, C.c_int]),
     "qsv_eval_observables": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),

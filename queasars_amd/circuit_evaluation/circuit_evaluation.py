@@ -298,6 +298,69 @@ class DeviceValueCache:
             pass
 
 
+class DeviceGradientPlan:
+    """The gradients of one list of circuits by one choice of parameters, prepared once (``StatevectorDevice.gradient_plan``;
+    include/qsv.h, GRADIENT PLANS): the shift tables live in device memory, and :meth:`run` queues what
+    ``gradients_of_device_parameters`` queues -- the same bits -- without rebuilding or uploading them.  Runs of a plan whose
+    shifted evaluations fit one chunk follow each other on the handle's stream without the host waiting in between."""
+
+    def __init__(self, owner: "StatevectorDevice", circuits: Sequence[CircuitIR], width: int, out_width: int, wrt=None):
+        self._owner = owner
+        self._id = -1
+        self._circuits = list(circuits)  # (the plan names their ids: they stay registered while it lives)
+        n = len(self._circuits)
+        if width < 0 or out_width < 0:
+            raise ValueError("width and out_width must not be negative")
+        ids, _need, _total = owner._batch_metadata(self._circuits) if n else (None, None, 0)
+        wrt_offsets, wrt_flat, _counts = owner._wrt_arguments(self._circuits, wrt)
+        out, n_shifted = C.c_int(-1), C.c_int64(0)
+        owner._check_gradient(owner._lib.qsv_gradient_plan_create(
+            owner._handle, n, _lib.as_ptr(ids) if n else None, int(width),
+            _lib.as_ptr(wrt_offsets) if wrt_offsets is not None else None, _lib.as_ptr(wrt_flat) if wrt_flat is not None else None,
+            int(out_width), C.byref(out), C.byref(n_shifted)))
+        self._id = int(out.value)
+        #: circuit evaluations one :meth:`run` queues
+        self.n_shifted = int(n_shifted.value)
+        self.width, self.out_width = int(width), int(out_width)
+
+    def run(self, matrix_ptr: int, event: int, out_ptr: int) -> int:
+        """Gradients at the points in the ``len(circuits) x width`` matrix at ``matrix_ptr`` into the ``len(circuits) x
+        out_width`` matrix at ``out_ptr`` (device memory; ``event`` as in ``gradients_of_device_parameters``), queued on the
+        handle's stream and not waited for.  Returns the circuit evaluations queued."""
+        owner = self._owner
+        if self._id < 0 or not owner._handle:
+            raise RuntimeError("the gradient plan is closed")
+        owner.last_gradient_evaluations = 0
+        owner._check_gradient(owner._lib.qsv_gradient_plan_run(
+            owner._handle, self._id, C.c_void_p(matrix_ptr) if matrix_ptr else None, C.c_void_p(event) if event else None,
+            C.c_void_p(out_ptr) if out_ptr else None))
+        owner.last_gradient_evaluations = self.n_shifted
+        return self.n_shifted
+
+    def stats(self) -> dict:
+        """``n_shifted``, ``n_chunks`` (of one run), ``n_runs``, ``n_host_waits`` (stream or event waits inside the runs so
+        far), ``table_bytes``."""
+        owner = self._owner
+        if self._id < 0 or not owner._handle:
+            raise RuntimeError("the gradient plan is closed")
+        raw = _lib.QsvGradientPlanStats()
+        owner._check(owner._lib.qsv_gradient_plan_stats(owner._handle, self._id, C.byref(raw)))
+        return {name: int(getattr(raw, name)) for name, _ in raw._fields_}
+
+    def close(self) -> None:
+        """Free the tables (idempotent; waits for the handle's stream.  The device's own end frees them as well)."""
+        pid, self._id = getattr(self, "_id", -1), -1
+        owner = getattr(self, "_owner", None)
+        if pid >= 0 and owner is not None and getattr(owner, "_handle", None):
+            owner._lib.qsv_gradient_plan_destroy(owner._handle, pid)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover
+            pass
+
+
 class StatevectorDevice:
     """Owns one ``qsv_t`` handle: the resident state buffers, plans and operator tables of one GPU.
 
@@ -995,6 +1058,12 @@ class StatevectorDevice:
         self.last_gradient_evaluations = int(n_shifted.value)
         return self.last_gradient_evaluations
 
+    def gradient_plan(self, circuits: Sequence[CircuitIR], width: int, out_width: int, wrt=None) -> DeviceGradientPlan:
+        """A :class:`DeviceGradientPlan` for ``circuits`` differentiated by ``wrt`` (as in :meth:`gradients`), for points in rows
+        of ``width`` doubles and gradients in rows of ``out_width``.  Checked as ``gradients_of_device_parameters`` checks
+        (``ValueError`` for a parameter without a shift rule); the operator must be set."""
+        return DeviceGradientPlan(self, circuits, width, out_width, wrt)
+
     def gradient_stats(self) -> dict:
         """``qsv_gradient_stats``: the last gradient call's shifted evaluations and chunks, how often the gradient scratch was
         allocated or grown since the device was created, and its size."""
@@ -1188,6 +1257,49 @@ def _device_matrix_arguments(evaluator, circuits, matrix, ready: bool):
     return stamp[1], stamp[3], event, remember
 
 
+class EvaluatorGradientPlan:
+    """``OperatorCircuitEvaluator.gradient_plan``: a :class:`DeviceGradientPlan` run under the evaluator's operator."""
+
+    def __init__(self, evaluator: "OperatorCircuitEvaluator", plan: DeviceGradientPlan, n_circuits: int):
+        self._evaluator = evaluator
+        self._plan = plan
+        self._n = int(n_circuits)
+        #: circuit evaluations one :meth:`run` queues
+        self.n_shifted = plan.n_shifted
+
+    def run(self, matrix, out, ready: bool = True) -> int:
+        """Gradients at the rows of ``matrix`` into ``out`` -- tensors of the shapes the plan was made for, on the stream of the
+        evaluator's handle --, queued and not waited for.  ``ready=False``: ``matrix`` is being written on the tensor's current
+        stream, which is not the handle's; the handle's stream waits for it.  Returns the circuit evaluations queued."""
+        import torch
+
+        evaluator, plan = self._evaluator, self._plan
+        for tensor, width in ((matrix, plan.width), (out, plan.out_width)):
+            if (not isinstance(tensor, torch.Tensor) or tensor.dtype != torch.float64 or tensor.shape != (self._n, width)
+                    or not tensor.is_contiguous() or not tensor.is_cuda or tensor.device.index != evaluator._device.device_index):
+                raise ValueError("matrix and out must be the contiguous float64 device tensors of the shapes the plan was made for")
+        marker = None
+        if not ready:
+            stream = torch.cuda.current_stream(matrix.device)
+            if not stream.query():
+                marker = torch.cuda.Event()
+                marker.record(stream)
+        with evaluator._device.operator_lock:
+            if evaluator._device._operator is not evaluator._operator:
+                evaluator._device.set_operator(evaluator._operator)
+            try:
+                return plan.run(matrix.data_ptr() if plan.width else 0, marker.cuda_event if marker is not None else 0,
+                                out.data_ptr() if plan.out_width else 0)
+            finally:
+                evaluator.last_gradient_evaluations = evaluator._device.last_gradient_evaluations
+
+    def stats(self) -> dict:
+        return self._plan.stats()
+
+    def close(self) -> None:
+        self._plan.close()
+
+
 class OperatorCircuitEvaluator(BaseCircuitEvaluator):
     """Exact expectation values of ``operator`` on the GPU (estimator branch of the reference).
 
@@ -1341,6 +1453,33 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
             finally:
                 self.last_gradient_evaluations = self._device.last_gradient_evaluations
         remember()
+
+    def gradient_plan(self, circuits: list[CircuitIR], matrix, out, wrt=None) -> "EvaluatorGradientPlan":
+        """:meth:`evaluate_gradients_device_to_device` prepared once for ``circuits``, ``wrt`` and the shapes of ``matrix`` and
+        ``out`` (tensors as there; neither is read or written here): the returned object's ``run(matrix, out)`` queues the same
+        gradients, bit for bit, without the shift tables being rebuilt and uploaded -- and, where the shifted evaluations fit
+        one chunk, without the host waiting between one run and the next (:class:`DeviceGradientPlan`)."""
+        import torch
+
+        if self._precision > 0:
+            raise ValueError("estimator_precision > 0 is emulated on the host")
+        if self._initial_state_circuit is not None:
+            circuits = [self._with_initial_state(c) for c in circuits]
+        n = len(circuits)
+        for name, tensor in (("matrix", matrix), ("out", out)):
+            if (not isinstance(tensor, torch.Tensor) or tensor.dtype != torch.float64 or tensor.dim() != 2 or tensor.shape[0] != n
+                    or not tensor.is_contiguous() or not tensor.is_cuda or tensor.device.index != self._device.device_index):
+                raise ValueError(f"{name} must be a contiguous 2-D float64 tensor of len(circuits) rows on the evaluator's device")
+        if _has_none(circuits):
+            raise ValueError("a gradient plan cannot skip circuits (None entries)")
+        _offsets, _flat, counts = StatevectorDevice._wrt_arguments(circuits, wrt)
+        if n and int(counts.max()) > out.shape[1]:
+            raise ValueError(f"the output has rows of {out.shape[1]} entries, a circuit's gradient has {int(counts.max())}")
+        with self._device.operator_lock:
+            if self._device._operator is not self._operator:
+                self._device.set_operator(self._operator)
+            plan = self._device.gradient_plan(circuits, int(matrix.shape[1]), int(out.shape[1]), wrt)
+        return EvaluatorGradientPlan(self, plan, n)
 
     def keep_states(self, circuits: list[CircuitIR], parameter_values: list[list[float]]) -> list[KeptState]:
         """The final states of the (circuit, parameter vector) pairs -- behind this evaluator's initial state, if it has one --

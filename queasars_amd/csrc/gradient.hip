@@ -1,4 +1,4 @@
-// Parameter-shift gradients: shift plan (host) and the expansion / combination kernels (gradient.hpp).
+// Parameter-shift gradients: shift plan (host), the expansion / combination kernels and the Adam step (gradient.hpp).
 #include "gradient.hpp"
 
 #include <vector>
@@ -76,7 +76,59 @@ gradient_combine_kernel(const double* __restrict__ values, const GradEntry* __re
     out[idx] = g;
 }
 
+// One wave per run.  Each lane takes the variables j = lane, lane + 64, ...: moments, update, the run's entry of x.  With a
+// tolerance the squares of a round's updates go from lane to lane in ascending j (every lane holds the same running sum), so
+// the norm is the sum a sequential loop forms.  Division and square root of doubles are correctly rounded (no fast-math), and
+// nothing is contracted: the bits are NumPy's.
+__global__ void __launch_bounds__(64) adam_step_kernel(const AdamStepArgs a) {
+#pragma clang fp contract(off)
+    const int r = blockIdx.x, lane = threadIdx.x;
+    if (a.active[r] == 0) return;  // (the whole wave: a stopped run keeps every bit)
+    const int size = a.sizes[r];
+    if (size < 1 || size > a.columns_stride || size > a.grad_width) return;  // (the caller's error, qsv.h: the run is left alone)
+    double* x = a.x + size_t(r) * size_t(a.width);
+    double* m = a.m + size_t(r) * size_t(a.grad_width);
+    double* v = a.v + size_t(r) * size_t(a.grad_width);
+    const double* gradient = a.gradient + size_t(r) * size_t(a.grad_width);
+    const int* columns = a.columns + size_t(r) * size_t(a.columns_stride);
+    double sum = 0.0;
+    for (int first = 0; first < size; first += 64) {  // (size is the wave's: every lane makes every round)
+        const int j = first + lane;
+        double square = 0.0;
+        if (j < size) {
+            const double g = gradient[j];
+            const double m_new = a.beta_1 * m[j] + a.one_minus_beta_1 * g;
+            const double v_new = a.beta_2 * v[j] + a.one_minus_beta_2 * (g * g);
+            const double m_hat = m_new / a.bias_1;
+            const double v_hat = v_new / a.bias_2;
+            const double u = a.lr * m_hat / (sqrt(v_hat) + a.eps);
+            m[j] = m_new;
+            v[j] = v_new;
+            const int col = columns[j];
+            if (col >= 0 && col < a.width) x[col] = x[col] - u;
+            square = u * u;
+        }
+        if (a.tol > 0.0) {
+            const int count = size - first < 64 ? size - first : 64;
+            for (int k = 0; k < count; ++k) sum = sum + __shfl(square, k, 64);
+        }
+    }
+    if (lane == 0) {
+        const long long done = a.iterations[r] + 1;
+        a.iterations[r] = done;
+        bool stop = done >= a.maxiter;
+        if (a.tol > 0.0 && sqrt(sum) < a.tol) stop = true;
+        if (stop) a.active[r] = 0;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_adam_step(const AdamStepArgs& args, hipStream_t stream) {
+    if (args.n_runs <= 0 || args.width <= 0) return hipSuccess;
+    hipLaunchKernelGGL(adam_step_kernel, dim3(unsigned(args.n_runs)), dim3(64), 0, stream, args);
+    return hipGetLastError();
+}
 
 hipError_t launch_gradient_expand(const double* base, int64_t base_stride, int base_width, const GradRow* rows, int64_t n_rows,
                                   double* out, int out_width, hipStream_t stream) {

@@ -1,6 +1,6 @@
 // Parameter-shift gradients (qsv.h: qsv_gradient_describe, qsv_gradient_circuits, qsv_gradient_device): the shift plan of a
 // circuit, and the two kernels around the shifted evaluations -- the expansion of base rows into shifted rows in front of them
-// and the combination of their values into gradient entries behind them.
+// and the combination of their values into gradient entries behind them.  And what consumes them on the device: the Adam step.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -51,5 +51,22 @@ hipError_t launch_gradient_expand(const double* base, int64_t base_stride, int b
 // product and difference rounded on its own.
 hipError_t launch_gradient_combine(const double* values, const GradEntry* entries, const int64_t* offsets, int64_t n_evals,
                                    int out_width, double cp, double cm, double* out, hipStream_t stream);
+
+// qsv_adam_step (qsv.h): one wave per run -- lanes stride over the run's variables, and the squared norm of the update is summed in
+// ascending j, one addition at a time --, one launch per iteration.
+struct AdamStepArgs {
+    int n_runs, width, columns_stride, grad_width;
+    double* x;
+    const int32_t* sizes;
+    const int32_t* columns;
+    double* m;
+    double* v;
+    const double* gradient;
+    uint8_t* active;
+    long long* iterations;
+    double lr, beta_1, beta_2, one_minus_beta_1, one_minus_beta_2, eps, tol, bias_1, bias_2;
+    long long maxiter;
+};
+hipError_t launch_adam_step(const AdamStepArgs& args, hipStream_t stream);
 
 }  // namespace qsv

@@ -401,6 +401,26 @@ struct qsv_handle {
     bool grad_copy_pending = false;
     const void* grad_checked[2] = {nullptr, nullptr};  // qsv_gradient_device's values / output last found to be this device's memory
     qsv_gradient_stats_t grad_stats{};
+    // gradient plans (qsv_gradient_plan_create): a plan's tables in device memory of its own, and what a run needs of them on the host
+    struct GradientPlan {
+        std::vector<int> ids;
+        int width = 0, out_width = 0;
+        size_t chunk = 1;                // shifted evaluations per chunk, as "gradient_chunk" stood when the plan was made
+        std::vector<GradRow> rows;       // the host's copy: which evaluation a shifted row belongs to
+        size_t n_entries = 0;
+        void* d_tab = nullptr;           // [GradRow x shifted][GradEntry x entries][int64 x (evaluations + 1)]
+        qsv_gradient_plan_stats_t stats{};
+    };
+    std::unordered_map<int, GradientPlan> grad_plans;
+    int next_grad_plan_id = 1;
+    // The layout the last run of a ONE-chunk plan left in the staging buffer, as cvar_snap is qsv_cvar_device's: valid while `epoch`
+    // is the handle's, for the next run of the same plan (expectation_to_device)
+    struct PlanSnap {
+        uint64_t epoch = 0;
+        int plan_id = 0;
+        size_t n_evals = 0;
+    } plan_snap;
+    uint64_t host_waits = 0;  // times the host waited for a stream or an event (sync_streams and the few direct waits a batch can meet)
 
     // device-resident value caches (qsv_value_cache_create; value_cache.hpp)
     std::unordered_map<int, ValueCache> value_caches;
@@ -436,6 +456,7 @@ inline hipStream_t ws(const qsv_t* h) { return h->work ? h->work : h->stream; }
 
 // Nothing on either stream may still be using a buffer that is about to be replaced.
 hipError_t sync_streams(qsv_t* h) {
+    h->host_waits += 1;
     hipError_t e = h->stream ? hipStreamSynchronize(h->stream) : hipSuccess;
     for (hipStream_t st : h->side_streams)
         if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -916,6 +937,7 @@ int upload_plans(qsv_t* h, const std::vector<Circuit*>& circs) {
         h->h_stage_words = want;
     } else {
         // the previous batch's copy out of the staging buffer must be complete before it is overwritten
+        h->host_waits += 1;
         QSV_HIP(h, hipStreamSynchronize(h->stream));
     }
     size_t cur = 0;
@@ -1539,6 +1561,7 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
                 // circuits) reset counters that other chain had begun to add to: its evaluations of four and five keys were
                 // combined from incomplete partial sums, or not at all -- a wrong value in the first batch of a handle.
                 QSV_HIP(h, hipMemsetAsync(h->d_factor_big_count.ptr, 0, cbytes, ws(h)));
+                h->host_waits += 1;
                 QSV_HIP(h, hipStreamSynchronize(ws(h)));
             }
         }
@@ -1981,6 +2004,7 @@ int eval_end(qsv_t* h, double* out) {
     }
     if (!arrived) {
         // (polling hipStreamQuery instead was measured: no faster, and it slowed concurrent callers down threefold)
+        h->host_waits += 1;
         QSV_HIP(h, hipStreamSynchronize(h->stream));
         for (size_t i = 0; i < h->side_streams.size(); ++i)
             if (used_mask >> i & 1u) QSV_HIP(h, hipStreamSynchronize(h->side_streams[i]));
@@ -2469,6 +2493,8 @@ void qsv_destroy(qsv_t* h) {
     if (h->h_out) (void)hipHostFree(h->h_out);
     if (h->h_samples) (void)hipHostFree(h->h_samples);
     if (h->h_grad_tab) (void)hipHostFree(h->h_grad_tab);
+    for (auto& plan : h->grad_plans)
+        if (plan.second.d_tab) (void)hipFree(plan.second.d_tab);
     if (h->ev_grad) (void)hipEventDestroy(h->ev_grad);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -3178,6 +3204,46 @@ int qsv_nft_step(qsv_t* h, const qsv_nft_step_args* in) {
     return QSV_OK;
 }
 
+int qsv_adam_step(qsv_t* h, const qsv_adam_step_args* in) {
+    if (!h || !in) return QSV_E_ARG;
+    // (between qsv_eval_begin and qsv_eval_end the calling thread holds the handle: it would wait for itself)
+    if (h->batch_owner.load() == std::this_thread::get_id())
+        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_adam_step goes between batches)");
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (in->n_runs < 0 || in->width < 0 || in->grad_width < 0 || in->columns_stride < 1 || !in->x || !in->sizes || !in->columns || !in->m ||
+        !in->v || !in->gradient || !in->active || !in->iterations)
+        return fail(h, QSV_E_ARG, "bad arguments");
+    if (in->grad_width < in->columns_stride)
+        return fail(h, QSV_E_ARG, "grad_width " + std::to_string(in->grad_width) + " is smaller than the " + std::to_string(in->columns_stride) +
+                                      " entries a run may search");
+    QSV_HIP(h, hipSetDevice(h->device));
+    AdamStepArgs a{};
+    a.n_runs = in->n_runs;
+    a.width = in->width;
+    a.columns_stride = in->columns_stride;
+    a.grad_width = in->grad_width;
+    a.x = in->x;
+    a.sizes = in->sizes;
+    a.columns = in->columns;
+    a.m = in->m;
+    a.v = in->v;
+    a.gradient = in->gradient;
+    a.active = in->active;
+    a.iterations = reinterpret_cast<long long*>(in->iterations);
+    a.lr = in->lr;
+    a.beta_1 = in->beta_1;
+    a.beta_2 = in->beta_2;
+    a.one_minus_beta_1 = in->one_minus_beta_1;
+    a.one_minus_beta_2 = in->one_minus_beta_2;
+    a.eps = in->eps;
+    a.tol = in->tol;
+    a.bias_1 = in->bias_1;
+    a.bias_2 = in->bias_2;
+    a.maxiter = in->maxiter;
+    QSV_HIP(h, launch_adam_step(a, h->stream));
+    return QSV_OK;
+}
+
 int qsv_eval_suggested_pushes(const qsv_t* h) {
     if (!h || !h->batch.open) return QSV_E_ARG;
     // Two pushes overlap the packing of the second half with the GPU work on the first -- worth it when there is GPU
@@ -3465,7 +3531,7 @@ static int sample_batch_locked(qsv_t* h, const BatchArgs& args, int shots, uint6
 // dev != null (qsv_cvar_device): the results go to dev->out in device memory and the call returns without waiting.  It can
 // allocate where sample_batch_locked can, and the first call after qsv_set_operator sorts the operator's values, which
 // allocates and waits (sort_states_by_value).
-static int expectation_to_device(qsv_t* h, const BatchArgs& args, double* device_out);
+static int expectation_to_device(qsv_t* h, const BatchArgs& args, double* device_out, const int* plan_id = nullptr);
 static int exact_cvar_locked(qsv_t* h, const BatchArgs& args, double alpha, double* out_cvar, const DeviceCall* dev = nullptr) {
     const size_t n_evals = args.circs.size();
     if (n_evals == 0) return QSV_OK;
@@ -3528,14 +3594,36 @@ static int exact_cvar_locked(qsv_t* h, const BatchArgs& args, double alpha, doub
 
 // alpha = 1 of the exact form with values and results in device memory: the expectation values, as a batch with
 // qsv_eval_push_device and qsv_eval_set_output computes them; with a mask they go through d_scratch, and a copy kernel leaves
-// the entries of switched-off evaluations alone (those evaluations do run: the expectation routes do not know the mask).
-static int expectation_to_device(qsv_t* h, const BatchArgs& args, double* device_out) {
+// plan_id (qsv_gradient_plan_run, the one chunk of a plan): the batch is remembered by it, and the same plan's next run, with
+// nothing in between that counts (handle: epoch), is that batch again as qsv_eval_begin knows it -- the layout stands, the
+// kernels read the descriptors from the device copy the last run's kernels made (batch.repeat, descs_base), and the host
+// neither writes a staging buffer nor waits.  Everything still goes to the handle's stream, in order.
+static int expectation_to_device(qsv_t* h, const BatchArgs& args, double* device_out, const int* plan_id) {
     const size_t n = args.circs.size();
     const ActiveMask mask = h->mask;
     h->mask = ActiveMask{};
     int rc = QSV_OK;
     if (mask.flags) rc = ensure(h, h->d_scratch, n * sizeof(double));
-    if (!rc) rc = eval_begin(h, args.circs, args.n_params);
+    qsv_handle::Batch& b = h->batch;
+    const bool remember = plan_id && !mask.flags && args.device_values && n > 0 && h->repeat_enabled && !h->profiling;
+    const bool again = remember && h->plan_snap.epoch == h->epoch && h->plan_snap.plan_id == *plan_id && h->plan_snap.n_evals == n;
+    h->plan_snap.epoch = 0;
+    if (!rc && again) {
+        // (what qsv_eval_begin sets for the previous batch again; the buffers eval_begin sizes have their sizes)
+        h->prof = qsv_profile{};
+        h->prof.n_evals = uint64_t(n);
+        b.circs = args.circs;
+        b.repeat = true;
+        b.whole_push = false;
+        b.pushed = 0;
+        b.n_pushes = 0;
+        b.aux_count = 0;
+        b.used_mask = 0;
+        b.chain_crossed = false;
+        b.sentinels = false;
+    } else if (!rc) {
+        rc = eval_begin(h, args.circs, args.n_params);
+    }
     if (!rc) {
         h->out_target = mask.flags ? static_cast<double*>(h->d_scratch.ptr) : device_out;
         h->batch.ways = 1;  // (every push on the handle's own stream, and the ordinary evaluations of a mixed batch behind whatever
@@ -3555,6 +3643,7 @@ static int expectation_to_device(qsv_t* h, const BatchArgs& args, double* device
     }
     if (rc) (void)sync_streams(h);
     eval_close(h);
+    if (!rc && remember) h->plan_snap = qsv_handle::PlanSnap{h->epoch, *plan_id, n};
     return rc;
 }
 
@@ -3938,26 +4027,31 @@ struct GradCall {
     int out_width;
 };
 
-// Gradients of circs[e] at row e of call.base by the parameters wrt[wrt_offsets[e] .. wrt_offsets[e + 1]) (wrt_offsets null:
-// by every parameter) into row e of call.out: the shift tables, then chunk by chunk the expansion kernel and the shifted
-// evaluations -- one batch of the ordinary driver each, values from and results into device memory, expectation_to_device --,
-// then the combination kernel.  Everything on the handle's stream; returns without waiting for the last chunk.
-static int gradient_locked(qsv_t* h, const std::vector<Circuit*>& circs, const int* circuit_ids, const int64_t* wrt_offsets,
-                           const int32_t* wrt, const GradCall& call, int64_t* out_n_shifted) {
-    const size_t n_evals = circs.size();
-    if (h->n_terms == 0) return fail(h, QSV_E_STATE, "no operator set (call qsv_set_operator first)");
+// The shift tables of a gradient call -- circs[e] by the parameters wrt[wrt_offsets[e] .. wrt_offsets[e + 1]) (wrt_offsets null: by
+// every parameter), points in rows of base_width values, gradients in rows of out_width -- and every check such a call makes.
+struct GradTables {
     std::vector<GradRow> rows;
     std::vector<GradEntry> entries;
-    std::vector<int64_t> offsets(n_evals + 1, 0);
+    std::vector<int64_t> offsets;
+};
+static int gradient_tables(qsv_t* h, const std::vector<Circuit*>& circs, const int* circuit_ids, const int64_t* wrt_offsets,
+                           const int32_t* wrt, int base_width, int out_width, GradTables& tab) {
+    const size_t n_evals = circs.size();
+    if (h->n_terms == 0) return fail(h, QSV_E_STATE, "no operator set (call qsv_set_operator first)");
+    std::vector<GradRow>& rows = tab.rows;
+    std::vector<GradEntry>& entries = tab.entries;
+    rows.clear();
+    entries.clear();
+    tab.offsets.assign(n_evals + 1, 0);
     const double shifts[4] = {grad_shift1(), -grad_shift1(), grad_shift3(), -grad_shift3()};
     for (size_t e = 0; e < n_evals; ++e) {
         const Circuit& c = *circs[e];
-        if (call.base_width < c.n_params)
-            return fail(h, QSV_E_ARG, "circuit needs " + std::to_string(c.n_params) + " parameter values, got " + std::to_string(call.base_width));
+        if (base_width < c.n_params)
+            return fail(h, QSV_E_ARG, "circuit needs " + std::to_string(c.n_params) + " parameter values, got " + std::to_string(base_width));
         const int64_t first = wrt_offsets ? wrt_offsets[e] : 0, count = wrt_offsets ? wrt_offsets[e + 1] - first : int64_t(c.n_params);
         if (count < 0) return fail(h, QSV_E_ARG, "wrt_offsets must be non-decreasing");
-        if (count > call.out_width)
-            return fail(h, QSV_E_ARG, "out_width " + std::to_string(call.out_width) + " is too small for " + std::to_string(count) + " gradient entries");
+        if (count > out_width)
+            return fail(h, QSV_E_ARG, "out_width " + std::to_string(out_width) + " is too small for " + std::to_string(count) + " gradient entries");
         if (count > 0 && wrt_offsets && !wrt) return fail(h, QSV_E_ARG, "wrt is null");
         for (int64_t j = 0; j < count; ++j) {
             const int64_t p = wrt_offsets ? int64_t(wrt[first + j]) : j;
@@ -3971,18 +4065,68 @@ static int gradient_locked(qsv_t* h, const std::vector<Circuit*>& circs, const i
             entries.push_back(GradEntry{int64_t(rows.size()), t, 0});
             for (int32_t k = 0; k < t; ++k) rows.push_back(GradRow{int32_t(e), int32_t(p), shifts[k]});
         }
-        offsets[e + 1] = int64_t(entries.size());
+        tab.offsets[e + 1] = int64_t(entries.size());
     }
+    return QSV_OK;
+}
+
+// What a gradient call queues once its tables are in device memory: chunk by chunk the expansion kernel and the shifted
+// evaluations -- one batch of the ordinary driver each, values from and results into device memory, expectation_to_device --,
+// then the combination kernel.  host_rows: the host's copy of the T rows (which evaluation's circuit a shifted row runs).
+// Everything on the handle's stream; returns without waiting for the last chunk.  plan_id: a plan's run -- its one chunk, if it
+// is one, is remembered under that id (expectation_to_device).
+static int gradient_chunks(qsv_t* h, const std::vector<Circuit*>& circs, const GradRow* host_rows, size_t T, size_t chunk, const GradRow* d_rows,
+                           const GradEntry* d_entries, const int64_t* d_offsets, const GradCall& call, const int* plan_id) {
+    const size_t n_evals = circs.size();
+    int rc;
+    if ((rc = ensure_counted(h, h->d_grad_values, std::max<size_t>(1, T) * sizeof(double)))) return rc;
+    double* values = static_cast<double*>(h->d_grad_values.ptr);
+    // the shifted rows: even width, so that every row starts on 16 bytes (an evaluation takes the first n_params of its row)
+    const int width = (std::max(call.base_width, 1) + 1) / 2 * 2;
+    const size_t row_bytes = size_t(width) * sizeof(double);
+    if (T > 0 && (rc = ensure_doubling(h, h->d_grad_rows, std::min(T, chunk) * row_bytes, chunk * row_bytes))) return rc;
+    double* matrix = static_cast<double*>(h->d_grad_rows.ptr);
+    BatchArgs args;
+    for (size_t t0 = 0; t0 < T; t0 += chunk) {
+        const size_t tc = std::min(chunk, T - t0);
+        if (t0 > 0 && h->async_pending) {  // (the chunk before this one may still be reading the rows)
+            QSV_HIP(h, sync_streams(h));
+            h->async_pending = false;
+        }
+        QSV_HIP(h, launch_gradient_expand(call.base, call.base_stride, call.base_width, d_rows + t0, int64_t(tc), matrix, width, h->stream));
+        args.circs.resize(tc);
+        for (size_t t = 0; t < tc; ++t) args.circs[t] = circs[size_t(host_rows[t0 + t].base_row)];
+        args.n_params.assign(tc, int64_t(width));
+        args.device_values = matrix;
+        if ((rc = expectation_to_device(h, args, values + t0, T <= chunk ? plan_id : nullptr))) return rc;
+        h->grad_stats.n_chunks += 1;
+    }
+    QSV_HIP(h, launch_gradient_combine(values, d_entries, d_offsets, int64_t(n_evals), call.out_width, grad_cp(), grad_cm(), call.out, h->stream));
+    return QSV_OK;
+}
+
+// Gradients of circs[e] at row e of call.base by the parameters wrt[wrt_offsets[e] .. wrt_offsets[e + 1]) (wrt_offsets null:
+// by every parameter) into row e of call.out: the shift tables, through the handle's pinned table into its device table, then
+// gradient_chunks.
+static int gradient_locked(qsv_t* h, const std::vector<Circuit*>& circs, const int* circuit_ids, const int64_t* wrt_offsets,
+                           const int32_t* wrt, const GradCall& call, int64_t* out_n_shifted) {
+    const size_t n_evals = circs.size();
+    GradTables tab;
+    int rc = gradient_tables(h, circs, circuit_ids, wrt_offsets, wrt, call.base_width, call.out_width, tab);
+    if (rc) return rc;
+    const std::vector<GradRow>& rows = tab.rows;
+    const std::vector<GradEntry>& entries = tab.entries;
+    const std::vector<int64_t>& offsets = tab.offsets;
     const size_t T = rows.size();
     if (out_n_shifted) *out_n_shifted = int64_t(T);
     h->grad_stats.n_shifted = int64_t(T);
     h->grad_stats.n_chunks = 0;
     if (n_evals == 0 || call.out_width <= 0) return QSV_OK;
-    int rc;
     // the three tables, back to back (each a multiple of 8 bytes), through pinned memory
     const size_t rows_bytes = T * sizeof(GradRow), entries_bytes = entries.size() * sizeof(GradEntry),
                  tab_bytes = rows_bytes + entries_bytes + offsets.size() * sizeof(int64_t);
     if (h->grad_copy_pending) {  // (the pinned table is written below: the last call's copy must have read it)
+        h->host_waits += 1;
         QSV_HIP(h, hipEventSynchronize(h->ev_grad));
         h->grad_copy_pending = false;
     }
@@ -3997,7 +4141,6 @@ static int gradient_locked(qsv_t* h, const std::vector<Circuit*>& circs, const i
         h->grad_stats.n_allocations += 1;
     }
     if ((rc = ensure_doubling(h, h->d_grad_tab, tab_bytes, size_t(-1) / 4))) return rc;
-    if ((rc = ensure_counted(h, h->d_grad_values, std::max<size_t>(1, T) * sizeof(double)))) return rc;
     char* ht = static_cast<char*>(h->h_grad_tab);
     if (rows_bytes) std::memcpy(ht, rows.data(), rows_bytes);
     if (entries_bytes) std::memcpy(ht + rows_bytes, entries.data(), entries_bytes);
@@ -4006,33 +4149,9 @@ static int gradient_locked(qsv_t* h, const std::vector<Circuit*>& circs, const i
     QSV_HIP(h, hipMemcpyAsync(dt, ht, tab_bytes, hipMemcpyHostToDevice, h->stream));
     QSV_HIP(h, hipEventRecord(h->ev_grad, h->stream));
     h->grad_copy_pending = true;
-    const GradRow* d_rows = reinterpret_cast<const GradRow*>(dt);
-    const GradEntry* d_entries = reinterpret_cast<const GradEntry*>(dt + rows_bytes);
-    const int64_t* d_offsets = reinterpret_cast<const int64_t*>(dt + rows_bytes + entries_bytes);
-    double* values = static_cast<double*>(h->d_grad_values.ptr);
-
-    // the shifted rows: even width, so that every row starts on 16 bytes (an evaluation takes the first n_params of its row)
-    const int width = (std::max(call.base_width, 1) + 1) / 2 * 2;
-    const size_t chunk = size_t(std::max(1, h->grad_chunk)), row_bytes = size_t(width) * sizeof(double);
-    if (T > 0 && (rc = ensure_doubling(h, h->d_grad_rows, std::min(T, chunk) * row_bytes, chunk * row_bytes))) return rc;
-    double* matrix = static_cast<double*>(h->d_grad_rows.ptr);
-    BatchArgs args;
-    for (size_t t0 = 0; t0 < T; t0 += chunk) {
-        const size_t tc = std::min(chunk, T - t0);
-        if (t0 > 0 && h->async_pending) {  // (the chunk before this one may still be reading the rows)
-            QSV_HIP(h, sync_streams(h));
-            h->async_pending = false;
-        }
-        QSV_HIP(h, launch_gradient_expand(call.base, call.base_stride, call.base_width, d_rows + t0, int64_t(tc), matrix, width, h->stream));
-        args.circs.resize(tc);
-        for (size_t t = 0; t < tc; ++t) args.circs[t] = circs[size_t(rows[t0 + t].base_row)];
-        args.n_params.assign(tc, int64_t(width));
-        args.device_values = matrix;
-        if ((rc = expectation_to_device(h, args, values + t0))) return rc;
-        h->grad_stats.n_chunks += 1;
-    }
-    QSV_HIP(h, launch_gradient_combine(values, d_entries, d_offsets, int64_t(n_evals), call.out_width, grad_cp(), grad_cm(), call.out, h->stream));
-    return QSV_OK;
+    return gradient_chunks(h, circs, rows.data(), T, size_t(std::max(1, h->grad_chunk)), reinterpret_cast<const GradRow*>(dt),
+                           reinterpret_cast<const GradEntry*>(dt + rows_bytes),
+                           reinterpret_cast<const int64_t*>(dt + rows_bytes + entries_bytes), call, nullptr);
 }
 
 int qsv_gradient_describe(int n_ops, const qsv_op* ops, int n_params, int32_t* out_n_terms) {
@@ -4137,6 +4256,124 @@ int qsv_gradient_stats(const qsv_t* h, qsv_gradient_stats_t* out) {
     std::lock_guard<std::mutex> lock(h->mu);
     *out = h->grad_stats;
     out->scratch_bytes = int64_t(h->d_grad_tab.bytes + h->d_grad_rows.bytes + h->d_grad_values.bytes + h->d_grad_base.bytes + h->d_grad_out.bytes);
+    return QSV_OK;
+}
+
+int qsv_gradient_plan_create(qsv_t* h, int n_evals, const int* circuit_ids, int width, const int64_t* wrt_offsets, const int32_t* wrt,
+                             int out_width, int* out_plan_id, int64_t* out_n_shifted) {
+    if (!h) return QSV_E_ARG;
+    if (h->batch_owner.load() == std::this_thread::get_id())
+        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_gradient_plan_create goes between batches)");
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (n_evals < 0 || width < 0 || out_width < 0 || !out_plan_id || (n_evals > 0 && !circuit_ids)) return fail(h, QSV_E_ARG, "bad arguments");
+    if (out_n_shifted) *out_n_shifted = 0;
+    QSV_HIP(h, hipSetDevice(h->device));
+    BatchArgs args;
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, nullptr, nullptr, args);
+    if (rc) return rc;
+    GradTables tab;
+    if ((rc = gradient_tables(h, args.circs, circuit_ids, wrt_offsets, wrt, width, out_width, tab))) return rc;
+    qsv_handle::GradientPlan plan;
+    plan.ids.assign(circuit_ids, circuit_ids + n_evals);
+    plan.width = width;
+    plan.out_width = out_width;
+    plan.chunk = size_t(std::max(1, h->grad_chunk));
+    plan.n_entries = tab.entries.size();
+    const size_t T = tab.rows.size();
+    const size_t rows_bytes = T * sizeof(GradRow), entries_bytes = tab.entries.size() * sizeof(GradEntry),
+                 tab_bytes = rows_bytes + entries_bytes + tab.offsets.size() * sizeof(int64_t);
+    QSV_HIP(h, hipMalloc(&plan.d_tab, tab_bytes));
+    // (the host vectors outlive the copies: the wait below)
+    char* dt = static_cast<char*>(plan.d_tab);
+    hipError_t e = hipSuccess;
+    if (rows_bytes) e = hipMemcpyAsync(dt, tab.rows.data(), rows_bytes, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && entries_bytes) e = hipMemcpyAsync(dt + rows_bytes, tab.entries.data(), entries_bytes, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(dt + rows_bytes + entries_bytes, tab.offsets.data(), tab.offsets.size() * sizeof(int64_t), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(plan.d_tab);
+        return fail(h, QSV_E_DEVICE, std::string("uploading a gradient plan's tables: ") + hipGetErrorString(e));
+    }
+    plan.rows = std::move(tab.rows);
+    plan.stats.n_shifted = int64_t(T);
+    plan.stats.n_chunks = int64_t((T + plan.chunk - 1) / plan.chunk);
+    plan.stats.table_bytes = int64_t(tab_bytes);
+    if (out_n_shifted) *out_n_shifted = int64_t(T);
+    const int id = h->next_grad_plan_id++;
+    h->grad_plans.emplace(id, std::move(plan));
+    *out_plan_id = id;
+    return QSV_OK;
+}
+
+int qsv_gradient_plan_run(qsv_t* h, int plan_id, const double* device_values, void* ready_event, double* device_out) {
+    if (!h) return QSV_E_ARG;
+    if (h->batch_owner.load() == std::this_thread::get_id())
+        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_gradient_plan_run goes between batches)");
+    std::lock_guard<std::mutex> lock(h->mu);
+    const auto it = h->grad_plans.find(plan_id);
+    if (it == h->grad_plans.end()) return fail(h, QSV_E_ARG, "unknown gradient plan " + std::to_string(plan_id));
+    qsv_handle::GradientPlan& plan = it->second;
+    const size_t n_evals = plan.ids.size();
+    if (n_evals > 0 && ((plan.out_width > 0 && !device_out) || (plan.width > 0 && !device_values))) return fail(h, QSV_E_ARG, "bad arguments");
+    if (n_evals == 0) return QSV_OK;
+    QSV_HIP(h, hipSetDevice(h->device));
+    const void* given[2] = {plan.width > 0 ? device_values : nullptr, plan.out_width > 0 ? device_out : nullptr};
+    static const char* const names[2] = {"device_values", "device_out"};
+    for (int i = 0; i < 2; ++i) {  // (as qsv_gradient_device: each buffer is asked about once)
+        if (!given[i] || given[i] == h->grad_checked[i]) continue;
+        hipPointerAttribute_t attr{};
+        if (hipPointerGetAttributes(&attr, given[i]) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != h->device) {
+            (void)hipGetLastError();
+            return fail(h, QSV_E_ARG, std::string(names[i]) + " is not memory of this handle's device");
+        }
+        h->grad_checked[i] = given[i];
+    }
+    if (h->n_terms == 0) return fail(h, QSV_E_STATE, "no operator set (call qsv_set_operator first)");
+    BatchArgs args;
+    int rc = resolve_batch(h, n_evals, plan.ids.data(), nullptr, nullptr, args);
+    if (rc) return rc;
+    const uint64_t waits_before = h->host_waits;
+    if (ready_event) QSV_HIP(h, hipStreamWaitEvent(h->stream, static_cast<hipEvent_t>(ready_event), 0));
+    const size_t T = plan.rows.size();
+    h->grad_stats.n_shifted = int64_t(T);
+    h->grad_stats.n_chunks = 0;
+    if (plan.out_width > 0) {
+        const char* dt = static_cast<const char*>(plan.d_tab);
+        const size_t rows_bytes = T * sizeof(GradRow), entries_bytes = plan.n_entries * sizeof(GradEntry);
+        const GradCall call{device_values, int64_t(plan.width), plan.width, device_out, plan.out_width};
+        rc = gradient_chunks(h, args.circs, plan.rows.data(), T, plan.chunk, reinterpret_cast<const GradRow*>(dt),
+                             reinterpret_cast<const GradEntry*>(dt + rows_bytes),
+                             reinterpret_cast<const int64_t*>(dt + rows_bytes + entries_bytes), call, &plan_id);
+        if (rc) (void)sync_streams(h);  // nothing of a failed call may still be running
+    }
+    plan.stats.n_host_waits += int64_t(h->host_waits - waits_before);
+    if (!rc) plan.stats.n_runs += 1;
+    return rc;
+}
+
+int qsv_gradient_plan_destroy(qsv_t* h, int plan_id) {
+    if (!h) return QSV_E_ARG;
+    if (h->batch_owner.load() == std::this_thread::get_id())
+        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_gradient_plan_destroy goes between batches)");
+    std::lock_guard<std::mutex> lock(h->mu);
+    const auto it = h->grad_plans.find(plan_id);
+    if (it == h->grad_plans.end()) return fail(h, QSV_E_ARG, "unknown gradient plan " + std::to_string(plan_id));
+    QSV_HIP(h, hipSetDevice(h->device));
+    QSV_HIP(h, sync_streams(h));  // (a run's kernels may still read the tables)
+    h->async_pending = false;
+    if (h->plan_snap.plan_id == plan_id) h->plan_snap.epoch = 0;
+    if (it->second.d_tab) (void)hipFree(it->second.d_tab);
+    h->grad_plans.erase(it);
+    return QSV_OK;
+}
+
+int qsv_gradient_plan_stats(const qsv_t* h, int plan_id, qsv_gradient_plan_stats_t* out) {
+    if (!h || !out) return QSV_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    const auto it = h->grad_plans.find(plan_id);
+    if (it == h->grad_plans.end()) return QSV_E_ARG;
+    *out = it->second.stats;
     return QSV_OK;
 }
 

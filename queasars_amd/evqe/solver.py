@@ -440,6 +440,10 @@ def _device_search_wanted(evaluator, n_runs: int, flag: Optional[bool], optimize
         if n_runs < 2 or optimizer.maxfev <= 0 or not _device_search_asked_for(evaluator, n_runs, flag, opt_in=True):
             return False
         return hasattr(evaluator, "evaluate_device_to_device") and bool(evaluator.device_resident_search_possible())
+    if isinstance(optimizer, Adam):  # (opt-in, as NFT: device_search.minimize_adam_on_device)
+        if n_runs < 2 or optimizer.maxiter <= 0 or not _device_search_asked_for(evaluator, n_runs, flag, opt_in=True):
+            return False
+        return callable(getattr(evaluator, "gradient_plan", None)) and bool(evaluator.device_resident_search_possible())
     if os.environ.get("QSV_SCALAR_SPSA") or not isinstance(optimizer, SPSA) or n_runs < 2:
         return False
     if not _device_search_asked_for(evaluator, n_runs, flag):
@@ -457,7 +461,8 @@ def _minimize_batched(evaluator, jobs: list, on_device: Optional[bool] = False) 
     """Advance every (circuit, run) pair to completion; one evaluate_circuits call per optimiser iteration of the whole
     set (SPSA proposes two points per run and iteration, NFT two or three).  ``on_device``: SPSA runs whose evaluator can
     read points from and leave values in device memory keep their whole state there (evqe/device_search.py); fresh NFT runs of
-    one configuration likewise, but only where asked for (``True`` or ``QSV_DEVICE_SEARCH=1``; ``None`` is the loop below)."""
+    one configuration likewise, but only where asked for (``True`` or ``QSV_DEVICE_SEARCH=1``; ``None`` is the loop below), and
+    so do fresh Adam runs of one configuration with an evaluator that has gradient plans (``None`` is :func:`_minimize_adam`)."""
     spsa = [] if os.environ.get("QSV_SCALAR_SPSA") else [job for job in jobs if isinstance(job[1], _SPSARun) and not job[1].done]
     if len(spsa) > 1 and len(spsa) == sum(1 for job in jobs if not job[1].done) and all(job[1].config is spsa[0][1].config for job in spsa):
         if _device_search_asked_for(evaluator, len(spsa), on_device):
@@ -469,6 +474,13 @@ def _minimize_batched(evaluator, jobs: list, on_device: Optional[bool] = False) 
         _minimize_spsa_vectorised(evaluator, spsa)
         return
     if jobs and all(isinstance(job[1], _AdamRun) for job in jobs):
+        waiting = [job for job in jobs if not job[1].done]
+        if len(waiting) > 1 and _device_search_asked_for(evaluator, len(waiting), on_device, opt_in=True):
+            from queasars_amd.evqe import device_search
+
+            if device_search.supported_adam(evaluator, waiting):
+                device_search.minimize_adam_on_device(evaluator, waiting)
+                return
         _minimize_adam(evaluator, jobs)
         return
     if any(isinstance(job[1], _AdamRun) for job in jobs):
