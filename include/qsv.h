@@ -676,6 +676,10 @@ int qsv_fitness_table_wait(const volatile uint64_t* own, int count, volatile int
  *                        key qubit, that trade half rows through memory (where its plan does not leave that qubit outside the tile:
  *                        as two tiles swept by one workgroup).  Other orders of the sums (1e-10 apart).  Applies to circuits
  *                        registered afterwards.
+ *   "side_prepare" 0|1   ... and a side whose plan qualifies (one pass, at most two tiles, its angle table, fold index and chain index
+ *                        within 4096 plan words) is prepared from ONE staged read of its plan and parameters, and keeps its threads'
+ *                        and tiles' factors in registers instead of handing them to itself through memory: the same expressions in
+ *                        the same order, the same bits.  Takes effect at the next launch.
  *   "side_diag" 0|1      ... and reads its values of D from a table of its own -- entry x of a side = D[x deposited in the side's
  *                        qubits], one run, filled when the circuit's plan is uploaded -- instead of gathering them from D, one
  *                        cache line per value: the same values, the same bits

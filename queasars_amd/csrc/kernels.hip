@@ -720,6 +720,197 @@ __device__ __forceinline__ void prepare_eval(const uint32_t* __restrict__ plan, 
     QSV_PSTAMP(7);  // tile info
 }
 
+// ---- the one-launch route's preparation (kModeSidePrepare) -----------------------------------------------------------------
+// A kEvalFused side is ONE workgroup (a half side: two) that prepares its evaluation and then runs it.  prepare_eval goes to
+// memory once per step -- parameters, angle entries, chain index, fold index, pass header, each behind the barrier of the one
+// before -- and leaves tables in the evaluation's region that the same workgroup then asks memory for again.  Here the
+// parameter vector, the plan's run of angle table | fold index | chain index (one contiguous run of the plan's words, plan.cpp)
+// and pass 0's header block are asked for TOGETHER, behind the circuit header; everything after that reads LDS, and what only
+// this workgroup wants -- a thread's own factor, the tiles' factors and base indices -- stays in registers (SidePrep).
+// Every matrix, factor and product is formed by prepare_eval's expressions in prepare_eval's order: the same bits.
+constexpr uint32_t kSidePrepRunWords = 4096;  // 16 KiB of plan words behind prepare_eval's scratch
+static_assert(kPrepScratchDoubles * sizeof(double) + kSidePrepRunWords * sizeof(uint32_t) <= kFusedFactorLdsBytes,
+              "every launch with kModeFusedFactor has the LDS for the staged plan run");
+constexpr int kSidePrepHeaderWords = int(kCircuitHeaderWords) + 1;  // the circuit's header and pass 0's offset
+struct SidePrep {
+    uint32_t n_real, n_qubits, pass_off;  // circuit header words 1 and 2, pass 0's offset
+    uint32_t hdr, mat_off, flags;         // pass 0's header words 0 .. 2
+    uint32_t base1;                       // base index of tile 1 (tile 0's is 0; a side here has at most two tiles)
+    double ttr, tti;                      // this thread's factor
+    double tfr[2], tfi[2];                // the tiles' factors
+};
+// ch: cp[0 .. kSidePrepHeaderWords).  Returns false -- nothing written to memory, no LDS anybody still reads -- where the plan
+// does not qualify: the caller then runs prepare_eval.  Every condition is uniform over the workgroup.
+__device__ __forceinline__ bool side_prepare(const uint32_t* __restrict__ plan, const EvalDesc& ev, const uint32_t (&ch)[kSidePrepHeaderWords],
+                                             const double* __restrict__ params, double* __restrict__ mats, double* scratch,
+                                             bool float_mats, SidePrep& sd QSV_PSTAMP_PARAMS) {
+    const uint32_t n_passes = ch[0], n_real = ch[1], n_qubits = ch[2], n_fold = ch[5], n_factors = ch[7];
+    const uint32_t run_begin = ch[3], run_end = ch[6] + ch[1];
+    QSV_PSTAMP(2);  // plan header
+    if (!(ev.n_params <= kPrepMaxParams && n_fold <= kPrepMaxFold && n_factors + n_fold <= kPrepMaxTrig && n_passes == 1 && n_qubits <= 32 &&
+          run_begin <= ch[4] && ch[4] <= ch[6] && run_end - run_begin <= kSidePrepRunWords))
+        return false;
+    double* sv = scratch;
+    double* sp = scratch + 4 * 32;
+    double* fm = sp + kPrepMaxParams;
+    double* trig = fm + 8 * kPrepMaxFold;
+    uint32_t* run = reinterpret_cast<uint32_t*>(scratch + kPrepScratchDoubles);
+    const uint32_t* __restrict__ cp = plan + ev.plan_base;
+    const double* __restrict__ p = params + ev.param_base;
+    double* __restrict__ out = mats + ev.mat_base;
+    // one trip: pass 0's header block (scalar registers), the parameter vector and the plan run (LDS)
+    uint32_t hw[kPassLoadColsOffset + kMaxThreadBits + 2];
+    load_words<int(kPassLoadColsOffset + kMaxThreadBits + 2)>(as_constant(cp) + ch[kCircuitHeaderWords], hw);
+    {
+        const uint32_t* __restrict__ src = cp + run_begin;
+        const uint32_t words = run_end - run_begin;
+        for (uint32_t i = threadIdx.x; i < ev.n_params; i += blockDim.x) sp[i] = p[i];
+        for (uint32_t i = threadIdx.x; i < words; i += blockDim.x) run[i] = src[i];
+    }
+    __syncthreads();
+    QSV_PSTAMP(3);  // parameters and plan run staged
+    const uint32_t hdr = hw[0];
+    const int k = hdr & 0xff, t = (hdr >> 16) & 0xff;
+    if ((hw[2] & (kPassCompactStore | kPassCompactLoad)) || blockDim.x < (1u << t) || n_qubits < uint32_t(k) || n_qubits - uint32_t(k) > 1u)
+        return false;  // (nobody reads what was staged: prepare_eval may write over it)
+    const uint32_t* table = run;
+    const uint32_t* fold = run + (ch[4] - run_begin);
+    const uint32_t* chains = run + (ch[6] - run_begin);
+    for (uint32_t i = threadIdx.x; i < 3u * (n_factors + n_fold); i += blockDim.x) {
+        const uint32_t f = i / 3u, which = i - 3u * f;
+        const uint32_t* e = table + size_t(f) * kAngleEntryWords;
+        if (int32_t(e[0]) < -1) continue;  // (a fixed matrix)
+        const int32_t pidx = int32_t(e[which]);
+        double angle = pidx >= 0 ? sp[pidx] : __hiloint2double(int(e[4 + 2 * which]), int(e[3 + 2 * which]));
+        if (which == 0) angle *= 0.5;
+        double sn, cs;
+#ifndef QSV_ABL_PREP_TRIG
+        sincos(angle, &sn, &cs);
+#else
+        sn = angle, cs = 1.0 - angle;  // (measurement: what the sines and cosines cost)
+#endif
+        trig[size_t(f) * 6 + 2 * which] = sn;
+        trig[size_t(f) * 6 + 2 * which + 1] = cs;
+    }
+    __syncthreads();
+    // the scheduled entries' matrices to the evaluation's region (the round loop reads them through scalar loads), the fold
+    // entries' to LDS
+    for (uint32_t j = threadIdx.x; j < n_real + n_fold; j += blockDim.x) {
+        double m[8];
+        if (j < n_real)
+            chain_matrix(table, chains[j], sp, m, trig);
+        else
+            entry_matrix_trig(table + size_t(n_factors + j - n_real) * kAngleEntryWords, trig + size_t(n_factors + j - n_real) * 6, m);
+        double* dst = j < n_real ? out + size_t(j) * 8 : fm + size_t(j - n_real) * 8;
+        if (float_mats && j < n_real) {
+            float* dstf = reinterpret_cast<float*>(dst);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) dstf[i] = float(m[i]);
+#pragma unroll
+            for (int i = 8; i < 16; ++i) dstf[i] = 0.f;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) dst[i] = m[i];
+        }
+    }
+    __syncthreads();
+    QSV_PSTAMP(4);  // matrices
+    for (uint32_t q = threadIdx.x; q < n_qubits; q += blockDim.x) {
+        const uint32_t first = fold[2 * q], count = fold[2 * q + 1];
+        double v0r = 1.0, v0i = 0.0, v1r = 0.0, v1i = 0.0;
+        for (uint32_t i = 0; i < count; ++i) {
+            double m[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) m[e] = fm[size_t(first + i - n_factors) * 8 + e];
+            const double a0r = v0r, a0i = v0i, a1r = v1r, a1i = v1i;
+            v0r = m[0] * a0r - m[1] * a0i + m[2] * a1r - m[3] * a1i;
+            v0i = m[0] * a0i + m[1] * a0r + m[2] * a1i + m[3] * a1r;
+            v1r = m[4] * a0r - m[5] * a0i + m[6] * a1r - m[7] * a1i;
+            v1i = m[4] * a0i + m[5] * a0r + m[6] * a1i + m[7] * a1r;
+        }
+        double* o = out + size_t(n_real) * 8 + size_t(q) * 4;
+        o[0] = v0r; o[1] = v0i; o[2] = v1r; o[3] = v1i;
+        sv[4 * q] = v0r; sv[4 * q + 1] = v0i; sv[4 * q + 2] = v1r; sv[4 * q + 3] = v1i;
+    }
+    double* pad = out + size_t(n_real) * 8 + size_t(n_qubits) * 4;
+    for (uint32_t i = threadIdx.x; i < kMatPadDoubles; i += blockDim.x) pad[i] = 0.0;
+    __syncthreads();
+    QSV_PSTAMP(5);  // initial factors
+    // this thread's own factor (prepare_eval's thread_factor[threadIdx.x])
+    sd.ttr = 1.0;
+    sd.tti = 0.0;
+#ifndef QSV_ABL_PREP_TABLES
+    if (threadIdx.x < (1u << t)) {
+        const uint32_t i = threadIdx.x;
+        double vr[kMaxThreadBits], vi[kMaxThreadBits];
+#pragma unroll
+        for (int u = 0; u < int(kMaxThreadBits); ++u) {
+            vr[u] = 1.0;
+            vi[u] = 0.0;
+            if (u < t) {
+                const double* v = sv + 4 * uint32_t(__builtin_ctz(hw[kPassLoadColsOffset + u])) + 2 * ((i >> u) & 1u);
+                vr[u] = v[0];
+                vi[u] = v[1];
+            }
+        }
+        double fr = 1.0, fi = 0.0;
+#pragma unroll
+        for (int u = 0; u < int(kMaxThreadBits); ++u) {
+            const double nr = fr * vr[u] - fi * vi[u];
+            fi = fr * vi[u] + fi * vr[u];
+            fr = nr;
+        }
+        sd.ttr = fr;
+        sd.tti = fi;
+    }
+#endif
+    // the tiles' factors and base indices (prepare_eval's tile_factor and TileInfo: one tile, or two with one qubit outside)
+    uint32_t tile_mask = 0;
+#pragma unroll
+    for (int j = 0; j < int(kMaxTileBits); ++j)
+        if (j < k) tile_mask |= 1u << hw[kPassHeaderWords + j];
+    const uint32_t all_qubits = n_qubits >= 32 ? 0xffffffffu : ((1u << n_qubits) - 1u);
+    const uint32_t outside = all_qubits & ~tile_mask;
+    const uint32_t n_tiles = 1u << (n_qubits - uint32_t(k));
+    auto tile_base = [&](uint64_t base) {
+#pragma unroll
+        for (int j = 0; j < int(kMaxTileBits); ++j)
+            if (j < k) {
+                const uint32_t ps = hw[kPassHeaderWords + j];
+                base = ((base >> ps) << (ps + 1)) | (base & ((uint64_t(1) << ps) - 1));
+            }
+        return base;
+    };
+    sd.base1 = n_tiles > 1 ? uint32_t(tile_base(1)) : 0u;
+#pragma unroll
+    for (uint32_t tile = 0; tile < 2; ++tile) {
+        double fr = 1.0, fi = 0.0;
+#ifndef QSV_ABL_PREP_TABLES
+        if (outside && tile < n_tiles) {
+            const uint64_t base = tile ? uint64_t(sd.base1) : 0u;
+            for (uint32_t m = outside; m; m &= m - 1u) {  // ascending qubits
+                const uint32_t q = uint32_t(__builtin_ctz(m));
+                const double* v = sv + 4 * q + 2 * ((base >> q) & 1u);
+                const double nr = fr * v[0] - fi * v[1];
+                fi = fr * v[1] + fi * v[0];
+                fr = nr;
+            }
+        }
+#endif
+        sd.tfr[tile] = fr;
+        sd.tfi[tile] = fi;
+    }
+    QSV_PSTAMP(6);  // this thread's factor, the tiles' factors
+    sd.n_real = n_real;
+    sd.n_qubits = n_qubits;
+    sd.pass_off = ch[kCircuitHeaderWords];
+    sd.hdr = hdr;
+    sd.mat_off = hw[1];
+    sd.flags = hw[2];
+    QSV_PSTAMP(7);
+    return true;
+}
+
 // (defined with the factor kernels below) the tail of a pass-0 launch under kModeFusedFactor
 template <typename real>
 __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ plan_arena, const EvalDesc& ev,
@@ -773,6 +964,9 @@ __global__ void __launch_bounds__(512, (Occupancy<R, XMODE, FIRST, FUSED>::waves
     const double* mats_base = mats_all;
     bool prepared_here = false;
     if constexpr (FIRST) prepared_here = a.mode & kModeFusedPrepare;
+    // (kModeSidePrepare, only ever set in the FUSED instantiation: what side_prepare hands to the pass body in registers)
+    bool side_prepared = false;
+    [[maybe_unused]] SidePrep sprep = {};
     if (prepared_here) {
         // This workgroup does prepare_kernel's work for its evaluation itself (virtual circuits of split evaluations:
         // one launch and its latency less in front of the contraction): descriptor and parameters from pinned host
@@ -784,7 +978,25 @@ __global__ void __launch_bounds__(512, (Occupancy<R, XMODE, FIRST, FUSED>::waves
         // (the device copy first, also of a null descriptor: a repeated batch reads its descriptors from that copy)
         if (threadIdx.x == 0 && block_x == 0) a.evals_out[slot] = ev;
         if (ev.flags & kEvalNull) return;
-        {
+        // (kModeSidePrepare: a side of the one-launch route, prepared by side_prepare where its plan qualifies)
+        bool side_route = false;
+        if constexpr (FUSED) side_route = (a.mode & kModeSidePrepare) && (a.mode & kModeFusedFactor) && (ev.flags & kEvalFused);
+        if (side_route) {
+            if constexpr (FUSED) {
+                // a side that is not of a kEvalHalves circuit has ONE working workgroup: the others leave on the descriptor alone,
+                // and a flagged one's second workgroup stays only for a half side (thirteen virtual qubits; the grid is two wide)
+                if (block_x > 0 && !(ev.flags & kEvalHalves)) return;
+                uint32_t ch[kSidePrepHeaderWords];
+                load_words<kSidePrepHeaderWords>(as_constant(plan_arena) + ev.plan_base, ch);
+                if (block_x > 0 && (ch[2] != uint32_t(kFusedLdsRowsBits) || block_x > 1)) return;
+#ifdef QSV_STAMPS
+                QSV_STAMP(0);  // descriptor
+                side_prepared = side_prepare(plan_arena, ev, ch, a.host_params, a.mats_out, reinterpret_cast<double*>(lds_raw), std::is_same<real, float>::value, sprep, st_acc, &st_last);
+#else
+                side_prepared = side_prepare(plan_arena, ev, ch, a.host_params, a.mats_out, reinterpret_cast<double*>(lds_raw), std::is_same<real, float>::value, sprep);
+#endif
+            }
+        } else {
             // a launch's grid is as wide as its largest evaluation: a workgroup beyond THIS evaluation's tiles leaves before
             // the preparation (its reads of parameters over PCIe, times the width of the grid, were most of such a launch)
             const uint32_t* c0 = plan_arena + ev.plan_base;
@@ -795,12 +1007,14 @@ __global__ void __launch_bounds__(512, (Occupancy<R, XMODE, FIRST, FUSED>::waves
             // (the one-launch route: a side's ONE workgroup sweeps all its tiles -- only a half side, kEvalHalves, has one per tile)
             if (FUSED && block_x > 0 && (ev.flags & kEvalFused) && !((ev.flags & kEvalHalves) && c0[2] == uint32_t(kFusedLdsRowsBits)) && (a.mode & kModeFusedFactor)) return;
         }
+        if (!side_prepared) {
 #ifdef QSV_STAMPS
-        QSV_STAMP(0);  // descriptor
-        prepare_eval(plan_arena, ev, a.host_params, a.mats_out, reinterpret_cast<double*>(lds_raw), std::is_same<real, float>::value, st_acc, &st_last);
+            if (!side_route) QSV_STAMP(0);  // descriptor
+            prepare_eval(plan_arena, ev, a.host_params, a.mats_out, reinterpret_cast<double*>(lds_raw), std::is_same<real, float>::value, st_acc, &st_last);
 #else
-        prepare_eval(plan_arena, ev, a.host_params, a.mats_out, reinterpret_cast<double*>(lds_raw), std::is_same<real, float>::value);
+            prepare_eval(plan_arena, ev, a.host_params, a.mats_out, reinterpret_cast<double*>(lds_raw), std::is_same<real, float>::value);
 #endif
+        }
         __builtin_amdgcn_s_waitcnt(0);
         __syncthreads();
         __builtin_amdgcn_s_dcache_inv();
@@ -822,13 +1036,33 @@ __global__ void __launch_bounds__(512, (Occupancy<R, XMODE, FIRST, FUSED>::waves
     if (ev.flags & kEvalNull) return;
     const bool side = ev.flags & kEvalSide;  // a virtual circuit of a split evaluation (split.hpp)
     cu32p cp = as_constant(plan_arena) + ev.plan_base;
-    const uint32_t n_passes = cp[0];
-    if (a.pass_index >= n_passes) return;
-    const uint32_t n_real = cp[1], n_qubits = cp[2];
-    cu32p pp = cp + cp[kCircuitHeaderWords + a.pass_index];
-    const uint32_t hdr = pp[0];
+    // (a side prepared by side_prepare is one pass, pass 0, and has the words below in scalar registers already: the two
+    // dependent trips for them -- circuit header, then pass header -- are not made again behind the preparation's fence)
+    uint32_t n_passes, n_real, n_qubits, pass_off;
+    if (side_prepared) {
+        n_passes = 1u;
+        n_real = sprep.n_real;
+        n_qubits = sprep.n_qubits;
+        pass_off = sprep.pass_off;
+    } else {
+        n_passes = cp[0];
+        if (a.pass_index >= n_passes) return;
+        n_real = cp[1];
+        n_qubits = cp[2];
+        pass_off = cp[kCircuitHeaderWords + a.pass_index];
+    }
+    cu32p pp = cp + pass_off;
+    uint32_t hdr, pass_mat_off, pass_flags;
+    if (side_prepared) {
+        hdr = sprep.hdr;
+        pass_mat_off = sprep.mat_off;
+        pass_flags = sprep.flags;
+    } else {
+        hdr = pp[0];
+        pass_mat_off = pp[1];
+        pass_flags = pp[2];
+    }
     const int k = hdr & 0xff, t = (hdr >> 16) & 0xff, n_rounds = hdr >> 24;
-    const uint32_t pass_flags = pp[2];
     const uint32_t tid = threadIdx.x;
     const uint32_t tid_ext = tid | (~tid & ((1u << kMaxThreadBits) - 1u)) << kMaxThreadBits;  // (gate predicates, plan.hpp)
     const bool all_active = blockDim.x == (1u << t);
@@ -840,7 +1074,7 @@ __global__ void __launch_bounds__(512, (Occupancy<R, XMODE, FIRST, FUSED>::waves
     cu32p glr = pp + kPassLoadColsOffset + kMaxThreadBits;   // register columns of the load layout
     cu32p gsr = pp + kPassStoreColsOffset + kMaxThreadBits;  // ... of the store layout
     cu32p rounds0 = pp + kPassRoundsOffset;
-    cf64p mats0 = as_constant(mats_base) + ev.mat_base + size_t(pp[1]) * 8;
+    cf64p mats0 = as_constant(mats_base) + ev.mat_base + size_t(pass_mat_off) * 8;
     cf64p vecs = as_constant(mats_base) + ev.mat_base + size_t(n_real) * 8;
 
     constexpr bool synth = FIRST;  // the launcher picks FIRST = (pass_index == 0 && mode & kModeSynthFirst)
@@ -905,7 +1139,10 @@ __global__ void __launch_bounds__(512, (Occupancy<R, XMODE, FIRST, FUSED>::waves
                                               size_t(a.pass_index) * (size_t(2) << (n_qubits - uint32_t(k))));
     // loaded once: a load inside the tile loop would make pass 0 wait for the previous tile's stores (same counter)
     double ttr = 1.0, tti = 0.0;
-    if (synth && active) {
+    if (side_prepared) {  // (this thread formed its factor itself)
+        ttr = sprep.ttr;
+        tti = sprep.tti;
+    } else if (synth && active) {
         ttr = thread_factor[2 * tid];
         tti = thread_factor[2 * tid + 1];
     }
@@ -960,8 +1197,15 @@ __global__ void __launch_bounds__(512, (Occupancy<R, XMODE, FIRST, FUSED>::waves
     for (uint32_t j = 0; j < n_tiles; ++j) {
         QSV_TL(0);
         // what depends on the tile number comes from prepare_kernel's table: one scalar load
+        // (a side prepared by side_prepare: tile 0 or tile 1, base index and factor in registers)
         uint32_t ti[4];
-        load_words<4>(tile_info + 4 * size_t(tile0 + j * tile_step), ti);
+        const bool second_tile = side_prepared && tile0 + j * tile_step != 0u;
+        if (side_prepared) {
+            ti[0] = second_tile ? sprep.base1 : 0u;
+            ti[1] = ti[2] = ti[3] = 0u;
+        } else {
+            load_words<4>(tile_info + 4 * size_t(tile0 + j * tile_step), ti);
+        }
         const uint64_t base = uint64_t(ti[0]) | uint64_t(ti[1]) << 32;
         // Per-element offsets do not depend on the tile, so hipcc would compute all of them once, ahead of the tile
         // loop, and keep (in fact spill) 3 * 2^R registers for them.  Recomputing them costs one v_xor per access:
@@ -973,8 +1217,14 @@ __global__ void __launch_bounds__(512, (Occupancy<R, XMODE, FIRST, FUSED>::waves
             // factors of the qubits outside the tile (one value per tile: tile_factor) and of the tile qubits held
             // by thread bits (one value per thread: thread_factor); the register qubits are expanded here.
             // (a compact pass 0 leaves the tile factor to pass 1)
-            const double tfr = cstore ? 1.0 : tile_factor[2 * size_t(tile0 + j * tile_step)];
-            const double tfi = cstore ? 0.0 : tile_factor[2 * size_t(tile0 + j * tile_step) + 1];
+            double tfr, tfi;
+            if (side_prepared) {
+                tfr = second_tile ? sprep.tfr[1] : sprep.tfr[0];
+                tfi = second_tile ? sprep.tfi[1] : sprep.tfi[0];
+            } else {
+                tfr = cstore ? 1.0 : tile_factor[2 * size_t(tile0 + j * tile_step)];
+                tfi = cstore ? 0.0 : tile_factor[2 * size_t(tile0 + j * tile_step) + 1];
+            }
             amp[0].re = real(tfr * ttr - tfi * tti);
             amp[0].im = real(tfr * tti + tfi * ttr);
 #pragma unroll

@@ -89,6 +89,9 @@ enum PassMode : uint32_t {
                              // the descriptor from host_evals (PassArgs below); no prepare launch ran for these evaluations
     kModeMasked = 2048u,     // (qsv_cvar_device only) PassArgs::active is given: the workgroups of an evaluation whose entry is 0
                              // leave at once (masked_out below); without the bit a launch executes what it did before the mask existed
+    kModeSidePrepare = 4096u, // (with kModeFusedFactor and kModeFusedPrepare) a kEvalFused side whose plan qualifies is prepared from ONE
+                              // staged read of its plan and parameters (kernels.hip side_prepare) and hands its thread factor, its tiles'
+                              // factors and base indices to the pass body in registers; the same bits as prepare_eval's, a launch may choose
 };
 // The optional mask of a device-resident CVaR call (qsv.h: qsv_cvar_device): entry e / stride decides evaluation e (its out_index,
 // the caller's numbering), 0 = skipped.  flags == nullptr: every evaluation runs.  The flags are written by an EARLIER launch on

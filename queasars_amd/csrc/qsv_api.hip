@@ -217,6 +217,7 @@ struct qsv_handle {
     bool repeat_enabled = true;
     bool chain_enabled = true;
     bool fused_lds_table = true;  // one-launch route: small sides hand their state to the Gram matrices through LDS (kModeFusedLdsTable)
+    bool side_prepare = true;     // one-launch route: a side is prepared from one staged read of its plan (kModeSidePrepare); asked at every launch
     int n_cus = 256;
     bool poll_results = true;  // a waiting end of a batch watches the (pinned) result buffer instead of the streams: the last
                                // workgroups' stores are visible about 5 us before hipStreamSynchronize returns (eval_end)
@@ -1399,6 +1400,8 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
                     a.mode |= kModeFusedLdsTable;
                     need = std::max(need, kFusedLdsTableEnd);
                 }
+                // (need >= kFusedFactorLdsBytes: room for the staged plan run behind prepare_eval's scratch)
+                if (p == 0 && (extra_mode & kModeFusedFactor) && h->side_prepare) a.mode |= kModeSidePrepare;
                 if (h->stamping) QSV_HIP(h, stamp(h, h->batch.launch_events[kind], true));
                 QSV_HIP(h, launch_pass(h->dtype, r, h->cfg.xmode, dim3(grid_x, unsigned(hi - lo), 2), threads, need, ws(h), a));
                 if (h->stamping) QSV_HIP(h, stamp(h, h->batch.launch_events[kind], false));
@@ -2402,6 +2405,7 @@ int qsv_create(int n_qubits, int dtype, int device, const qsv_plan_config* cfg, 
     if (const char* env = getenv("QSV_REPEAT")) h->repeat_enabled = atoi(env) != 0;
     if (const char* env = getenv("QSV_REPEAT_DESCS")) h->repeat_device_descs = atoi(env) != 0;
     if (const char* env = getenv("QSV_FUSED_LDS")) h->fused_lds_table = atoi(env) != 0;
+    if (const char* env = getenv("QSV_SIDE_PREPARE")) h->side_prepare = atoi(env) != 0;
     if (const char* env = getenv("QSV_SIDE_DIAG")) h->side_diag = atoi(env) != 0;
     if (const char* env = getenv("QSV_SIDES_R3")) h->sides_r3 = atoi(env) != 0;
     {
@@ -4546,6 +4550,8 @@ int qsv_set_option(qsv_t* h, const char* name, int value) {
         h->split_sampling = value != 0;
     } else if (key == "fused_lds_table") {  // one-launch route: sides' states handed to their Gram matrices through LDS (same bits either way)
         h->fused_lds_table = value != 0;
+    } else if (key == "side_prepare") {  // one-launch route: a side prepared from one staged read of its plan (same bits either way).  The next launch.
+        h->side_prepare = value != 0;
     } else if (key == "sides_r3") {  // one-launch route: sides with eight amplitudes per thread, three-key sides on two workgroups.  Circuits registered afterwards.
         h->sides_r3 = value != 0;
     } else if (key == "side_diag") {  // one-launch route: a side's values of D from a table of its own (one run) instead of gathered from D
