@@ -695,6 +695,11 @@ int qsv_fitness_table_wait(const volatile uint64_t* own, int count, volatile int
  *   "streams" 1..4       HIP streams the pushes of a batch cycle over (at most as many as were created with the handle)
  *   "gradient_chunk" 0..1048576  shifted evaluations a gradient call expands and runs at a time (0: the default, 8192); the same
  *                        bits at any value
+ *   "max_grid_y" 0..limit  x-mask groups of a general operator (qsv_set_operator), and rows of an observable set
+ *                        (qsv_observables_create), that one launch takes: such a launch has one row of workgroups per group, and an
+ *                        operator may hold more groups than the device's largest gridDim.y (hipDeviceAttributeMaxGridDimY, read
+ *                        when the handle is created: the default, 0, and the largest value accepted).  More groups go in several
+ *                        launches with the partial sums laid out as one launch lays them out: the same bits at any value
  * Returns QSV_E_ARG for an unknown name or a value out of range.
  */
 int qsv_set_option(qsv_t* h, const char* name, int value);

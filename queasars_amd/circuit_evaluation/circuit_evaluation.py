@@ -1128,7 +1128,8 @@ class StatevectorDevice:
     # -- measurement support ----------------------------------------------------------------------
     def set_option(self, name: str, value: int) -> None:
         """Switches of the handle (``qsv_set_option``): "split", "factor", "split_sampling" (0 / 1), "streams" (1 .. 4),
-        "gradient_chunk" (shifted evaluations per chunk of a gradient call, 0 = the default).
+        "gradient_chunk" (shifted evaluations per chunk of a gradient call, 0 = the default), "max_grid_y" (x-mask groups or
+        observable rows per launch, 0 = the device's largest gridDim.y).
         A circuit keeps the form it was registered in; the cache of the previous batch is dropped."""
         self._check(self._lib.qsv_set_option(self._handle, name.encode(), int(value)))
         self._last_batch = None

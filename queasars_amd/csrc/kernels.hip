@@ -2269,7 +2269,8 @@ __global__ void __launch_bounds__(256) pauli_groups_kernel(const cx<real>* __res
                                                            const uint64_t* __restrict__ term_z,
                                                            const double* __restrict__ term_coef,
                                                            const uint32_t* __restrict__ term_odd,
-                                                           double* __restrict__ partials) {
+                                                           double* __restrict__ partials, uint32_t first_group,
+                                                           uint32_t n_groups) {
     // The group's terms are staged in LDS once per workgroup, kChunk at a time (z mask, and the coefficient filed under
     // "weight of Re" or "weight of Im"): the pair loop then reads them by broadcast instead of going back to global
     // memory for every amplitude pair.
@@ -2277,7 +2278,8 @@ __global__ void __launch_bounds__(256) pauli_groups_kernel(const cx<real>* __res
     __shared__ double red[4];
     __shared__ uint64_t sz[kChunk];
     __shared__ double s_re[kChunk], s_im[kChunk];
-    const PauliGroup g = groups[blockIdx.y];
+    const uint32_t group = first_group + blockIdx.y;  // (the launch covers groups first_group ... of the operator's n_groups)
+    const PauliGroup g = groups[group];
     const int slot = blockIdx.z;
     const cx<real>* __restrict__ st = states + uint64_t(slot) * state_stride;
     const uint64_t low_mask = (uint64_t(1) << g.pivot) - 1;
@@ -2310,23 +2312,25 @@ __global__ void __launch_bounds__(256) pauli_groups_kernel(const cx<real>* __res
         }
     }
     const double total = block_sum_256(2.0 * acc, red);
-    if (threadIdx.x == 0) partials[(size_t(slot) * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = total;
+    if (threadIdx.x == 0) partials[(size_t(slot) * n_groups + group) * gridDim.x + blockIdx.x] = total;
 }
 
 hipError_t launch_pauli_groups(int dtype, const void* states, uint64_t state_stride, int n_qubits, int n_slots,
                                int n_groups, const PauliGroup* groups, const uint64_t* term_z,
                                const double* term_coef, const uint32_t* term_odd, int nb, double* partials,
-                               hipStream_t stream) {
+                               hipStream_t stream, int first_group, int group_count) {
+    if (group_count < 0) group_count = n_groups - first_group;
+    if (n_slots <= 0 || group_count <= 0) return hipSuccess;
     const uint64_t n_pairs = uint64_t(1) << (n_qubits - 1);
-    dim3 grid(nb, n_groups, n_slots);
+    dim3 grid(nb, group_count, n_slots);
     if (dtype == 0)
         hipLaunchKernelGGL(pauli_groups_kernel<double>, grid, dim3(256), 0, stream,
                            reinterpret_cast<const cx<double>*>(states), state_stride, n_pairs, groups, term_z,
-                           term_coef, term_odd, partials);
+                           term_coef, term_odd, partials, uint32_t(first_group), uint32_t(n_groups));
     else
         hipLaunchKernelGGL(pauli_groups_kernel<float>, grid, dim3(256), 0, stream,
                            reinterpret_cast<const cx<float>*>(states), state_stride, n_pairs, groups, term_z,
-                           term_coef, term_odd, partials);
+                           term_coef, term_odd, partials, uint32_t(first_group), uint32_t(n_groups));
     return hipGetLastError();
 }
 

@@ -284,10 +284,13 @@ struct PauliGroup {
     uint32_t pivot;   // highest set bit of x
     uint32_t pad;
 };
+// partials[(slot * n_groups + g) * nb + b]: workgroup b's share of group g on state slot `slot`.  One launch covers the
+// groups first_group .. first_group + group_count - 1 (grid nb x group_count x n_slots; group_count < 0: all from first_group):
+// the caller keeps group_count within the device's largest gridDim.y, the layout does not depend on how it slices.
 hipError_t launch_pauli_groups(int dtype, const void* states, uint64_t state_stride, int n_qubits, int n_slots,
                                int n_groups, const PauliGroup* groups, const uint64_t* term_z,
                                const double* term_coef, const uint32_t* term_odd, int nb, double* partials,
-                               hipStream_t stream);
+                               hipStream_t stream, int first_group = 0, int group_count = -1);
 hipError_t launch_pauli_combine(const double* partials, uint32_t per_slot, const double* diag_partials,
                                 uint32_t diag_per_eval, int n_slots, const EvalDesc* evals, double* out,
                                 hipStream_t stream);
@@ -317,7 +320,8 @@ struct ObsTerm {
     uint32_t pad;
     double scale;  // 2 (-1)^floor(ny / 2), or 1 in the diagonal group
 };
-// partials[(slot * nb + b) * n_terms + k]: workgroup b's share of string k on state slot s (grid nb x n_rows x n_slots)
+// partials[(slot * nb + b) * n_terms + k]: workgroup b's share of string k on state slot s (grid nb x n_rows x n_slots; a
+// row names its strings itself, so a caller with more rows than the device's largest gridDim.y launches slices of `rows`)
 hipError_t launch_pauli_terms(int dtype, const void* states, uint64_t state_stride, int n_qubits, int n_slots, int n_rows,
                               const ObsRow* rows, const ObsTerm* terms, uint32_t n_terms, int nb, double* partials,
                               hipStream_t stream);

@@ -219,6 +219,8 @@ struct qsv_handle {
     bool fused_lds_table = true;  // one-launch route: small sides hand their state to the Gram matrices through LDS (kModeFusedLdsTable)
     bool side_prepare = true;     // one-launch route: a side is prepared from one staged read of its plan (kModeSidePrepare); asked at every launch
     int n_cus = 256;
+    int max_grid_y = 65535, device_max_grid_y = 65535;  // the device's largest gridDim.y (and what option "max_grid_y" makes of it):
+                                                          // launches with one row of workgroups per x-mask group are sliced by it
     bool poll_results = true;  // a waiting end of a batch watches the (pinned) result buffer instead of the streams: the last
                                // workgroups' stores are visible about 5 us before hipStreamSynchronize returns (eval_end)
     hipStream_t work = nullptr;  // stream of the push being issued (null: `stream`)
@@ -1909,12 +1911,16 @@ int eval_push(qsv_t* h, size_t first, size_t count, const double* values, const 
         if (rc) return rc;
         if (!h->diagonal && !in_split) {
             QSV_HIP(h, stamp(h, b.exp_events, true));
-            QSV_HIP(h, launch_pauli_groups(h->dtype, h->d_states.ptr, uint64_t(1) << h->n, h->n, int(gc), h->n_groups,
-                                           static_cast<const PauliGroup*>(h->d_groups.ptr),
-                                           static_cast<const uint64_t*>(h->d_z.ptr),
-                                           static_cast<const double*>(h->d_cre.ptr),
-                                           static_cast<const uint32_t*>(h->d_term_odd.ptr), h->pauli_nb,
-                                           static_cast<double*>(h->d_term_partials.ptr), h->stream));
+            // (an operator may have more x-mask groups than gridDim.y can be: slices of the groups, the partial sums where one
+            // launch puts them)
+            for (int g1 = 0; g1 < h->n_groups; g1 += h->max_grid_y)
+                QSV_HIP(h, launch_pauli_groups(h->dtype, h->d_states.ptr, uint64_t(1) << h->n, h->n, int(gc), h->n_groups,
+                                               static_cast<const PauliGroup*>(h->d_groups.ptr),
+                                               static_cast<const uint64_t*>(h->d_z.ptr),
+                                               static_cast<const double*>(h->d_cre.ptr),
+                                               static_cast<const uint32_t*>(h->d_term_odd.ptr), h->pauli_nb,
+                                               static_cast<double*>(h->d_term_partials.ptr), h->stream, g1,
+                                               std::min(h->max_grid_y, h->n_groups - g1)));
             QSV_HIP(h, launch_pauli_combine(static_cast<const double*>(h->d_term_partials.ptr),
                                             uint32_t(h->n_groups) * uint32_t(h->pauli_nb),
                                             h->has_diag_part ? static_cast<const double*>(h->d_partials.ptr) : nullptr,
@@ -2310,9 +2316,11 @@ int eval_observables_locked(qsv_t* h, const ObservableSet& set, const BatchArgs&
         return combine(g0, gc);
     };
     auto on_state = [&](size_t g0, size_t gc) -> int {
-        QSV_HIP(h, launch_pauli_terms(h->dtype, h->d_states.ptr, uint64_t(1) << h->n, h->n, int(gc), set.n_rows,
-                                      static_cast<const ObsRow*>(set.d_rows.ptr), static_cast<const ObsTerm*>(set.d_terms.ptr),
-                                      uint32_t(T), set.nb, partials, h->stream));
+        // (a set may have more rows than gridDim.y can be: slices of the rows, each row names its strings' places itself)
+        for (int r0 = 0; r0 < set.n_rows; r0 += h->max_grid_y)
+            QSV_HIP(h, launch_pauli_terms(h->dtype, h->d_states.ptr, uint64_t(1) << h->n, h->n, int(gc), std::min(h->max_grid_y, set.n_rows - r0),
+                                          static_cast<const ObsRow*>(set.d_rows.ptr) + r0, static_cast<const ObsTerm*>(set.d_terms.ptr),
+                                          uint32_t(T), set.nb, partials, h->stream));
         QSV_HIP(h, launch_pauli_terms_reduce(partials, set.nb, uint32_t(T), static_cast<const ObsTerm*>(set.d_terms.ptr), int(gc),
                                              values, h->stream));
         return combine(g0, gc);
@@ -2411,6 +2419,9 @@ int qsv_create(int n_qubits, int dtype, int device, const qsv_plan_config* cfg, 
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) h->n_cus = cus;
+        int grid_y = 0;
+        if (hipDeviceGetAttribute(&grid_y, hipDeviceAttributeMaxGridDimY, device) == hipSuccess && grid_y > 0)
+            h->max_grid_y = h->device_max_grid_y = grid_y;
     }
     {
         int large_bar = 0;
@@ -4565,6 +4576,9 @@ int qsv_set_option(qsv_t* h, const char* name, int value) {
     } else if (key == "streams") {
         if (value < 1 || value > h->n_lane_streams + 1) return fail(h, QSV_E_ARG, "streams must be between 1 and the number the handle was created with");
         h->n_streams = value;
+    } else if (key == "max_grid_y") {  // x-mask groups / observable rows per launch (0: the device's largest gridDim.y); the same bits at any value
+        if (value < 0 || value > h->device_max_grid_y) return fail(h, QSV_E_ARG, "max_grid_y must be between 0 and the device's largest gridDim.y");
+        h->max_grid_y = value ? value : h->device_max_grid_y;
     } else if (key == "gradient_chunk") {  // shifted evaluations per chunk of a gradient call (0: the default); the same bits at any value
         if (value < 0 || value > (1 << 20)) return fail(h, QSV_E_ARG, "gradient_chunk must be between 0 and 1048576");
         h->grad_chunk = value ? value : kGradientChunkRows;
