@@ -267,22 +267,22 @@ int qsv_eval_results_seen(qsv_t* h);
  */
 typedef struct qsv_spsa_step_args {
     int32_t n_runs, width;
-    double* x;
-    uint8_t* active;
-    int64_t* iterations;
-    const double* delta_accept;
-    const double* values;
-    const double* delta_propose;
-    double* points;
+    double* x;                   /* [n_runs][width] */
+    uint8_t* active;             /* [n_runs] */
+    int64_t* iterations;         /* [n_runs] */
+    const double* delta_accept;  /* [n_runs][width], the signs the values were measured with */
+    const double* values;        /* [2 n_runs]: f(x + eps delta), f(x - eps delta) per run */
+    const double* delta_propose; /* [n_runs][width] */
+    double* points;              /* [2 n_runs][width] */
     double eps, lr;
     int32_t trust_region, maxiter;
-    int32_t window;
+    int32_t window;              /* termination rule: allowed_consecutive_violations + 1, 0 = no rule */
     int32_t reserved;
     double min_rel;
-    int64_t maxfev;
-    double* previous;
-    int64_t* n_values;
-    double* changes;
+    int64_t maxfev;              /* < 0: none */
+    double* previous;            /* [n_runs] */
+    int64_t* n_values;           /* [n_runs] */
+    double* changes;             /* [n_runs][window] */
 } qsv_spsa_step_args;
 int qsv_spsa_step(qsv_t* h, const qsv_spsa_step_args* args);
 /*
@@ -322,12 +322,12 @@ typedef struct qsv_nft_step_args {
     const int32_t* sizes;
     const int32_t* columns;
     double* recycled;
-    int32_t accept, accept_with_base;
+    int32_t accept, accept_with_base;   /* flags: any non-zero value is "yes" */
     int64_t accept_iteration;
     int32_t propose, propose_with_base;
     int64_t propose_iteration;
-    const double* values;
-    double* points;
+    const double* values;        /* [3 n_runs] (base, plus, minus per run) or [2 n_runs] */
+    double* points;              /* [3 n_runs][width] or [2 n_runs][width], rows in the order of the values */
 } qsv_nft_step_args;
 int qsv_nft_step(qsv_t* h, const qsv_nft_step_args* args);
 /*

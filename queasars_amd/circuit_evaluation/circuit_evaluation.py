@@ -1213,6 +1213,27 @@ def _check_initial_state(initial_state_circuit: Optional[CircuitIR], n_qubits: i
         )
 
 
+def _composed_list(evaluator, circuits: list) -> list:
+    """``circuits`` behind the evaluator's initial state, kept by IDENTITY of the list: the device-to-device methods are called
+    with the same list object iteration after iteration, and the library keys its batch layout on the composed circuits.  (One
+    list is kept: a caller that alternates between two composes at every change.)"""
+    if evaluator._initial_state_circuit is None:
+        return circuits
+    kept = evaluator._composed_lists
+    if kept is None or kept[0] is not circuits:
+        kept = evaluator._composed_lists = (circuits, [evaluator._composed.get(c) for c in circuits])
+    return kept[1]
+
+
+def _is_device_matrix(tensor, n_rows: int, device, width: Optional[int] = None) -> bool:
+    """Is ``tensor`` a contiguous 2-D float64 tensor of ``n_rows`` rows (of ``width`` entries, where given) on the torch
+    device ``device``?  What the gradient methods ask of their matrices; each says what it wanted in its own words."""
+    import torch
+
+    return (isinstance(tensor, torch.Tensor) and tensor.dtype == torch.float64 and tensor.dim() == 2 and tensor.shape[0] == n_rows
+            and (width is None or tensor.shape[1] == width) and tensor.is_contiguous() and tensor.device == device)
+
+
 def _device_matrix_arguments(evaluator, circuits, matrix, ready: bool):
     """What the device-resident methods of both evaluators check and work out about a parameter matrix: returns
     ``(pointer, width, event, remember)`` -- where the matrix is, its row length, a ``hipEvent_t`` after which it is complete
@@ -1262,9 +1283,12 @@ class EvaluatorGradientPlan:
     """``OperatorCircuitEvaluator.gradient_plan``: a :class:`DeviceGradientPlan` run under the evaluator's operator."""
 
     def __init__(self, evaluator: "OperatorCircuitEvaluator", plan: DeviceGradientPlan, n_circuits: int):
+        import torch
+
         self._evaluator = evaluator
         self._plan = plan
         self._n = int(n_circuits)
+        self._where = torch.device("cuda", evaluator._device.device_index)
         #: circuit evaluations one :meth:`run` queues
         self.n_shifted = plan.n_shifted
 
@@ -1276,8 +1300,7 @@ class EvaluatorGradientPlan:
 
         evaluator, plan = self._evaluator, self._plan
         for tensor, width in ((matrix, plan.width), (out, plan.out_width)):
-            if (not isinstance(tensor, torch.Tensor) or tensor.dtype != torch.float64 or tensor.shape != (self._n, width)
-                    or not tensor.is_contiguous() or not tensor.is_cuda or tensor.device.index != evaluator._device.device_index):
+            if not _is_device_matrix(tensor, self._n, self._where, width):
                 raise ValueError("matrix and out must be the contiguous float64 device tensors of the shapes the plan was made for")
         marker = None
         if not ready:
@@ -1348,6 +1371,8 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
 
     def _with_initial_state(self, circuit: CircuitIR) -> CircuitIR:
         return self._composed.get(circuit)
+
+    _composed_list = _composed_list
 
     def evaluate_circuits(self, circuits: list[CircuitIR], parameter_values: list[list[float]]) -> list[float]:
         """``parameter_values`` may also be a 2-D float64 tensor in THIS device's memory (anything with ``is_cuda`` /
@@ -1433,15 +1458,10 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
 
         if self._precision > 0:
             raise ValueError("estimator_precision > 0 is emulated on the host")
-        if self._initial_state_circuit is not None:
-            kept = self._composed_lists
-            if kept is None or kept[0] is not circuits:
-                kept = self._composed_lists = (circuits, [self._with_initial_state(c) for c in circuits])
-            circuits = kept[1]
+        circuits = self._composed_list(circuits)
         pointer, width, event, remember = _device_matrix_arguments(self, circuits, matrix, ready=True)
         n = len(circuits)
-        if (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.dim() != 2 or out.shape[0] != n
-                or not out.is_contiguous() or out.device != matrix.device):
+        if not _is_device_matrix(out, n, matrix.device):
             raise ValueError("the output must be a contiguous 2-D float64 tensor of len(circuits) rows on the matrix's device")
         _offsets, _flat, counts = StatevectorDevice._wrt_arguments(circuits, wrt)
         if n and int(counts.max()) > out.shape[1]:
@@ -1468,8 +1488,7 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
             circuits = [self._with_initial_state(c) for c in circuits]
         n = len(circuits)
         for name, tensor in (("matrix", matrix), ("out", out)):
-            if (not isinstance(tensor, torch.Tensor) or tensor.dtype != torch.float64 or tensor.dim() != 2 or tensor.shape[0] != n
-                    or not tensor.is_contiguous() or not tensor.is_cuda or tensor.device.index != self._device.device_index):
+            if not _is_device_matrix(tensor, n, torch.device("cuda", self._device.device_index)):
                 raise ValueError(f"{name} must be a contiguous 2-D float64 tensor of len(circuits) rows on the evaluator's device")
         if _has_none(circuits):
             raise ValueError("a gradient plan cannot skip circuits (None entries)")
@@ -1528,11 +1547,7 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         state and its device-side ids are kept by identity)."""
         if self._precision > 0:
             raise ValueError("estimator_precision > 0 is emulated on the host")
-        if self._initial_state_circuit is not None:
-            kept = self._composed_lists
-            if kept is None or kept[0] is not circuits:
-                kept = self._composed_lists = (circuits, [self._with_initial_state(c) for c in circuits])
-            circuits = kept[1]
+        circuits = self._composed_list(circuits)
         with self._device.operator_lock:
             if self._device._operator is not self._operator:
                 self._device.set_operator(self._operator)
@@ -1680,6 +1695,8 @@ class OperatorSamplerCircuitEvaluator(BaseCircuitEvaluator):
     def statevector_device(self) -> StatevectorDevice:
         return self._device
 
+    _composed_list = _composed_list
+
     #: what ``device_resident_search=None`` of the solver's configuration means for this evaluator (evqe/solver.py): the host
     #: driver, as before the device search could take it -- ``True`` opts in
     device_resident_search_by_default = False
@@ -1710,11 +1727,7 @@ class OperatorSamplerCircuitEvaluator(BaseCircuitEvaluator):
 
         if self._shots is not None and self._shots > StatevectorDevice.MAX_CVAR_SHOTS:
             raise ValueError(f"more than {StatevectorDevice.MAX_CVAR_SHOTS} shots are sorted on the host: use evaluate_circuits")
-        if self._initial_state_circuit is not None:
-            kept = self._composed_lists
-            if kept is None or kept[0] is not circuits:
-                kept = self._composed_lists = (circuits, [self._composed.get(c) for c in circuits])
-            circuits = kept[1]
+        circuits = self._composed_list(circuits)
         pointer, width, event, remember = _device_matrix_arguments(self, circuits, matrix, ready=True)
         n = len(circuits)
         if out.dtype != torch.float64 or out.numel() < n or not out.is_contiguous() or out.device != matrix.device:

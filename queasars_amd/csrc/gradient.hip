@@ -80,7 +80,7 @@ gradient_combine_kernel(const double* __restrict__ values, const GradEntry* __re
 // tolerance the squares of a round's updates go from lane to lane in ascending j (every lane holds the same running sum), so
 // the norm is the sum a sequential loop forms.  Division and square root of doubles are correctly rounded (no fast-math), and
 // nothing is contracted: the bits are NumPy's.
-__global__ void __launch_bounds__(64) adam_step_kernel(const AdamStepArgs a) {
+__global__ void __launch_bounds__(64) adam_step_kernel(const qsv_adam_step_args a) {
 #pragma clang fp contract(off)
     const int r = blockIdx.x, lane = threadIdx.x;
     if (a.active[r] == 0) return;  // (the whole wave: a stopped run keeps every bit)
@@ -124,7 +124,7 @@ __global__ void __launch_bounds__(64) adam_step_kernel(const AdamStepArgs a) {
 
 }  // namespace
 
-hipError_t launch_adam_step(const AdamStepArgs& args, hipStream_t stream) {
+hipError_t launch_adam_step(const qsv_adam_step_args& args, hipStream_t stream) {
     if (args.n_runs <= 0 || args.width <= 0) return hipSuccess;
     hipLaunchKernelGGL(adam_step_kernel, dim3(unsigned(args.n_runs)), dim3(64), 0, stream, args);
     return hipGetLastError();

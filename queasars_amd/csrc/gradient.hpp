@@ -53,20 +53,7 @@ hipError_t launch_gradient_combine(const double* values, const GradEntry* entrie
                                    int out_width, double cp, double cm, double* out, hipStream_t stream);
 
 // qsv_adam_step (qsv.h): one wave per run -- lanes stride over the run's variables, and the squared norm of the update is summed in
-// ascending j, one addition at a time --, one launch per iteration.
-struct AdamStepArgs {
-    int n_runs, width, columns_stride, grad_width;
-    double* x;
-    const int32_t* sizes;
-    const int32_t* columns;
-    double* m;
-    double* v;
-    const double* gradient;
-    uint8_t* active;
-    long long* iterations;
-    double lr, beta_1, beta_2, one_minus_beta_1, one_minus_beta_2, eps, tol, bias_1, bias_2;
-    long long maxiter;
-};
-hipError_t launch_adam_step(const AdamStepArgs& args, hipStream_t stream);
+// ascending j, one addition at a time --, one launch per iteration.  The arguments are the public struct's.
+hipError_t launch_adam_step(const qsv_adam_step_args& args, hipStream_t stream);
 
 }  // namespace qsv

@@ -2091,7 +2091,7 @@ __global__ void __launch_bounds__(256) reduce_partials_kernel(const double* __re
 // the host computes x + eps * delta in two roundings), and the reference's termination rule (queasars/utility/
 // spsa_termination.py:46-94 with accepted = True) in thread 0.  The norm of an update is a fixed-order sum over the run's row
 // (strided partial sums, then a tree): deterministic, not the host's order.
-__global__ void __launch_bounds__(256) spsa_step_kernel(const SpsaStepArgs a) {
+__global__ void __launch_bounds__(256) spsa_step_kernel(const qsv_spsa_step_args a) {
 #pragma clang fp contract(off)  // (every product and sum below is rounded on its own, as NumPy's are: x - u * lr must not become one fma)
     __shared__ double red[256];
     __shared__ double s_scale;
@@ -2172,7 +2172,7 @@ __global__ void __launch_bounds__(256) spsa_step_kernel(const SpsaStepArgs a) {
     }
 }
 
-hipError_t launch_spsa_step(const SpsaStepArgs& args, hipStream_t stream) {
+hipError_t launch_spsa_step(const qsv_spsa_step_args& args, hipStream_t stream) {
     if (args.n_runs <= 0 || args.width <= 0) return hipSuccess;
     hipLaunchKernelGGL(spsa_step_kernel, dim3(unsigned(args.n_runs)), dim3(256), 0, stream, args);
     return hipGetLastError();
@@ -2203,7 +2203,7 @@ __device__ __forceinline__ void nft_write_row(double* __restrict__ dst, const do
     if (tid == 64 && last < width) dst[last] = last == col ? x[last] + shift : x[last];
 }
 
-__global__ void __launch_bounds__(256) nft_step_kernel(const NftStepArgs a) {
+__global__ void __launch_bounds__(256) nft_step_kernel(const qsv_nft_step_args a) {
 #pragma clang fp contract(off)  // (every sum below is rounded on its own, as the host's Python floats are)
     const int r = blockIdx.x, tid = threadIdx.x;
     const int size = a.sizes[r];
@@ -2243,7 +2243,7 @@ __global__ void __launch_bounds__(256) nft_step_kernel(const NftStepArgs a) {
     }
 }
 
-hipError_t launch_nft_step(const NftStepArgs& args, hipStream_t stream) {
+hipError_t launch_nft_step(const qsv_nft_step_args& args, hipStream_t stream) {
     if (args.n_runs <= 0 || args.width <= 0) return hipSuccess;
     hipLaunchKernelGGL(nft_step_kernel, dim3(unsigned(args.n_runs)), dim3(256), 0, stream, args);
     return hipGetLastError();

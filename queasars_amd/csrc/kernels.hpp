@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "../../include/qsv.h"
+
 namespace qsv {
 
 // One evaluation (circuit + parameter vector) inside a launch group.
@@ -395,45 +397,15 @@ hipError_t launch_cvar_exact(int dtype, const double* probs, uint64_t dim, unsig
 
 // ---- the optimiser's share of a lock-step SPSA iteration (qsv.h: qsv_spsa_step) -----------------------------------------------
 // One workgroup per run: accept the iteration whose two values are in `values` (update x, count, stopping rules), then write
-// the two points of the next iteration.  Either half may be left out (values / delta_propose null).
-struct SpsaStepArgs {
-    int n_runs, width;
-    double* x;                    // [n_runs][width]
-    unsigned char* active;        // [n_runs]
-    long long* iterations;        // [n_runs]
-    const double* delta_accept;   // [n_runs][width], the signs the values were measured with
-    const double* values;         // [2 n_runs]: f(x + eps delta), f(x - eps delta) per run
-    const double* delta_propose;  // [n_runs][width]
-    double* points;               // [2 n_runs][width]
-    double eps, lr;
-    int trust_region, maxiter;
-    int window;                   // termination rule: allowed_consecutive_violations + 1, 0 = no rule
-    double min_rel;
-    long long maxfev;             // < 0: none
-    double* previous;             // [n_runs]
-    long long* n_values;          // [n_runs]
-    double* changes;              // [n_runs][window]
-};
-hipError_t launch_spsa_step(const SpsaStepArgs& args, hipStream_t stream);
+// the two points of the next iteration.  Either half may be left out (values / delta_propose null).  The arguments are the
+// public struct's, member by member as qsv.h documents them.
+hipError_t launch_spsa_step(const qsv_spsa_step_args& args, hipStream_t stream);
 
 // ---- the optimiser's share of a lock-step NFT iteration (qsv.h: qsv_nft_step) -------------------------------------------------
 // One workgroup per run: accept the iteration whose two or three values are in `values` (one coordinate of x moves to the fitted
 // sinusoid's minimum, the fitted minimum is kept in `recycled`), then write the two or three points of the next iteration.
 // Either half may be left out.  Rows of x and points need 8-byte alignment only.
-struct NftStepArgs {
-    int n_runs, width, columns_stride;
-    double* x;                    // [n_runs][width]
-    const int* sizes;             // [n_runs]: searched variables per run, 1 .. columns_stride
-    const int* columns;           // [n_runs][columns_stride]: column of x of variable j
-    double* recycled;             // [n_runs]
-    int accept, accept_with_base;
-    long long accept_iteration;
-    int propose, propose_with_base;
-    long long propose_iteration;
-    const double* values;         // [3 n_runs] (base, plus, minus per run) or [2 n_runs]
-    double* points;               // [3 n_runs][width] or [2 n_runs][width], rows in the order of the values
-};
-hipError_t launch_nft_step(const NftStepArgs& args, hipStream_t stream);
+hipError_t launch_nft_step(const qsv_nft_step_args& args, hipStream_t stream);
 
 hipError_t launch_probabilities(int dtype, const void* state, uint64_t dim, int n_slots, double* probs,
                                 hipStream_t stream);

@@ -3147,49 +3147,34 @@ int qsv_eval_staging(qsv_t* h, int first, int count, double** values) {
     return QSV_OK;
 }
 
-int qsv_spsa_step(qsv_t* h, const qsv_spsa_step_args* in) {
-    if (!h || !in) return QSV_E_ARG;
+// The opening the step entry points have in common: a handle and arguments, no batch of the calling thread's open on the
+// handle, the handle's lock (held by `lock` until the caller returns) and its device.
+static int step_begin(qsv_t* h, const void* args, const char* name, std::unique_lock<std::mutex>& lock) {
+    if (!h || !args) return QSV_E_ARG;
     // (between qsv_eval_begin and qsv_eval_end the calling thread holds the handle: it would wait for itself)
     if (h->batch_owner.load() == std::this_thread::get_id())
-        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_spsa_step goes between batches)");
-    std::lock_guard<std::mutex> lock(h->mu);
+        return fail(h, QSV_E_STATE, std::string("a batch is open on this handle (") + name + " goes between batches)");
+    lock = std::unique_lock<std::mutex>(h->mu);
+    QSV_HIP(h, hipSetDevice(h->device));
+    return QSV_OK;
+}
+
+int qsv_spsa_step(qsv_t* h, const qsv_spsa_step_args* in) {
+    std::unique_lock<std::mutex> lock;
+    if (const int rc = step_begin(h, in, "qsv_spsa_step", lock)) return rc;
     if (in->n_runs < 0 || in->width < 0 || !in->x || !in->active || !in->iterations) return fail(h, QSV_E_ARG, "bad arguments");
     if (in->values && !in->delta_accept) return fail(h, QSV_E_ARG, "values without the signs they were measured with");
     if (in->delta_propose && !in->points) return fail(h, QSV_E_ARG, "a proposal needs somewhere to go");
     if (in->window < 0 || (in->window > 0 && (!in->previous || !in->n_values || !in->changes)))
         return fail(h, QSV_E_ARG, "the termination rule needs its state");
     if (!(in->eps > 0)) return fail(h, QSV_E_ARG, "eps must be positive");
-    QSV_HIP(h, hipSetDevice(h->device));
-    SpsaStepArgs a{};
-    a.n_runs = in->n_runs;
-    a.width = in->width;
-    a.x = in->x;
-    a.active = in->active;
-    a.iterations = reinterpret_cast<long long*>(in->iterations);
-    a.delta_accept = in->delta_accept;
-    a.values = in->values;
-    a.delta_propose = in->delta_propose;
-    a.points = in->points;
-    a.eps = in->eps;
-    a.lr = in->lr;
-    a.trust_region = in->trust_region;
-    a.maxiter = in->maxiter;
-    a.window = in->window;
-    a.min_rel = in->min_rel;
-    a.maxfev = in->maxfev;
-    a.previous = in->previous;
-    a.n_values = reinterpret_cast<long long*>(in->n_values);
-    a.changes = in->changes;
-    QSV_HIP(h, launch_spsa_step(a, h->stream));
+    QSV_HIP(h, launch_spsa_step(*in, h->stream));
     return QSV_OK;
 }
 
 int qsv_nft_step(qsv_t* h, const qsv_nft_step_args* in) {
-    if (!h || !in) return QSV_E_ARG;
-    // (between qsv_eval_begin and qsv_eval_end the calling thread holds the handle: it would wait for itself)
-    if (h->batch_owner.load() == std::this_thread::get_id())
-        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_nft_step goes between batches)");
-    std::lock_guard<std::mutex> lock(h->mu);
+    std::unique_lock<std::mutex> lock;
+    if (const int rc = step_begin(h, in, "qsv_nft_step", lock)) return rc;
     if (in->n_runs < 0 || in->width < 0 || in->columns_stride < 1 || !in->x || !in->sizes || !in->columns || !in->recycled)
         return fail(h, QSV_E_ARG, "bad arguments");
     if (in->accept && !in->values) return fail(h, QSV_E_ARG, "an accept needs the values it fits");
@@ -3198,64 +3183,20 @@ int qsv_nft_step(qsv_t* h, const qsv_nft_step_args* in) {
         return fail(h, QSV_E_ARG, "a negative iteration number");
     if ((reinterpret_cast<uintptr_t>(in->x) & 7u) || (reinterpret_cast<uintptr_t>(in->points) & 7u))
         return fail(h, QSV_E_ARG, "x and points must be aligned as doubles are");
-    QSV_HIP(h, hipSetDevice(h->device));
-    NftStepArgs a{};
-    a.n_runs = in->n_runs;
-    a.width = in->width;
-    a.columns_stride = in->columns_stride;
-    a.x = in->x;
-    a.sizes = in->sizes;
-    a.columns = in->columns;
-    a.recycled = in->recycled;
-    a.accept = in->accept != 0;
-    a.accept_with_base = in->accept_with_base != 0;
-    a.accept_iteration = in->accept_iteration;
-    a.propose = in->propose != 0;
-    a.propose_with_base = in->propose_with_base != 0;
-    a.propose_iteration = in->propose_iteration;
-    a.values = in->values;
-    a.points = in->points;
-    QSV_HIP(h, launch_nft_step(a, h->stream));
+    QSV_HIP(h, launch_nft_step(*in, h->stream));
     return QSV_OK;
 }
 
 int qsv_adam_step(qsv_t* h, const qsv_adam_step_args* in) {
-    if (!h || !in) return QSV_E_ARG;
-    // (between qsv_eval_begin and qsv_eval_end the calling thread holds the handle: it would wait for itself)
-    if (h->batch_owner.load() == std::this_thread::get_id())
-        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_adam_step goes between batches)");
-    std::lock_guard<std::mutex> lock(h->mu);
+    std::unique_lock<std::mutex> lock;
+    if (const int rc = step_begin(h, in, "qsv_adam_step", lock)) return rc;
     if (in->n_runs < 0 || in->width < 0 || in->grad_width < 0 || in->columns_stride < 1 || !in->x || !in->sizes || !in->columns || !in->m ||
         !in->v || !in->gradient || !in->active || !in->iterations)
         return fail(h, QSV_E_ARG, "bad arguments");
     if (in->grad_width < in->columns_stride)
         return fail(h, QSV_E_ARG, "grad_width " + std::to_string(in->grad_width) + " is smaller than the " + std::to_string(in->columns_stride) +
                                       " entries a run may search");
-    QSV_HIP(h, hipSetDevice(h->device));
-    AdamStepArgs a{};
-    a.n_runs = in->n_runs;
-    a.width = in->width;
-    a.columns_stride = in->columns_stride;
-    a.grad_width = in->grad_width;
-    a.x = in->x;
-    a.sizes = in->sizes;
-    a.columns = in->columns;
-    a.m = in->m;
-    a.v = in->v;
-    a.gradient = in->gradient;
-    a.active = in->active;
-    a.iterations = reinterpret_cast<long long*>(in->iterations);
-    a.lr = in->lr;
-    a.beta_1 = in->beta_1;
-    a.beta_2 = in->beta_2;
-    a.one_minus_beta_1 = in->one_minus_beta_1;
-    a.one_minus_beta_2 = in->one_minus_beta_2;
-    a.eps = in->eps;
-    a.tol = in->tol;
-    a.bias_1 = in->bias_1;
-    a.bias_2 = in->bias_2;
-    a.maxiter = in->maxiter;
-    QSV_HIP(h, launch_adam_step(a, h->stream));
+    QSV_HIP(h, launch_adam_step(*in, h->stream));
     return QSV_OK;
 }
 

@@ -1,38 +1,49 @@
-"""The lock-step SPSA search of a population with its state ON THE DEVICE.
+"""Lock-step parameter searches of a population with their state ON THE DEVICE: SPSA, NFT and Adam.
 
-``solver._minimize_spsa_vectorised`` keeps every run's iterate in host memory: an iteration builds the 2 R points in NumPy,
-hands them to the evaluator (packing, PCIe), waits for the 2 R values and updates the iterates -- and the GPU idles while
-the host does its share (8.0 ms per search of 64 individuals at 20 qubits, of which the device is busy for 3).  Here the
-iterates, the pre-drawn sign vectors, the points and the function values are tensors in device memory, the evaluator reads
-the points where they are and leaves the values where the update reads them (``qsv_eval_push_device`` /
-``qsv_eval_set_output`` for the exact estimator, ``qsv_cvar_device`` for the sampler evaluator's CVaR), and everything of an iteration -- proposal, evaluation, update, the termination rule -- is queued
-on ONE HIP stream without the host waiting for any of it; the host looks at the device every few iterations only to see
-whether every run has stopped.
+The host drivers (``solver._minimize_batched``, ``_minimize_spsa_vectorised``, ``_minimize_adam``) keep every run's iterate in
+host memory: an iteration builds the points in NumPy, hands them to the evaluator (packing, PCIe), waits for the values and
+updates the iterates -- and the GPU idles while the host does its share (SPSA: 8.0 ms per search of 64 individuals at 20 qubits,
+of which the device is busy for 3).  Here iterates, points and values are tensors in device memory, the evaluator reads the
+points where they are and leaves its results where the optimiser's step reads them, and everything of an iteration is queued on
+ONE HIP stream without the host waiting for any of it.  What the three drivers share is written once:
 
-Arithmetic: element by element the expressions of ``_SPSARun.propose`` / ``accept`` (reference: qiskit_algorithms' SPSA with
-constant gains as the notebook configures it, mutation.py:63-75 for the batched callback), in the same order; the one
-difference is the trust region's norm, summed by the device in its own order, so an iterate can differ from the host
-driver's in the last bits (tests hold the two to 1e-9 and to the same stopping iterations).  The termination rule is the
-reference's ``SPSATerminationChecker`` (queasars/utility/spsa_termination.py:46-94) as array operations; the runs' host-side
-checker objects are not fed (nothing reads them afterwards).  Runs that have stopped stay in the batch with their updates
-masked -- taking them out would mean waiting for the device --, and are not counted: ``nfev`` is two per iteration a run
-was active, as on the host.  An evaluator whose ``evaluate_device_to_device`` takes a mask (the sampler evaluator) is handed
-the runs' ``active`` flags, so that the two evaluations of a stopped run cost a dispatch and nothing else.
+* the LAYOUT (:class:`_PackedRuns`, :func:`_full_point`): one row per run, the run's whole parameter vector -- its own ``x``, or
+  (``run.embed``: a layer inside the individual's fully parameterised circuit) the base vector with ``x`` at the layer's
+  positions --, zero-padded to the widest; ``columns`` says where in its row each run's variables are;
+* the STREAM (:func:`_on_search_stream`): the one the evaluator's handle launches on, ordered after the caller's on entry and
+  before it on exit -- or, for a library that works in host memory (the host tests' emulations), no stream at all;
+* the RULE that sends a search here, in two parts: what ``(evaluator, configuration, number of runs)`` decide
+  (:func:`possible`, :func:`possible_nft`, :func:`possible_adam` -- ``solver._device_search_wanted`` asks these before the runs
+  exist, to decide whether layer searches embed their runs) and what only the runs can say (fresh runs of one configuration
+  object: :func:`supported`, :func:`supported_nft`, :func:`supported_adam`, which ask both).
 
-With a sampling evaluator (``sampler_shots`` given) every iteration draws one seed from the evaluator's generator, as an
-``evaluate_circuits`` call of the host driver does -- also the up to ``look_every - 1`` iterations queued after the last run
-has stopped and before the host has looked: the generator then stands further on than after the same search on the host.
+SPSA (:func:`minimize_spsa_on_device`, ``qsv_spsa_step``).  Arithmetic: element by element the expressions of
+``_SPSARun.propose`` / ``accept`` (reference: qiskit_algorithms' SPSA with constant gains as the notebook configures it,
+mutation.py:63-75 for the batched callback), in the same order; the one difference is the trust region's norm, summed by the
+device in its own order, so an iterate can differ from the host driver's in the last bits (tests hold the two to 1e-9 and to the
+same stopping iterations).  The termination rule is the reference's ``SPSATerminationChecker``
+(queasars/utility/spsa_termination.py:46-94) as array operations; the runs' host-side checker objects are not fed (nothing reads
+them afterwards).  The host looks at the device every few iterations only to see whether every run has stopped.  Runs that have
+stopped stay in the batch with their updates masked -- taking them out would mean waiting for the device --, and are not
+counted: ``nfev`` is two per iteration a run was active, as on the host.  An evaluator whose ``evaluate_device_to_device`` takes
+a mask (the sampler evaluator) is handed the runs' ``active`` flags, so that the two evaluations of a stopped run cost a dispatch
+and nothing else.  With a sampling evaluator (``sampler_shots`` given) every iteration draws one seed from the evaluator's
+generator, as an ``evaluate_circuits`` call of the host driver does -- also the up to ``look_every - 1`` iterations queued after
+the last run has stopped and before the host has looked: the generator then stands further on than after the same search on the
+host.
 
-NFT searches (:func:`minimize_nft_on_device`, ``qsv_nft_step``) are simpler: fresh runs of one configuration move in perfect
-lock-step, the host knows every iteration's form and the last iteration before it starts (:func:`nft_schedule`), and it never
-looks at the device inside a search.
+NFT (:func:`minimize_nft_on_device`, ``qsv_nft_step``) is simpler: fresh runs of one configuration move in perfect lock-step,
+the host knows every iteration's form and the last iteration before it starts (:func:`nft_schedule`), and it never looks at the
+device inside a search.
 
-Adam searches (:func:`minimize_adam_on_device`, ``qsv_adam_step``) differentiate instead of evaluating: one gradient plan per
-search (``OperatorCircuitEvaluator.gradient_plan``; include/qsv.h, GRADIENT PLANS), whose runs follow each other on the stream
-with one step launch between them.  The step's arithmetic is ``_AdamRun.accept_gradient``'s, bit for bit.
+Adam (:func:`minimize_adam_on_device`, ``qsv_adam_step``) differentiates instead of evaluating: one gradient plan per search
+(``OperatorCircuitEvaluator.gradient_plan``; include/qsv.h, GRADIENT PLANS), whose runs follow each other on the stream with one
+step launch between them.  The step's arithmetic is ``_AdamRun.accept_gradient``'s, bit for bit.
 """
 
 from __future__ import annotations
+
+import contextlib
 
 import numpy as np
 
@@ -40,26 +51,146 @@ import numpy as np
 _MAX_SIGN_BYTES = 256 << 20
 
 
+# ---- the layout ---------------------------------------------------------------------------------------------------------------
+
+
+def _positions(run) -> np.ndarray:
+    """Where in its parameter vector (:func:`_full_point`) a run's variables are."""
+    return np.arange(run.x.size) if run.embed is None else run.embed[1]
+
+
+def _row_length(run) -> int:
+    return run.x.size if run.embed is None else run.embed[0].size
+
+
+def _full_point(run, point: np.ndarray) -> np.ndarray:
+    """The parameter vector the evaluator gets for a run's point: the point itself, or (``run.embed = (base, positions)``: the
+    run's variables are entries of a longer vector whose other entries do not move) the base vector with the point at the
+    positions."""
+    if run.embed is None:
+        return point
+    base, positions = run.embed
+    full = base.copy()
+    full[positions] = point
+    return full
+
+
+class _PackedRuns:
+    """Runs laid out as one zero-padded matrix: row i of ``x_host`` (``n_runs`` x ``width``) is ``_full_point(run, run.x)``, of
+    which ``lengths[i]`` entries are the run's and ``sizes[i]`` are searched, at the columns ``where[i]`` -- which are also the
+    first ``sizes[i]`` entries of row i of ``columns_host`` (``n_runs`` x ``stride``, int32: what the step kernels index with).
+    Entries of a row that are not searched travel into every point untouched."""
+
+    def __init__(self, runs):
+        self.runs = runs
+        self.where = [_positions(run) for run in runs]
+        self.lengths = np.array([_row_length(run) for run in runs])
+        self.sizes = np.array([run.x.size for run in runs], dtype=np.int32)
+        self.n_runs, self.width, self.stride = len(runs), int(self.lengths.max()), int(self.sizes.max())
+        self.x_host = np.zeros((self.n_runs, self.width))
+        self.columns_host = np.zeros((self.n_runs, self.stride), dtype=np.int32)
+        for i, run in enumerate(runs):
+            self.x_host[i, : self.lengths[i]] = _full_point(run, run.x)
+            self.columns_host[i, : self.sizes[i]] = self.where[i]
+
+    def draw_signs(self, n_iter: int) -> np.ndarray:
+        """Every run's SPSA sign vectors of the next ``n_iter`` iterations from the run's own generator -- what ``propose()``
+        would draw call by call: one draw of the lot gives the same numbers --, zero where a row is not searched (x +- eps * 0
+        leaves those entries where they are, the update is zero there and the norm does not see them).  As bytes,
+        ``(n_iter, n_runs, width)``: an eighth of the transfer, which was a tenth of a short search."""
+        signs = np.zeros((n_iter, self.n_runs, self.width), dtype=np.int8)
+        for i, run in enumerate(self.runs):
+            signs[:, i, self.where[i]] = 1 - 2 * run.rng.binomial(1, 0.5, size=(n_iter, run.x.size))
+        return signs
+
+    def write_back(self, x_final: np.ndarray) -> None:
+        """The inverse: every run's ``x`` from its row of ``x_final``."""
+        for i, run in enumerate(self.runs):
+            run.x = x_final[i, self.where[i]].copy()
+
+
+# ---- the stream ---------------------------------------------------------------------------------------------------------------
+
+
+@contextlib.contextmanager
+def _on_search_stream(evaluator):
+    """Inside: torch's current stream is the one the evaluator's handle launches on, which has been told to wait for the
+    caller's; on the way out -- also when the body raises -- the caller's stream is told to wait for it.  Yields the torch
+    device to allocate on.  Nothing here waits on the host.  A statevector device without ``device_index`` is a library that
+    works in host memory -- the NumPy emulations of the step contracts that the host tests drive the searches with: the same
+    tensors, pointers and calls, on the CPU and without a stream."""
+    import torch
+
+    index = evaluator.statevector_device.device_index
+    if index is None:
+        yield torch.device("cpu")
+        return
+    from queasars_amd.distributed import _chain_state
+
+    device = torch.device("cuda", index)
+    stream = _chain_state(evaluator, device)["stream"]
+    caller = torch.cuda.current_stream(device)
+    stream.wait_stream(caller)
+    try:
+        with torch.cuda.stream(stream):
+            yield device
+    finally:
+        caller.wait_stream(stream)
+
+
+# ---- the rule -----------------------------------------------------------------------------------------------------------------
+
+
+def _evaluator_can(evaluator, n_runs: int, method: str) -> bool:
+    """At least two runs, and an evaluator that has ``method`` and says its device can hold a search."""
+    return n_runs >= 2 and callable(getattr(evaluator, method, None)) and bool(evaluator.device_resident_search_possible())
+
+
+def possible(evaluator, config, n_runs: int) -> bool:
+    """Could :func:`minimize_spsa_on_device` take ``n_runs`` fresh runs of ``config``, as far as anyone can say before they exist?
+    An evaluator that reads points from and leaves values in device memory (the exact estimator; the sampler evaluator with the
+    exact distribution or up to 4096 shots) on a GPU, something to do, and no termination rule or the one the device implements.
+    (The one thing :func:`supported` may still refuse such runs for is the size of their sign vectors.)"""
+    checker = config.termination_checker
+    # (by name: solver.py imports this module, and a class object from there would close the circle)
+    return (_evaluator_can(evaluator, n_runs, "evaluate_device_to_device") and config.maxiter > 0
+            and (checker is None or type(checker).__name__ == "SPSATerminationChecker"))
+
+
+def possible_nft(evaluator, config, n_runs: int) -> bool:
+    """:func:`possible` for :func:`minimize_nft_on_device`: the same evaluators, a schedule that is not empty."""
+    return _evaluator_can(evaluator, n_runs, "evaluate_device_to_device") and len(nft_schedule(config)[0]) > 0
+
+
+def possible_adam(evaluator, config, n_runs: int) -> bool:
+    """:func:`possible` for :func:`minimize_adam_on_device`: an evaluator with gradient plans, on a GPU."""
+    return _evaluator_can(evaluator, n_runs, "gradient_plan") and int(config.maxiter) > 0
+
+
+def _in_lock_step(runs, run_class) -> bool:
+    """What only the runs can say: every one a ``run_class`` of ONE configuration object with something to search, unfinished and
+    at the same iteration as the others."""
+    if not runs or not all(isinstance(run, run_class) for run in runs):
+        return False
+    cfg, first = runs[0].config, runs[0].iteration
+    return not any(run.config is not cfg or run.iteration != first or run.done or run.x.size < 1 for run in runs)
+
+
 def supported(evaluator, jobs) -> bool:
-    """Can :func:`minimize_spsa_on_device` take these jobs?  An evaluator that reads points from and leaves values in device
-    memory (the exact estimator; the sampler evaluator with the exact distribution or up to 4096 shots) on a GPU, fresh SPSA
-    runs of one configuration."""
-    if len(jobs) < 2 or not hasattr(evaluator, "evaluate_device_to_device"):
-        return False
-    if not evaluator.device_resident_search_possible():
-        return False
+    """Can :func:`minimize_spsa_on_device` take these jobs?  :func:`possible`, and fresh SPSA runs of one configuration."""
+    from queasars_amd.evqe.solver import _SPSARun
+
     runs = [run for _, run in jobs]
-    cfg = runs[0].config
-    if any(run.config is not cfg or run.iteration != 0 or run.nfev != 0 or run.done for run in runs):
+    if not _in_lock_step(runs, _SPSARun) or any(run.iteration != 0 or run.nfev != 0 for run in runs):
         return False
+    cfg = runs[0].config
     # (the sign vectors of every iteration are drawn ahead, as float64 rows of the widest run's width -- on the host and again on
     # the device: long optimisations of many deep individuals with embedded parameter vectors would be hundreds of megabytes;
     # beyond a quarter of a gigabyte the host driver, which draws them iteration by iteration, takes the search)
-    width = max(run.embed[0].size if run.embed is not None else run.x.size for run in runs)
+    width = max(_row_length(run) for run in runs)
     if int(cfg.maxiter) * len(runs) * width * 8 > _MAX_SIGN_BYTES:  # (as doubles on the device; bytes on the host)
         return False
-    checker = cfg.termination_checker
-    return cfg.maxiter > 0 and (checker is None or type(checker).__name__ == "SPSATerminationChecker")
+    return possible(evaluator, cfg, len(runs))
 
 
 def minimize_spsa_on_device(evaluator, jobs, look_every: int = 8) -> None:
@@ -74,41 +205,23 @@ def minimize_spsa_on_device(evaluator, jobs, look_every: int = 8) -> None:
     import torch
 
     from queasars_amd import _lib
-    from queasars_amd.distributed import _chain_state
 
     if os.environ.get("QSV_DEVICE_SEARCH_TORCH") == "1":
         return _minimize_with_torch_operations(evaluator, jobs, look_every)
-    runs = [run for _, run in jobs]
-    cfg = runs[0].config
-    n_iter = int(cfg.maxiter)
-    # A run's variables may be entries of a longer parameter vector (run.embed: a layer inside the individual's fully
-    # parameterised circuit): the row is that vector, the signs are zero everywhere else -- x +- eps * 0 leaves the other
-    # entries where they are, the update is zero there and the norm does not see them.
-    where = [run.embed[1] if run.embed is not None else np.arange(run.x.size) for run in runs]
-    lengths = np.array([run.embed[0].size if run.embed is not None else run.x.size for run in runs])
-    width, n_runs = int(lengths.max()), len(runs)
-    x_host = np.zeros((n_runs, width))
-    # (the signs travel as bytes -- an eighth of the transfer, which was a tenth of a short search -- and become doubles on the device)
-    signs_host = np.zeros((n_iter, n_runs, width), dtype=np.int8)
-    for i, run in enumerate(runs):
-        if run.embed is not None:
-            x_host[i, : lengths[i]] = run.embed[0]
-        x_host[i, where[i]] = run.x
-        signs_host[:, i, where[i]] = 1 - 2 * run.rng.binomial(1, 0.5, size=(n_iter, run.x.size))
+    pack = _PackedRuns([run for _, run in jobs])
+    cfg = pack.runs[0].config
+    n_iter, n_runs, width = int(cfg.maxiter), pack.n_runs, pack.width
+    signs_host = pack.draw_signs(n_iter)
     circuits = [circuit for circuit, _ in jobs for _ in (0, 1)]
     checker = cfg.termination_checker
     window = checker.allowed_consecutive_violations + 1 if checker is not None else 0
 
     dev = evaluator.statevector_device
-    device = torch.device("cuda", dev.device_index)
-    stream = _chain_state(evaluator, device)["stream"]  # (the stream the evaluator's handle launches on)
-    caller = torch.cuda.current_stream(device)
-    stream.wait_stream(caller)
     lib, handle = dev._lib, dev._handle
     takes_mask = _takes_mask(evaluator)
-    with torch.cuda.stream(stream):
-        x = torch.from_numpy(x_host).to(device)
-        signs = torch.from_numpy(signs_host).to(device).to(torch.float64)
+    with _on_search_stream(evaluator) as device:
+        x = torch.from_numpy(pack.x_host).to(device)
+        signs = torch.from_numpy(signs_host).to(device).to(torch.float64)  # (bytes on the way, doubles on the device)
         points = torch.empty((2 * n_runs, width), dtype=torch.float64, device=device)
         values = torch.empty(2 * n_runs, dtype=torch.float64, device=device)
         active = torch.ones(n_runs, dtype=torch.uint8, device=device)
@@ -140,9 +253,12 @@ def minimize_spsa_on_device(evaluator, jobs, look_every: int = 8) -> None:
                 evaluator.evaluate_device_to_device(circuits, points, values)
         x_final = x.cpu().numpy()
         done_iterations = iterations.cpu().numpy()
-    caller.wait_stream(stream)
-    for i, run in enumerate(runs):
-        run.x = x_final[i, where[i]].copy()
+    _spsa_write_back(pack, x_final, done_iterations)
+
+
+def _spsa_write_back(pack: _PackedRuns, x_final, done_iterations) -> None:
+    pack.write_back(x_final)
+    for i, run in enumerate(pack.runs):
         run.iteration = int(done_iterations[i])
         run.nfev = 2 * int(done_iterations[i])
         run.done = True
@@ -173,17 +289,10 @@ def supported_nft(evaluator, jobs) -> bool:
     memory, on a GPU; at least two runs, every one a fresh NFT run of one configuration object with something to search."""
     from queasars_amd.evqe.solver import _NFTRun
 
-    if len(jobs) < 2 or not hasattr(evaluator, "evaluate_device_to_device"):
-        return False
-    if not evaluator.device_resident_search_possible():
-        return False
     runs = [run for _, run in jobs]
-    if not all(isinstance(run, _NFTRun) for run in runs):
+    if not _in_lock_step(runs, _NFTRun) or any(run.iteration != 0 or run.nfev != 0 for run in runs):
         return False
-    cfg = runs[0].config
-    if any(run.config is not cfg or run.iteration != 0 or run.nfev != 0 or run.done or run.x.size < 1 for run in runs):
-        return False
-    return len(nft_schedule(cfg)[0]) > 0
+    return possible_nft(evaluator, runs[0].config, len(runs))
 
 
 def minimize_nft_on_device(evaluator, jobs, state: dict | None = None) -> None:
@@ -211,39 +320,20 @@ def minimize_nft_on_device(evaluator, jobs, state: dict | None = None) -> None:
     import torch
 
     from queasars_amd import _lib
-    from queasars_amd.distributed import _chain_state
 
-    runs = [run for _, run in jobs]
-    cfg = runs[0].config
-    with_base, nfev = nft_schedule(cfg)
-    n_iter = len(with_base)
-    # (run.embed: the run's variables are entries of a longer parameter vector -- the row is that vector, `columns` says where
-    # the variables are, and the other entries travel into every point untouched)
-    where = [run.embed[1] if run.embed is not None else np.arange(run.x.size) for run in runs]
-    lengths = np.array([run.embed[0].size if run.embed is not None else run.x.size for run in runs])
-    sizes_host = np.array([run.x.size for run in runs], dtype=np.int32)
-    width, n_runs, stride = int(lengths.max()), len(runs), int(sizes_host.max())
-    x_host = np.zeros((n_runs, width))
-    columns_host = np.zeros((n_runs, stride), dtype=np.int32)
-    for i, run in enumerate(runs):
-        if run.embed is not None:
-            x_host[i, : lengths[i]] = run.embed[0]
-        x_host[i, where[i]] = run.x
-        columns_host[i, : sizes_host[i]] = where[i]
+    pack = _PackedRuns([run for _, run in jobs])
+    with_base, nfev = nft_schedule(pack.runs[0].config)
+    n_iter, n_runs, width = len(with_base), pack.n_runs, pack.width
     # (the same two list objects call after call: the evaluators key their caches on identity)
     three = [circuit for circuit, _ in jobs for _ in (0, 1, 2)]
     two = [circuit for circuit, _ in jobs for _ in (0, 1)]
 
     dev = evaluator.statevector_device
-    device = torch.device("cuda", dev.device_index)
-    stream = _chain_state(evaluator, device)["stream"]  # (the stream the evaluator's handle launches on)
-    caller = torch.cuda.current_stream(device)
-    stream.wait_stream(caller)
     lib, handle = dev._lib, dev._handle
-    with torch.cuda.stream(stream):
-        x = torch.from_numpy(x_host).to(device)
-        sizes = torch.from_numpy(sizes_host).to(device)
-        columns = torch.from_numpy(columns_host).to(device)
+    with _on_search_stream(evaluator) as device:
+        x = torch.from_numpy(pack.x_host).to(device)
+        sizes = torch.from_numpy(pack.sizes).to(device)
+        columns = torch.from_numpy(pack.columns_host).to(device)
         recycled = torch.zeros(n_runs, dtype=torch.float64, device=device)
         points = torch.empty((3 * n_runs, width), dtype=torch.float64, device=device)
         values = torch.empty(3 * n_runs, dtype=torch.float64, device=device)
@@ -251,7 +341,7 @@ def minimize_nft_on_device(evaluator, jobs, state: dict | None = None) -> None:
         if state is not None:
             state.update(x=x, recycled=recycled, points=points, values=values)
         args = _lib.QsvNftStepArgs(
-            n_runs=n_runs, width=width, columns_stride=stride, reserved=0, x=x.data_ptr(), sizes=sizes.data_ptr(),
+            n_runs=n_runs, width=width, columns_stride=pack.stride, reserved=0, x=x.data_ptr(), sizes=sizes.data_ptr(),
             columns=columns.data_ptr(), recycled=recycled.data_ptr(), values=values.data_ptr(), points=points.data_ptr())
         for k in range(n_iter + 1):
             # accept iteration k - 1 (its values are in `values`), propose iteration k
@@ -266,9 +356,8 @@ def minimize_nft_on_device(evaluator, jobs, state: dict | None = None) -> None:
                 evaluator.evaluate_device_to_device(two, points_two, values_two)
         x_final = x.cpu().numpy()
         recycled_final = recycled.cpu().numpy()
-    caller.wait_stream(stream)
-    for i, run in enumerate(runs):
-        run.x = x_final[i, where[i]].copy()
+    pack.write_back(x_final)
+    for i, run in enumerate(pack.runs):
         run.iteration = n_iter
         run.nfev = nfev
         run._recycled = float(recycled_final[i])
@@ -282,18 +371,11 @@ def supported_adam(evaluator, jobs) -> bool:
     has not moved yet (``m`` and ``v`` zero: the device starts its moments there)."""
     from queasars_amd.evqe.solver import _AdamRun
 
-    if len(jobs) < 2 or not callable(getattr(evaluator, "gradient_plan", None)):
-        return False
-    if not evaluator.device_resident_search_possible():
-        return False
     runs = [run for _, run in jobs]
-    if not all(isinstance(run, _AdamRun) for run in runs):
+    if not _in_lock_step(runs, _AdamRun) or any(np.any(run.m) or np.any(run.v) for run in runs):
         return False
-    cfg, first = runs[0].config, runs[0].iteration
-    if any(run.config is not cfg or run.iteration != first or run.done or run.x.size < 1 or np.any(run.m) or np.any(run.v)
-           for run in runs):
-        return False
-    return int(cfg.maxiter) > first
+    cfg = runs[0].config
+    return int(cfg.maxiter) > runs[0].iteration and possible_adam(evaluator, cfg, len(runs))
 
 
 def minimize_adam_on_device(evaluator, jobs, look_every: int = 8, state: dict | None = None) -> None:
@@ -314,32 +396,19 @@ def minimize_adam_on_device(evaluator, jobs, look_every: int = 8, state: dict | 
     ``_minimize_adam`` checks what the evaluator reports.
 
     ``state``: a dictionary that receives the search's tensors and the plan before the first iteration is queued."""
-    import contextlib
     import ctypes as C
 
     import torch
 
     from queasars_amd import _lib
 
-    runs = [run for _, run in jobs]
+    pack = _PackedRuns([run for _, run in jobs])
+    runs, n_runs, stride = pack.runs, pack.n_runs, pack.stride
     cfg = runs[0].config
     first = int(runs[0].iteration)
     n_iter = int(cfg.maxiter) - first
-    # (run.embed: the run's variables are entries of a longer parameter vector -- the row is that vector, `columns` says where
-    # the variables are; the gradient is taken by exactly those)
-    where = [run.embed[1] if run.embed is not None else np.arange(run.x.size) for run in runs]
-    lengths = np.array([run.embed[0].size if run.embed is not None else run.x.size for run in runs])
-    sizes_host = np.array([run.x.size for run in runs], dtype=np.int32)
-    width, n_runs, stride = int(lengths.max()), len(runs), int(sizes_host.max())
-    x_host = np.zeros((n_runs, width))
-    columns_host = np.zeros((n_runs, stride), dtype=np.int32)
-    for i, run in enumerate(runs):
-        if run.embed is not None:
-            x_host[i, : lengths[i]] = run.embed[0]
-        x_host[i, where[i]] = run.x
-        columns_host[i, : sizes_host[i]] = where[i]
     circuits = [circuit for circuit, _ in jobs]
-    wrt = [[int(p) for p in positions] for positions in where]
+    wrt = [[int(p) for p in positions] for positions in pack.where]  # (the gradient is taken by exactly the searched entries)
     cost = []
     for circuit, positions in zip(circuits, wrt):
         terms = circuit.gradient_terms()
@@ -347,22 +416,10 @@ def minimize_adam_on_device(evaluator, jobs, look_every: int = 8, state: dict | 
 
     dev = evaluator.statevector_device
     lib, handle = dev._lib, dev._handle
-    if dev.device_index is None:
-        # (a library that works in host memory -- the NumPy emulation of the two contracts that the host tests drive this
-        # function with: the same tensors, pointers and calls, no stream)
-        device, stream, on_stream = torch.device("cpu"), None, contextlib.nullcontext()
-    else:
-        from queasars_amd.distributed import _chain_state
-
-        device = torch.device("cuda", dev.device_index)
-        stream = _chain_state(evaluator, device)["stream"]  # (the stream the evaluator's handle launches on)
-        caller = torch.cuda.current_stream(device)
-        stream.wait_stream(caller)
-        on_stream = torch.cuda.stream(stream)
-    with on_stream:
-        x = torch.from_numpy(x_host.copy()).to(device)
-        sizes = torch.from_numpy(sizes_host).to(device)
-        columns = torch.from_numpy(columns_host).to(device)
+    with _on_search_stream(evaluator) as device:
+        x = torch.from_numpy(pack.x_host).to(device)
+        sizes = torch.from_numpy(pack.sizes).to(device)
+        columns = torch.from_numpy(pack.columns_host).to(device)
         m = torch.zeros((n_runs, stride), dtype=torch.float64, device=device)
         v = torch.zeros((n_runs, stride), dtype=torch.float64, device=device)
         gradient = torch.zeros((n_runs, stride), dtype=torch.float64, device=device)
@@ -375,7 +432,7 @@ def minimize_adam_on_device(evaluator, jobs, look_every: int = 8, state: dict | 
             if state is not None:
                 state.update(x=x, m=m, v=v, gradient=gradient, active=active, iterations=iterations, plan=plan)
             args = _lib.QsvAdamStepArgs(
-                n_runs=n_runs, width=width, columns_stride=stride, grad_width=stride, x=x.data_ptr(), sizes=sizes.data_ptr(),
+                n_runs=n_runs, width=pack.width, columns_stride=stride, grad_width=stride, x=x.data_ptr(), sizes=sizes.data_ptr(),
                 columns=columns.data_ptr(), m=m.data_ptr(), v=v.data_ptr(), gradient=gradient.data_ptr(), active=active.data_ptr(),
                 iterations=iterations.data_ptr(), lr=cfg.lr, beta_1=cfg.beta_1, beta_2=cfg.beta_2,
                 one_minus_beta_1=1 - cfg.beta_1, one_minus_beta_2=1 - cfg.beta_2, eps=cfg.eps, tol=cfg.tol, maxiter=int(cfg.maxiter))
@@ -390,11 +447,9 @@ def minimize_adam_on_device(evaluator, jobs, look_every: int = 8, state: dict | 
             done_iterations = iterations.cpu().numpy()
         finally:
             plan.close()
-    if stream is not None:
-        caller.wait_stream(stream)
+    pack.write_back(x_final)
     for i, run in enumerate(runs):
-        size = int(sizes_host[i])
-        run.x = x_final[i, where[i]].copy()
+        size = int(pack.sizes[i])
         run.m = m_final[i, :size].copy()
         run.v = v_final[i, :size].copy()
         run.nfev += (int(done_iterations[i]) - first) * cost[i]
@@ -419,33 +474,17 @@ def _takes_mask(evaluator) -> bool:
 def _minimize_with_torch_operations(evaluator, jobs, look_every: int = 8) -> None:
     import torch
 
-    from queasars_amd.distributed import _chain_state
-
-    runs = [run for _, run in jobs]
-    cfg = runs[0].config
+    pack = _PackedRuns([run for _, run in jobs])
+    cfg = pack.runs[0].config
     eps, lr, n_iter = cfg.perturbation, cfg.learning_rate, int(cfg.maxiter)
-    where = [run.embed[1] if run.embed is not None else np.arange(run.x.size) for run in runs]
-    lengths = np.array([run.embed[0].size if run.embed is not None else run.x.size for run in runs])
-    width, n_runs = int(lengths.max()), len(runs)
-    x_host = np.zeros((n_runs, width))
-    signs_host = np.zeros((n_iter, n_runs, width), dtype=np.int8)
-    for i, run in enumerate(runs):
-        if run.embed is not None:
-            x_host[i, : lengths[i]] = run.embed[0]
-        x_host[i, where[i]] = run.x
-        # (what propose() would draw call by call: one draw of the lot gives the same numbers)
-        signs_host[:, i, where[i]] = 1 - 2 * run.rng.binomial(1, 0.5, size=(n_iter, run.x.size))
+    n_runs, width = pack.n_runs, pack.width
+    signs_host = pack.draw_signs(n_iter)
     circuits = [circuit for circuit, _ in jobs for _ in (0, 1)]
     checker = cfg.termination_checker
     window = checker.allowed_consecutive_violations + 1 if checker is not None else 0
 
-    dev = evaluator.statevector_device
-    device = torch.device("cuda", dev.device_index)
-    stream = _chain_state(evaluator, device)["stream"]  # (the stream the evaluator's handle launches on)
-    caller = torch.cuda.current_stream(device)
-    stream.wait_stream(caller)
-    with torch.cuda.stream(stream):
-        x = torch.from_numpy(x_host).to(device)
+    with _on_search_stream(evaluator) as device:
+        x = torch.from_numpy(pack.x_host).to(device)
         signs = torch.from_numpy(signs_host).to(device).to(torch.float64)
         points = torch.empty((2 * n_runs, width), dtype=torch.float64, device=device)
         values = torch.empty(2 * n_runs, dtype=torch.float64, device=device)
@@ -495,9 +534,4 @@ def _minimize_with_torch_operations(evaluator, jobs, look_every: int = 8) -> Non
                 break
         x_final = x.cpu().numpy()
         done_iterations = iterations.cpu().numpy()
-    caller.wait_stream(stream)
-    for i, run in enumerate(runs):
-        run.x = x_final[i, where[i]].copy()
-        run.iteration = int(done_iterations[i])
-        run.nfev = 2 * int(done_iterations[i])
-        run.done = True
+    _spsa_write_back(pack, x_final, done_iterations)

@@ -33,6 +33,8 @@ from typing import Any, Callable, Optional, Sequence, Union
 
 import numpy as np
 
+from queasars_amd.evqe import device_search
+from queasars_amd.evqe.device_search import _full_point, _PackedRuns, _positions  # (the run layout is stated there)
 from queasars_amd.evqe.genome import EVQEIndividual, EVQEPopulation, new_random_seed
 
 
@@ -293,7 +295,7 @@ def _minimize_adam(evaluator, jobs: list) -> None:
     _require_gradients(evaluator, jobs[0][1].config)
     wrt, cost = {}, {}
     for circuit, run in jobs:
-        positions = list(range(run.x.size)) if run.embed is None else [int(p) for p in run.embed[1]]
+        positions = _positions(run).tolist()
         terms = circuit.gradient_terms()
         wrt[id(run)] = positions
         cost[id(run)] = sum(max(0, terms[p]) for p in positions)
@@ -309,16 +311,6 @@ def _minimize_adam(evaluator, jobs: list) -> None:
         for (_, run), gradient in zip(active, gradients):
             run.accept_gradient(gradient, cost[id(run)])
         active = [job for job in active if not job[1].done]
-
-
-def _full_point(run, point: np.ndarray) -> np.ndarray:
-    """The parameter vector the evaluator gets for a run's point (run.embed)."""
-    if run.embed is None:
-        return point
-    base, positions = run.embed
-    full = base.copy()
-    full[positions] = point
-    return full
 
 
 def _minimize_spsa_vectorised(evaluator, jobs: list) -> None:
@@ -349,13 +341,10 @@ def _minimize_spsa_vectorised(evaluator, jobs: list) -> None:
     active = np.array([i for i, run in enumerate(runs) if not run.done], dtype=np.int64)
     embedded = any(run.embed is not None for run in runs)
     if embedded:
-        # (every run's variables are entries of a longer vector: the rows the evaluator gets are the base vectors with the
-        # points scattered into them)
-        full_sizes = np.array([run.embed[0].size if run.embed is not None else run.x.size for run in runs])
-        full = np.zeros((n_runs, int(full_sizes.max())))
-        for i, run in enumerate(runs):
-            if run.embed is not None:
-                full[i, : full_sizes[i]] = run.embed[0]
+        # (every run's variables are entries of a longer vector: the rows the evaluator gets are the runs' full vectors -- the
+        # shared layout of device_search.py -- with the points scattered over the variables' own entries)
+        packed = _PackedRuns(runs)
+        full, full_sizes = packed.x_host, packed.lengths
     circuits_of = {}
     while active.size:
         key = active.tobytes()
@@ -365,7 +354,7 @@ def _minimize_spsa_vectorised(evaluator, jobs: list) -> None:
             if embedded:
                 rows, cols, src = [], [], []
                 for a, i in enumerate(active):
-                    positions = runs[i].embed[1] if runs[i].embed is not None else np.arange(sizes[i])
+                    positions = packed.where[i]
                     rows.append(np.full(positions.size, 2 * a))
                     cols.append(positions)
                     src.append(np.arange(positions.size))
@@ -434,27 +423,48 @@ def _device_search_asked_for(evaluator, n_runs: int, flag: Optional[bool], opt_i
     return bool(flag) or env == "1"
 
 
+# What can keep its state on the device (evqe/device_search.py), by run class: the optimiser's class; is ``None`` of the
+# configuration's ``device_resident_search`` the host driver whatever the evaluator (opt-in: _device_search_asked_for)?; and the
+# names in device_search of the rule before the runs exist, the rule over the runs, and the driver -- looked up when they are
+# called (tests and measurements replace them).
+_DEVICE_SEARCHES = {
+    _SPSARun: (SPSA, False, "possible", "supported", "minimize_spsa_on_device"),
+    _NFTRun: (NFT, True, "possible_nft", "supported_nft", "minimize_nft_on_device"),
+    _AdamRun: (Adam, True, "possible_adam", "supported_adam", "minimize_adam_on_device"),
+}
+
+
 def _device_search_wanted(evaluator, n_runs: int, flag: Optional[bool], optimizer) -> bool:
-    """Will a search of ``n_runs`` fresh runs of ``optimizer`` keep its state on the device (_minimize_batched's rule)?"""
-    if isinstance(optimizer, NFT):
-        if n_runs < 2 or optimizer.maxfev <= 0 or not _device_search_asked_for(evaluator, n_runs, flag, opt_in=True):
-            return False
-        return hasattr(evaluator, "evaluate_device_to_device") and bool(evaluator.device_resident_search_possible())
-    if isinstance(optimizer, Adam):  # (opt-in, as NFT: device_search.minimize_adam_on_device)
-        if n_runs < 2 or optimizer.maxiter <= 0 or not _device_search_asked_for(evaluator, n_runs, flag, opt_in=True):
-            return False
-        return callable(getattr(evaluator, "gradient_plan", None)) and bool(evaluator.device_resident_search_possible())
-    if os.environ.get("QSV_SCALAR_SPSA") or not isinstance(optimizer, SPSA) or n_runs < 2:
-        return False
-    if not _device_search_asked_for(evaluator, n_runs, flag):
-        return False
-    if not hasattr(evaluator, "evaluate_device_to_device") or not evaluator.device_resident_search_possible():
-        return False
-    checker = optimizer.termination_checker
-    return optimizer.maxiter > 0 and (checker is None or type(checker) is SPSATerminationChecker)
+    """Will a search of ``n_runs`` fresh runs of ``optimizer`` keep its state on the device?  What ``_minimize_batched`` will find,
+    said before the runs exist: asked for, and possible by the device search's own rule."""
+    for optimizer_class, opt_in, possible, _, _ in _DEVICE_SEARCHES.values():
+        if isinstance(optimizer, optimizer_class):
+            if optimizer_class is SPSA and os.environ.get("QSV_SCALAR_SPSA"):
+                return False
+            return (_device_search_asked_for(evaluator, n_runs, flag, opt_in)
+                    and getattr(device_search, possible)(evaluator, optimizer, n_runs))
+    return False
 
 
 _DEVICE_SEARCH_MIN_RUNS = 16  # (config 4 on one MI355X: searches of 25 - 64 runs 1.5 x faster end to end, of 10 runs no faster)
+
+
+def _searched_on_device(evaluator, waiting: list, on_device: Optional[bool]) -> bool:
+    """Hand the unfinished jobs to their optimiser's device search, if there are several, all of one run class and one
+    configuration, it is asked for and the search says it can take them; says whether that happened."""
+    if len(waiting) < 2:
+        return False
+    first = waiting[0][1]
+    entry = _DEVICE_SEARCHES.get(type(first))
+    if entry is None or not all(type(job[1]) is type(first) and job[1].config is first.config for job in waiting):
+        return False
+    _, opt_in, _, supported, minimize = entry
+    if not _device_search_asked_for(evaluator, len(waiting), on_device, opt_in):
+        return False
+    if not getattr(device_search, supported)(evaluator, waiting):
+        return False
+    getattr(device_search, minimize)(evaluator, waiting)
+    return True
 
 
 def _minimize_batched(evaluator, jobs: list, on_device: Optional[bool] = False) -> None:
@@ -463,36 +473,20 @@ def _minimize_batched(evaluator, jobs: list, on_device: Optional[bool] = False) 
     read points from and leave values in device memory keep their whole state there (evqe/device_search.py); fresh NFT runs of
     one configuration likewise, but only where asked for (``True`` or ``QSV_DEVICE_SEARCH=1``; ``None`` is the loop below), and
     so do fresh Adam runs of one configuration with an evaluator that has gradient plans (``None`` is :func:`_minimize_adam`)."""
-    spsa = [] if os.environ.get("QSV_SCALAR_SPSA") else [job for job in jobs if isinstance(job[1], _SPSARun) and not job[1].done]
-    if len(spsa) > 1 and len(spsa) == sum(1 for job in jobs if not job[1].done) and all(job[1].config is spsa[0][1].config for job in spsa):
-        if _device_search_asked_for(evaluator, len(spsa), on_device):
-            from queasars_amd.evqe import device_search
-
-            if device_search.supported(evaluator, spsa):
-                device_search.minimize_spsa_on_device(evaluator, spsa)
-                return
-        _minimize_spsa_vectorised(evaluator, spsa)
+    active = [job for job in jobs if not job[1].done]
+    spsa = [] if os.environ.get("QSV_SCALAR_SPSA") else [job for job in active if isinstance(job[1], _SPSARun)]
+    if len(spsa) > 1 and len(spsa) == len(active) and all(job[1].config is spsa[0][1].config for job in spsa):
+        if not _searched_on_device(evaluator, spsa, on_device):
+            _minimize_spsa_vectorised(evaluator, spsa)
         return
     if jobs and all(isinstance(job[1], _AdamRun) for job in jobs):
-        waiting = [job for job in jobs if not job[1].done]
-        if len(waiting) > 1 and _device_search_asked_for(evaluator, len(waiting), on_device, opt_in=True):
-            from queasars_amd.evqe import device_search
-
-            if device_search.supported_adam(evaluator, waiting):
-                device_search.minimize_adam_on_device(evaluator, waiting)
-                return
-        _minimize_adam(evaluator, jobs)
+        if not _searched_on_device(evaluator, active, on_device):
+            _minimize_adam(evaluator, jobs)
         return
     if any(isinstance(job[1], _AdamRun) for job in jobs):
         raise ValueError("Adam runs cannot share a search with runs of another optimiser")
-    active = [job for job in jobs if not job[1].done]
-    if (len(active) > 1 and all(isinstance(job[1], _NFTRun) and job[1].config is active[0][1].config for job in active)
-            and _device_search_asked_for(evaluator, len(active), on_device, opt_in=True)):
-        from queasars_amd.evqe import device_search
-
-        if device_search.supported_nft(evaluator, active):
-            device_search.minimize_nft_on_device(evaluator, active)
-            return
+    if active and isinstance(active[0][1], _NFTRun) and _searched_on_device(evaluator, active, on_device):
+        return
     while active:
         circuits, params, counts = [], [], []
         for circuit, run in active:

@@ -224,3 +224,128 @@ def test_the_binding_matches_the_header():
     lib = _lib.load()
     assert hasattr(lib, "qsv_nft_step")
     assert lib.qsv_nft_step(None, None) == _lib.QSV_E_ARG  # (no handle)
+
+
+# ---- the driver, on a library in host memory --------------------------------------------------------------------------------
+
+
+def _array(pointer, kind, shape):
+    return np.ctypeslib.as_array(C.cast(C.c_void_p(pointer), C.POINTER(kind)), shape=shape)
+
+
+class _HostLibrary:
+    """``qsv_nft_step`` on host memory, row by row through ``_NFTRun.propose`` / ``accept`` themselves: a scratch run is given
+    the row's variables and the state the call names, and what it leaves goes back into the arrays."""
+
+    def __init__(self):
+        self.steps = 0
+
+    def qsv_nft_step(self, handle, reference):
+        a = reference._obj
+        self.steps += 1
+        if (a.n_runs < 0 or a.width < 0 or a.columns_stride < 1 or not all((a.x, a.sizes, a.columns, a.recycled))
+                or (a.accept and not a.values) or (a.propose and not a.points)):
+            return _lib.QSV_E_ARG
+        x = _array(a.x, C.c_double, (a.n_runs, a.width))
+        sizes = _array(a.sizes, C.c_int32, (a.n_runs,))
+        columns = _array(a.columns, C.c_int32, (a.n_runs, a.columns_stride))
+        recycled = _array(a.recycled, C.c_double, (a.n_runs,))
+        never_resets = S.NFT(maxfev=1 << 30, reset_interval=0)  # (the call says which form an iteration has, not the run)
+        for r in range(a.n_runs):
+            where = columns[r, : sizes[r]].astype(np.int64)
+            if a.accept:
+                k = 3 if a.accept_with_base else 2
+                run = never_resets.new_run(x[r, where], seed=None)
+                run.iteration, run._needs_base, run._recycled = int(a.accept_iteration), bool(a.accept_with_base), float(recycled[r])
+                run.accept(*_array(a.values, C.c_double, (k * a.n_runs,))[k * r : k * r + k].tolist())
+                x[r, where] = run.x
+                recycled[r] = run._recycled
+            if a.propose:
+                k = 3 if a.propose_with_base else 2
+                run = never_resets.new_run(x[r, where], seed=None)
+                run.iteration, run._recycled = int(a.propose_iteration), None if a.propose_with_base else float(recycled[r])
+                run.embed = (x[r].copy(), where)
+                proposed = run.propose()
+                assert len(proposed) == k
+                _array(a.points, C.c_double, (k * a.n_runs, a.width))[k * r : k * r + k] = [S._full_point(run, p) for p in proposed]
+        return _lib.QSV_OK
+
+
+class _HostDevice:
+    device_index = None  # (host memory: the searches make their tensors there)
+    _handle = None
+
+    def __init__(self):
+        self._lib = _HostLibrary()
+
+    def _check(self, rc):
+        assert rc == _lib.QSV_OK
+
+
+class _Circuit:
+    def __init__(self, n_parameters):
+        self.num_parameters = n_parameters
+
+
+def _smooth(point) -> float:
+    p = np.asarray(point, dtype=np.float64)
+    return float(np.sum(np.cos(p - 0.3 * np.arange(1, p.size + 1))) + 0.1 * np.sum(np.sin(p) * np.sin(np.roll(p, 1) + 0.2)))
+
+
+class _BothWays:
+    """The same smooth function of a circuit's parameter vector from lists (``evaluate_circuits``: the generic loop) and from
+    rows of a matrix in host memory into a vector there (``evaluate_device_to_device``: the device driver)."""
+
+    def __init__(self):
+        self.statevector_device = _HostDevice()
+        self.lists = []
+
+    def device_resident_search_possible(self):
+        return True
+
+    def evaluate_circuits(self, circuits, parameter_values):
+        return [_smooth(p) for p in parameter_values]
+
+    def evaluate_device_to_device(self, circuits, matrix, out):
+        if not any(circuits is seen for seen in self.lists):
+            self.lists.append(circuits)
+        rows, values = matrix.numpy(), out.numpy()
+        assert rows.shape[0] == len(circuits) <= values.size
+        for i, circuit in enumerate(circuits):
+            values[i] = _smooth(rows[i, : circuit.num_parameters])
+
+
+def _embedded_nft_jobs(cfg):
+    """Five jobs, two of them on a layer inside a longer vector."""
+    rng = np.random.default_rng(9)
+    jobs = []
+    for total, positions in ((7, [1, 2, 5]), (1, None), (4, [0, 3]), (2, None), (3, None)):
+        if positions is None:
+            jobs.append((_Circuit(total), cfg.new_run(rng.normal(size=total), seed=None)))
+        else:
+            base = rng.normal(size=total)
+            run = cfg.new_run(base[positions], seed=None)
+            run.embed = (base, np.array(positions, dtype=np.int64))
+            jobs.append((_Circuit(total), run))
+    return jobs
+
+
+def test_the_driver_leaves_what_the_generic_loop_leaves():
+    """``minimize_nft_on_device`` with its tensors in host memory and ``qsv_nft_step`` played by ``_NFTRun`` itself: every run is
+    left, bit for bit, as ``_minimize_batched``'s loop leaves it, and the evaluator has seen two list objects throughout."""
+    cfg = S.NFT(maxfev=23, reset_interval=4)
+    host, device = _embedded_nft_jobs(cfg), _embedded_nft_jobs(cfg)
+    S._minimize_batched(_BothWays(), host, on_device=False)
+    ev = _BothWays()
+    assert device_search.supported_nft(ev, device)
+    device_search.minimize_nft_on_device(ev, device)
+    flags, nfev = device_search.nft_schedule(cfg)
+    assert ev.statevector_device._lib.steps == len(flags) + 1
+    assert len(ev.lists) == 2 and sorted(len(seen) for seen in ev.lists) == [10, 15]
+    for (_, a), (_, b) in zip(host, device):
+        assert a.done is True and b.done is True
+        assert np.array_equal(a.x, b.x) and a.x.dtype == b.x.dtype
+        assert a.iteration == b.iteration == len(flags) and a.nfev == b.nfev == nfev
+        assert a._recycled == b._recycled and type(b._recycled) is float
+        assert a._needs_base == b._needs_base
+    assert any(not np.array_equal(run.x, fresh.x) for (_, run), (_, fresh) in zip(device, _embedded_nft_jobs(cfg)))

@@ -149,3 +149,141 @@ def test_more_shots_than_the_device_sorts_stay_on_the_host():
     assert sampler.device_resident_search_possible() is False
     with pytest.raises(ValueError, match="shots"):
         sampler.evaluate_device_to_device([], None, None)
+
+
+# ---- the run layout -------------------------------------------------------------------------------------------------------
+
+
+def _mixed_runs(cfg):
+    """Five runs: two on a layer inside a longer vector -- base vectors of different lengths, positions that do not follow each
+    other --, three on rows of their own, of sizes 1, 2 and 3."""
+    import numpy as np
+
+    rng = np.random.default_rng(11)
+    runs = []
+    for total, positions in ((9, [1, 4, 7]), (4, [0, 3])):
+        base = rng.normal(size=total)
+        run = cfg.new_run(rng.normal(size=len(positions)), seed=total)
+        run.embed = (base, np.array(positions, dtype=np.int64))
+        runs.append(run)
+    runs[2:2] = [cfg.new_run(rng.normal(size=1), seed=1)]  # (embedded and own rows interleaved)
+    runs += [cfg.new_run(rng.normal(size=size), seed=size) for size in (2, 3)]
+    return runs
+
+
+def test_the_run_layout_and_its_inverse():
+    """One statement of the layout (``device_search._PackedRuns``): every row is ``_full_point(run, run.x)`` behind zeros,
+    ``columns_host`` says where the run's variables are, and the way back hands every run exactly its own entries."""
+    import numpy as np
+
+    runs = _mixed_runs(S.SPSA(maxiter=3))
+    assert S._full_point is device_search._full_point
+    pack = device_search._PackedRuns(runs)
+    assert pack.n_runs == 5 and pack.width == 9 and pack.stride == 3
+    assert pack.x_host.shape == (5, 9) and pack.x_host.dtype == np.float64
+    assert pack.columns_host.shape == (5, 3) and pack.columns_host.dtype == np.int32 and pack.sizes.dtype == np.int32
+    assert pack.lengths.tolist() == [9, 4, 1, 2, 3] and pack.sizes.tolist() == [3, 2, 1, 2, 3]
+    for i, run in enumerate(runs):
+        row = S._full_point(run, run.x)
+        assert row.size == pack.lengths[i]
+        assert np.array_equal(pack.x_host[i], np.concatenate([row, np.zeros(9 - row.size)]))
+        want = run.embed[1] if run.embed is not None else np.arange(run.x.size)
+        assert np.array_equal(pack.where[i], want)
+        assert np.array_equal(pack.columns_host[i, : run.x.size], want)
+        assert not pack.columns_host[i, run.x.size :].any()
+    bases = [None if run.embed is None else run.embed[0].copy() for run in runs]
+    perturbed = pack.x_host + np.arange(1, 46, dtype=np.float64).reshape(5, 9)
+    kept = perturbed.copy()
+    pack.write_back(perturbed)
+    for i, run in enumerate(runs):
+        assert np.array_equal(run.x, kept[i, pack.where[i]]) and run.x.dtype == np.float64
+        assert not np.shares_memory(run.x, perturbed)
+        if run.embed is not None:
+            assert np.array_equal(run.embed[0], bases[i])  # (the base vector is not the run's to move)
+    assert np.array_equal(perturbed, kept)
+
+
+def test_the_signs_are_the_draws_of_propose():
+    """``draw_signs``: per run the numbers ``propose()`` would draw call by call, at the run's columns, zero elsewhere."""
+    import numpy as np
+
+    cfg = S.SPSA(maxiter=4)
+    runs, twins = _mixed_runs(cfg), _mixed_runs(cfg)
+    pack = device_search._PackedRuns(runs)
+    signs = pack.draw_signs(4)
+    assert signs.shape == (4, 5, 9) and signs.dtype == np.int8
+    for i, twin in enumerate(twins):
+        for k in range(4):
+            twin.propose()
+            assert np.array_equal(signs[k, i, pack.where[i]], twin._delta)
+        others = np.setdiff1d(np.arange(9), pack.where[i])
+        assert not signs[:, i, others].any()
+
+
+# ---- one rule -------------------------------------------------------------------------------------------------------------
+
+
+class _Capable:
+    """An evaluator as both halves of the rule see it: with everything, or with one thing missing."""
+
+    def __init__(self, possible=True, values=True, plans=True):
+        self._possible = possible
+        if values:
+            self.evaluate_device_to_device = lambda circuits, matrix, out: pytest.fail("the rule evaluates nothing")
+        if plans:
+            self.gradient_plan = lambda *a, **k: pytest.fail("the rule plans nothing")
+
+    def device_resident_search_possible(self):
+        return self._possible
+
+
+class _AnotherRule(S.SPSATerminationChecker):
+    """A termination rule the device does not implement."""
+
+    def fresh(self):
+        return _AnotherRule(self.minimum_relative_change, self.allowed_consecutive_violations, self.maxfev)
+
+
+def _rule_cases():
+    evaluators = {"capable": dict(), "not possible": dict(possible=False), "no evaluate_device_to_device": dict(values=False),
+                  "no gradient_plan": dict(plans=False)}
+    optimisers = {
+        "SPSA maxiter=0": lambda: S.SPSA(maxiter=0), "SPSA maxiter=5": lambda: S.SPSA(maxiter=5),
+        "SPSA its own checker": lambda: S.SPSA(maxiter=5, termination_checker=S.SPSATerminationChecker(1e-3, 2)),
+        "SPSA another checker": lambda: S.SPSA(maxiter=5, termination_checker=_AnotherRule(1e-3, 2)),
+        "NFT maxfev=0": lambda: S.NFT(maxfev=0), "NFT maxfev=10": lambda: S.NFT(maxfev=10),
+        "Adam maxiter=0": lambda: S.Adam(maxiter=0), "Adam maxiter=5": lambda: S.Adam(maxiter=5),
+    }
+    return [pytest.param(kwargs, make, id=f"{ev}-{opt}") for ev, kwargs in evaluators.items() for opt, make in optimisers.items()]
+
+
+def _supported_for(optimiser):
+    return {S.SPSA: device_search.supported, S.NFT: device_search.supported_nft, S.Adam: device_search.supported_adam}[type(optimiser)]
+
+
+def _fresh_jobs(optimiser, n_runs):
+    return [(object(), optimiser.new_run([0.1 * (k + 1)] * (1 + k % 3), seed=k)) for k in range(n_runs)]
+
+
+@pytest.mark.parametrize("kwargs,make", _rule_cases())
+def test_the_prediction_is_the_rule(kwargs, make):
+    """What ``_device_search_wanted`` says before the runs exist is what ``supported*`` says of fresh runs, case by case."""
+    optimiser = make()
+    for n_runs in (1, 2, S._DEVICE_SEARCH_MIN_RUNS):
+        wanted = S._device_search_wanted(_Capable(**kwargs), n_runs, True, optimiser)
+        assert wanted is _supported_for(optimiser)(_Capable(**kwargs), _fresh_jobs(optimiser, n_runs))
+        can = (n_runs >= 2 and kwargs.get("possible", True) and getattr(optimiser, "maxiter", None) != 0
+               and getattr(optimiser, "maxfev", None) != 0 and not isinstance(getattr(optimiser, "termination_checker", None), _AnotherRule)
+               and kwargs.get("plans" if isinstance(optimiser, S.Adam) else "values", True))
+        assert wanted is can
+
+
+def test_the_sign_ceiling_is_the_one_thing_the_prediction_cannot_know(monkeypatch):
+    spsa = S.SPSA(maxiter=5)
+    jobs = _fresh_jobs(spsa, 4)  # (rows of up to 3 entries: 5 iterations x 4 runs x 3 doubles = 480 bytes of signs)
+    assert S._device_search_wanted(_Capable(), 4, True, spsa) is True
+    monkeypatch.setattr(device_search, "_MAX_SIGN_BYTES", 480)
+    assert device_search.supported(_Capable(), jobs) is True
+    monkeypatch.setattr(device_search, "_MAX_SIGN_BYTES", 479)
+    assert device_search.supported(_Capable(), jobs) is False
+    assert S._device_search_wanted(_Capable(), 4, True, spsa) is True
