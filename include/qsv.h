@@ -464,6 +464,23 @@ int qsv_cvar_device(qsv_t* h, int n_evals, const int* circuit_ids, int width, co
                     int shots /* 0: the exact distribution */, uint64_t seed, double alpha,
                     const uint8_t* device_active /* may be NULL */, int active_stride, double* device_out);
 
+/*
+ * Exact readout: the k most probable basis states of every evaluation, selected on the device.  For evaluation i,
+ * out_states[i * k + j] is the j-th entry of its 2^n exact probabilities |amplitude|^2 under the total order PROBABILITY
+ * DESCENDING, BASIS-STATE INDEX ASCENDING (states of equal probability -- the zeros of a shallow circuit -- come in index order;
+ * probabilities are compared as doubles), out_probs[i * k + j] that probability, and out_values[i * k + j] (may be NULL) the
+ * diagonal operator's value on the state, sum_k c_k (-1)^popcount(state & z_k), as qsv_sample_batch gathers it.  The order is
+ * total, so the result is unique and the same bits on every call.  Replaces the last step of the reference's
+ * _solve_by_evolution -- measuring the best individual once more for result.eigenstate
+ * (evolving_ansatz_minimum_eigensolver.py:442-454) and taking its most probable states on the host -- without sampling noise
+ * and without moving 2^n doubles (qsv_probabilities) to sort them there.  Circuits that have a split form are read from their two
+ * side tables, the others from the probabilities their last gate pass writes, group by group as qsv_exact_cvar_batch; no sort of
+ * 2^n pairs takes place.  1 <= k <= min(1024, 2^n), else QSV_E_ARG; out_values without a diagonal operator on the handle
+ * QSV_E_STATE; more than 28 qubits, and circuits on kept states, QSV_E_UNSUPPORTED.  No operator is needed when out_values is NULL.
+ */
+int qsv_top_states(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
+                   int k, uint64_t* out_states, double* out_probs, double* out_values /* may be NULL */);
+
 /* ---- sampled values of a host-side scoring function ------------------------------------------------ */
 
 /*

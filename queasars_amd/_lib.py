@@ -251,6 +251,7 @@ SIGNATURES = {
     "qsv_sample_batch": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, C.c_uint64, _P, _P]),
     "qsv_sample_cvar_batch": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, C.c_uint64, C.c_double, _P]),
     "qsv_exact_cvar_batch": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_double, _P]),
+    "qsv_top_states": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P]),
     "qsv_cvar_device": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_uint64, C.c_double, _P, C.c_int, _P]),
     "qsv_value_cache_create": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "qsv_value_cache_destroy": (C.c_int, [_P, C.c_int]),

@@ -11,6 +11,7 @@ from queasars_amd.circuit_evaluation.circuit_evaluation import (  # noqa: F401
     OperatorSamplerCircuitEvaluator,
     StatevectorDevice,
     measure_quasi_distributions,
+    most_probable_states,
 )
 from queasars_amd.circuit_evaluation.configured_primitives import (  # noqa: F401
     ConfiguredEstimatorV2,

@@ -942,6 +942,37 @@ class StatevectorDevice:
                                                    float(alpha), _lib.as_ptr(out)))
         return out.tolist()
 
+    #: most states per evaluation :meth:`top_states` selects (csrc/kernels.hpp kTopMaxStates)
+    MAX_TOP_STATES = 1024
+
+    def top_states(
+        self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]], k: int, with_values: bool = False
+    ) -> tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        """The ``k`` most probable basis states of every (circuit, parameter vector) pair under the EXACT output
+        distribution, selected on the device (``qsv_top_states``): ``states[i, j]`` (uint64) in the order probability
+        descending, basis-state index ascending, ``probabilities[i, j]``, and with ``with_values`` (diagonal operator set on
+        the device) ``values[i, j]``, the operator's value on each state.  ``1 <= k <= min(MAX_TOP_STATES, 2**n_qubits)``.
+        Deterministic; only ``k`` entries per pair cross PCIe, not the ``2**n_qubits`` of :meth:`probabilities`."""
+        n = len(circuits)
+        if len(parameter_values) != n:
+            raise ValueError("circuits and parameter_values must have the same length")
+        k = int(k)
+        if not 1 <= k <= min(self.MAX_TOP_STATES, 1 << self._n_qubits):
+            raise ValueError(f"k must be between 1 and min({self.MAX_TOP_STATES}, 2**n_qubits), got {k}")
+        states = np.empty((n, k), dtype=np.uint64)
+        probabilities = np.empty((n, k), dtype=np.float64)
+        values = np.empty((n, k), dtype=np.float64) if with_values else None
+        if n == 0:
+            return states, probabilities, values
+        ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
+        self._check(
+            self._lib.qsv_top_states(
+                self._handle, n, _lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat), k,
+                _lib.as_ptr(states), _lib.as_ptr(probabilities), _lib.as_ptr(values) if with_values else None,
+            )
+        )
+        return states, probabilities, values
+
     def cvar_of_device_parameters(
         self,
         circuits: Sequence[CircuitIR],
@@ -1225,6 +1256,19 @@ def _composed_list(evaluator, circuits: list) -> list:
     return kept[1]
 
 
+def _evaluator_top_states(evaluator, circuits: list, parameter_values: list, k: int):
+    """:meth:`StatevectorDevice.top_states` for an operator evaluator's circuits: behind its initial state, and with the
+    operator's values (else ``None``) when its operator is diagonal -- set on the shared device inside the operator lock, as
+    every evaluation does."""
+    circuits = [evaluator._composed.get(c) for c in circuits]
+    device = evaluator._device
+    with device.operator_lock:
+        with_values = evaluator._operator.is_diagonal()
+        if with_values and device._operator is not evaluator._operator:
+            device.set_operator(evaluator._operator)
+        return device.top_states(circuits, parameter_values, k, with_values=with_values)
+
+
 def _is_device_matrix(tensor, n_rows: int, device, width: Optional[int] = None) -> bool:
     """Is ``tensor`` a contiguous 2-D float64 tensor of ``n_rows`` rows (of ``width`` entries, where given) on the torch
     device ``device``?  What the gradient methods ask of their matrices; each says what it wanted in its own words."""
@@ -1373,6 +1417,7 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         return self._composed.get(circuit)
 
     _composed_list = _composed_list
+    top_states = _evaluator_top_states
 
     def evaluate_circuits(self, circuits: list[CircuitIR], parameter_values: list[list[float]]) -> list[float]:
         """``parameter_values`` may also be a 2-D float64 tensor in THIS device's memory (anything with ``is_cuda`` /
@@ -1598,6 +1643,18 @@ def measure_quasi_distributions(
     return out
 
 
+def most_probable_states(
+    device: StatevectorDevice, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]], k: int
+) -> list[dict[str, float]]:
+    """``{bitstring: probability}`` of the ``k`` most probable basis states per circuit under the exact distribution
+    (:meth:`StatevectorDevice.top_states`), most probable first -- the part of ``result.eigenstate`` the reference's users
+    decode (evolving_ansatz_minimum_eigensolver.py:442-454).  Bitstrings are ``format(state, f"0{n}b")``: qubit 0 last, as
+    the reference's measured distributions spell them."""
+    states, probabilities, _ = device.top_states(circuits, parameter_values, k)
+    n = device.n_qubits
+    return [{format(int(s), f"0{n}b"): float(p) for s, p in zip(row, probs)} for row, probs in zip(states, probabilities)]
+
+
 def _cvar_of_samples(values: np.ndarray, alpha: float) -> float:
     """Expectation / CVaR_alpha of equally weighted samples: what `_get_expectation` computes on the measured
     distribution (reference: expectation_calculation.py:14-32), evaluated on the sorted sample values."""
@@ -1696,6 +1753,7 @@ class OperatorSamplerCircuitEvaluator(BaseCircuitEvaluator):
         return self._device
 
     _composed_list = _composed_list
+    top_states = _evaluator_top_states
 
     #: what ``device_resident_search=None`` of the solver's configuration means for this evaluator (evqe/solver.py): the host
     #: driver, as before the device search could take it -- ``True`` opts in

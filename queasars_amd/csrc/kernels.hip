@@ -4604,6 +4604,173 @@ hipError_t launch_cvar_exact(int dtype, const double* probs, uint64_t dim, unsig
     return hipGetLastError();
 }
 
+// ---- exact readout: the k most probable basis states (kernels.hpp: launch_top_states) ---------------------------------------
+// LDS of a workgroup: kTopMaxStates candidates -- sorted, best first, places past the k-th (or past what has been seen) hold
+// the "none" pair, which is behind every real pair -- and behind them a buffer of as many places that collects, through an LDS
+// counter, the pairs that beat the current k-th key.  Which thread appends first does not matter: under a total order the best
+// k of a set are unique, and a pair is dropped only when k better ones are known.
+constexpr uint32_t kTopSlots = 2 * kTopMaxStates, kTopBuffer = kTopSlots - kTopMaxStates;
+constexpr uint32_t kTopPerThread = 8;  // pairs a thread reads between two looks at the counter
+constexpr double kTopNoneP = -1.0;     // (probabilities are >= +0.0)
+constexpr uint32_t kTopNoneI = 0xffffffffu;
+
+__device__ __forceinline__ bool top_before(double pa, uint32_t ia, double pb, uint32_t ib) {
+    return pa > pb || (pa == pb && ia < ib);
+}
+
+// candidates + the first `count` places of the buffer -> the best k of them, sorted, in the candidates; the counter back to 0.
+// Every thread of the workgroup calls it; what was written to LDS before the call is seen, and the result is seen after it.
+__device__ void top_sort_keep(double* sp, uint32_t* si, uint32_t* counter, uint32_t count, uint32_t k) {
+    const uint32_t t = threadIdx.x;
+    for (uint32_t j = kTopMaxStates + count + t; j < kTopSlots; j += 256) {
+        sp[j] = kTopNoneP;
+        si[j] = kTopNoneI;
+    }
+    __syncthreads();
+    for (uint32_t size = 2; size <= kTopSlots; size <<= 1)
+        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+            for (uint32_t x = t; x < kTopSlots / 2; x += 256) {
+                const uint32_t lo = ((x & ~(stride - 1)) << 1) | (x & (stride - 1)), hi = lo + stride;
+                const double pa = sp[lo], pb = sp[hi];
+                const uint32_t ia = si[lo], ib = si[hi];
+                const bool forward = (lo & size) == 0;  // (the last merge: all forward, best first)
+                if (forward ? top_before(pb, ib, pa, ia) : top_before(pa, ia, pb, ib)) {
+                    sp[lo] = pb;
+                    si[lo] = ib;
+                    sp[hi] = pa;
+                    si[hi] = ia;
+                }
+            }
+            __syncthreads();
+        }
+    for (uint32_t j = k + t; j < kTopMaxStates; j += 256) {
+        sp[j] = kTopNoneP;
+        si[j] = kTopNoneI;
+    }
+    if (t == 0) *counter = 0;
+    __syncthreads();
+}
+
+// The best k of the pairs item(0 .. len - 1), sorted, into sp / si [0, k) (places past len hold the "none" pair).  item(pos, p, i)
+// gives pair `pos`; thread t reads pairs t, t + 256, ... of each tile of 256 kTopPerThread.
+template <typename Item>
+__device__ void top_select(const Item& item, uint32_t len, uint32_t k, double* sp, uint32_t* si, uint32_t* counter) {
+    const uint32_t t = threadIdx.x;
+    for (uint32_t j = t; j < kTopMaxStates; j += 256) {
+        sp[j] = kTopNoneP;
+        si[j] = kTopNoneI;
+    }
+    if (t == 0) *counter = 0;
+    __syncthreads();
+    double key_p = kTopNoneP;  // the k-th candidate: what a pair has to beat
+    uint32_t key_i = kTopNoneI;
+    for (uint32_t base = 0; base < len; base += 256 * kTopPerThread) {
+        double p[kTopPerThread];
+        uint32_t id[kTopPerThread];
+        uint32_t pending = 0;
+#pragma unroll
+        for (uint32_t u = 0; u < kTopPerThread; ++u) {
+            const uint32_t pos = base + u * 256 + t;
+            p[u] = kTopNoneP;
+            id[u] = kTopNoneI;
+            if (pos < len) item(pos, p[u], id[u]);
+            if (top_before(p[u], id[u], key_p, key_i)) pending |= 1u << u;
+        }
+        for (;;) {
+#pragma unroll
+            for (uint32_t u = 0; u < kTopPerThread; ++u)
+                if (pending & (1u << u)) {
+                    const uint32_t slot = atomicAdd(counter, 1u);
+                    if (slot < kTopBuffer) {
+                        sp[kTopMaxStates + slot] = p[u];
+                        si[kTopMaxStates + slot] = id[u];
+                        pending &= ~(1u << u);
+                    }
+                }
+            __syncthreads();
+            const uint32_t count = *counter;
+            __syncthreads();  // (everybody has read the counter before anybody moves it again)
+            if (count <= kTopBuffer) break;
+            // the buffer is full and some pairs are still in registers: fold it into the candidates, then offer those again
+            top_sort_keep(sp, si, counter, kTopBuffer, k);
+            key_p = sp[k - 1];
+            key_i = si[k - 1];
+#pragma unroll
+            for (uint32_t u = 0; u < kTopPerThread; ++u)
+                if ((pending & (1u << u)) && !top_before(p[u], id[u], key_p, key_i)) pending &= ~(1u << u);
+        }
+    }
+    top_sort_keep(sp, si, counter, *counter, k);
+}
+
+// block b of evaluation e: the best k states of [b range, (b + 1) range) (range >= k), sorted, to list e * gridDim.x + b
+template <typename real>
+__global__ void __launch_bounds__(256) top_chunks_kernel(const uint32_t* __restrict__ plan_arena, const EvalDesc* __restrict__ evals,
+                                                         const double* __restrict__ probs_all, uint64_t dim,
+                                                         const cx<real>* __restrict__ sides, uint64_t side_stride, uint32_t range,
+                                                         uint32_t k, double* __restrict__ list_p, uint32_t* __restrict__ list_i) {
+    __shared__ double sp[kTopSlots];
+    __shared__ uint32_t si[kTopSlots];
+    __shared__ uint32_t counter;
+    const EvalDesc ev = evals[blockIdx.y];
+    const ExactSource<real> src = exact_source<real>(plan_arena, ev, blockIdx.y, probs_all, dim, sides, side_stride);
+    const uint32_t first = blockIdx.x * range;
+    top_select([&](uint32_t pos, double& p, uint32_t& i) {
+        i = first + pos;
+        p = src(i);
+    }, range, k, sp, si, &counter);
+    const size_t at = (size_t(blockIdx.y) * gridDim.x + blockIdx.x) * k;
+    for (uint32_t j = threadIdx.x; j < k; j += 256) {
+        list_p[at + j] = sp[j];
+        list_i[at + j] = si[j];
+    }
+}
+
+// evaluation e: the best k pairs of its blocks' lists, to row evals[e].out_index of the outputs
+__global__ void __launch_bounds__(256) top_merge_kernel(const EvalDesc* __restrict__ evals, uint32_t n_pairs, uint32_t k,
+                                                        const double* __restrict__ list_p, const uint32_t* __restrict__ list_i,
+                                                        const double* __restrict__ diag, uint64_t* __restrict__ out_states,
+                                                        double* __restrict__ out_probs, double* __restrict__ out_values) {
+    __shared__ double sp[kTopSlots];
+    __shared__ uint32_t si[kTopSlots];
+    __shared__ uint32_t counter;
+    const double* lp = list_p + size_t(blockIdx.x) * n_pairs;
+    const uint32_t* li = list_i + size_t(blockIdx.x) * n_pairs;
+    top_select([&](uint32_t pos, double& p, uint32_t& i) {
+        p = lp[pos];
+        i = li[pos];
+    }, n_pairs, k, sp, si, &counter);
+    const size_t row = size_t(evals[blockIdx.x].out_index) * k;
+    for (uint32_t j = threadIdx.x; j < k; j += 256) {
+        const uint32_t state = si[j];
+        out_states[row + j] = state;
+        out_probs[row + j] = sp[j];
+        if (diag) out_values[row + j] = diag[state];
+    }
+}
+
+hipError_t launch_top_states(int dtype, const double* probs, uint64_t dim, unsigned n_evals, uint32_t k, const double* diag,
+                             void* scratch, uint64_t* out_states, double* out_probs, double* out_values, hipStream_t stream,
+                             const PassArgs& a) {
+    if (n_evals == 0) return hipSuccess;
+    if (k < 1 || k > kTopMaxStates || k > dim || dim > (uint64_t(1) << 28) || (dim & (dim - 1)) || (diag && !out_values))
+        return hipErrorInvalidValue;
+    // (a range holds at least k states: it is the whole dimension, or kTopMinRange >= kTopMaxStates and more)
+    const uint32_t blocks = top_states_blocks(dim), range = uint32_t(dim / blocks);
+    const size_t pairs = size_t(n_evals) * blocks * k;
+    double* list_p = static_cast<double*>(scratch);
+    uint32_t* list_i = reinterpret_cast<uint32_t*>(list_p + pairs);
+    if (dtype == 0)
+        hipLaunchKernelGGL(top_chunks_kernel<double>, dim3(blocks, n_evals), dim3(256), 0, stream, a.plan, a.evals, probs, dim,
+                           static_cast<const cx<double>*>(a.wtab), a.wtab_stride, range, k, list_p, list_i);
+    else
+        hipLaunchKernelGGL(top_chunks_kernel<float>, dim3(blocks, n_evals), dim3(256), 0, stream, a.plan, a.evals, probs, dim,
+                           static_cast<const cx<float>*>(a.wtab), a.wtab_stride, range, k, list_p, list_i);
+    hipLaunchKernelGGL(top_merge_kernel, dim3(n_evals), dim3(256), 0, stream, a.evals, blocks * k, k, list_p, list_i, diag,
+                       out_states, out_probs, out_values);
+    return hipGetLastError();
+}
+
 static unsigned stream_blocks(uint64_t dim) {
     const uint64_t want = (dim + 255) / 256;
     return unsigned(want < 4096 ? want : 4096);

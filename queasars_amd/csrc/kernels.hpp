@@ -395,6 +395,30 @@ hipError_t launch_cvar_exact(int dtype, const double* probs, uint64_t dim, unsig
                              const double* sorted_values, double alpha, double* chunk_scratch, double* out, hipStream_t stream,
                              const PassArgs& args);
 
+// ---- exact readout: the k most probable basis states (qsv.h: qsv_top_states) ------------------------------------------------
+// For each evaluation of a group the first k entries of its 2^n probabilities under the total order "probability descending,
+// basis-state index ascending" (compared as doubles; the order is total, so the answer does not depend on scheduling).  The
+// probabilities are read as launch_cvar_exact reads them: probs[slot e][2^n], or the two side tables of a split circuit.  Two
+// launches: every workgroup of top_chunks_kernel streams a contiguous range of states and keeps its best k in LDS (states that
+// beat the current k-th key are appended to an LDS buffer, which is bitonic-sorted into the candidates whenever it fills), then
+// one workgroup per evaluation runs the same procedure over the blocks' lists and writes, at evals[e].out_index * k,
+// out_states / out_probs and -- diag != null -- out_values = diag[state].  No library sort of 2^n pairs, no 2^n temporary.
+// 1 <= k <= min(kTopMaxStates, dim), dim <= 2^28.  scratch: top_states_scratch_bytes(dim, k, n_evals) bytes.
+// PassArgs: plan, evals (the group's device descriptors), wtab / wtab_stride (side tables).
+constexpr uint32_t kTopMaxStates = 1024;
+constexpr uint32_t kTopMinRange = 8192, kTopMaxBlocks = 512;  // a block's fewest states / most blocks per evaluation
+inline uint32_t top_states_blocks(uint64_t dim) {
+    const uint64_t want = dim / kTopMinRange;  // (dim is a power of two: the ranges are equal)
+    return uint32_t(want < 1 ? 1 : want > kTopMaxBlocks ? kTopMaxBlocks : want);
+}
+inline size_t top_states_scratch_bytes(uint64_t dim, uint32_t k, size_t n_evals) {
+    const size_t pairs = n_evals * size_t(top_states_blocks(dim)) * size_t(k);  // (a block's list: k pairs)
+    return pairs * (sizeof(double) + sizeof(uint32_t));  // every list's probabilities, then every list's indices
+}
+hipError_t launch_top_states(int dtype, const double* probs, uint64_t dim, unsigned n_evals, uint32_t k, const double* diag,
+                             void* scratch, uint64_t* out_states, double* out_probs, double* out_values, hipStream_t stream,
+                             const PassArgs& args);
+
 // ---- the optimiser's share of a lock-step SPSA iteration (qsv.h: qsv_spsa_step) -----------------------------------------------
 // One workgroup per run: accept the iteration whose two values are in `values` (update x, count, stopping rules), then write
 // the two points of the next iteration.  Either half may be left out (values / delta_propose null).  The arguments are the

@@ -3641,6 +3641,67 @@ int qsv_exact_cvar_batch(qsv_t* h, int n_evals, const int* circuit_ids, const in
     return rc ? rc : exact_cvar_locked(h, args, alpha, out_cvar);
 }
 
+// The k most probable basis states of every evaluation of a batch: the circuits group by group as in exact_cvar_locked (split
+// circuits as their two virtual circuits, the others with the probabilities written by their last gate pass), then
+// launch_top_states, which writes row out_index of the three outputs in pinned host memory (states | probabilities | values).
+static int top_states_locked(qsv_t* h, const BatchArgs& args, int k, uint64_t* out_states, double* out_probs, double* out_values) {
+    const size_t n_evals = args.circs.size();
+    if (n_evals == 0) return QSV_OK;
+    if (out_values && !(h->has_diag_part && h->diagonal))
+        return fail(h, QSV_E_STATE, "the values of the top states need a diagonal operator (call qsv_set_operator with I/Z terms only)");
+    const uint64_t dim = uint64_t(1) << h->n;
+    const SplitRule rule = split_rule(h, SplitUse::Sampling);
+    const size_t n_split = rule.count(args.circs), n_plain = n_evals - n_split;
+    const size_t G = size_t(h->group), SG = size_t(std::max(1, h->side_slots));
+    const size_t rows = n_evals * size_t(k);
+    // device scratch: the probabilities of a group of ordinary evaluations | the blocks' lists of a group of either kind
+    const size_t probs_bytes = std::min(G, n_plain) * dim * 8;
+    const size_t lists_off = ((probs_bytes + 63) / 64) * 64;
+    const size_t lists_bytes = top_states_scratch_bytes(dim, uint32_t(k), std::max(std::min(G, n_plain), std::min(SG, n_split)));
+    int rc;
+    if ((rc = ensure(h, h->d_scratch, lists_off + lists_bytes))) return rc;
+    if ((rc = ensure_host_out(h, 3 * rows))) return rc;
+    uint64_t* const states = reinterpret_cast<uint64_t*>(h->h_out);
+    double* const result_probs = h->h_out + rows;
+    double* const values = out_values ? h->h_out + 2 * rows : nullptr;
+    double* probs = static_cast<double*>(h->d_scratch.ptr);
+    void* lists = static_cast<char*>(h->d_scratch.ptr) + lists_off;
+    const double* diag = out_values ? static_cast<const double*>(h->d_diag.ptr) : nullptr;
+    const bool fuse = h->geo.blocks_per_state == 1;
+    auto consume = [&](size_t g0, size_t gc) -> int {
+        PassArgs a{};
+        a.plan = static_cast<const uint32_t*>(h->d_arena.ptr);
+        a.wtab = h->d_side.ptr;
+        a.wtab_stride = h->side_stride;
+        a.evals = batch_evals(h) + g0;
+        QSV_HIP(h, launch_top_states(h->dtype, probs, dim, unsigned(gc), uint32_t(k), diag, lists, states, result_probs, values, h->stream, a));
+        return QSV_OK;
+    };
+    const StateRun run{rule, SG, G, fuse, kModeSynthFirst | kModeFinalStore | kModeSidesOnly,
+                       kModeSynthFirst | kModeFinalProbs | (fuse ? kModeFusedPrepare : 0u)};
+    if ((rc = run_to_states(h, args, run, consume, consume))) return rc;
+    QSV_HIP(h, hipStreamSynchronize(h->stream));
+    std::memcpy(out_states, states, rows * sizeof(uint64_t));
+    std::memcpy(out_probs, result_probs, rows * sizeof(double));
+    if (out_values) std::memcpy(out_values, values, rows * sizeof(double));
+    return QSV_OK;
+}
+
+int qsv_top_states(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params, int k,
+                   uint64_t* out_states, double* out_probs, double* out_values) {
+    if (!h) return QSV_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets || !out_states || !out_probs))) return fail(h, QSV_E_ARG, "bad arguments");
+    if (h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "the top states are available up to 28 qubits");
+    if (k < 1 || k > int(kTopMaxStates) || uint64_t(k) > (uint64_t(1) << h->n))
+        return fail(h, QSV_E_ARG, "k must be between 1 and min(" + std::to_string(kTopMaxStates) + ", 2^n)");
+    QSV_HIP(h, hipSetDevice(h->device));
+    BatchArgs args;
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args,
+                           "circuits on kept states have no top states (qsv_eval_* only)");
+    return rc ? rc : top_states_locked(h, args, k, out_states, out_probs, out_values);
+}
+
 int qsv_cvar_device(qsv_t* h, int n_evals, const int* circuit_ids, int width, const double* device_values, void* ready_event,
                     int shots, uint64_t seed, double alpha, const uint8_t* device_active, int active_stride, double* device_out) {
     if (!h) return QSV_E_ARG;

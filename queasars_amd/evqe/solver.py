@@ -590,6 +590,10 @@ class EVQEResult:
     mean_expectation_values: list[float] = field(default_factory=list)
     # the aux operators' values at the best individual, a list or dict as they were given (None: none were given)
     aux_operators_evaluated: Optional[Union[list[float], dict[Any, float]]] = None
+    # the most probable basis states of the best individual, bitstring (qubit 0 last) -> exact probability, most probable
+    # first (None: not asked for), and -- under a diagonal operator -- bitstring -> the operator's value on it
+    eigenstate: Optional[dict[str, float]] = None
+    eigenstate_values: Optional[dict[str, float]] = None
 
 
 # ---- the solver -----------------------------------------------------------------------------------------------
@@ -848,7 +852,8 @@ class EVQEMinimumEigensolver:
         return EVQEPopulation(tuple(selected), population.species_representatives, None, None)
 
     # -- main loop ------------------------------------------------------------------------------------------
-    def compute_minimum_eigenvalue(self, evaluator, search_evaluator=None, aux_operators=None) -> EVQEResult:
+    def compute_minimum_eigenvalue(self, evaluator, search_evaluator=None, aux_operators=None,
+                                   eigenstate_states: Optional[int] = None) -> EVQEResult:
         """``search_evaluator``: a second evaluator of the SAME operator for the parameter searches alone -- a single-precision
         handle: the points a search compares differ by far more than 1e-6 (the reference's own tests run their searches on an
         estimator with precision 0.05, test/minimum_eigensolvers/evqe/solver.py:20-27), a layer search on kept states is bound
@@ -860,7 +865,15 @@ class EVQEMinimumEigensolver:
         ``evaluator.evaluate_observables`` (reference: evolving_ansatz_minimum_eigensolver.py:177-199, :461-476); the values go
         to ``result.aux_operators_evaluated`` in the same shape.  They use no random stream of the solver and are not counted
         in ``circuit_evaluations``.  (A sampling evaluator draws its samples with its own generator, after the run, as the
-        reference's aux sampler evaluators do.)  In a sharded run every rank evaluates them itself."""
+        reference's aux sampler evaluators do.)  In a sharded run every rank evaluates them itself.
+
+        ``eigenstate_states``: how many of the best individual's most probable basis states to read out after the run, in one
+        ``top_states`` call on the evaluator's ``statevector_device`` -- exact probabilities, selected on the device
+        (reference: the distribution measured for ``result.eigenstate``, evolving_ansatz_minimum_eigensolver.py:442-454, of
+        which users decode the most probable states).  They go to ``result.eigenstate`` (bitstring -> probability, most
+        probable first) and, when the evaluator's operator is diagonal, their values to ``result.eigenstate_values``.  Like the
+        aux operators the call uses no random stream of the solver, is not counted in ``circuit_evaluations`` and is made by
+        every rank of a sharded run itself.  ``None``: no call, both stay ``None``."""
         cfg = self.configuration
         searcher = evaluator if search_evaluator is None else search_evaluator
         if searcher.n_qubits != evaluator.n_qubits:
@@ -871,6 +884,8 @@ class EVQEMinimumEigensolver:
             for op in (aux_operators.values() if isinstance(aux_operators, dict) else aux_operators):
                 if op.num_qubits != evaluator.n_qubits:
                     raise ValueError(f"an aux operator acts on {op.num_qubits} qubits, the evaluator on {evaluator.n_qubits}")
+        if eigenstate_states is not None and getattr(evaluator, "statevector_device", None) is None:
+            raise ValueError("eigenstate_states needs an evaluator with a statevector_device (a device evaluator)")
         if cfg.termination_criterion is not None:
             cfg.termination_criterion.reset_state()
         population = EVQEPopulation.random_population(
@@ -939,7 +954,22 @@ class EVQEMinimumEigensolver:
             evaluations.pop()
         if aux_operators is not None:
             result.aux_operators_evaluated = self._evaluate_aux_operators(evaluator, result.best_individual, aux_operators)
+        if eigenstate_states is not None:
+            result.eigenstate, result.eigenstate_values = self._read_eigenstate(evaluator, result.best_individual, eigenstate_states)
         return result
+
+    def _read_eigenstate(self, evaluator, individual: EVQEIndividual, k: int):
+        """The ``k`` most probable basis states of ``individual`` and, where the evaluator knows them, their values: one
+        ``top_states`` call -- the evaluator's own (behind its initial state, with its operator's values) where it has one,
+        else its device's."""
+        circuit = individual.get_parameterized_quantum_circuit(shared=self.share_circuits)
+        read = getattr(evaluator, "top_states", None)
+        if not callable(read):
+            read = evaluator.statevector_device.top_states
+        states, probabilities, values = read([circuit], [list(individual.parameter_values)], int(k))
+        names = [format(int(s), f"0{evaluator.n_qubits}b") for s in states[0]]
+        eigenstate = {name: float(p) for name, p in zip(names, probabilities[0])}
+        return eigenstate, None if values is None else {name: float(v) for name, v in zip(names, values[0])}
 
     def _evaluate_aux_operators(self, evaluator, individual: EVQEIndividual, aux_operators):
         """The aux operators' values at ``individual``, one call of ``evaluator.evaluate_observables``."""
