@@ -708,6 +708,11 @@ int qsv_fitness_table_wait(const volatile uint64_t* own, int count, volatile int
  *                        8-byte store, visible about 5 us before the stream's completion signal (diagonal operators)
  *   "repeat_layout" 0|1  a batch with the previous batch's circuit ids and counts, nothing registered or set in between,
  *                        keeps that batch's layout (an optimiser's next iteration)
+ *   "replay_launches" 0|1  ... and, where that batch went through in ONE push that made nothing but kernel launches (no mask, no
+ *                        profiling, no second chain of launches on another stream), its push queues those launches again as they were
+ *                        recorded -- grids, instantiations and argument structs by value, only the call's own pointers set anew
+ *                        (parameter values, descriptors, result buffer) -- instead of deriving them from the circuits once more: the
+ *                        same launches, the same bits.  Default 1 (QSV_REPLAY=0: off); needs "repeat_layout".
  *   "split_sampling" 0|1 split circuits are sampled from their side tables
  *   "streams" 1..4       HIP streams the pushes of a batch cycle over (at most as many as were created with the handle)
  *   "gradient_chunk" 0..1048576  shifted evaluations a gradient call expands and runs at a time (0: the default, 8192); the same
@@ -720,6 +725,9 @@ int qsv_fitness_table_wait(const volatile uint64_t* own, int count, volatile int
  * Returns QSV_E_ARG for an unknown name or a value out of range.
  */
 int qsv_set_option(qsv_t* h, const char* name, int value);
+
+/* Pushes of this handle, since it was created, that queued a kept layout's recorded launches ("replay_launches"). */
+long long qsv_replayed_pushes(const qsv_t* h);
 
 int qsv_set_profiling(qsv_t* h, int enabled);
 int qsv_get_profile(const qsv_t* h, qsv_profile* out);

@@ -707,16 +707,18 @@ class StatevectorDevice:
         row_length: int,
         ready_event: int = 0,
         out_device_pointer: int = 0,
+        as_list: bool = False,
     ) -> Optional[np.ndarray]:
         """:meth:`expectation_values` for parameter values that ALREADY LIVE IN DEVICE MEMORY (``qsv_eval_push_device``): a
         row-major ``len(circuits) x row_length`` matrix of doubles at ``device_pointer`` on this handle's GPU, circuit i
         taking the first ``num_parameters`` values of row i.  Nothing is packed and nothing crosses PCIe on the way in.
         ``ready_event``: a ``hipEvent_t`` (as an integer) after which the matrix is complete, 0 when it already is.  The matrix
         must stay unchanged until the call returns.  ``out_device_pointer``: as :meth:`expectation_values_to_device` (results
-        left on the device, no wait, None returned)."""
+        left on the device, no wait, None returned).  ``as_list``: the results as a list of floats (built by the helper where it
+        is there: no array in between)."""
         n = len(circuits)
         if n == 0:
-            return None if out_device_pointer else np.zeros(0, dtype=np.float64)
+            return None if out_device_pointer else ([] if as_list else np.zeros(0, dtype=np.float64))
         if row_length < 0 or (row_length > 0 and not device_pointer):
             raise ValueError("device_pointer / row_length do not describe a matrix")
         ids, need, _total = self._batch_metadata(circuits)
@@ -725,13 +727,19 @@ class StatevectorDevice:
             counts = np.full(n, row_length, dtype=np.int64)
             cached = self._row_counts = ((n, row_length), counts, counts.ctypes.data)
         counts = cached[1]
-        out = None if out_device_pointer else np.empty(n, dtype=np.float64)
         fast = None if os.environ.get("QSV_LIBRARY") else _load_pyhelp_module()
         if fast is not None:
             # (the whole batch in one call of the extension module; the address of the id array is kept with the array)
             kept = self._ids_address
             if kept is None or kept[0] is not ids:
                 kept = self._ids_address = (ids, ids.ctypes.data)
+            if as_list and not out_device_pointer and hasattr(fast, "eval_device_matrix_list"):
+                values = fast.eval_device_matrix_list(self._handle.value, n, kept[1], cached[2], device_pointer, ready_event)
+                if values.__class__ is not list:
+                    self._check(values)
+                return values
+        out = None if out_device_pointer else np.empty(n, dtype=np.float64)
+        if fast is not None:
             rc = fast.eval_device_matrix(self._handle.value, n, kept[1], cached[2], device_pointer, ready_event,
                                          out.ctypes.data if out is not None else 0, out_device_pointer)
             self._check(rc)
@@ -1160,7 +1168,8 @@ class StatevectorDevice:
     def set_option(self, name: str, value: int) -> None:
         """Switches of the handle (``qsv_set_option``): "split", "factor", "split_sampling" (0 / 1), "streams" (1 .. 4),
         "gradient_chunk" (shifted evaluations per chunk of a gradient call, 0 = the default), "max_grid_y" (x-mask groups or
-        observable rows per launch, 0 = the device's largest gridDim.y).
+        observable rows per launch, 0 = the device's largest gridDim.y), "repeat_layout" / "replay_launches" (0 / 1: a repeated batch
+        keeps its layout / queues its recorded launches again).
         A circuit keeps the form it was registered in; the cache of the previous batch is dropped."""
         self._check(self._lib.qsv_set_option(self._handle, name.encode(), int(value)))
         self._last_batch = None
@@ -1178,6 +1187,14 @@ class StatevectorDevice:
             value = getattr(prof, name)
             out[name] = list(value) if hasattr(value, "__len__") else value
         return out
+
+    def replayed_pushes(self) -> int:
+        """Pushes of this handle so far that queued a kept layout's recorded launches again (``qsv_replayed_pushes``; option
+        "replay_launches")."""
+        count = int(self._lib.qsv_replayed_pushes(self._handle))
+        if count < 0:
+            self._check(count)
+        return count
 
     def bench_gate(self, target: int, control: int = -1, theta=1.0, phi=0.5, lam=0.25, reps: int = 100) -> float:
         """Average device milliseconds of one read-modify-write sweep applying a single u / cu3 gate."""
@@ -1436,7 +1453,10 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
             if self._device._operator is not self._operator:
                 self._device.set_operator(self._operator)
             if matrix is not None:
-                values = self._evaluate_device_matrix(circuits, matrix)
+                # (exact values leave as the list they are returned as: no array, no tolist())
+                values = self._evaluate_device_matrix(circuits, matrix, as_list=self._precision == 0)
+                if values.__class__ is list:
+                    return values
             else:
                 values = self._device.expectation_values(circuits, parameter_values)
         if self._precision > 0:
@@ -1456,9 +1476,9 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
             values = values + self._rng.normal(0.0, self._precision, size=values.shape)
         return values.tolist()
 
-    def _evaluate_device_matrix(self, circuits, matrix, ready: bool = False, out_device_pointer: int = 0) -> Optional[np.ndarray]:
+    def _evaluate_device_matrix(self, circuits, matrix, ready: bool = False, out_device_pointer: int = 0, as_list: bool = False):
         pointer, width, event, remember = _device_matrix_arguments(self, circuits, matrix, ready)
-        out = self._device.expectation_values_of_device_parameters(circuits, pointer, width, event, out_device_pointer)
+        out = self._device.expectation_values_of_device_parameters(circuits, pointer, width, event, out_device_pointer, as_list)
         remember()
         return out
 

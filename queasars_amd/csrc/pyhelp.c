@@ -382,6 +382,46 @@ static PyObject* eval_device_matrix(PyObject* self, PyObject* const* args, Py_ss
     return PyLong_FromLong(rc);
 }
 
+/* eval_device_matrix with the results waited for and handed back as a Python list of floats, built here:
+ * eval_device_matrix_list(handle, n, ids_address, counts_address, device_values, ready_event) -> list, or the library's status (an
+ * int, never 0) when the call failed.  What OperatorCircuitEvaluator.evaluate_circuits returns is such a list: through
+ * eval_device_matrix it allocates a NumPy array for the results and converts it with tolist(). */
+static PyObject* eval_device_matrix_list(PyObject* self, PyObject* const* args, Py_ssize_t nargs) {
+    (void)self;
+    if (nargs != 6) {
+        PyErr_SetString(PyExc_TypeError, "eval_device_matrix_list(handle, n, ids, counts, device_values, ready_event)");
+        return NULL;
+    }
+    void* p[6];
+    for (int i = 0; i < 6; ++i) {
+        if (i == 1) continue;
+        p[i] = PyLong_AsVoidPtr(args[i]);
+        if (!p[i] && PyErr_Occurred()) return NULL;
+    }
+    const Py_ssize_t n = PyLong_AsSsize_t(args[1]);
+    if (n == -1 && PyErr_Occurred()) return NULL;
+    if (!p[0] || n <= 0 || !p[2] || !p[3]) {
+        PyErr_SetString(PyExc_ValueError, "eval_device_matrix_list: null handle or arrays");
+        return NULL;
+    }
+    double stack[256];
+    double* out = n <= 256 ? stack : (double*)malloc((size_t)n * sizeof(double));
+    if (!out) return PyErr_NoMemory();
+    const int rc = qsv_py_expectation_values_devparams((qsv_t*)p[0], n, (const int*)p[2], (const int64_t*)p[3], (const double*)p[4],
+                                                       p[5], out, NULL);
+    PyObject* list = rc ? PyLong_FromLong(rc) : PyList_New(n);
+    for (Py_ssize_t i = 0; !rc && list && i < n; ++i) {
+        PyObject* v = PyFloat_FromDouble(out[i]);
+        if (!v) {
+            Py_CLEAR(list);
+            break;
+        }
+        PyList_SET_ITEM(list, i, v);
+    }
+    if (out != stack) free(out);
+    return list;
+}
+
 /* qsv_py_expectation_values the same way: eval_vectors(handle, n, ids_address, counts_address, vectors, scratch_address,
  * capacity, out_address) -> rc (-100: a Python exception is set and is raised instead). */
 static PyObject* eval_vectors(PyObject* self, PyObject* const* args, Py_ssize_t nargs) {
@@ -447,6 +487,8 @@ static PyObject* has_none(PyObject* self, PyObject* const* args, Py_ssize_t narg
 static PyMethodDef helper_methods[] = {
     {"eval_device_matrix", (PyCFunction)(void (*)(void))eval_device_matrix, METH_FASTCALL,
      "eval_device_matrix(handle, n, ids, counts, device_values, ready_event, out, device_out) -> rc: a batch whose parameter values live in device memory"},
+    {"eval_device_matrix_list", (PyCFunction)(void (*)(void))eval_device_matrix_list, METH_FASTCALL,
+     "eval_device_matrix_list(handle, n, ids, counts, device_values, ready_event) -> list of floats (or the status of a failed call)"},
     {"eval_vectors", (PyCFunction)(void (*)(void))eval_vectors, METH_FASTCALL,
      "eval_vectors(handle, n, ids, counts, vectors, scratch, capacity, out) -> rc: a batch of host parameter vectors"},
     {"has_none", (PyCFunction)(void (*)(void))has_none, METH_FASTCALL, "has_none(seq): some element of a list or tuple is None"},

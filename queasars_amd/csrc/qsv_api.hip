@@ -215,6 +215,15 @@ struct qsv_handle {
     // in between, is that batch again (an optimiser's next iteration over the same population): eval_begin keeps its layout.
     uint64_t epoch = 1;
     bool repeat_enabled = true;
+    bool replay_enabled = true;   // a repeated whole-push batch queues the kept layout's recorded launches again (replay_push)
+    uint64_t replayed_pushes = 0;  // pushes that did (qsv_replayed_pushes)
+    // QSV_HOST_TIMING=1 (read when the handle is created): where the host's share of a qsv_eval_begin / push / end call goes,
+    // summed over the handle's life and printed when it is destroyed.  Off: one test of `on` per phase.
+    struct HostTiming {
+        bool on = false, in_push = false;
+        uint64_t calls = 0, replays = 0;
+        double begin_us = 0, push_us = 0, launch_us = 0, end_us = 0, copy_us = 0;  // (push_us holds launch_us, end_us holds copy_us: reported apart)
+    } timing;
     bool chain_enabled = true;
     bool fused_lds_table = true;  // one-launch route: small sides hand their state to the Gram matrices through LDS (kModeFusedLdsTable)
     bool side_prepare = true;     // one-launch route: a side is prepared from one staged read of its plan (kModeSidePrepare); asked at every launch
@@ -375,6 +384,39 @@ struct qsv_handle {
         size_t n_pushes = 0;
         const double* dev_params = nullptr;  // this push's parameter values live in device memory (qsv_eval_push_device):
                                              // where evaluation 0's values would be -- descriptors index it like the staging buffer
+        // The launches of the kept layout's one push, as that push made them (eval_push records, replay_push queues them again
+        // for a batch that repeats): lives and dies with the kept layout -- dropped wherever a batch is laid out afresh
+        // (batch_layout), and usable only while `epoch` is the handle's and the batch is a repeat (snap_epoch == epoch).
+        struct LaunchEntry {
+            enum Kind : uint8_t { Prepare, Pass, Reduce, Factor, FactorTerms, Contract, PauliGroups, PauliCombine } kind = Pass;
+            int stream = -1;  // -1: the handle's own stream; i: side_streams[i]
+            // Pass: the kernel's instantiation and launch shape
+            int dtype = 0, r = 0, xmode = 0, threads = 0;
+            dim3 grid;
+            size_t lds = 0;
+            PassArgs a{};  // Pass, Factor, FactorTerms, Contract: the argument struct by value
+            // patched at every replay (see replay_push): offsets from the descriptor / result bases, -1 where the launch takes none
+            int64_t host_evals_off = -1, result_off = -1;
+            bool takes_params = false;
+            // the other kinds' arguments: functions of the layout alone
+            int n = 0, n2 = 0, n3 = 0;          // evaluations (Prepare, Reduce, Factor*, PauliGroups, PauliCombine) / first group, groups (PauliGroups) / most keys (Factor)
+            uint32_t blocks = 0;                // Reduce: partial sums per evaluation; Contract: chunks
+            const double* partials = nullptr;   // Reduce: where they are
+            double* out = nullptr;              // Reduce: a device destination that is not the result buffer (d_out)
+            const EvalDesc* evals = nullptr;    // Prepare: the device descriptors written; Reduce, PauliCombine: those read (may be null)
+        };
+        struct LaunchRecord {
+            std::vector<LaunchEntry> entries;
+            bool recording = false;  // a push is appending to it
+            bool spoiled = false;    // ... and did something that is not a kernel launch on one of the handle's streams
+            bool usable = false;     // the push made nothing but kernel launches, and ended well
+            uint64_t epoch = 0;      // the handle's when the push ended
+            int ways = 0;            // streams the batch cycled over (slots and launch groups follow it)
+            bool no_direct_env = false;  // what single_workgroup_path found in the environment
+            unsigned used_mask = 0;  // side streams the push left work on
+            size_t aux_count = 0;    // ordinary evaluations it put on the auxiliary stream
+            qsv_profile prof{};      // what the push added to the handle's counters (they are zero when a batch begins)
+        } record;
     } batch;
     std::unique_lock<std::mutex> batch_lock;  // held from begin to end
     // qsv_cvar_device: its device_active for the duration of the call (run_group and batch_ship hand it to their launches) ...
@@ -456,6 +498,55 @@ inline hipStream_t ws(const qsv_t* h) { return h->work ? h->work : h->stream; }
         if (_e != hipSuccess)                                                                     \
             return fail((h), QSV_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));    \
     } while (0)
+
+// QSV_HOST_TIMING: adds the time between its construction and its destruction to one of the handle's phase sums (a launch
+// call's only inside qsv_eval_push, whose own sum is reported without them)
+struct PhaseClock {
+    using Timing = qsv_handle::HostTiming;
+    double* acc = nullptr;
+    std::chrono::steady_clock::time_point t0;
+    PhaseClock(qsv_t* h, double Timing::*phase, bool in_push_only = false) {
+        if (h->timing.on && (!in_push_only || h->timing.in_push)) {
+            acc = &(h->timing.*phase);
+            t0 = std::chrono::steady_clock::now();
+        }
+    }
+    ~PhaseClock() {
+        if (acc) *acc += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    }
+};
+
+// a kernel launch of the batch path: QSV_HIP, and timed as a launch call
+#define QSV_LAUNCH(h, expr)                                                       \
+    do {                                                                          \
+        PhaseClock _launch_clock((h), &PhaseClock::Timing::launch_us, true);      \
+        QSV_HIP((h), expr);                                                       \
+    } while (0)
+
+// ---- the launch record of a kept layout (qsv_handle::Batch::LaunchRecord) ---------------------------------
+using LaunchEntry = qsv_handle::Batch::LaunchEntry;
+
+// the push being recorded did something a replay cannot repeat by launching kernels (or launched where a record cannot say)
+void record_spoil(qsv_t* h) {
+    if (h->batch.record.recording) h->batch.record.spoiled = true;
+}
+
+// the entry of a launch on the stream of the push being issued; null when no push is being recorded
+LaunchEntry* record_entry(qsv_t* h, LaunchEntry::Kind kind, hipStream_t st) {
+    qsv_handle::Batch::LaunchRecord& rec = h->batch.record;
+    if (!rec.recording) return nullptr;
+    int index = -1;
+    if (st != h->stream) {
+        for (size_t i = 0; i < h->side_streams.size(); ++i)
+            if (h->side_streams[i] == st) index = int(i);
+        if (index < 0) rec.spoiled = true;
+    }
+    rec.entries.emplace_back();
+    LaunchEntry& e = rec.entries.back();
+    e.kind = kind;
+    e.stream = index;
+    return &e;
+}
 
 // Nothing on either stream may still be using a buffer that is about to be replaced.
 hipError_t sync_streams(qsv_t* h) {
@@ -1017,6 +1108,30 @@ const double* params_base(const qsv_t* h) {
     return reinterpret_cast<const double*>(static_cast<const char*>(h->h_batch) + h->batch.desc_bytes);
 }
 
+// where the kernels of the current batch write results: the caller's device buffer (qsv_eval_set_output) or the pinned one
+double* result_base(const qsv_t* h) { return h->out_target ? h->out_target : h->h_out; }
+
+// a recorded launch's argument struct, and which of its call-dependent pointers it carries (replay_push sets them anew)
+void record_args(qsv_t* h, LaunchEntry& e, const PassArgs& a) {
+    e.a = a;
+    e.host_evals_off = a.host_evals ? int64_t(a.host_evals - descs_base(h)) : -1;
+    e.takes_params = a.host_params != nullptr;
+    e.result_off = a.result_out ? int64_t(a.result_out - result_base(h)) : -1;
+    if ((a.host_params && a.host_params != params_base(h)) || a.active.flags) record_spoil(h);
+}
+
+void record_pass(qsv_t* h, int r, dim3 grid, int threads, size_t lds, const PassArgs& a) {
+    LaunchEntry* e = record_entry(h, LaunchEntry::Pass, ws(h));
+    if (!e) return;
+    record_args(h, *e, a);
+    e->dtype = h->dtype;
+    e->r = r;
+    e->xmode = h->cfg.xmode;
+    e->grid = grid;
+    e->threads = threads;
+    e->lds = lds;
+}
+
 int ensure_host_out(qsv_t* h, size_t count) {
     if (h->h_out_count >= count) return QSV_OK;
     if (h->h_out) {
@@ -1068,6 +1183,8 @@ int batch_layout(qsv_t* h, const std::vector<Circuit*>& circs, const std::vector
     int rc;
     h->epoch += 1;  // (whatever an earlier batch left in the staging buffer is overwritten below)
     b.repeat = false;
+    b.record.entries.clear();  // (the launches of the layout that goes)
+    b.record.usable = false;
     if (h->async_pending) {  // the kernels of a batch that ended without waiting read the staging buffers written below
         QSV_HIP(h, sync_streams(h));
         h->async_pending = false;
@@ -1206,10 +1323,17 @@ int batch_ship(qsv_t* h, size_t first, size_t count, const double* values, size_
     }
     const EvalDesc* host_evals = descs_base(h);
     const double* ship_params = params_base(h);
-    if (count > n_fused)
-        QSV_HIP(h, launch_prepare(static_cast<const uint32_t*>(h->d_arena.ptr), host_evals + first + n_fused,
-                                  static_cast<EvalDesc*>(h->d_batch.ptr) + first + n_fused, ship_params,
-                                  static_cast<double*>(h->d_mats.ptr), int(count - n_fused), ws(h), 1, 0, h->dtype, h->mask));
+    if (count > n_fused) {
+        QSV_LAUNCH(h, launch_prepare(static_cast<const uint32_t*>(h->d_arena.ptr), host_evals + first + n_fused,
+                                     static_cast<EvalDesc*>(h->d_batch.ptr) + first + n_fused, ship_params,
+                                     static_cast<double*>(h->d_mats.ptr), int(count - n_fused), ws(h), 1, 0, h->dtype, h->mask));
+        if (LaunchEntry* e = record_entry(h, LaunchEntry::Prepare, ws(h))) {
+            e->host_evals_off = int64_t(first + n_fused);
+            e->evals = static_cast<EvalDesc*>(h->d_batch.ptr) + first + n_fused;
+            e->takes_params = true;
+            e->n = int(count - n_fused);
+        }
+    }
     return QSV_OK;
 }
 
@@ -1405,7 +1529,8 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
                 // (need >= kFusedFactorLdsBytes: room for the staged plan run behind prepare_eval's scratch)
                 if (p == 0 && (extra_mode & kModeFusedFactor) && h->side_prepare) a.mode |= kModeSidePrepare;
                 if (h->stamping) QSV_HIP(h, stamp(h, h->batch.launch_events[kind], true));
-                QSV_HIP(h, launch_pass(h->dtype, r, h->cfg.xmode, dim3(grid_x, unsigned(hi - lo), 2), threads, need, ws(h), a));
+                QSV_LAUNCH(h, launch_pass(h->dtype, r, h->cfg.xmode, dim3(grid_x, unsigned(hi - lo), 2), threads, need, ws(h), a));
+                record_pass(h, r, dim3(grid_x, unsigned(hi - lo), 2), threads, need, a);
                 if (h->stamping) QSV_HIP(h, stamp(h, h->batch.launch_events[kind], false));
                 h->prof.n_pass_launches += 1;
                 h->prof.kernel_launches[kind] += 1;
@@ -1515,8 +1640,9 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
         }
         const int kind = (p == 0 && (mode & kModeSynthFirst)) ? 0 : 1;  // which instantiation of the kernel runs
         if (h->stamping) QSV_HIP(h, stamp(h, h->batch.launch_events[kind], true));
-        QSV_HIP(h, launch_pass(h->dtype, h->geo.r, h->cfg.xmode, grid, h->geo.threads_launch,
-                               std::max(h->geo.lds_bytes, fused ? kFusedPrepareLdsBytes : size_t(0)), ws(h), a));
+        QSV_LAUNCH(h, launch_pass(h->dtype, h->geo.r, h->cfg.xmode, grid, h->geo.threads_launch,
+                                  std::max(h->geo.lds_bytes, fused ? kFusedPrepareLdsBytes : size_t(0)), ws(h), a));
+        record_pass(h, h->geo.r, grid, h->geo.threads_launch, std::max(h->geo.lds_bytes, fused ? kFusedPrepareLdsBytes : size_t(0)), a);
         if (h->stamping) QSV_HIP(h, stamp(h, h->batch.launch_events[kind], false));
         h->prof.n_pass_launches += 1;
         h->prof.n_state_passes += n_plain;
@@ -1565,6 +1691,7 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
                 // slots.  Left to run in stream order, a clear that came late (its stream still busy with this chain's virtual
                 // circuits) reset counters that other chain had begun to add to: its evaluations of four and five keys were
                 // combined from incomplete partial sums, or not at all -- a wrong value in the first batch of a handle.
+                record_spoil(h);
                 QSV_HIP(h, hipMemsetAsync(h->d_factor_big_count.ptr, 0, cbytes, ws(h)));
                 h->host_waits += 1;
                 QSV_HIP(h, hipStreamSynchronize(ws(h)));
@@ -1573,9 +1700,14 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
         a.evals = batch_evals(h) + first;
         a.result_out = h->out_target ? h->out_target : h->h_out;
         if (h->stamping) QSV_HIP(h, stamp(h, h->batch.launch_events[2], true));
-        QSV_HIP(h, launch_factor(h->dtype, unsigned(n_unfused), static_cast<double*>(h->d_factor.ptr),
-                                 static_cast<const double*>(h->d_quad.ptr), h->n, ws(h), a, static_cast<double*>(h->d_factor_big.ptr),
-                                 static_cast<uint32_t*>(h->d_factor_big_count.ptr), most_keys));
+        QSV_LAUNCH(h, launch_factor(h->dtype, unsigned(n_unfused), static_cast<double*>(h->d_factor.ptr),
+                                    static_cast<const double*>(h->d_quad.ptr), h->n, ws(h), a, static_cast<double*>(h->d_factor_big.ptr),
+                                    static_cast<uint32_t*>(h->d_factor_big_count.ptr), most_keys));
+        if (LaunchEntry* e = record_entry(h, LaunchEntry::Factor, ws(h))) {
+            record_args(h, *e, a);
+            e->n = int(n_unfused);
+            e->n3 = most_keys;
+        }
         if (h->stamping) QSV_HIP(h, stamp(h, h->batch.launch_events[2], false));
         h->prof.kernel_launches[2] += 1;  // (the launches of the route, timed as one)
       }
@@ -1602,10 +1734,21 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
         // general operator: every term's two small matrices from the side tables, summed per evaluation into d_out
         a.evals = batch_evals(h) + first;
         if (h->stamping) QSV_HIP(h, stamp(h, h->batch.launch_events[2], true));
-        QSV_HIP(h, launch_factor_terms(h->dtype, unsigned(n_split), static_cast<const FactorTerm*>(h->d_fterms.ptr), h->n_fterms,
-                                       static_cast<double*>(h->d_fpart.ptr), ws(h), a));
-        QSV_HIP(h, launch_reduce_partials(static_cast<const double*>(h->d_fpart.ptr), kFactorTermWaves, int(n_split),
-                                          static_cast<double*>(h->d_out.ptr), ws(h), batch_evals(h) + first));
+        QSV_LAUNCH(h, launch_factor_terms(h->dtype, unsigned(n_split), static_cast<const FactorTerm*>(h->d_fterms.ptr), h->n_fterms,
+                                          static_cast<double*>(h->d_fpart.ptr), ws(h), a));
+        if (LaunchEntry* e = record_entry(h, LaunchEntry::FactorTerms, ws(h))) {
+            record_args(h, *e, a);
+            e->n = int(n_split);
+        }
+        QSV_LAUNCH(h, launch_reduce_partials(static_cast<const double*>(h->d_fpart.ptr), kFactorTermWaves, int(n_split),
+                                             static_cast<double*>(h->d_out.ptr), ws(h), batch_evals(h) + first));
+        if (LaunchEntry* e = record_entry(h, LaunchEntry::Reduce, ws(h))) {
+            e->partials = static_cast<const double*>(h->d_fpart.ptr);
+            e->blocks = kFactorTermWaves;
+            e->n = int(n_split);
+            e->out = static_cast<double*>(h->d_out.ptr);
+            e->evals = batch_evals(h) + first;
+        }
         if (h->stamping) QSV_HIP(h, stamp(h, h->batch.launch_events[2], false));
         h->prof.kernel_launches[2] += 1;
         for (size_t i = 0; i < n_split; ++i) {
@@ -1624,7 +1767,12 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
         a.evals = batch_evals(h) + first;
         if (h->stamping) QSV_HIP(h, stamp(h, h->batch.launch_events[2], true));
         const unsigned contract_chunks = unsigned((uint64_t(1) << h->n) / (uint64_t(h->geo.threads_launch) << kSplitLoopBits));
-        QSV_HIP(h, launch_contract(h->dtype, contract_chunks, unsigned(n_split), h->geo.threads_launch, ws(h), a));
+        QSV_LAUNCH(h, launch_contract(h->dtype, contract_chunks, unsigned(n_split), h->geo.threads_launch, ws(h), a));
+        if (LaunchEntry* e = record_entry(h, LaunchEntry::Contract, ws(h))) {
+            record_args(h, *e, a);
+            e->blocks = contract_chunks;
+            e->n = int(n_split);
+        }
         if (h->stamping) QSV_HIP(h, stamp(h, h->batch.launch_events[2], false));
         h->prof.kernel_launches[2] += 1;
         for (size_t i = 0; i < n_split; ++i) {
@@ -1765,6 +1913,123 @@ size_t order_split_first(qsv_t* h, size_t first, size_t count, size_t* n_cont = 
     return n_split;
 }
 
+// The expectation kernels of the general-operator path over the gc states of a launch group: x-mask groups [g1, g1 + groups), then
+// their combination into d_out (every argument but these is the operator's or the handle's; both run on the handle's own stream)
+hipError_t launch_pauli_groups_of(qsv_t* h, int gc, int g1, int groups) {
+    return launch_pauli_groups(h->dtype, h->d_states.ptr, uint64_t(1) << h->n, h->n, gc, h->n_groups,
+                               static_cast<const PauliGroup*>(h->d_groups.ptr), static_cast<const uint64_t*>(h->d_z.ptr),
+                               static_cast<const double*>(h->d_cre.ptr), static_cast<const uint32_t*>(h->d_term_odd.ptr), h->pauli_nb,
+                               static_cast<double*>(h->d_term_partials.ptr), h->stream, g1, groups);
+}
+hipError_t launch_pauli_combine_of(qsv_t* h, int gc, const EvalDesc* evals) {
+    return launch_pauli_combine(static_cast<const double*>(h->d_term_partials.ptr), uint32_t(h->n_groups) * uint32_t(h->pauli_nb),
+                                h->has_diag_part ? static_cast<const double*>(h->d_partials.ptr) : nullptr, partials_per_state(h), gc,
+                                evals, static_cast<double*>(h->d_out.ptr), h->stream);
+}
+
+// a push's own reduction into the result buffer, as a record entry
+LaunchEntry reduce_entry(LaunchEntry e, const double* partials, int n, int64_t result_off, const EvalDesc* evals) {
+    e.partials = partials;
+    e.n = n;
+    e.result_off = result_off;
+    e.evals = evals;
+    return e;
+}
+
+// what a push adds to the handle's counters (they are zero when a batch begins: `from` is the recorded push's total)
+void add_push_counters(qsv_profile& to, const qsv_profile& from) {
+    to.n_pass_launches += from.n_pass_launches;
+    to.n_state_passes += from.n_state_passes;
+    to.state_bytes += from.state_bytes;
+    to.moved_bytes += from.moved_bytes;
+    for (int k = 0; k < 3; ++k) {
+        to.kernel_launches[k] += from.kernel_launches[k];
+        to.kernel_bytes[k] += from.kernel_bytes[k];
+        to.kernel_moved_bytes[k] += from.kernel_moved_bytes[k];
+        to.kernel_flops[k] += from.kernel_flops[k];
+        to.kernel_states[k] += from.kernel_states[k];
+    }
+}
+
+// The one push of a batch that repeats the batch before it, whose push was recorded (eval_push: the record is usable, the handle's
+// epoch has not moved, the batch cycles over as many streams): the recorded launches again, in their order, each on its stream.
+//
+// Set anew at every replay -- what may differ from the recording call although the layout is the same:
+//   host_evals  (PassArgs; launch_prepare's)  descs_base(h): the pinned descriptors on the recording call, their device copy on a
+//               repeat (repeat_device_descs), at the recorded offset
+//   host_params (PassArgs; launch_prepare's)  params_base(h): the staging buffer or this call's device memory (qsv_eval_push_device)
+//   result_out  (PassArgs; launch_reduce_partials' destination)  result_base(h): the pinned result buffer or this call's device
+//               buffer (qsv_eval_set_output), at the recorded offset
+//   active      (PassArgs; launch_prepare's)  the empty mask: no record is made or used under a mask
+// Every other field is a function of the layout, the operator and the handle, none of which can change without the epoch moving
+// (registrations, qsv_set_operator, qsv_set_option, qsv_set_profiling, every batch_layout, a new staging buffer) or the batch
+// being laid out afresh: plan, mats / mats_out, evals / evals_out, states, wtab, diag, partials, quad, factor_scratch,
+// factor_counters, prefix_states, side_diag are device buffers of the handle that only a batch_layout, an operator or a registration
+// replaces; state_stride, wtab_stride, n_full, dephase are the handle's; pass_index, mode, tiles_per_block, region_stride,
+// partial_chunks follow the circuits' plans and forms, the options and the number of streams (the record's `ways`).  Grid, block,
+// LDS bytes and the kernel's instantiation likewise.  Device buffers a call may replace without a layout (d_partials, d_out,
+// d_fpart, the result buffer) are replaced in eval_begin only, which lays the batch out.
+int replay_push(qsv_t* h, size_t count, const double* values) {
+    qsv_handle::Batch& b = h->batch;
+    qsv_handle::Batch::LaunchRecord& rec = b.record;
+    const size_t total = size_t(b.param_base[count - 1]) + b.n_params[count - 1];
+    double* hp = reinterpret_cast<double*>(static_cast<char*>(h->h_batch) + b.desc_bytes);
+    if (total > 0 && !b.dev_params && values != hp) std::memcpy(hp, values, total * sizeof(double));  // (as batch_ship)
+    const EvalDesc* descs = descs_base(h);
+    const double* params = params_base(h);
+    double* result = result_base(h);
+    for (LaunchEntry& e : rec.entries) {
+        hipStream_t const st = e.stream < 0 ? h->stream : h->side_streams[size_t(e.stream)];
+        PassArgs& a = e.a;
+        a.host_evals = e.host_evals_off >= 0 ? descs + e.host_evals_off : nullptr;
+        a.host_params = e.takes_params ? params : nullptr;
+        a.result_out = e.result_off >= 0 ? result + e.result_off : nullptr;
+        a.active = ActiveMask{};
+        switch (e.kind) {
+        case LaunchEntry::Prepare:
+            QSV_LAUNCH(h, launch_prepare(static_cast<const uint32_t*>(h->d_arena.ptr), a.host_evals, const_cast<EvalDesc*>(e.evals), params,
+                                         static_cast<double*>(h->d_mats.ptr), e.n, st, 1, 0, h->dtype, ActiveMask{}));
+            break;
+        case LaunchEntry::Pass:
+            QSV_LAUNCH(h, launch_pass(e.dtype, e.r, e.xmode, e.grid, e.threads, e.lds, st, a));
+            break;
+        case LaunchEntry::Reduce:
+            QSV_LAUNCH(h, launch_reduce_partials(e.partials, e.blocks, e.n, e.out ? e.out : a.result_out, st, e.evals));
+            break;
+        case LaunchEntry::Factor:
+            QSV_LAUNCH(h, launch_factor(h->dtype, unsigned(e.n), static_cast<double*>(h->d_factor.ptr), static_cast<const double*>(h->d_quad.ptr),
+                                        h->n, st, a, static_cast<double*>(h->d_factor_big.ptr),
+                                        static_cast<uint32_t*>(h->d_factor_big_count.ptr), e.n3));
+            break;
+        case LaunchEntry::FactorTerms:
+            QSV_LAUNCH(h, launch_factor_terms(h->dtype, unsigned(e.n), static_cast<const FactorTerm*>(h->d_fterms.ptr), h->n_fterms,
+                                              static_cast<double*>(h->d_fpart.ptr), st, a));
+            break;
+        case LaunchEntry::Contract:
+            QSV_LAUNCH(h, launch_contract(h->dtype, e.blocks, unsigned(e.n), h->geo.threads_launch, st, a));
+            break;
+        case LaunchEntry::PauliGroups:
+            QSV_LAUNCH(h, launch_pauli_groups_of(h, e.n, e.n2, e.n3));
+            break;
+        case LaunchEntry::PauliCombine:
+            QSV_LAUNCH(h, launch_pauli_combine_of(h, e.n, e.evals));
+            break;
+        }
+    }
+    // (what later code goes by, once the launches are queued)
+    add_push_counters(h->prof, rec.prof);
+    b.pushed = count;
+    b.n_pushes = 1;
+    b.whole_push = true;
+    b.used_mask |= rec.used_mask;
+    b.aux_count = rec.aux_count;
+    b.chain_now = false;
+    h->chain_stream = -1;
+    h->replayed_pushes += 1;
+    h->timing.replays += 1;
+    return QSV_OK;
+}
+
 int eval_push(qsv_t* h, size_t first, size_t count, const double* values, const double* device_values = nullptr) {
     qsv_handle::Batch& b = h->batch;
     if (first != b.pushed) return fail(h, QSV_E_STATE, "evaluations must be pushed in order");
@@ -1779,8 +2044,12 @@ int eval_push(qsv_t* h, size_t first, size_t count, const double* values, const 
             h->work = nullptr;
             h->stamping = false;
             h->batch.dev_params = nullptr;  // (a property of the push: other paths lay batches out and ship them too)
+            h->batch.record.recording = false;
+            h->timing.in_push = false;
         }
     } guard{h};
+    PhaseClock push_clock(h, &PhaseClock::Timing::push_us);
+    h->timing.in_push = h->timing.on;
     h->stamping = h->profiling;
     EvalDesc* hd = static_cast<EvalDesc*>(h->h_batch);  // pinned; prepare_kernel reads it after this point
     if (b.repeat && !(first == 0 && count == b.circs.size())) {
@@ -1795,10 +2064,23 @@ int eval_push(qsv_t* h, size_t first, size_t count, const double* values, const 
         QSV_HIP(h, sync_streams(h));
         h->async_pending = false;
     }
-    b.whole_push = first == 0 && count == b.circs.size();
     // (values in device memory: the descriptors' offsets are those of the staging buffer, so the base is where evaluation 0's
     // values would be)
     b.dev_params = device_values && count > 0 ? device_values - b.param_base[first] : nullptr;
+    const bool whole = first == 0 && count == b.circs.size();
+    qsv_handle::Batch::LaunchRecord& rec = b.record;
+    // (a record is made, and used, only where nothing but the call's own pointers can differ from one call to the next: no mask,
+    // no per-launch events, descriptors that the kernels read where the host left them)
+    const bool record_ok = whole && h->replay_enabled && h->repeat_enabled && !h->profiling && !h->mask.flags && !h->bar_ship && count > 0;
+    const bool no_direct_env = h->geo.blocks_per_state == 1 && h->diagonal && getenv("QSV_NO_DIRECT") != nullptr;
+    if (b.repeat && record_ok && rec.usable && rec.epoch == h->epoch && rec.ways == b.ways && rec.no_direct_env == no_direct_env)
+        return replay_push(h, count, values);
+    b.whole_push = whole;
+    rec.recording = !b.repeat && record_ok && b.have_ids;
+    if (rec.recording) {
+        rec.entries.clear();
+        rec.usable = rec.spoiled = false;
+    }
     const size_t ways = size_t(std::max(1, b.ways)), lane = ways > 1 ? size_t(b.n_pushes) % ways : 0;
     const size_t P = b.circs.size();
     size_t n_cont = b.snap_n_cont;
@@ -1839,6 +2121,7 @@ int eval_push(qsv_t* h, size_t first, size_t count, const double* values, const 
     h->chain_stream = -1;
     const size_t push_index = b.n_pushes;
     if (b.chain_crossed && push_index >= ways && h->n_lane_streams >= 1) {
+        record_spoil(h);
         QSV_HIP(h, hipEventRecord(h->ev_join, h->stream));
         QSV_HIP(h, hipStreamWaitEvent(h->side_streams[0], h->ev_join, 0));
         QSV_HIP(h, hipEventRecord(h->ev_join, h->side_streams[0]));
@@ -1859,6 +2142,7 @@ int eval_push(qsv_t* h, size_t first, size_t count, const double* values, const 
         if (n_fused == n_split && n_halved > 0 && working > size_t(h->n_cus)) b.chain_now = true;
     }
     if (b.chain_now) {
+        record_spoil(h);  // (two streams, and events between them)
         h->chain_stream = lane == 0 ? 0 : -2;  // (-2: the handle's own stream, lane 0's)
         b.chain_crossed = true;
         if (lane == 0) {
@@ -1913,19 +2197,19 @@ int eval_push(qsv_t* h, size_t first, size_t count, const double* values, const 
             QSV_HIP(h, stamp(h, b.exp_events, true));
             // (an operator may have more x-mask groups than gridDim.y can be: slices of the groups, the partial sums where one
             // launch puts them)
-            for (int g1 = 0; g1 < h->n_groups; g1 += h->max_grid_y)
-                QSV_HIP(h, launch_pauli_groups(h->dtype, h->d_states.ptr, uint64_t(1) << h->n, h->n, int(gc), h->n_groups,
-                                               static_cast<const PauliGroup*>(h->d_groups.ptr),
-                                               static_cast<const uint64_t*>(h->d_z.ptr),
-                                               static_cast<const double*>(h->d_cre.ptr),
-                                               static_cast<const uint32_t*>(h->d_term_odd.ptr), h->pauli_nb,
-                                               static_cast<double*>(h->d_term_partials.ptr), h->stream, g1,
-                                               std::min(h->max_grid_y, h->n_groups - g1)));
-            QSV_HIP(h, launch_pauli_combine(static_cast<const double*>(h->d_term_partials.ptr),
-                                            uint32_t(h->n_groups) * uint32_t(h->pauli_nb),
-                                            h->has_diag_part ? static_cast<const double*>(h->d_partials.ptr) : nullptr,
-                                            partials_per_state(h), int(gc), batch_evals(h) + g0,
-                                            static_cast<double*>(h->d_out.ptr), h->stream));
+            for (int g1 = 0; g1 < h->n_groups; g1 += h->max_grid_y) {
+                QSV_LAUNCH(h, launch_pauli_groups_of(h, int(gc), g1, std::min(h->max_grid_y, h->n_groups - g1)));
+                if (LaunchEntry* e = record_entry(h, LaunchEntry::PauliGroups, h->stream)) {
+                    e->n = int(gc);
+                    e->n2 = g1;
+                    e->n3 = std::min(h->max_grid_y, h->n_groups - g1);
+                }
+            }
+            QSV_LAUNCH(h, launch_pauli_combine_of(h, int(gc), batch_evals(h) + g0));
+            if (LaunchEntry* e = record_entry(h, LaunchEntry::PauliCombine, h->stream)) {
+                e->n = int(gc);
+                e->evals = batch_evals(h) + g0;
+            }
             QSV_HIP(h, stamp(h, b.exp_events, false));
         }
     }
@@ -1934,23 +2218,36 @@ int eval_push(qsv_t* h, size_t first, size_t count, const double* values, const 
         // cross-stream join in front of one final reduction (the join alone cost 15-30 us at the end of every call).
         QSV_HIP(h, stamp(h, b.exp_events, true));
         h->work = n_split > 0 && factor_path(h) ? plain_stream : lane_stream;
-        if (n_split > 0 && factor_path(h))  // (the split evaluations' results are already there: the others, by descriptor)
-            QSV_HIP(h, launch_reduce_partials(static_cast<const double*>(h->d_partials.ptr), partials_per_state(h),
-                                              int(count - n_split), h->out_target ? h->out_target : h->h_out, ws(h),
-                                              batch_evals(h) + first + n_split));
-        else
-            QSV_HIP(h, launch_reduce_partials(static_cast<const double*>(h->d_partials.ptr) + first * size_t(partials_per_state(h)),
-                                              partials_per_state(h), int(count), (h->out_target ? h->out_target : h->h_out) + first,
-                                              ws(h)));
+        LaunchEntry* e = record_entry(h, LaunchEntry::Reduce, ws(h));
+        if (n_split > 0 && factor_path(h)) {  // (the split evaluations' results are already there: the others, by descriptor)
+            QSV_LAUNCH(h, launch_reduce_partials(static_cast<const double*>(h->d_partials.ptr), partials_per_state(h),
+                                                 int(count - n_split), result_base(h), ws(h), batch_evals(h) + first + n_split));
+            if (e) *e = reduce_entry(*e, static_cast<const double*>(h->d_partials.ptr), int(count - n_split), 0, batch_evals(h) + first + n_split);
+        } else {
+            QSV_LAUNCH(h, launch_reduce_partials(static_cast<const double*>(h->d_partials.ptr) + first * size_t(partials_per_state(h)),
+                                                 partials_per_state(h), int(count), result_base(h) + first, ws(h)));
+            if (e) *e = reduce_entry(*e, static_cast<const double*>(h->d_partials.ptr) + first * size_t(partials_per_state(h)), int(count), int64_t(first), nullptr);
+        }
+        if (e) e->blocks = partials_per_state(h);
         QSV_HIP(h, stamp(h, b.exp_events, false));
     }
     b.pushed = first + count;
+    if (rec.recording) {
+        rec.usable = !rec.spoiled;
+        rec.epoch = h->epoch;
+        rec.ways = b.ways;
+        rec.no_direct_env = no_direct_env;
+        rec.used_mask = b.used_mask;
+        rec.aux_count = b.aux_count;
+        rec.prof = h->prof;
+    }
     return QSV_OK;
 }
 
 int eval_end(qsv_t* h, double* out) {
     qsv_handle::Batch& b = h->batch;
     const size_t n_evals = b.circs.size();
+    PhaseClock end_clock(h, &PhaseClock::Timing::end_us);  // (the copy-out inside it is reported apart)
     if (b.pushed != n_evals) return fail(h, QSV_E_STATE, "not every evaluation of the batch was pushed");
     if (n_evals == 0) return QSV_OK;
     const unsigned used_mask = b.used_mask;
@@ -2018,10 +2315,13 @@ int eval_end(qsv_t* h, double* out) {
         for (size_t i = 0; i < h->side_streams.size(); ++i)
             if (used_mask >> i & 1u) QSV_HIP(h, hipStreamSynchronize(h->side_streams[i]));
     }
-    if (h->out_target) {  // (a waiting end of a batch with a device output: the caller also gets a host copy)
-        if (out) QSV_HIP(h, hipMemcpy(out, h->out_target, n_evals * sizeof(double), hipMemcpyDefault));
-    } else {
-        std::memcpy(out, h->h_out, n_evals * sizeof(double));
+    {
+        PhaseClock copy_clock(h, &PhaseClock::Timing::copy_us);
+        if (h->out_target) {  // (a waiting end of a batch with a device output: the caller also gets a host copy)
+            if (out) QSV_HIP(h, hipMemcpy(out, h->out_target, n_evals * sizeof(double), hipMemcpyDefault));
+        } else {
+            std::memcpy(out, h->h_out, n_evals * sizeof(double));
+        }
     }
 
     if (h->profiling) {
@@ -2411,6 +2711,8 @@ int qsv_create(int n_qubits, int dtype, int device, const qsv_plan_config* cfg, 
     if (const char* env = getenv("QSV_CHAIN_STREAM")) h->chain_enabled = atoi(env) != 0;
     if (const char* env = getenv("QSV_POLL")) h->poll_results = atoi(env) != 0;
     if (const char* env = getenv("QSV_REPEAT")) h->repeat_enabled = atoi(env) != 0;
+    if (const char* env = getenv("QSV_REPLAY")) h->replay_enabled = atoi(env) != 0;
+    if (const char* env = getenv("QSV_HOST_TIMING")) h->timing.on = atoi(env) != 0;
     if (const char* env = getenv("QSV_REPEAT_DESCS")) h->repeat_device_descs = atoi(env) != 0;
     if (const char* env = getenv("QSV_FUSED_LDS")) h->fused_lds_table = atoi(env) != 0;
     if (const char* env = getenv("QSV_SIDE_PREPARE")) h->side_prepare = atoi(env) != 0;
@@ -2488,6 +2790,15 @@ void qsv_destroy(qsv_t* h) {
     if (!h) return;
     if (getenv("QSV_COALESCE_DEBUG") && h->cq_batches)
         fprintf(stderr, "qsv_eval_coalesced: %llu batches, last expectation %zu\n", (unsigned long long)h->cq_batches, h->cq_expected);
+    if (h->timing.on && h->timing.calls) {
+        const qsv_handle::HostTiming& t = h->timing;
+        const double per = 1.0 / double(t.calls);
+        fprintf(stderr,
+                "qsv host timing over %llu qsv_eval_begin calls (%llu replayed pushes), us per call: begin %.2f  push without launch calls %.2f  "
+                "launch calls %.2f  end and poll %.2f  copy-out %.2f\n",
+                (unsigned long long)t.calls, (unsigned long long)t.replays, t.begin_us * per, (t.push_us - t.launch_us) * per,
+                t.launch_us * per, (t.end_us - t.copy_us) * per, t.copy_us * per);
+    }
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (hipStream_t st : h->side_streams) {
@@ -3052,6 +3363,8 @@ int qsv_eval_begin(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t*
     std::unique_lock<std::mutex> lock(h->mu);
     if (h->batch.open) return fail(h, QSV_E_STATE, "a batch is already open on this handle");
     if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_counts))) return fail(h, QSV_E_ARG, "bad arguments");
+    PhaseClock begin_clock(h, &PhaseClock::Timing::begin_us);
+    h->timing.calls += 1;
     QSV_HIP(h, hipSetDevice(h->device));
     {
         // The previous batch again (same circuits, same counts, nothing changed in between -- an optimiser's next iteration):
@@ -4556,6 +4869,8 @@ int qsv_set_option(qsv_t* h, const char* name, int value) {
         h->poll_results = value != 0;
     } else if (key == "repeat_layout") {
         h->repeat_enabled = value != 0;
+    } else if (key == "replay_launches") {  // a repeated whole-push batch queues its recorded launches again (the same launches, the same bits)
+        h->replay_enabled = value != 0;
     } else if (key == "split_max_keys") {
         if (value < 0 || value > kMaxSplitKeys) return fail(h, QSV_E_ARG, "split_max_keys must be between 0 and 5");
         h->split_max_keys = value;
@@ -4596,6 +4911,12 @@ int qsv_set_profiling(qsv_t* h, int enabled) {
     h->epoch += 1;
     h->profiling = enabled != 0;
     return QSV_OK;
+}
+
+long long qsv_replayed_pushes(const qsv_t* h) {
+    if (!h) return QSV_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    return (long long)h->replayed_pushes;
 }
 
 int qsv_get_profile(const qsv_t* h, qsv_profile* out) {
