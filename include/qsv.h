@@ -634,6 +634,59 @@ typedef struct qsv_gradient_plan_stats_t {
 } qsv_gradient_plan_stats_t;
 int qsv_gradient_plan_stats(const qsv_t* h, int plan_id, qsv_gradient_plan_stats_t* out);
 
+/*
+ * ADJOINT GRADIENTS: the same derivatives from ONE reverse sweep of the state per evaluation instead of two
+ * or four circuit evaluations per entry -- for circuits that go through the state (route QSV_ROUTE_PASSES), where a shifted
+ * evaluation costs a sweep per gate pass and a gradient thousands of them.  With E = Re<psi|H|psi>, psi = U_G ... U_1 |0..0>
+ * and H_h the Hermitian part of H (what qsv_set_operator keeps): psi_G = psi, lambda_G = H_h psi; for g = G .. 1,
+ * psi_(g-1) = U_g^dagger psi_g, every angle slot a of gate g that reads a parameter adds 2 Re<lambda_g| dU_g/da |psi_(g-1)> to
+ * that parameter's entry (for cu3 the derivative's control-0 block is zero), then lambda_(g-1) = U_g^dagger lambda_g.  id gates
+ * and literal angles add nothing; a parameter no gate reads has entry 0.0; a parameter SEVERAL angle slots read gets the sum --
+ * what parameter shift refuses.  E = Re<psi|lambda_G> comes as a by-product.
+ *
+ * qsv_adjoint_describe (no handle, no device): how the sweep of a circuit differentiated by wrt[0 .. n_wrt) (n_wrt < 0: by every
+ * parameter) is cut into RUNS -- consecutive gates, walked last to first, whose targets and controls lie among the qubits of one
+ * workgroup tile (*out_tile_bits qubits, the lowest *out_low_bits always among them; both may be NULL).  The sweep ends at the
+ * earliest gate that reads a requested parameter; gates in front of it are never swept.  Returns the number of runs (the first
+ * capacity_runs of them are written: run r's tile qubits out_masks[r], its smallest and largest op index out_first_op[r] /
+ * out_last_op[r]; run 0 holds the circuit's last gates) and *out_n_gates, the non-id gates swept; QSV_E_ARG for an op kind, a
+ * qubit, a parameter or a wrt index out of range.  A gate's run and that run's mask do not depend on wrt.
+ */
+int qsv_adjoint_describe(int n_qubits, int n_ops, const qsv_op* ops, int n_params, int n_wrt, const int32_t* wrt, int capacity_runs,
+                         uint64_t* out_masks, int32_t* out_first_op, int32_t* out_last_op, int64_t* out_n_gates,
+                         int32_t* out_tile_bits, int32_t* out_low_bits);
+/*
+ * Gradients by the adjoint sweep: arguments, wrt_offsets / wrt and the layout of `out` as qsv_gradient_circuits, plus
+ * out_values (may be NULL): E of every evaluation.  Each launch group's circuits run their ordinary plans into state slots (no
+ * split route, as qsv_prefix_create runs them), then on the handle's stream: lambda = H_h psi into a scratch buffer of one
+ * launch group's states (allocated on first need, grown by need), one launch per run, one combination.  Deterministic: an
+ * evaluation's row and value are the same bits in any batch, at any position of a launch group, from either entry point and
+ * on every call, and the entries of a wrt subset are, bit for bit, those entries of the full gradient.
+ * Errors: no operator set QSV_E_STATE; a wrt index outside the circuit's parameters QSV_E_ARG; a circuit on a kept state
+ * QSV_E_UNSUPPORTED.
+ */
+int qsv_adjoint_gradient_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
+                                  const int64_t* wrt_offsets /* NULL: every parameter of each circuit */, const int32_t* wrt,
+                                  double* out /* host; packed back to back by the wrt counts */, double* out_values /* may be NULL */);
+/*
+ * The same with the points READ FROM and the gradients LEFT IN device memory, with qsv_gradient_device's layout (rows of `width`
+ * / out_width doubles, zeros behind a row's entries, out_width smaller than an evaluation's entries QSV_E_ARG), its ready_event
+ * and its stream contract: queued on the handle's stream, not waited for.  device_out_values (may be NULL): n_evals doubles.
+ */
+int qsv_adjoint_gradient_device(qsv_t* h, int n_evals, const int* circuit_ids, int width, const double* device_values, void* ready_event,
+                                const int64_t* wrt_offsets, const int32_t* wrt, int out_width, double* device_out,
+                                double* device_out_values /* may be NULL */);
+/* Counters of the last adjoint call: gates swept and states swept (one for H and one per run, summed over its evaluations), launches
+ * of the run kernel; the scratch's present size in device memory and how often it was allocated or grown since the handle was created. */
+typedef struct qsv_adjoint_stats_t {
+    int64_t n_gates;
+    int64_t n_runs;
+    int64_t n_state_sweeps;
+    int64_t scratch_bytes;
+    int64_t n_allocations;
+} qsv_adjoint_stats_t;
+int qsv_adjoint_stats(const qsv_t* h, qsv_adjoint_stats_t* out);
+
 /* ---- several observables per evaluation ---------------------------------------------------------- */
 
 /*

@@ -192,6 +192,18 @@ class QsvGradientPlanStats(C.Structure):
     ]
 
 
+class QsvAdjointStats(C.Structure):
+    """``qsv_adjoint_stats_t`` of include/qsv.h."""
+
+    _fields_ = [
+        ("n_gates", C.c_int64),
+        ("n_runs", C.c_int64),
+        ("n_state_sweeps", C.c_int64),
+        ("scratch_bytes", C.c_int64),
+        ("n_allocations", C.c_int64),
+    ]
+
+
 class QsvValueCacheStats(C.Structure):
     """``qsv_value_cache_stats_t`` of include/qsv.h."""
 
@@ -267,6 +279,11 @@ SIGNATURES = {
     "qsv_gradient_plan_run": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "qsv_gradient_plan_destroy": (C.c_int, [_P, C.c_int]),
     "qsv_gradient_plan_stats": (C.c_int, [_P, C.c_int, C.POINTER(QsvGradientPlanStats)]),
+    "qsv_adjoint_describe": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "qsv_adjoint_gradient_circuits": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "qsv_adjoint_gradient_device": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P]),
+    "qsv_adjoint_stats": (C.c_int, [_P, C.POINTER(QsvAdjointStats)]),
     "qsv_observables_create": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.POINTER(C.c_int)]),
     "qsv_observables_destroy": (C.c_int, [_P, C.c_int]),
     "qsv_eval_observables": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),

@@ -41,7 +41,7 @@ from queasars_amd.circuit_evaluation.expectation_calculation import (
     get_expectation_with_bitstring_evaluator,
     get_expectation_with_operator,
 )
-from queasars_amd.ir import QSV_OP_DTYPE, CircuitIR, PauliOperator
+from queasars_amd.ir import OP_ID, QSV_OP_DTYPE, CircuitIR, PauliOperator
 
 
 class CircuitEvaluatorException(Exception):
@@ -1110,6 +1110,62 @@ class StatevectorDevice:
         self._check(self._lib.qsv_gradient_stats(self._handle, C.byref(stats)))
         return {name: int(getattr(stats, name)) for name, _ in _lib.QsvGradientStats._fields_}
 
+    # -- adjoint gradients ------------------------------------------------------------------------
+    def adjoint_gradients(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]], wrt=None,
+                          return_values: bool = False):
+        """The gradients :meth:`gradients` returns, from one reverse sweep of the state per circuit
+        (``qsv_adjoint_gradient_circuits``) instead of shifted evaluations: one 1-D array per circuit, ``wrt`` as
+        there.  A parameter that several angle slots read gets the sum over them (parameter shift refuses it).  With
+        ``return_values`` also the expectation values, a by-product of the sweep: ``(gradients, values)``.
+        :attr:`last_gradient_evaluations` counts ONE per (circuit, point)."""
+        n = len(circuits)
+        if len(parameter_values) != n:
+            raise ValueError("circuits and parameter_values must have the same length")
+        self.last_gradient_evaluations = 0
+        if n == 0:
+            return ([], np.zeros(0)) if return_values else []
+        ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
+        wrt_offsets, wrt_flat, counts = self._wrt_arguments(circuits, wrt)
+        out = np.zeros(max(1, int(counts.sum())), dtype=np.float64)
+        values = np.zeros(n, dtype=np.float64)
+        self._check_gradient(self._lib.qsv_adjoint_gradient_circuits(
+            self._handle, n, _lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat),
+            _lib.as_ptr(wrt_offsets) if wrt_offsets is not None else None, _lib.as_ptr(wrt_flat) if wrt_flat is not None else None,
+            _lib.as_ptr(out), _lib.as_ptr(values)))
+        self.last_gradient_evaluations = n
+        ends = np.cumsum(counts)
+        gradients = [out[int(e - c): int(e)].copy() for c, e in zip(counts, ends)]
+        return (gradients, values) if return_values else gradients
+
+    def adjoint_gradients_of_device_parameters(self, circuits: Sequence[CircuitIR], matrix_ptr: int, width: int, event: int, out_ptr: int,
+                                               out_width: int, wrt=None, values_ptr: int = 0) -> int:
+        """:meth:`adjoint_gradients` with the layout and the contract of :meth:`gradients_of_device_parameters`
+        (``qsv_adjoint_gradient_device``): points read from and gradients left in device memory, queued on the handle's stream,
+        not waited for.  ``values_ptr``: device memory for ``len(circuits)`` expectation values, or 0.  Returns
+        ``len(circuits)``, the evaluations counted."""
+        n = len(circuits)
+        self.last_gradient_evaluations = 0
+        if n == 0:
+            return 0
+        if width < 0 or (width > 0 and not matrix_ptr) or out_width < 0 or (out_width > 0 and not out_ptr):
+            raise ValueError("matrix_ptr / width / out_ptr / out_width do not describe a matrix and its gradients")
+        ids, _need, _total = self._batch_metadata(circuits)
+        wrt_offsets, wrt_flat, _counts = self._wrt_arguments(circuits, wrt)
+        self._check_gradient(self._lib.qsv_adjoint_gradient_device(
+            self._handle, n, _lib.as_ptr(ids), int(width), C.c_void_p(matrix_ptr) if width else None,
+            C.c_void_p(event) if event else None, _lib.as_ptr(wrt_offsets) if wrt_offsets is not None else None,
+            _lib.as_ptr(wrt_flat) if wrt_flat is not None else None, int(out_width), C.c_void_p(out_ptr) if out_width else None,
+            C.c_void_p(values_ptr) if values_ptr else None))
+        self.last_gradient_evaluations = n
+        return n
+
+    def adjoint_stats(self) -> dict:
+        """``qsv_adjoint_stats``: the last adjoint call's swept gates, run-kernel launches and state sweeps, the adjoint scratch's
+        size and how often it was allocated or grown since the device was created."""
+        stats = _lib.QsvAdjointStats()
+        self._check(self._lib.qsv_adjoint_stats(self._handle, C.byref(stats)))
+        return {name: int(getattr(stats, name)) for name, _ in _lib.QsvAdjointStats._fields_}
+
     # -- several observables ---------------------------------------------------------------------
     MAX_OBSERVABLE_SETS = 16
 
@@ -1385,6 +1441,18 @@ class EvaluatorGradientPlan:
         self._plan.close()
 
 
+#: how an :class:`OperatorCircuitEvaluator` differentiates
+GRADIENT_METHODS = ("parameter_shift", "adjoint", "auto")
+
+
+def _has_shared_parameter(circuit: CircuitIR) -> bool:
+    """Does more than one angle slot of ``circuit`` read the same parameter?  (``id`` gates read nothing.)"""
+    rows = circuit.packed()
+    slots = np.concatenate([rows[name][rows["kind"] != OP_ID] for name in ("p_theta", "p_phi", "p_lambda")])
+    slots = slots[slots >= 0]
+    return len(np.unique(slots)) != len(slots)
+
+
 class OperatorCircuitEvaluator(BaseCircuitEvaluator):
     """Exact expectation values of ``operator`` on the GPU (estimator branch of the reference).
 
@@ -1393,6 +1461,12 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         value, seeded by ``seed`` (the reference's estimators emulate shot noise this way; 0 = exact)
     :param initial_state_circuit: optional circuit prepended to every evaluated circuit; it must not have free
         parameters and must act on exactly as many qubits as the operator
+    :param gradient_method: how :meth:`evaluate_gradients` and :meth:`evaluate_gradients_device_to_device` differentiate:
+        ``"parameter_shift"`` (the default; two or four circuit evaluations per entry), ``"adjoint"`` (one reverse sweep of the
+        state per circuit; also for parameters that several angle slots read) or ``"auto"``: the adjoint
+        sweep for a circuit whose ``circuit_cost`` route is ``"gate passes"`` or that has a parameter several slots read,
+        parameter shift for every other circuit.  ``last_gradient_evaluations`` counts one per (circuit, point) for circuits
+        differentiated by the sweep.  A device-resident Adam search needs ``"parameter_shift"``.
     """
 
     def __init__(
@@ -1404,11 +1478,15 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         device: int = 0,
         seed: Optional[int] = None,
         statevector_device: Optional[StatevectorDevice] = None,
+        gradient_method: str = "parameter_shift",
     ):
         if not isinstance(operator, PauliOperator):
             raise ValueError("The operator must be a PauliOperator!")
         if estimator_precision < 0:
             raise ValueError("estimator_precision must not be negative!")
+        if gradient_method not in GRADIENT_METHODS:
+            raise ValueError(f"gradient_method must be one of {GRADIENT_METHODS}, got {gradient_method!r}")
+        self.gradient_method = gradient_method
         _check_initial_state(initial_state_circuit, operator.num_qubits, "the amount of qubits in the given operator")
         if initial_state_circuit is not None and initial_state_circuit.num_parameters:
             raise ValueError("The initial state circuit must not have free parameters!")
@@ -1494,15 +1572,19 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
                 self._device.set_operator(self._operator)
             return self._evaluate_device_matrix(circuits, matrix, ready)
 
-    #: circuit evaluations the last :meth:`evaluate_gradients` / :meth:`evaluate_gradients_device_to_device` call ran
+    #: circuit evaluations the last :meth:`evaluate_gradients` / :meth:`evaluate_gradients_device_to_device` call ran (a circuit
+    #: differentiated by the adjoint sweep counts ONE per point)
     last_gradient_evaluations = 0
+    #: ... per circuit, for the methods "adjoint" and "auto" of :meth:`evaluate_gradients`
+    last_gradient_evaluation_counts: list = []
 
     def evaluate_gradients(self, circuits: list[CircuitIR], parameter_values: list[list[float]], wrt=None) -> list[np.ndarray]:
-        """Exact gradients of :meth:`evaluate_circuits` by parameter shift on the device
-        (:meth:`StatevectorDevice.gradients`): one 1-D array per circuit, entry j the derivative by parameter ``wrt[j]`` of that
+        """Exact gradients of :meth:`evaluate_circuits` on the device, by the evaluator's ``gradient_method`` -- parameter shift
+        (:meth:`StatevectorDevice.gradients`, the default), the adjoint sweep (:meth:`StatevectorDevice.adjoint_gradients`) or
+        one of the two per circuit ("auto"): one 1-D array per circuit, entry j the derivative by parameter ``wrt[j]`` of that
         circuit (``wrt``: None for every parameter, one list of indices for all circuits, or one list per circuit).  The
         initial state circuit's literal angles carry no parameters: indices are the circuit's own.
-        :attr:`last_gradient_evaluations` counts the circuit evaluations the call ran."""
+        :attr:`last_gradient_evaluations` counts the circuit evaluations the call ran (one per circuit the sweep took)."""
         if self._precision > 0:
             raise ValueError("estimator_precision > 0 is emulated on the host: gradients are exact")
         if self._initial_state_circuit is not None:
@@ -1510,10 +1592,62 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         with self._device.operator_lock:
             if self._device._operator is not self._operator:
                 self._device.set_operator(self._operator)
-            try:
-                return self._device.gradients(circuits, parameter_values, wrt)
-            finally:
-                self.last_gradient_evaluations = self._device.last_gradient_evaluations
+            if self.gradient_method == "parameter_shift":
+                try:
+                    return self._device.gradients(circuits, parameter_values, wrt)
+                finally:
+                    self.last_gradient_evaluations = self._device.last_gradient_evaluations
+            return self._gradients_by_method(circuits, parameter_values, wrt)
+
+    def _adjoint_rows(self, circuits) -> list[int]:
+        """The circuits of a gradient call that go to the adjoint sweep under this evaluator's method (operator lock held)."""
+        if self.gradient_method == "adjoint":
+            return list(range(len(circuits)))
+        self._device._register_many([c for c in circuits if self._device._serial not in c._registered])
+        return [i for i, c in enumerate(circuits)
+                if self._device.circuit_cost(c)["route"] == "gate passes" or _has_shared_parameter(c)]
+
+    @staticmethod
+    def _wrt_per_circuit(n: int, wrt):
+        """``wrt`` of a gradient call as one entry per circuit (None: every parameter)."""
+        if wrt is None:
+            return [None] * n
+        wrt = list(wrt)
+        if all(np.ndim(w) == 0 for w in wrt):
+            return [wrt] * n
+        if len(wrt) != n:
+            raise ValueError("wrt must be None, one list of parameter indices, or one list per circuit")
+        return wrt
+
+    def _gradients_by_method(self, circuits, parameter_values, wrt) -> list[np.ndarray]:
+        """``evaluate_gradients`` for "adjoint" and "auto": the batch split by method, the rows put back in the caller's order
+        (operator lock held)."""
+        n = len(circuits)
+        self.last_gradient_evaluations = 0
+        if n == 0:
+            return []
+        per_circuit = self._wrt_per_circuit(n, wrt)
+        sweep = self._adjoint_rows(circuits)
+        taken = set(sweep)
+        shift = [i for i in range(n) if i not in taken]
+        out: list = [None] * n
+        evaluations = 0
+        counts = [1] * n
+        for i in shift:
+            terms = circuits[i].gradient_terms()
+            counts[i] = sum(max(0, terms[p]) for p in (range(len(terms)) if per_circuit[i] is None else per_circuit[i]))
+        self.last_gradient_evaluation_counts = counts
+        for rows, method in ((sweep, self._device.adjoint_gradients), (shift, self._device.gradients)):
+            if not rows:
+                continue
+            part_wrt = None if wrt is None else [
+                list(range(circuits[i].num_parameters)) if per_circuit[i] is None else per_circuit[i] for i in rows]
+            part = method([circuits[i] for i in rows], [parameter_values[i] for i in rows], part_wrt)
+            evaluations += self._device.last_gradient_evaluations
+            for i, row in zip(rows, part):
+                out[i] = row
+        self.last_gradient_evaluations = evaluations
+        return out
 
     def evaluate_gradients_device_to_device(self, circuits: list[CircuitIR], matrix, out, wrt=None) -> None:
         """Points from a device matrix (one row per circuit), gradients into the 2-D device tensor ``out`` (one row per
@@ -1534,11 +1668,51 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         with self._device.operator_lock:
             if self._device._operator is not self._operator:
                 self._device.set_operator(self._operator)
-            try:
-                self._device.gradients_of_device_parameters(circuits, pointer, width, event, out.data_ptr(), out.shape[1], wrt)
-            finally:
-                self.last_gradient_evaluations = self._device.last_gradient_evaluations
+            if self.gradient_method == "parameter_shift":
+                try:
+                    self._device.gradients_of_device_parameters(circuits, pointer, width, event, out.data_ptr(), out.shape[1], wrt)
+                finally:
+                    self.last_gradient_evaluations = self._device.last_gradient_evaluations
+            else:
+                self._gradients_device_by_method(circuits, matrix, pointer, width, event, out, wrt)
         remember()
+
+    def _gradients_device_by_method(self, circuits, matrix, pointer, width, event, out, wrt) -> None:
+        """``evaluate_gradients_device_to_device`` for "adjoint" and "auto" (operator lock held).  A batch that one method takes
+        whole is queued where it is and not waited for; a MIXED one goes through gathered copies of the points and scatters the
+        rows back with torch, whose stream need not be the handle's: such a call waits for the device around each part."""
+        import torch
+
+        n = len(circuits)
+        self.last_gradient_evaluations = 0
+        if n == 0:
+            return
+        sweep = self._adjoint_rows(circuits)
+        if len(sweep) == n:
+            self._device.adjoint_gradients_of_device_parameters(circuits, pointer, width, event, out.data_ptr(), out.shape[1], wrt)
+            self.last_gradient_evaluations = n
+            return
+        if not sweep:
+            self._device.gradients_of_device_parameters(circuits, pointer, width, event, out.data_ptr(), out.shape[1], wrt)
+            self.last_gradient_evaluations = self._device.last_gradient_evaluations
+            return
+        per_circuit = self._wrt_per_circuit(n, wrt)
+        taken = set(sweep)
+        shift = [i for i in range(n) if i not in taken]
+        evaluations = 0
+        for rows, method in ((sweep, self._device.adjoint_gradients_of_device_parameters),
+                             (shift, self._device.gradients_of_device_parameters)):
+            index = torch.tensor(rows, dtype=torch.int64, device=matrix.device)
+            points = matrix.index_select(0, index).contiguous()
+            part = torch.zeros((len(rows), out.shape[1]), dtype=torch.float64, device=matrix.device)
+            part_wrt = None if wrt is None else [
+                list(range(circuits[i].num_parameters)) if per_circuit[i] is None else per_circuit[i] for i in rows]
+            torch.cuda.synchronize(matrix.device)  # (the gathered points are complete)
+            method([circuits[i] for i in rows], points.data_ptr(), int(points.shape[1]), 0, part.data_ptr(), int(part.shape[1]), part_wrt)
+            evaluations += self._device.last_gradient_evaluations
+            torch.cuda.synchronize(matrix.device)  # (... and so are the part's rows)
+            out.index_copy_(0, index, part)
+        self.last_gradient_evaluations = evaluations
 
     def gradient_plan(self, circuits: list[CircuitIR], matrix, out, wrt=None) -> "EvaluatorGradientPlan":
         """:meth:`evaluate_gradients_device_to_device` prepared once for ``circuits``, ``wrt`` and the shapes of ``matrix`` and

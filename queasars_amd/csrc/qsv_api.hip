@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/qsv.h"
+#include "adjoint.hpp"
 #include "gradient.hpp"
 #include "value_cache.hpp"
 #include "kernels.hpp"
@@ -76,6 +77,7 @@ struct Circuit {
     uint32_t plan_base = 0;         // word offset in the device arena
     int prefix_id = -1;             // >= 0: the circuit continues that kept state (qsv_circuit_create_on_prefix) instead of |0..0>
     std::vector<int32_t> grad_terms;  // per parameter: shifted evaluations its derivative takes (gradient.hpp: gradient_plan)
+    std::vector<qsv_op> ops;          // the ops as they were registered: what the adjoint sweep plans and differentiates (adjoint.hpp)
 };
 
 // A kept state (qsv_prefix_create): one slot of the handle's prefix buffer, alive while the caller holds it or a circuit
@@ -465,6 +467,11 @@ struct qsv_handle {
         int plan_id = 0;
         size_t n_evals = 0;
     } plan_snap;
+    // adjoint gradients (qsv_adjoint_gradient_circuits / qsv_adjoint_gradient_device; adjoint.hpp): lambda of one launch group's
+    // states, the call's tables, the group's gate matrices and partial sums; the host form's points, rows and values
+    DeviceBuffer d_adj_lambda, d_adj_tab, d_adj_mats, d_adj_partials, d_adj_epart, d_adj_base, d_adj_out, d_adj_values;
+    const void* adj_checked[3] = {nullptr, nullptr, nullptr};  // qsv_adjoint_gradient_device's pointers last found to be this device's memory
+    qsv_adjoint_stats_t adj_stats{};
     uint64_t host_waits = 0;  // times the host waited for a stream or an event (sync_streams and the few direct waits a batch can meet)
 
     // device-resident value caches (qsv_value_cache_create; value_cache.hpp)
@@ -682,6 +689,7 @@ int build_circuit(qsv_t* h, int n_ops, const qsv_op* ops, int n_params, bool fol
         }
     }
     out->n_params = n_params;
+    out->ops.assign(ops, ops + n_ops);
     out->grad_terms.assign(size_t(n_params), 0);
     (void)gradient_plan(n_ops, ops, n_params, out->grad_terms.data());
     std::vector<AngleSource> angles;
@@ -2809,7 +2817,8 @@ void qsv_destroy(qsv_t* h) {
     for (DeviceBuffer* b : {&h->d_z, &h->d_cre, &h->d_diag, &h->d_order, &h->d_sorted, &h->d_term_partials, &h->d_groups, &h->d_term_odd, &h->d_arena,
                             &h->d_states, &h->d_wtab, &h->d_side, &h->d_factor, &h->d_factor_count, &h->d_factor_big, &h->d_factor_big_count, &h->d_quad, &h->d_fterms, &h->d_fpart, &h->d_batch, &h->d_mats, &h->d_partials, &h->d_out, &h->d_scratch, &h->d_prefix, &h->d_sdiag,
                             &h->d_obs_partials, &h->d_obs_values, &h->d_grad_tab, &h->d_grad_rows, &h->d_grad_values, &h->d_grad_base,
-                            &h->d_grad_out})
+                            &h->d_grad_out, &h->d_adj_lambda, &h->d_adj_tab, &h->d_adj_mats, &h->d_adj_partials, &h->d_adj_epart, &h->d_adj_base,
+                            &h->d_adj_out, &h->d_adj_values})
         if (b->ptr) (void)hipFree(b->ptr);
     for (auto& kv : h->obs_sets) free_observable_set(kv.second);
     for (auto& kv : h->value_caches) free_value_cache(kv.second);
@@ -4586,6 +4595,310 @@ int qsv_gradient_stats(const qsv_t* h, qsv_gradient_stats_t* out) {
     std::lock_guard<std::mutex> lock(h->mu);
     *out = h->grad_stats;
     out->scratch_bytes = int64_t(h->d_grad_tab.bytes + h->d_grad_rows.bytes + h->d_grad_values.bytes + h->d_grad_base.bytes + h->d_grad_out.bytes);
+    return QSV_OK;
+}
+
+// ---- adjoint gradients (qsv.h: ADJOINT GRADIENTS; adjoint.hpp) -----------------------------------------------------------------
+
+int qsv_adjoint_describe(int n_qubits, int n_ops, const qsv_op* ops, int n_params, int n_wrt, const int32_t* wrt, int capacity_runs,
+                         uint64_t* out_masks, int32_t* out_first_op, int32_t* out_last_op, int64_t* out_n_gates,
+                         int32_t* out_tile_bits, int32_t* out_low_bits) {
+    if (capacity_runs < 0 || (capacity_runs > 0 && (!out_masks || !out_first_op || !out_last_op))) return QSV_E_ARG;
+    AdjointPlan plan;
+    const int rc = adjoint_plan(n_qubits, n_ops, ops, n_params, n_wrt, wrt, &plan);
+    if (rc) return rc;
+    for (size_t r = 0; r < plan.runs.size() && r < size_t(capacity_runs); ++r) {
+        out_masks[r] = plan.runs[r].mask;
+        out_first_op[r] = plan.runs[r].first_op;
+        out_last_op[r] = plan.runs[r].last_op;
+    }
+    if (out_n_gates) *out_n_gates = int64_t(plan.gates.size());
+    if (out_tile_bits) *out_tile_bits = kAdjointTileBits;
+    if (out_low_bits) *out_low_bits = kAdjointLowBits;
+    return int(plan.runs.size());
+}
+
+// The points and the output of an adjoint call, all in device memory.
+struct AdjCall {
+    const double* base;
+    int width;
+    double* out;
+    int out_width;
+    double* out_values;
+};
+
+static int ensure_adjoint(qsv_t* h, DeviceBuffer& b, size_t bytes) {
+    if (!(b.bytes >= bytes && b.ptr)) h->adj_stats.n_allocations += 1;
+    return ensure(h, b, bytes);
+}
+
+// What both entry points run with the lock held: the call's tables, the forward run group by group, and behind each group the H
+// application, the runs and the combination on the handle's stream.  Returns without waiting.
+static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, const int64_t* wrt_offsets, const int32_t* wrt,
+                          const AdjCall& call) {
+    const size_t n_evals = args.circs.size();
+    if (h->n_terms == 0) return fail(h, QSV_E_STATE, "no operator set (call qsv_set_operator first)");
+    h->adj_stats.n_gates = h->adj_stats.n_runs = h->adj_stats.n_state_sweeps = 0;
+    // ---- the tables: per distinct circuit its swept gates, runs and the slots that read each parameter; per evaluation its entries
+    struct CircuitTables {
+        uint32_t gate_base, run_base, slot_base;
+        AdjointPlan plan;                 // differentiated by every parameter: every other sweep of the circuit is a front part of it
+        std::vector<uint32_t> slot_first;  // per parameter: its slots are slots[slot_base + slot_first[p] .. + slot_first[p + 1])
+    };
+    std::unordered_map<const Circuit*, CircuitTables> tables;
+    std::vector<AdjGate> gates;
+    std::vector<AdjRunDesc> runs;
+    std::vector<uint32_t> slots;
+    std::vector<AdjEntry> entries;
+    std::vector<int64_t> entry_offsets(n_evals + 1, 0);
+    std::vector<uint32_t> eval_runs(n_evals, 0), eval_gates(n_evals, 0);
+    uint32_t max_gates = 0;
+    for (size_t e = 0; e < n_evals; ++e) {
+        const Circuit& c = *args.circs[e];
+        if (call.width < c.n_params)
+            return fail(h, QSV_E_ARG, "circuit needs " + std::to_string(c.n_params) + " parameter values, got " + std::to_string(call.width));
+        const int64_t first = wrt_offsets ? wrt_offsets[e] : 0, count = wrt_offsets ? wrt_offsets[e + 1] - first : int64_t(c.n_params);
+        if (count < 0) return fail(h, QSV_E_ARG, "wrt_offsets must be non-decreasing");
+        if (count > call.out_width)
+            return fail(h, QSV_E_ARG, "out_width " + std::to_string(call.out_width) + " is too small for " + std::to_string(count) + " gradient entries");
+        if (count > 0 && wrt_offsets && !wrt) return fail(h, QSV_E_ARG, "wrt is null");
+        for (int64_t j = 0; wrt_offsets && j < count; ++j)
+            if (wrt[first + j] < 0 || wrt[first + j] >= c.n_params)
+                return fail(h, QSV_E_ARG, "wrt index " + std::to_string(wrt[first + j]) + " is outside the " + std::to_string(c.n_params) +
+                                              " parameters of circuit " + std::to_string(circuit_ids[e]));
+        auto it = tables.find(&c);
+        if (it == tables.end()) {
+            CircuitTables t;
+            if (adjoint_plan(h->n, int(c.ops.size()), c.ops.data(), c.n_params, -1, nullptr, &t.plan))
+                return fail(h, QSV_E_ARG, "circuit " + std::to_string(circuit_ids[e]) + " cannot be planned for the adjoint sweep");
+            t.gate_base = uint32_t(gates.size());
+            t.run_base = uint32_t(runs.size());
+            t.slot_base = uint32_t(slots.size());
+            std::vector<std::vector<uint32_t>> readers(size_t(c.n_params));
+            for (const AdjointRun& r : t.plan.runs) {
+                runs.push_back(AdjRunDesc{r.mask, uint32_t(r.first_gate), uint32_t(r.n_gates)});
+                for (int32_t g = r.first_gate; g < r.first_gate + r.n_gates; ++g) {
+                    const qsv_op& o = c.ops[size_t(t.plan.gates[size_t(g)])];
+                    auto tile_bit = [&](int q) { return uint8_t(__builtin_popcountll(r.mask & ((uint64_t(1) << q) - 1))); };
+                    AdjGate ag{};
+                    ag.kind = o.kind;
+                    ag.tpos = tile_bit(o.target);
+                    ag.cpos = o.kind == QSV_OP_CU3 ? tile_bit(o.control) : uint8_t(QSV_NO_CONTROL);
+                    const int32_t p[3] = {o.p_theta, o.p_phi, o.p_lambda};
+                    const double lit[3] = {o.theta, o.phi, o.lambda};
+                    for (int s = 0; s < 3; ++s) {
+                        ag.p[s] = p[s] >= 0 ? p[s] : -1;
+                        ag.lit[s] = lit[s];
+                        if (p[s] >= 0) readers[size_t(p[s])].push_back(uint32_t(3 * g + s));
+                    }
+                    gates.push_back(ag);
+                }
+            }
+            t.slot_first.assign(size_t(c.n_params) + 1, 0);
+            for (int p = 0; p < c.n_params; ++p) {
+                slots.insert(slots.end(), readers[size_t(p)].begin(), readers[size_t(p)].end());
+                t.slot_first[size_t(p) + 1] = t.slot_first[size_t(p)] + uint32_t(readers[size_t(p)].size());
+            }
+            it = tables.emplace(&c, std::move(t)).first;
+        }
+        const CircuitTables& t = it->second;
+        if (wrt_offsets) {  // (its own sweep: the front part of the circuit's that reaches the earliest gate reading one of ITS parameters)
+            AdjointPlan own;
+            (void)adjoint_plan(h->n, int(c.ops.size()), c.ops.data(), c.n_params, int(count), wrt + first, &own);
+            eval_runs[e] = uint32_t(own.runs.size());
+            eval_gates[e] = uint32_t(own.gates.size());
+        } else {
+            eval_runs[e] = uint32_t(t.plan.runs.size());
+            eval_gates[e] = uint32_t(t.plan.gates.size());
+        }
+        max_gates = std::max(max_gates, eval_gates[e]);
+        for (int64_t j = 0; j < count; ++j) {
+            const size_t p = size_t(wrt_offsets ? int64_t(wrt[first + j]) : j);
+            entries.push_back(AdjEntry{t.slot_base + t.slot_first[p], t.slot_first[p + 1] - t.slot_first[p]});
+        }
+        entry_offsets[e + 1] = int64_t(entries.size());
+        h->adj_stats.n_gates += int64_t(eval_gates[e]);
+        h->adj_stats.n_state_sweeps += 1 + int64_t(eval_runs[e]);
+    }
+    if (n_evals == 0) return QSV_OK;
+
+    // ---- the forward run's layout (ordinary plans into state slots, never split: as qsv_prefix_create runs them)
+    const size_t G = std::max<size_t>(1, std::min<size_t>(size_t(h->group), 4096));
+    const StateRun run{SplitRule{}, 1, G, false, 0, kModeSynthFirst | kModeFinalStore};
+    BatchRelease release{h};
+    StateLayout lay;
+    h->prof = qsv_profile{};
+    int rc = lay_out_states(h, args, run, lay);
+    if (rc) return rc;
+    std::vector<AdjEval> evals(n_evals);
+    for (size_t j = 0; j < n_evals; ++j) {
+        const size_t e = h->batch.eval_at[j];
+        const CircuitTables& t = tables.at(args.circs[e]);
+        evals[j] = AdjEval{t.gate_base, t.run_base, eval_runs[e], eval_gates[e], uint32_t(e), 0};
+    }
+    // one blob: [gates][runs][entries][entry offsets][slots, padded to 8 bytes][evaluations by position]
+    auto padded = [](size_t bytes) { return (bytes + 7) / 8 * 8; };
+    const size_t off_gates = 0, off_runs = off_gates + gates.size() * sizeof(AdjGate), off_entries = off_runs + runs.size() * sizeof(AdjRunDesc),
+                 off_offsets = off_entries + entries.size() * sizeof(AdjEntry), off_slots = off_offsets + entry_offsets.size() * sizeof(int64_t),
+                 off_evals = off_slots + padded(slots.size() * sizeof(uint32_t)), tab_bytes = off_evals + evals.size() * sizeof(AdjEval);
+    std::vector<char> blob(tab_bytes, 0);
+    auto put = [&](size_t off, const void* src, size_t bytes) {
+        if (bytes) std::memcpy(blob.data() + off, src, bytes);
+    };
+    put(off_gates, gates.data(), gates.size() * sizeof(AdjGate));
+    put(off_runs, runs.data(), runs.size() * sizeof(AdjRunDesc));
+    put(off_entries, entries.data(), entries.size() * sizeof(AdjEntry));
+    put(off_offsets, entry_offsets.data(), entry_offsets.size() * sizeof(int64_t));
+    put(off_slots, slots.data(), slots.size() * sizeof(uint32_t));
+    put(off_evals, evals.data(), evals.size() * sizeof(AdjEval));
+    const size_t gc_max = std::min(G, n_evals);
+    const uint64_t dim = uint64_t(1) << h->n;
+    const uint32_t blocks = adjoint_blocks(h->n), op_blocks = adjoint_op_blocks(h->n);
+    if ((rc = ensure_adjoint(h, h->d_adj_tab, tab_bytes)) || (rc = ensure_adjoint(h, h->d_adj_lambda, gc_max * dim * h->amp_bytes)) ||
+        (rc = ensure_adjoint(h, h->d_adj_mats, gc_max * std::max<size_t>(1, max_gates) * kAdjointMatDoubles * sizeof(double))) ||
+        (rc = ensure_adjoint(h, h->d_adj_partials, gc_max * 3 * std::max<size_t>(1, max_gates) * blocks * sizeof(double))) ||
+        (rc = ensure_adjoint(h, h->d_adj_epart, gc_max * op_blocks * sizeof(double))))
+        return rc;
+    // (lay_out_states has waited for whatever an earlier call without a wait left running: nothing reads the old tables)
+    QSV_HIP(h, hipMemcpy(h->d_adj_tab.ptr, blob.data(), tab_bytes, hipMemcpyHostToDevice));
+    const char* dt = static_cast<const char*>(h->d_adj_tab.ptr);
+    const AdjGate* d_gates = reinterpret_cast<const AdjGate*>(dt + off_gates);
+    const AdjRunDesc* d_runs = reinterpret_cast<const AdjRunDesc*>(dt + off_runs);
+    const AdjEntry* d_entries = reinterpret_cast<const AdjEntry*>(dt + off_entries);
+    const int64_t* d_offsets = reinterpret_cast<const int64_t*>(dt + off_offsets);
+    const uint32_t* d_slots = reinterpret_cast<const uint32_t*>(dt + off_slots);
+    const AdjEval* d_evals = reinterpret_cast<const AdjEval*>(dt + off_evals);
+    double* mats = static_cast<double*>(h->d_adj_mats.ptr);
+    double* partials = static_cast<double*>(h->d_adj_partials.ptr);
+    double* e_partials = static_cast<double*>(h->d_adj_epart.ptr);
+    const bool streaming = h->stream_mode != 0;
+    auto sweep = [&](size_t g0, size_t gc) -> int {
+        QSV_HIP(h, launch_adjoint_prepare(d_evals + g0, int(gc), d_gates, max_gates, call.base, call.width, mats, h->stream));
+        QSV_HIP(h, launch_adjoint_apply_operator(h->dtype, h->d_states.ptr, h->d_adj_lambda.ptr, h->n, int(gc),
+                                                 h->has_diag_part ? static_cast<const double*>(h->d_diag.ptr) : nullptr, h->n_groups,
+                                                 static_cast<const PauliGroup*>(h->d_groups.ptr), static_cast<const uint64_t*>(h->d_z.ptr),
+                                                 static_cast<const double*>(h->d_cre.ptr), static_cast<const uint32_t*>(h->d_term_odd.ptr),
+                                                 streaming, e_partials, h->stream));
+        uint32_t most_runs = 0;
+        for (size_t j = g0; j < g0 + gc; ++j) most_runs = std::max(most_runs, evals[j].n_runs);
+        for (uint32_t r = 0; r < most_runs; ++r) {
+            QSV_HIP(h, launch_adjoint_run(h->dtype, h->d_states.ptr, h->d_adj_lambda.ptr, h->n, int(gc), r, d_evals + g0, d_runs, d_gates, mats,
+                                          max_gates, streaming, partials, h->stream));
+            h->adj_stats.n_runs += 1;
+        }
+        QSV_HIP(h, launch_adjoint_combine(d_evals + g0, int(gc), d_offsets, d_entries, d_slots, partials, max_gates, blocks, e_partials,
+                                          op_blocks, call.out_width, call.out, call.out_values, h->stream));
+        return QSV_OK;
+    };
+    return run_laid_out(h, args, run, lay, {}, sweep);
+}
+
+int qsv_adjoint_gradient_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
+                                  const int64_t* wrt_offsets, const int32_t* wrt, double* out, double* out_values) {
+    if (!h) return QSV_E_ARG;
+    if (h->batch_owner.load() == std::this_thread::get_id())
+        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_adjoint_gradient_circuits goes between batches)");
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets))) return fail(h, QSV_E_ARG, "bad arguments");
+    if (n_evals == 0) return QSV_OK;
+    QSV_HIP(h, hipSetDevice(h->device));
+    BatchArgs packed;
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, packed, "adjoint gradients of a circuit on a kept state are not built");
+    if (rc) return rc;
+    // the points as one matrix, a row per evaluation (rows of an even number of doubles); the gradient rows as wide as the longest request
+    int64_t width = 2, out_width = 1, total_out = 0;
+    for (int e = 0; e < n_evals; ++e) {
+        width = std::max(width, (packed.n_params[size_t(e)] + 1) / 2 * 2);
+        const int64_t count = wrt_offsets ? wrt_offsets[e + 1] - wrt_offsets[e] : int64_t(packed.circs[size_t(e)]->n_params);
+        if (count < 0) return fail(h, QSV_E_ARG, "wrt_offsets must be non-decreasing");
+        out_width = std::max(out_width, count);
+        total_out += count;
+        if (packed.n_params[size_t(e)] < packed.circs[size_t(e)]->n_params)
+            return fail(h, QSV_E_ARG, "circuit needs " + std::to_string(packed.circs[size_t(e)]->n_params) + " parameter values, got " +
+                                          std::to_string(packed.n_params[size_t(e)]));
+    }
+    if (total_out > 0 && !out) return fail(h, QSV_E_ARG, "out is null");
+    if (width > (1 << 24) || out_width > (1 << 24)) return fail(h, QSV_E_ARG, "too many parameters");
+    std::vector<double> base(size_t(n_evals) * size_t(width), 0.0);
+    for (size_t e = 0, cur = 0; e < size_t(n_evals); cur += size_t(packed.n_params[e]), ++e)
+        if (packed.n_params[e]) std::memcpy(base.data() + e * size_t(width), packed.values.data() + cur, size_t(packed.n_params[e]) * sizeof(double));
+    if (h->async_pending) {  // (the buffers below may still be read or written by a call that did not wait)
+        QSV_HIP(h, sync_streams(h));
+        h->async_pending = false;
+    }
+    if ((rc = ensure_adjoint(h, h->d_adj_base, base.size() * sizeof(double))) ||
+        (rc = ensure_adjoint(h, h->d_adj_out, size_t(n_evals) * size_t(out_width) * sizeof(double))) ||
+        (rc = ensure_adjoint(h, h->d_adj_values, size_t(n_evals) * sizeof(double))))
+        return rc;
+    QSV_HIP(h, hipMemcpy(h->d_adj_base.ptr, base.data(), base.size() * sizeof(double), hipMemcpyHostToDevice));
+    BatchArgs args;
+    args.circs = packed.circs;
+    args.values.assign(1, 0.0);
+    args.n_params.assign(size_t(n_evals), width);
+    args.device_values = static_cast<const double*>(h->d_adj_base.ptr);
+    const AdjCall call{args.device_values, int(width), static_cast<double*>(h->d_adj_out.ptr), int(out_width), static_cast<double*>(h->d_adj_values.ptr)};
+    rc = adjoint_locked(h, args, circuit_ids, wrt_offsets, wrt, call);
+    if (rc) {
+        (void)sync_streams(h);
+        return rc;
+    }
+    std::vector<double> rows(size_t(n_evals) * size_t(out_width));
+    std::vector<double> values(static_cast<size_t>(n_evals));
+    QSV_HIP(h, hipMemcpyAsync(rows.data(), h->d_adj_out.ptr, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QSV_HIP(h, hipMemcpyAsync(values.data(), h->d_adj_values.ptr, values.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QSV_HIP(h, sync_streams(h));
+    h->async_pending = false;
+    for (size_t e = 0, cur = 0; e < size_t(n_evals); ++e) {
+        const size_t count = size_t(wrt_offsets ? wrt_offsets[e + 1] - wrt_offsets[e] : int64_t(packed.circs[e]->n_params));
+        if (count) std::memcpy(out + cur, rows.data() + e * size_t(out_width), count * sizeof(double));
+        cur += count;
+    }
+    if (out_values) std::memcpy(out_values, values.data(), values.size() * sizeof(double));
+    return QSV_OK;
+}
+
+int qsv_adjoint_gradient_device(qsv_t* h, int n_evals, const int* circuit_ids, int width, const double* device_values, void* ready_event,
+                                const int64_t* wrt_offsets, const int32_t* wrt, int out_width, double* device_out, double* device_out_values) {
+    if (!h) return QSV_E_ARG;
+    if (h->batch_owner.load() == std::this_thread::get_id())
+        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_adjoint_gradient_device goes between batches)");
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (n_evals < 0 || width < 0 || out_width < 0 || (n_evals > 0 && (!circuit_ids || (out_width > 0 && !device_out) || (width > 0 && !device_values))))
+        return fail(h, QSV_E_ARG, "bad arguments");
+    if (n_evals == 0) return QSV_OK;
+    QSV_HIP(h, hipSetDevice(h->device));
+    const void* given[3] = {width > 0 ? device_values : nullptr, out_width > 0 ? device_out : nullptr, device_out_values};
+    static const char* const names[3] = {"device_values", "device_out", "device_out_values"};
+    for (int i = 0; i < 3; ++i) {  // (a search hands over the same buffers call after call: each is asked about once)
+        if (!given[i] || given[i] == h->adj_checked[i]) continue;
+        hipPointerAttribute_t attr{};
+        if (hipPointerGetAttributes(&attr, given[i]) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != h->device) {
+            (void)hipGetLastError();
+            return fail(h, QSV_E_ARG, std::string(names[i]) + " is not memory of this handle's device");
+        }
+        h->adj_checked[i] = given[i];
+    }
+    BatchArgs args;
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, nullptr, nullptr, args, "adjoint gradients of a circuit on a kept state are not built");
+    if (rc) return rc;
+    args.n_params.assign(size_t(n_evals), int64_t(width));
+    args.device_values = width > 0 ? device_values : nullptr;
+    if (ready_event) QSV_HIP(h, hipStreamWaitEvent(h->stream, static_cast<hipEvent_t>(ready_event), 0));
+    const AdjCall call{device_values, width, device_out, out_width, device_out_values};
+    rc = adjoint_locked(h, args, circuit_ids, wrt_offsets, wrt, call);
+    if (rc)
+        (void)sync_streams(h);  // nothing of a failed call may still be running
+    else
+        h->async_pending = true;
+    return rc;
+}
+
+int qsv_adjoint_stats(const qsv_t* h, qsv_adjoint_stats_t* out) {
+    if (!h || !out) return QSV_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    *out = h->adj_stats;
+    out->scratch_bytes = int64_t(h->d_adj_lambda.bytes + h->d_adj_tab.bytes + h->d_adj_mats.bytes + h->d_adj_partials.bytes + h->d_adj_epart.bytes +
+                                 h->d_adj_base.bytes + h->d_adj_out.bytes + h->d_adj_values.bytes);
     return QSV_OK;
 }
 

@@ -163,7 +163,11 @@ def possible_nft(evaluator, config, n_runs: int) -> bool:
 
 
 def possible_adam(evaluator, config, n_runs: int) -> bool:
-    """:func:`possible` for :func:`minimize_adam_on_device`: an evaluator with gradient plans, on a GPU."""
+    """:func:`possible` for :func:`minimize_adam_on_device`: an evaluator with gradient plans, on a GPU, whose gradients are
+    parameter shift (a gradient plan is a parameter-shift plan: an evaluator told to differentiate by the adjoint sweep, or to
+    choose per circuit, runs the host driver)."""
+    if getattr(evaluator, "gradient_method", "parameter_shift") != "parameter_shift":
+        return False
     return _evaluator_can(evaluator, n_runs, "gradient_plan") and int(config.maxiter) > 0
 
 

@@ -291,7 +291,9 @@ def _require_gradients(evaluator, optimizer) -> None:
 def _minimize_adam(evaluator, jobs: list) -> None:
     """:func:`_minimize_batched` for Adam runs: ONE ``evaluate_gradients`` call per iteration for all runs, each run
     differentiated by its free parameters only (the searched layer of an embedded run).  A run's ``nfev`` counts its shifted
-    evaluations, by the circuit's shift plan; their sum is checked against what the evaluator reports."""
+    evaluations, by the circuit's shift plan; their sum is checked against what the evaluator reports.  An evaluator whose
+    ``gradient_method`` is not "parameter_shift" reports each circuit's count itself (one for a circuit differentiated by the
+    adjoint sweep)."""
     _require_gradients(evaluator, jobs[0][1].config)
     wrt, cost = {}, {}
     for circuit, run in jobs:
@@ -304,6 +306,12 @@ def _minimize_adam(evaluator, jobs: list) -> None:
         circuits = [circuit for circuit, _ in active]
         params = [_full_point(run, run.x).tolist() for _, run in active]
         gradients = evaluator.evaluate_gradients(circuits, params, [wrt[id(run)] for _, run in active])
+        if getattr(evaluator, "gradient_method", "parameter_shift") != "parameter_shift":
+            # (the adjoint sweep, for all circuits or for those the evaluator chose: it says what each circuit's gradient cost)
+            for (_, run), gradient, spent in zip(active, gradients, evaluator.last_gradient_evaluation_counts):
+                run.accept_gradient(gradient, spent)
+            active = [job for job in active if not job[1].done]
+            continue
         counted = sum(cost[id(run)] for _, run in active)
         reported = getattr(evaluator, "last_gradient_evaluations", counted)
         if reported != counted:
