@@ -186,6 +186,13 @@ typedef struct qsv_circuit_form_t {
     uint32_t mask_x, mask_y; /* qubits of side x, side y (without the keys) */
 } qsv_circuit_form_t;
 int qsv_circuit_form(qsv_t* h, int circuit_id, qsv_circuit_form_t* out);
+/*
+ * The same, but n_virtual, halves and outer describe the side plans the one-launch route RUNS for the circuit under the
+ * operator and options set now: those of its reduced form (option "final_controls") where it has one and that route takes it,
+ * else qsv_circuit_form's.  mask_x, mask_y and everything else as qsv_circuit_form: every other consumer of the side states
+ * runs the full form.
+ */
+int qsv_circuit_launch_form(qsv_t* h, int circuit_id, qsv_circuit_form_t* out);
 
 /*
  * Expectation values real(<psi_i|H|psi_i>) of n_evals (circuit, parameter vector) pairs, |psi_i> prepared from
@@ -746,13 +753,19 @@ int qsv_fitness_table_wait(const volatile uint64_t* own, int count, volatile int
  *                        key qubit, that trade half rows through memory (where its plan does not leave that qubit outside the tile:
  *                        as two tiles swept by one workgroup).  Other orders of the sums (1e-10 apart).  Applies to circuits
  *                        registered afterwards.
+ *   "final_controls" 0|1 ... and a side simulates no key qubit for a key whose control on it is FINAL (nothing targets the control after
+ *                        the key's first gate; qsv_split_describe_reduced): the rows of that key are the two halves of the one state.
+ *                        Only on that route; every other consumer of side states keeps the full form.  Other orders of the sums
+ *                        (1e-10 apart).  Applies to circuits registered afterwards; QSV_FINAL_CONTROLS=0 in the environment.
  *   "side_prepare" 0|1   ... and a side whose plan qualifies (one pass, at most two tiles, its angle table, fold index and chain index
  *                        within 4096 plan words) is prepared from ONE staged read of its plan and parameters, and keeps its threads'
  *                        and tiles' factors in registers instead of handing them to itself through memory: the same expressions in
  *                        the same order, the same bits.  Takes effect at the next launch.
  *   "side_diag" 0|1      ... and reads its values of D from a table of its own -- entry x of a side = D[x deposited in the side's
  *                        qubits], one run, filled when the circuit's plan is uploaded -- instead of gathering them from D, one
- *                        cache line per value: the same values, the same bits
+ *                        cache line per value: the same values, the same bits.  A side on the reduced form ("final_controls")
+ *                        always has and reads a table of its own, whatever this option says: with 0 only the sides on the full
+ *                        form gather from D itself
  *   "split_max_keys" 0..5 most cut keys of a split form (default 5; four and five: quadratic operators only).  Applies to
  *                        circuits registered afterwards.
  *   "chain_stream" 0|1   in a push that holds split evaluations of both kinds (finished by the launch that runs their
@@ -817,6 +830,28 @@ int qsv_plan_build(int n_qubits, int dtype, int n_ops, const qsv_op* ops, const 
  */
 int qsv_split_describe(int n_qubits, int n_ops, const qsv_op* ops, int max_side, uint64_t* mask_a, qsv_op* ops_a,
                        int capacity_a, int* n_ops_a, qsv_op* ops_b, int capacity_b, int* n_ops_b);
+
+/*
+ * The REDUCED form of the same partition and keys (csrc/split.hpp, reduce_final_controls), without touching any device.
+ * A key whose control c is FINAL -- nothing targets c after the key's first gate -- needs no key qubit on the control's
+ * side: a_kappa(x) = a(x) [x_c = kappa_j].  Return value and mask_a as qsv_split_describe.  Per side s (0 = A, 1 = B):
+ *   simulated_keys[s]  the keys (bits of kappa) the side still simulates with a key qubit;
+ *   final_keys[s]      the keys whose final control lies on the side (the other bits of kappa);
+ *   key_bits[s * QSV_SPLIT_MAX_KEYS + j]  key j's bit in the side's index: its key qubit's, or its final control's
+ *                      (-1 beyond the K keys);
+ *   qubits[s * 32 + p] the register's qubit at position p of the side's index, p < popcount(side) (-1 beyond): the
+ *                      qubits that are no final controls in ascending order, then the final controls in key order.
+ * The op lists are on popcount(side) + popcount(simulated_keys[s]) qubits: the real qubits as `qubits` orders them, then
+ * the simulated keys in ascending order.  With a, b the final states of the two circuits and e_s(kappa, i) the index
+ * made of the side's real bits of i and, for each simulated key j, kappa_j at key_bits[s][j]:
+ *   psi[i] = sum_kappa  [i_c = kappa_j for every final key j of A] a[e_A(kappa, i)]
+ *                     * [i_c = kappa_j for every final key j of B] b[e_B(kappa, i)].
+ * Used by the CPU-side tests; the one-launch route runs this form where a side gets smaller (option "final_controls").
+ */
+#define QSV_SPLIT_MAX_KEYS 8
+int qsv_split_describe_reduced(int n_qubits, int n_ops, const qsv_op* ops, int max_side, uint64_t* mask_a, qsv_op* ops_a,
+                               int capacity_a, int* n_ops_a, qsv_op* ops_b, int capacity_b, int* n_ops_b,
+                               uint32_t* simulated_keys, uint32_t* final_keys, int* key_bits, int* qubits);
 
 /* Library version string. */
 const char* qsv_version(void);

@@ -242,6 +242,7 @@ SIGNATURES = {
     "qsv_circuits_create_on_prefixes": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
     "qsv_circuit_cost": (C.c_int, [_P, C.c_int, C.POINTER(QsvCircuitCost)]),
     "qsv_circuit_form": (C.c_int, [_P, C.c_int, C.POINTER(QsvCircuitForm)]),
+    "qsv_circuit_launch_form": (C.c_int, [_P, C.c_int, C.POINTER(QsvCircuitForm)]),
     "qsv_eval_circuits": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     "qsv_eval_coalesced": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_double, C.POINTER(C.c_double)]),
     "qsv_eval_begin": (C.c_int, [_P, C.c_int, _P, _P]),
@@ -297,6 +298,11 @@ SIGNATURES = {
     "qsv_split_describe": (
         C.c_int,
         [C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_uint64), _P, C.c_int, C.POINTER(C.c_int), _P, C.c_int, C.POINTER(C.c_int)],
+    ),
+    "qsv_split_describe_reduced": (
+        C.c_int,
+        [C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_uint64), _P, C.c_int, C.POINTER(C.c_int), _P, C.c_int, C.POINTER(C.c_int),
+         _P, _P, _P, _P],
     ),
     "qsv_plan_build": (
         C.c_int,

@@ -607,8 +607,16 @@ class StatevectorDevice:
         route as its QSV_ROUTE_* number), and its split form -- virtual qubits, amplitudes per thread, half sides, swept
         tiles and qubit masks of side x and side y, whether it may take the one-launch route and whether the sampler
         draws it from its side tables.  Reads, computes nothing."""
+        return self._form(self._lib.qsv_circuit_form, circuit)
+
+    def circuit_launch_form(self, circuit: CircuitIR) -> dict:
+        """As :meth:`circuit_form`, but ``n_virtual``, ``halves`` and ``outer`` are those of the side plans the one-launch route
+        runs under the operator and options set now (``qsv_circuit_launch_form``): the reduced form's where it takes one."""
+        return self._form(self._lib.qsv_circuit_launch_form, circuit)
+
+    def _form(self, call, circuit: CircuitIR) -> dict:
         form = _lib.QsvCircuitForm()
-        self._check(self._lib.qsv_circuit_form(self._handle, self.circuit_id(circuit), C.byref(form)))
+        self._check(call(self._handle, self.circuit_id(circuit), C.byref(form)))
         return {"route": form.route, "n_keys": form.n_keys, "n_virtual": tuple(form.n_virtual),
                 "amps_per_thread": form.amps_per_thread, "halves": bool(form.halves), "outer": tuple(form.outer),
                 "one_launch": bool(form.one_launch), "split_sampled": bool(form.split_sampled), "mask_x": form.mask_x,

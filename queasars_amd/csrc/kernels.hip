@@ -912,7 +912,7 @@ __device__ __forceinline__ bool side_prepare(const uint32_t* __restrict__ plan, 
 }
 
 // (defined with the factor kernels below) the tail of a pass-0 launch under kModeFusedFactor
-template <typename real>
+template <typename real, bool REDUCED>
 __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ plan_arena, const EvalDesc& ev,
                                                   const cx<real>* __restrict__ slot_tables, uint64_t side_stride,
                                                   const double* __restrict__ diag, const PassScalars& a, unsigned char* lds,
@@ -923,7 +923,9 @@ __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ p
 // FUSED (only with FIRST and R = 4): the instantiation the one-launch route of split evaluations runs (kModeFusedFactor) -- the
 // only one that carries the sides' Gram sums and the combination behind the virtual circuits (fused_factor_tail): the other
 // first-pass kernels are the leaner for it (a third fewer scalar spills), this one has registers to spare.
-template <typename real, int R, int XMODE, bool FIRST, bool FUSED = false>
+// REDUCED (only with FUSED): the launch holds sides on the reduced split form (kModeFusedReduced) -- only this instantiation's
+// tail carries what they need, so that a launch without them runs the tail it always ran.
+template <typename real, int R, int XMODE, bool FIRST, bool FUSED = false, bool REDUCED = false>
 __global__ void __launch_bounds__(512, (Occupancy<R, XMODE, FIRST, FUSED>::waves_per_simd))
     pass_kernel(const uint32_t* __restrict__ plan_arena, const double* __restrict__ mats_all,
                 const EvalDesc* __restrict__ evals, cx<real>* __restrict__ states, cx<real>* __restrict__ wtabs,
@@ -1646,11 +1648,11 @@ __global__ void __launch_bounds__(512, (Occupancy<R, XMODE, FIRST, FUSED>::waves
             QSV_STAMP_FLUSH(0u);
             for (int ph = 0; ph < kStampPhases; ++ph) st_acc[ph] = 0;
             st_last = qsv_stamp_now();
-            fused_factor_tail<real>(plan_arena, ev, wt0, a.wtab_stride, diag, a, lds_raw, t >= 9 ? 8u : 4u, table_in_lds ? 1u : table_lds_rows ? 2u : 0u, halves_side ? tile0 : 0xffffffffu, st_acc, &st_last);
+            fused_factor_tail<real, REDUCED>(plan_arena, ev, wt0, a.wtab_stride, diag, a, lds_raw, t >= 9 ? 8u : 4u, table_in_lds ? 1u : table_lds_rows ? 2u : 0u, halves_side ? tile0 : 0xffffffffu, st_acc, &st_last);
             QSV_STAMP_FLUSH(7u);
 #else
             // (Gram waves: by the virtual circuit's own geometry, never by the launch's block size)
-            fused_factor_tail<real>(plan_arena, ev, wt0, a.wtab_stride, diag, a, lds_raw, t >= 9 ? 8u : 4u, table_in_lds ? 1u : table_lds_rows ? 2u : 0u, halves_side ? tile0 : 0xffffffffu);
+            fused_factor_tail<real, REDUCED>(plan_arena, ev, wt0, a.wtab_stride, diag, a, lds_raw, t >= 9 ? 8u : 4u, table_in_lds ? 1u : table_lds_rows ? 2u : 0u, halves_side ? tile0 : 0xffffffffu);
 #endif
             return;
         }
@@ -1700,6 +1702,11 @@ static hipError_t launch_pass_t(dim3 grid, int threads, size_t lds_bytes, hipStr
     cx<real>* st = reinterpret_cast<cx<real>*>(args.states);
     const bool first = args.pass_index == 0 && (args.mode & kModeSynthFirst);
     if constexpr (R == 4 || R == 3) {
+        if (first && (args.mode & kModeFusedFactor) && (args.mode & kModeFusedReduced)) {
+            hipLaunchKernelGGL((pass_kernel<real, R, XMODE, true, true, true>), grid, dim3(threads), lds, stream, args.plan, args.mats,
+                               args.evals, st, reinterpret_cast<cx<real>*>(args.wtab), args.diag, args.partials, sc);
+            return hipGetLastError();
+        }
         if (first && (args.mode & kModeFusedFactor)) {
             hipLaunchKernelGGL((pass_kernel<real, R, XMODE, true, true>), grid, dim3(threads), lds, stream, args.plan, args.mats,
                                args.evals, st, reinterpret_cast<cx<real>*>(args.wtab), args.diag, args.partials, sc);
@@ -1723,6 +1730,9 @@ static hipError_t configure_t(size_t lds_bytes) {
     if (e != hipSuccess) return e;
     if constexpr (R == 4 || R == 3) {
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pass_kernel<real, R, XMODE, true, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) return e;
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pass_kernel<real, R, XMODE, true, true, true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
         if (e != hipSuccess) return e;
     }
@@ -3888,6 +3898,60 @@ __global__ void __launch_bounds__(1024) factor_combine_kernel(const uint32_t* __
     if (tid == 0) result_out[ev.out_index] = total;
 }
 
+// Entry pi of weight w of the FULL form's table (2^n_keys product terms) from the partial matrices of a reduced side
+// (kernels.hpp kSplitReduced: `reduced` is the side's word, `slots` its two words of weight slots): the waves' sums are sums
+// over one block of x each -- wave g over block g / waves_per_block -- for the 2^S simulated rows.  Rows kappa, kappa' whose
+// final-key bits differ: zero.  Else the entry of the simulated rows over the block those bits name, the block's waves in
+// order and each wave's four row partials in order (factor_sum_partials' order); the imaginary part changes sign where the
+// simulated rows come in the other order; the weight of a real qubit is the weight of its position in the reduced side, and
+// the bit of a final control is the same for the whole block: the plain sum or nothing.
+__device__ __forceinline__ double factor_reduced_entry(const double* partial, const uint32_t* __restrict__ slots, uint32_t reduced,
+                                                       uint32_t n_keys, uint32_t bits, uint32_t waves_per_block, uint32_t w, uint32_t pi) {
+    const uint32_t n_final = reduced & 3u, n_sim = (reduced >> 2) & 3u, low_bits = bits - n_final;
+    uint32_t ja, jb, part;
+    if (n_keys == 1)
+        split_entry_of<2>(pi, &ja, &jb, &part);
+    else if (n_keys == 2)
+        split_entry_of<4>(pi, &ja, &jb, &part);
+    else
+        split_entry_of<8>(pi, &ja, &jb, &part);
+    uint32_t ra = 0, rb = 0;  // the rows in the reduced side's order of the keys: final controls, then simulated keys
+    for (uint32_t r = 0; r < n_keys; ++r) {
+        const uint32_t key = reduced >> (4u + 2u * r) & 3u;
+        ra |= (ja >> key & 1u) << r;
+        rb |= (jb >> key & 1u) << r;
+    }
+    const uint32_t x_block = ra & ((1u << n_final) - 1u);
+    if (x_block != (rb & ((1u << n_final) - 1u))) return 0.0;
+    const uint32_t sa = ra >> n_final, sb = rb >> n_final, J = 1u << n_sim;
+    uint32_t entry = sa;
+    double sign = 1.0;
+    if (sa != sb) {
+        const uint32_t lo = sa < sb ? sa : sb, hi = sa < sb ? sb : sa;
+        uint32_t o = hi - lo - 1u;
+        for (uint32_t i = 0; i < lo; ++i) o += J - 1u - i;
+        entry = J + 2u * o + (part - 1u);
+        if (part == 2u && sa > sb) sign = -1.0;
+    }
+    uint32_t weight = w;
+    if (w >= 2u) {
+        uint32_t at = 0;  // the reduced side's position of the full form's local qubit w - 2
+        for (uint32_t p = 0; p < bits; ++p)
+            if ((slots[p >> 3] >> (4u * (p & 7u)) & 15u) == w - 2u) at = p;
+        if (at < low_bits)
+            weight = 2u + at;
+        else if (x_block >> (at - low_bits) & 1u)
+            weight = 0u;
+        else
+            return 0.0;
+    }
+    double v = 0.0;
+    for (uint32_t g = x_block * waves_per_block; g < (x_block + 1u) * waves_per_block; ++g)
+#pragma unroll
+        for (uint32_t row = 0; row < 4; ++row) v += partial[(size_t(g) * kFactorWeights + weight) * 64 + row * 16 + entry];
+    return sign * v;
+}
+
 // The two launches above as the tail of the kernel that ran the virtual circuits (pass_kernel, kModeFusedFactor): the side's
 // final state has just been stored to its half of the slot; four waves -- eight for a virtual circuit whose own tile needs
 // 512 threads; never a function of the launch's block size: the assignment of table blocks to waves, and with it the order
@@ -3898,7 +3962,7 @@ __global__ void __launch_bounds__(1024) factor_combine_kernel(const uint32_t* __
 // workgroup barrier, then agent-scope loads of both sets (MI355X_MICROARCH.md, hand-offs with sc1 stores and loads in place
 // of a release / acquire pair, first row: one unsharded counter, the last adder told by its add's return value).  The order in
 // which the two sides finish does not enter any sum.
-template <typename real>
+template <typename real, bool REDUCED>
 __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ plan_arena, const EvalDesc& ev,
                                                   const cx<real>* __restrict__ slot_tables, uint64_t side_stride,
                                                   const double* __restrict__ diag, const PassScalars& a, unsigned char* lds,
@@ -3923,11 +3987,28 @@ __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ p
     const uint32_t tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // (the side's state: in its half of the slot -- or still in LDS, where the pass left it for this tail alone)
     const cx<real>* tab = table_in_lds ? reinterpret_cast<const cx<real>*>(lds + kFusedLdsTableOffset) : slot_tables + (is_b ? side_stride >> 1 : 0);
+    // A REDUCED side (kernels.hpp kSplitReduced; split.hpp): F of the keys have their final control among the side's real qubits --
+    // the F highest -- and no key qubit, so the state is 2^S rows (simulated keys) of 2^bits, and row kappa of the full form is
+    // the block of x whose final-control bits are kappa's.  The waves are dealt out over the 2^F blocks, kWaves >> F to a block
+    // (the host takes the form only where that is at least one wave and a block at least 64 x), each taking every (kWaves >> F)-th
+    // table block of 64 of its block of x: a wave's sums are sums over ONE block, and the table is put together from them below.
+    // (REDUCED: the instantiation of a launch that holds such sides; any other launch holds none, and its tail knows at compile time)
+    const uint32_t reduced = REDUCED ? sp[kSplitReduced + xy] : 0u, n_final = reduced & 3u, n_sim = (reduced >> 2) & 3u;
+    const uint32_t body_keys = n_final ? n_sim : n_keys;
+    const uint32_t waves_per_block = kWaves >> n_final;
+    uint32_t red_first = 0xffffffu, red_end = 0u;
+    if (n_final && waves_per_block && wave < kWaves) {
+        const uint32_t x_block = wave / waves_per_block, blocks = factor_block_count(bits) >> n_final;
+        red_first = x_block * blocks + wave % waves_per_block;
+        red_end = (x_block + 1u) * blocks;
+    }
     // (the values of D this wave's blocks will want: asked for before the wait below, whose stores they do not depend on)
     double dq[kFactorDAhead], dq_pairs[kFactorDAheadPairs];
     {
         const uint32_t worker = wave < kWaves ? wave : 0xffffffu;
-        if (n_keys < 3) {
+        if (n_final) {
+            factor_prefetch_d(dq, diag, bits, mask, red_first, waves_per_block, red_end);
+        } else if (n_keys < 3) {
             if (halves)  // (a half side: the blocks of its half of x)
                 factor_prefetch_d(dq, diag, bits, mask, wave < kWaves ? (factor_block_count(bits) >> 1) * hh + wave : 0xffffffu, kWaves, (factor_block_count(bits) >> 1) * (hh + 1u));
             else
@@ -4003,8 +4084,14 @@ __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ p
         const uint32_t w = wave < kWaves ? wave : 0u;
         cx<real>* stage = reinterpret_cast<cx<real>*>(lds) + size_t(w) * 9 * 64;
         double* out = partial + size_t(w) * kFactorWeights * 64;
-        const uint32_t first = wave < kWaves ? wave : 0xffffffu, step = kWaves;
+        const uint32_t first = wave < kWaves ? wave : 0xffffffu, step = n_final ? waves_per_block : kWaves;
         double* sink = wave < kWaves ? out : nullptr;
+        HalfRows half_rows;
+        uint32_t half_first = first, half_end = 0xffffffffu;
+        if (n_final) {  // (a reduced side: this wave's blocks of its block of x)
+            half_first = red_first;
+            half_end = red_end;
+        }
 #ifdef QSV_ABL_TAIL_GRAM  // (measurement: the tail without its Gram sums)
         if (sink)
             for (uint32_t i = tid & 63u; i < kFactorWeights * 64; i += 64) sink[i] = 0.0;
@@ -4013,8 +4100,6 @@ __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ p
 #else
         // (a half side of one or two keys: row j = (its last key bit, the others): mine where they lie in the tile, the partner's in my
         // rows' other halves of x, so that entry x of each lies at x; blocks of my half of x only)
-        HalfRows half_rows;
-        uint32_t half_first = first, half_end = 0xffffffffu;
         if (halves && n_keys < 3) {
             const uint32_t own_rows = (1u << n_keys) >> 1, half_x = 1u << (bits - 1u), blocks = factor_block_count(bits) >> 1;
 #pragma unroll
@@ -4027,14 +4112,15 @@ __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ p
             half_first = wave < kWaves ? blocks * hh + wave : 0xffffffu;
             half_end = blocks * (hh + 1u);
         }
-        if (n_keys == 0)
+        if (body_keys == 0)
 #endif
-            factor_side_body<real, 1, true>(tab, bits, mask, diag, first, step, stage, dstage_all + w * 64, sink, dq QSV_PSTAMP_ARGS);
+            factor_side_body<real, 1, true>(tab, bits, mask, diag, half_first, step, stage, dstage_all + w * 64, sink, dq QSV_PSTAMP_ARGS,
+                                            half_rows, half_end);
 #ifndef QSV_ABL_TAIL_GRAM
-        else if (n_keys == 1)
+        else if (body_keys == 1)
             factor_side_body<real, 2, true>(tab, bits, mask, diag, half_first, step, stage, dstage_all + w * 64, sink, dq QSV_PSTAMP_ARGS,
                                             half_rows, half_end);
-        else if (n_keys == 2)
+        else if (body_keys == 2)
             factor_side_body<real, 4, false>(tab, bits, mask, diag, half_first, step, stage, dstage_all + w * 64, sink, dq QSV_PSTAMP_ARGS,
                                              half_rows, half_end);
         else if (halves) {
@@ -4065,7 +4151,9 @@ __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ p
     // this XCD's L2 holds dirty -- the side tables of sixteen workgroups; an agent-scope release did that: 46 us per launch)
     for (uint32_t idx = tid; idx < (2u + bits) * NQ; idx += blockDim.x) {
         const uint32_t w = idx / NQ, pi = idx % NQ;
-        __hip_atomic_store(mine + w * 64 + pi, factor_sum_partials(partial, kWaves, w, pi, n_keys), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const double v = n_final ? factor_reduced_entry(partial, sp + kSplitReducedSlots + 2u * xy, reduced, n_keys, bits, waves_per_block, w, pi)
+                                 : factor_sum_partials(partial, kWaves, w, pi, n_keys);
+        __hip_atomic_store(mine + w * 64 + pi, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave, before the barrier the signalling lane joins
     __syncthreads();
@@ -4096,6 +4184,11 @@ __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ p
     const double d00 = whole_diag[0];
     double* gram = reinterpret_cast<double*>(lds);  // [side][weight][kFactorPitch] (the partial matrices are no longer needed)
     const uint32_t side_bits[2] = {bx, by};
+    // (half sides: two partial tables a side; a reduced side has key qubits for its simulated keys only and is never one.  Known
+    // before the loads below go out: a word of the block read between them would make each wait for the one before)
+    const bool any_halves = ev.flags & kEvalHalves;
+    const bool two_halves[2] = {any_halves && (!REDUCED || sp[kSplitReduced] == 0u) && bx + n_keys == uint32_t(kFusedLdsRowsBits),
+                                any_halves && (!REDUCED || sp[kSplitReduced + 1] == 0u) && by + n_keys == uint32_t(kFusedLdsRowsBits)};
     {
         // (all of a thread's loads first, then its LDS writes: at eight terms a thread has up to five values per side to fetch,
         // and a loop that stored each before asking for the next paid a memory round trip per value)
@@ -4111,7 +4204,7 @@ __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ p
                     const double* entry = slot + size_t(s2) * kFactorSlices * kFactorWeights * 64 + (idx / NQ) * 64 + idx % NQ;
                     fetched[s2][it] = __hip_atomic_load(entry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     // (half sides: the sums over the two halves of x, the lower first)
-                    if ((ev.flags & kEvalHalves) && side_bits[s2] + n_keys == uint32_t(kFusedLdsRowsBits))
+                    if (two_halves[s2])
                         fetched[s2][it] += __hip_atomic_load(entry + kFactorWeights * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
             }
@@ -4800,9 +4893,12 @@ hipError_t launch_state_to_f64(int dtype, const void* state, uint64_t dim, doubl
 
 __global__ void __launch_bounds__(256) side_diag_kernel(const double* __restrict__ diag, double* __restrict__ side_diag, const SideDiagJobs jobs) {
     const SideDiagJob j = jobs.job[blockIdx.y];
-    const uint32_t count = 1u << j.bits;
-    for (uint32_t x = blockIdx.x * blockDim.x + threadIdx.x; x < count; x += gridDim.x * blockDim.x)
-        side_diag[size_t(j.base) + x] = diag[deposit_bits(x, j.mask)];
+    const uint32_t count = 1u << j.bits, n_top = j.top & 3u, low_bits = j.bits - n_top;
+    for (uint32_t x = blockIdx.x * blockDim.x + threadIdx.x; x < count; x += gridDim.x * blockDim.x) {
+        uint32_t at = deposit_bits(x & ((1u << low_bits) - 1u), j.mask);
+        for (uint32_t t = 0; t < n_top; ++t) at |= (x >> (low_bits + t) & 1u) << (j.top >> (2u + 5u * t) & 31u);
+        side_diag[size_t(j.base) + x] = diag[at];
+    }
 }
 
 hipError_t launch_side_diag(const double* diag, double* side_diag, const SideDiagJobs& jobs, int n_jobs, hipStream_t stream) {

@@ -61,9 +61,17 @@ constexpr int kSideMaxOwnBits = 16;  // ... and a side's own qubits (launch_fact
 //       per value -- a 12-qubit side's 4096 lines, times the sixteen sides an XCD serves, do not fit its L2 (measured: a zero-key
 //       circuit split 8 + 12 took 39 us where one split 10 + 10 took 31; with the values as one run 34).  Written by the host when
 //       the plan is uploaded (qsv_api.hip upload_plans), filled by side_diag_kernel right behind the copy.
+//   [674] side X REDUCED (split.hpp, reduce_final_controls; 0: the full form) [675] side Y.  Only in the block the one-launch
+//       route's descriptors name for a circuit it runs reduced; the side's plan is then that of the reduced virtual circuit and
+//       its state has no key qubit for a FINAL key: bits 0..1 F, the number of final keys (1 .. 3); bits 2..3 S, the number of
+//       simulated keys; bits 4..9: the key (bit of kappa) behind row bit r = 0, 1, 2, two bits each -- the row bits are the
+//       side's F final controls, its highest real qubits (in key order), then its S key qubits, i.e. index bits
+//       [bits - F, bits + S) of its state.  [676 .. 678) side X, [678 .. 680) side Y: the full form's local qubit (weight slot)
+//       of each real position of the reduced side, four bits each.  The table such a side hands off has the full form's layout.
 constexpr uint32_t kNoSideDiag = 0xffffffffu;
 constexpr uint32_t kSplitLoopCols = 4, kSplitLoopPos = 9, kSplitMaskX = 14, kSplitMaskY = 15, kSplitLaneTable = 16, kSplitWaveTable = 144,
-                   kSplitChunkLow = 160, kSplitChunkHigh = 416, kSplitSideDiag = 672, kSplitBlockWords = 674;
+                   kSplitChunkLow = 160, kSplitChunkHigh = 416, kSplitSideDiag = 672, kSplitReduced = 674, kSplitReducedSlots = 676,
+                   kSplitBlockWords = 680;
 constexpr int kSplitLoopBits = 5, kSplitMaxLoopX = 2;
 constexpr uint32_t kSplitFlags = 3, kSplitSwapXY = 1u;
 
@@ -94,6 +102,9 @@ enum PassMode : uint32_t {
     kModeSidePrepare = 4096u, // (with kModeFusedFactor and kModeFusedPrepare) a kEvalFused side whose plan qualifies is prepared from ONE
                               // staged read of its plan and parameters (kernels.hip side_prepare) and hands its thread factor, its tiles'
                               // factors and base indices to the pass body in registers; the same bits as prepare_eval's, a launch may choose
+    kModeFusedReduced = 8192u, // (with kModeFusedFactor) at least one evaluation of the launch runs a side on the reduced split form
+                               // (kSplitReduced above): the launch takes the instantiation whose tail reads those words.  A launch
+                               // without the bit must hold no such side -- its tail never looks
 };
 // The optional mask of a device-resident CVaR call (qsv.h: qsv_cvar_device): entry e / stride decides evaluation e (its out_index,
 // the caller's numbering), 0 = skipped.  flags == nullptr: every evaluation runs.  The flags are written by an EARLIER launch on
@@ -173,8 +184,10 @@ static_assert(kFusedLdsRowsEnd <= kFusedLdsTableEnd, "a launch with kModeFusedLd
 // 10 gates, 11 store / reduce, 12 epilogue.
 constexpr int kStampPasses = 8, kStampPhases = 16;
 // A batch of sides' own tables of D: out[base + x] = diag[x deposited in mask], x < 2^bits (upload_plans)
+// (a reduced side: `mask` without its final controls; `top` names them -- count in bits 0..1, then the qubit of each, five bits
+// apiece, in the order of the table's highest bits; 0: none)
 struct SideDiagJob {
-    uint32_t base, mask, bits;
+    uint32_t base, mask, bits, top;
 };
 constexpr int kSideDiagJobsPerLaunch = 128;
 struct SideDiagJobs {

@@ -64,6 +64,12 @@ struct Circuit {
     CircuitPlan plan;               // words: everything of this circuit that lives in the device arena; stats: of the
                                     // ordinary multi-pass plan, once it exists
     SplitInfo split;
+    // The form the ONE-LAUNCH route runs instead where a side has final controls (split.hpp, reduce_final_controls; option
+    // "final_controls"): plans of the reduced sides and a split block of their own behind the full form's, which every other
+    // consumer of side states keeps.  A side that is not reduced shares the full form's plan.  By side X / Y of the block:
+    // the side's qubits without its final controls, and the final controls as SideDiagJob::top wants them.
+    SplitInfo reduced;
+    uint32_t reduced_mask[2] = {0, 0}, reduced_top[2] = {0, 0};
     // The ordinary plan of a circuit that has a split form is scheduled when something first needs it (a general
     // operator, a state read-out, sampling): a population of fresh structures under a diagonal operator never does,
     // and its scheduling was half the cost of registering a structure.
@@ -280,6 +286,8 @@ struct qsv_handle {
     DeviceBuffer d_sdiag;
     size_t sdiag_used = 0;             // doubles handed out
     bool side_diag = true;             // (QSV_SIDE_DIAG=0: the sums gather from D itself, as before round 4)
+    bool final_controls = true;        // one-launch route: a side simulates no key qubit for a key whose control on it is final (split.hpp,
+                                       // reduce_final_controls); circuits registered afterwards.  QSV_FINAL_CONTROLS=0 / option "final_controls"
     bool sides_r3 = true;              // one-launch route at 20 qubits: sides of up to twelve virtual qubits planned with EIGHT amplitudes per thread
                                        // (a gate phase is one wave's issue time over its own amplitudes: twice the waves, half the time),
                                        // three-key sides of thirteen as two workgroups each (kEvalHalves); circuits registered afterwards
@@ -362,6 +370,7 @@ struct qsv_handle {
         std::vector<std::pair<hipEvent_t, hipEvent_t>> launch_events[3];  // per launch: [0] first pass, [1] later passes, [2] contraction
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         bool split_any = false; // some evaluation of the batch runs split: the descriptor array has a second region
+        bool reduced = false;   // ... and those with a reduced form run it (side_form): laid out by the expectation route for its one-launch route
         std::vector<char> split;  // per evaluation
         bool cont_any = false;  // some evaluation continues a kept state (Circuit::prefix_id): a push puts those last
         size_t snap_n_cont = 0;
@@ -676,6 +685,86 @@ CircuitPlan build_ordinary_plan(const qsv_t* h, const std::vector<GateIn>& gates
     return two;
 }
 
+// The reduced form of a circuit whose full form takes the one-launch route (Circuit::reduced): a side with final controls is
+// planned anew without their keys -- one tile, one pass, the full form's amplitudes per thread, or it keeps the full form --
+// and a copy of the split block says which keys are whose (kernels.hpp kSplitReduced).  sx: the side that is X in the block.
+// The tail deals its Gram waves out over the 2^F blocks of x (kernels.hip fused_factor_tail): at least one wave per block and 64
+// x per block.  Appends to out->plan.words.
+void plan_reduced_sides(const qsv_t* h, const PlanConfig& pc, const SplitCircuits& sc, int sx, Circuit* out) {
+    const SplitInfo& full = out->split;
+    const ReducedSplit rs = reduce_final_controls(sc);
+    if (!rs.any || sc.n_keys > 3) return;
+    SplitInfo red = full;
+    std::vector<uint32_t>& w = out->plan.words;
+    const size_t words_before = w.size();
+    const int side_tile = std::max(h->geo.k, std::min(h->geo.r + 9, int(kMaxTileBits)));
+    uint32_t word[2] = {0, 0}, slots[2][2] = {{0, 0}, {0, 0}};
+    bool any = false;
+    for (int s = 0; s < 2; ++s) {
+        const int xy = s == sx ? 0 : 1;
+        out->reduced_mask[xy] = uint32_t(sc.mask[s]);
+        out->reduced_top[xy] = 0;
+        if (!rs.final_keys[s]) continue;
+        const int n_final = __builtin_popcount(rs.final_keys[s]), n_sim = __builtin_popcount(rs.simulated_keys[s]), nv = rs.n_virtual[s];
+        PlanConfig side = pc;
+        side.reg_bits = full.side_r;
+        side.compact = false;
+        side.tile_bits = full.side_r == 3 ? std::min(nv, 12) : std::min(nv, side_tile);
+        side.lane_bits = 0;  // (one tile, synthesised, its state read back by its own workgroup only: build_circuit)
+        if (nv > side.tile_bits || side.tile_bits <= side.reg_bits) continue;
+        const int t = side.tile_bits - side.reg_bits, gram_waves = t >= 9 ? 8 : 4;
+        if ((1 << n_final) > gram_waves || sc.n_side[s] - n_final < 6) continue;
+        const CircuitPlan p = build_plan(nv, rs.gates[s], rs.angles[s], side);
+        if (p.stats.n_passes != 1) continue;
+        red.stats[s] = p.stats;
+        red.t[s] = t;
+        red.outer[s] = 0;
+        red.tile_bits[s] = side.tile_bits;
+        red.n_virtual[s] = nv;
+        red.off_side[s] = uint32_t(w.size());
+        w.insert(w.end(), p.words.begin(), p.words.end());
+        word[xy] = uint32_t(n_final) | uint32_t(n_sim) << 2;
+        int row = 0;  // (row bits: the final controls in key order, then the simulated keys)
+        for (int pass = 0; pass < 2; ++pass)
+            for (int j = 0; j < sc.n_keys; ++j)
+                if (((rs.final_keys[s] >> j) & 1u) == uint32_t(pass == 0)) word[xy] |= uint32_t(j) << (4 + 2 * row++);
+        std::vector<int> qubit;  // the register's qubit of each local qubit of the full form
+        for (int q = 0; q < h->n; ++q)
+            if (sc.mask[s] >> q & 1u) qubit.push_back(q);
+        for (int pos = 0; pos < sc.n_side[s]; ++pos) slots[xy][pos >> 3] |= uint32_t(rs.qubit_of[s][size_t(pos)]) << (4 * (pos & 7));
+        uint32_t top = uint32_t(n_final), low_mask = uint32_t(sc.mask[s]);
+        for (int f = 0; f < n_final; ++f) {
+            const int q = qubit[size_t(rs.qubit_of[s][size_t(sc.n_side[s] - n_final + f)])];
+            top |= uint32_t(q) << (2 + 5 * f);
+            low_mask &= ~(1u << q);
+        }
+        out->reduced_mask[xy] = low_mask;
+        out->reduced_top[xy] = top;
+        any = true;
+    }
+    if (!any) {
+        w.resize(words_before);
+        return;
+    }
+    // (half sides: the thirteen-qubit sides that keep the full form, under the full form's rule)
+    red.halves = full.halves && ((word[sx == 0 ? 0 : 1] == 0 && full.n_virtual[0] == kFusedLdsRowsBits) ||
+                                 (word[sx == 1 ? 0 : 1] == 0 && full.n_virtual[1] == kFusedLdsRowsBits));
+    const std::vector<uint32_t> block(w.begin() + long(full.off_block), w.begin() + long(full.off_block) + long(kSplitBlockWords));
+    red.off_block = uint32_t(w.size());
+    w.insert(w.end(), block.begin(), block.end());
+    uint32_t* blk = w.data() + red.off_block;
+    for (int xy = 0; xy < 2; ++xy) {
+        blk[kSplitReduced + xy] = word[xy];
+        blk[kSplitReducedSlots + 2 * xy] = slots[xy][0];
+        blk[kSplitReducedSlots + 2 * xy + 1] = slots[xy][1];
+    }
+    red.ok = true;
+    out->reduced = red;
+    if (getenv("QSV_SPLIT_DEBUG"))
+        fprintf(stderr, "split: reduced virtual %d/%d (full %d/%d) halves %d\n", red.n_virtual[0], red.n_virtual[1], full.n_virtual[0],
+                full.n_virtual[1], int(red.halves));
+}
+
 // Validate an op list and schedule it.  Touches only immutable parts of the handle (n, cfg), so it needs no lock and
 // several threads may build plans at the same time.
 int build_circuit(qsv_t* h, int n_ops, const qsv_op* ops, int n_params, bool fold, Circuit* out, std::string* err) {
@@ -867,6 +956,8 @@ int build_circuit(qsv_t* h, int n_ops, const qsv_op* ops, int n_params, bool fol
                         fprintf(stderr, "split: keys %d sides %d+%d virtual %d/%d tiles 2^%d/2^%d passes %d/%d fused %d\n", sp.n_keys, sc.n_side[0],
                                 sc.n_side[1], sp.n_virtual[0], sp.n_virtual[1], sp.outer[0], sp.outer[1], sp.stats[0].n_passes,
                                 sp.stats[1].n_passes, int(sp.fused));
+                    // (`blk` is not used below: the words may move)
+                    if (sp.fused && h->final_controls) plan_reduced_sides(h, pc, sc, sx, out);
                 } else {
                     w.resize(sp.off_side[0] ? sp.off_side[0] : w.size());
                     sp = SplitInfo{};
@@ -976,9 +1067,11 @@ int upload_plans(qsv_t* h, const std::vector<Circuit*>& circs) {
     size_t need = 0, need_d = 0;
     // (doubles of the two sides' own tables of D: split circuits whose expectation comes from Gram sums -- a quadratic diagonal operator)
     auto side_diag_doubles = [&](const Circuit* c) -> size_t {
-        if (!h->side_diag || !h->d_diag.ptr || !c->split.ok || !(h->diagonal && h->quadratic && h->d_quad.ptr)) return 0;
+        if (!h->d_diag.ptr || !c->split.ok || !(h->diagonal && h->quadratic && h->d_quad.ptr)) return 0;
         const uint32_t* blk = c->plan.words.data() + c->split.off_block;
-        return (size_t(1) << blk[1]) + (size_t(1) << blk[2]);
+        // (a reduced form's block names tables of its own, whatever the option says: a reduced side's table is in the order of ITS
+        // qubits, which no mask describes -- the same values of D either way, so the option still changes no bit)
+        return ((size_t(1) << blk[1]) + (size_t(1) << blk[2])) * ((h->side_diag ? 1 : 0) + (c->reduced.ok ? 1 : 0));
     };
     for (Circuit* c : circs)
         if (!c->uploaded && !c->staged) {
@@ -1049,12 +1142,22 @@ int upload_plans(qsv_t* h, const std::vector<Circuit*>& circs) {
             // the sides' own tables of D: named in the split block, filled behind the copy below
             uint32_t* blk = c->plan.words.data() + c->split.off_block;
             blk[kSplitSideDiag] = blk[kSplitSideDiag + 1] = kNoSideDiag;
-            if (side_diag_doubles(c))
+            if (h->side_diag && side_diag_doubles(c))
                 for (uint32_t xy = 0; xy < 2; ++xy) {
                     blk[kSplitSideDiag + xy] = uint32_t(h->sdiag_used);
                     jobs.push_back(SideDiagJob{uint32_t(h->sdiag_used), blk[kSplitMaskX + xy], blk[1 + xy]});
                     h->sdiag_used += size_t(1) << blk[1 + xy];
                 }
+            if (c->reduced.ok) {
+                uint32_t* rblk = c->plan.words.data() + c->reduced.off_block;
+                rblk[kSplitSideDiag] = rblk[kSplitSideDiag + 1] = kNoSideDiag;
+                if (side_diag_doubles(c))
+                    for (uint32_t xy = 0; xy < 2; ++xy) {
+                        rblk[kSplitSideDiag + xy] = uint32_t(h->sdiag_used);
+                        jobs.push_back(SideDiagJob{uint32_t(h->sdiag_used), c->reduced_mask[xy], rblk[1 + xy], c->reduced_top[xy]});
+                        h->sdiag_used += size_t(1) << rblk[1 + xy];
+                    }
+            }
         }
         std::memcpy(h->h_stage + cur, c->plan.words.data(), c->plan.words.size() * 4);
         c->plan_base = uint32_t(h->arena_used_words + cur);
@@ -1163,12 +1266,17 @@ struct EventPair {
 // launches the slice's gate passes, all asynchronously, so the host can prepare the next slice meanwhile.
 
 // doubles of an evaluation's matrix region(s): one for the ordinary plan, or one per virtual circuit when it runs split
+// The form of a split circuit the batch laid out now runs: the reduced one (Circuit::reduced) where the batch is the
+// expectation route's and that route is the one-launch one (Batch::reduced), else the full form.
+const SplitInfo& side_form(const qsv_t* h, const Circuit& c) { return h->batch.reduced && c.reduced.ok ? c.reduced : c.split; }
+
 size_t mat_doubles_of(const qsv_t* h, const Circuit& c, bool split, int side) {
     if (!split)
         return mat_region_doubles(uint32_t(c.plan.stats.n_real_gates), uint32_t(h->n), h->geo.t, h->n - h->geo.k,
                                   c.plan.stats.n_passes);
-    return mat_region_doubles(uint32_t(c.split.stats[side].n_real_gates), uint32_t(c.split.n_virtual[side]), c.split.t[side],
-                              c.split.outer[side], c.split.stats[side].n_passes);
+    const SplitInfo& sp = side_form(h, c);
+    return mat_region_doubles(uint32_t(sp.stats[side].n_real_gates), uint32_t(sp.n_virtual[side]), sp.t[side],
+                              sp.outer[side], sp.stats[side].n_passes);
 }
 
 // Whether a circuit runs as the two virtual circuits of its split form (split.hpp) in a call of one kind (split_rule):
@@ -1178,6 +1286,7 @@ size_t mat_doubles_of(const qsv_t* h, const Circuit& c, bool split, int side) {
 struct SplitRule {
     bool allow = false;
     int max_keys = 3;
+    bool reduced = false;  // the one-launch route's reduced forms where circuits have them (the expectation route only: eval_begin)
     bool takes(const Circuit& c) const { return allow && c.split.ok && c.split.n_keys <= max_keys && c.prefix_id < 0; }
     size_t count(const std::vector<Circuit*>& circs) const {
         return size_t(std::count_if(circs.begin(), circs.end(), [&](const Circuit* c) { return takes(*c); }));
@@ -1191,6 +1300,7 @@ int batch_layout(qsv_t* h, const std::vector<Circuit*>& circs, const std::vector
     int rc;
     h->epoch += 1;  // (whatever an earlier batch left in the staging buffer is overwritten below)
     b.repeat = false;
+    b.reduced = rule.reduced;
     b.record.entries.clear();  // (the launches of the layout that goes)
     b.record.usable = false;
     if (h->async_pending) {  // the kernels of a batch that ended without waiting read the staging buffers written below
@@ -1278,11 +1388,12 @@ int batch_layout(qsv_t* h, const std::vector<Circuit*>& circs, const std::vector
             if (b.split_any) hd[n_evals + i] = EvalDesc{0, 0, slot, uint32_t(i), 0, 0, kEvalNull, 0};
         } else {
             // one descriptor per virtual circuit: side A here, side B in the second region
+            const SplitInfo& sp = side_form(h, c);
             for (int s = 0; s < 2; ++s) {
                 hd[size_t(s) * n_evals + i] =
-                    EvalDesc{c.plan_base + c.split.off_side[s], uint32_t(mcur), slot, uint32_t(i), uint32_t(pcur),
-                             uint32_t(n_params[i]), kEvalSide | (s ? kEvalSideB : 0u) | (c.split.fused ? kEvalFused : 0u) | (c.split.fused && c.split.halves ? kEvalHalves : 0u),
-                             c.plan_base + c.split.off_block};
+                    EvalDesc{c.plan_base + sp.off_side[s], uint32_t(mcur), slot, uint32_t(i), uint32_t(pcur),
+                             uint32_t(n_params[i]), kEvalSide | (s ? kEvalSideB : 0u) | (sp.fused ? kEvalFused : 0u) | (sp.fused && sp.halves ? kEvalHalves : 0u),
+                             c.plan_base + sp.off_block};
                 mcur += mat_doubles_of(h, c, true, s);
             }
         }
@@ -1382,6 +1493,8 @@ bool factor_terms_path(const qsv_t* h) { return h->factor_enabled && !h->diagona
 
 // Split evaluations flagged kEvalFused are finished by the launch that runs their virtual circuits (quadratic operator).
 bool fused_route(const qsv_t* h) { return factor_path(h) && h->d_factor_count.ptr != nullptr && h->fused_factor; }
+// ... with the reduced forms of circuits that have one (Circuit::reduced): a reduced side's values of D come from its own table only
+bool reduced_route(const qsv_t* h) { return fused_route(h) && h->final_controls && h->d_diag.ptr != nullptr; }
 
 // The kinds of call that may run circuits split, and what each needs of the final states: the expectation value under the
 // operator set now (eval_begin; qsv_circuit_cost also asks before an operator is set), samples or the exact CVaR (read from the
@@ -1431,6 +1544,7 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
         mode &= ~uint32_t(kModeSynthFirst | kModeFusedPrepare | kModeDirectResult);
     }
     const bool any_split = n_split > 0;
+    if (b.reduced && (mode & kModeSidesOnly)) return fail(h, QSV_E_STATE, "internal: a batch laid out for reduced sides runs its sides only");
     const size_t n_plain = count - n_split;
     if (h->mask.flags) mode |= kModeMasked;  // (qsv_cvar_device with a mask: every launch below carries the bit and the pointer)
     PassArgs a{};
@@ -1467,7 +1581,7 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
     const bool fuse_ok = fused_route(h) && !(mode & kModeSidesOnly);
     if (fuse_ok) {
         n_unfused = 0;
-        while (n_unfused < n_split && !circs[eval_of(first + n_unfused)]->split.fused) ++n_unfused;
+        while (n_unfused < n_split && !side_form(h, *circs[eval_of(first + n_unfused)]).fused) ++n_unfused;
     }
     const bool two_chains = b.chain_now && h->chain_stream != -1 && n_unfused > 0 && n_split > n_unfused && factor_path(h);
     // (the chain's stream: the second lane's, or -- for a push on the second lane -- the handle's own, which `work` = null means)
@@ -1491,7 +1605,7 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
             *passes = 1;
             *tiles = 1;
             for (size_t i = lo; i < hi; ++i) {
-                const SplitInfo& sp = circs[eval_of(first + i)]->split;
+                const SplitInfo& sp = side_form(h, *circs[eval_of(first + i)]);
                 for (int s = 0; s < 2; ++s) {
                     tile = std::max(tile, sp.tile_bits[s]);
                     t = std::max(t, sp.t[s]);
@@ -1510,9 +1624,13 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
             shape_of(lo, hi, &threads, &lds, &passes, &tiles);
             if (extra_mode & kModeFusedFactor) threads = at_least_four_waves(threads);
             // (fused: ONE workgroup per side, one tile -- or, a half side, one of its two tiles -- then on to the side's Gram matrices)
-            bool any_halves = false;
+            bool any_halves = false, any_reduced = false;
             if (extra_mode & kModeFusedFactor)
-                for (size_t i = lo; i < hi; ++i) any_halves |= circs[eval_of(first + i)]->split.halves;
+                for (size_t i = lo; i < hi; ++i) {
+                    const Circuit& c = *circs[eval_of(first + i)];
+                    any_halves |= side_form(h, c).halves;
+                    any_reduced |= &side_form(h, c) == &c.reduced;  // (the launch then needs the tail that knows reduced sides)
+                }
             // (a side's one workgroup sweeps its tiles itself, whatever the grid's width: pass_kernel)
             a.tiles_per_block = (extra_mode & kModeFusedFactor) ? tiles : 1u;
             const unsigned grid_x = (extra_mode & kModeFusedFactor) ? (any_halves ? 2u : 1u) : tiles;
@@ -1529,13 +1647,14 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
                 if (p == 0 && (extra_mode & kModeFusedFactor)) need = std::max(need, kFusedFactorLdsBytes);
                 // at most one workgroup per CU in flight anyway (two per evaluation): room for the sides' states in LDS
                 size_t working = 0;
-                for (size_t i = lo; i < hi; ++i) working += working_workgroups(circs[eval_of(first + i)]->split);
+                for (size_t i = lo; i < hi; ++i) working += working_workgroups(side_form(h, *circs[eval_of(first + i)]));
                 if (p == 0 && (extra_mode & kModeFusedFactor) && h->dtype == QSV_F64 && (h->fused_lds_table || any_halves) && working <= size_t(h->n_cus)) {
                     a.mode |= kModeFusedLdsTable;
                     need = std::max(need, kFusedLdsTableEnd);
                 }
                 // (need >= kFusedFactorLdsBytes: room for the staged plan run behind prepare_eval's scratch)
                 if (p == 0 && (extra_mode & kModeFusedFactor) && h->side_prepare) a.mode |= kModeSidePrepare;
+                if (p == 0 && any_reduced) a.mode |= kModeFusedReduced;
                 if (h->stamping) QSV_HIP(h, stamp(h, h->batch.launch_events[kind], true));
                 QSV_LAUNCH(h, launch_pass(h->dtype, r, h->cfg.xmode, dim3(grid_x, unsigned(hi - lo), 2), threads, need, ws(h), a));
                 record_pass(h, r, dim3(grid_x, unsigned(hi - lo), 2), threads, need, a);
@@ -1557,11 +1676,11 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
             // amplitude ones first within each kind, but a range may hold both kinds -- every split evaluation under an operator
             // that has no one-launch route)
             for (size_t at = lo; at < hi;) {
-                const int r = circs[eval_of(first + at)]->split.side_r == 3 ? 3 : h->geo.r;
+                const int r = side_form(h, *circs[eval_of(first + at)]).side_r == 3 ? 3 : h->geo.r;
                 size_t end = at;
                 bool halves_here = false;
-                while (end < hi && (circs[eval_of(first + end)]->split.side_r == 3 ? 3 : h->geo.r) == r) {
-                    halves_here |= circs[eval_of(first + end)]->split.halves;
+                while (end < hi && (side_form(h, *circs[eval_of(first + end)]).side_r == 3 ? 3 : h->geo.r) == r) {
+                    halves_here |= side_form(h, *circs[eval_of(first + end)]).halves;
                     ++end;
                 }
                 // (half sides need the launch's states in LDS: at most one working workgroup per compute unit)
@@ -1569,8 +1688,8 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
                     size_t to = end;
                     if (halves_here && (extra_mode & kModeFusedFactor)) {
                         size_t wg = 0;
-                        for (to = from; to < end && wg + working_workgroups(circs[eval_of(first + to)]->split) <= size_t(h->n_cus); ++to)
-                            wg += working_workgroups(circs[eval_of(first + to)]->split);
+                        for (to = from; to < end && wg + working_workgroups(side_form(h, *circs[eval_of(first + to)])) <= size_t(h->n_cus); ++to)
+                            wg += working_workgroups(side_form(h, *circs[eval_of(first + to)]));
                         if (to == from) to = from + 1;
                     }
                     const int rc3 = launch_sides(from, to, extra_mode, r);
@@ -1586,8 +1705,8 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
         // (the one-launch kind: as one launch -- unless the group is too large for one with the sides' states in LDS and holds half
         // sides, which lead the range: those go first, to the chain stream where the push has one free, the others follow as before)
         size_t n_halved = 0, all_working = 0;
-        while (n_unfused + n_halved < n_split && circs[eval_of(first + n_unfused + n_halved)]->split.halves) ++n_halved;
-        for (size_t i = n_unfused; i < n_split; ++i) all_working += working_workgroups(circs[eval_of(first + i)]->split);
+        while (n_unfused + n_halved < n_split && side_form(h, *circs[eval_of(first + n_unfused + n_halved)]).halves) ++n_halved;
+        for (size_t i = n_unfused; i < n_split; ++i) all_working += working_workgroups(side_form(h, *circs[eval_of(first + i)]));
         if (n_halved > 0 && n_unfused + n_halved < n_split && all_working > size_t(h->n_cus)) {
             // (too many for one launch with the sides' states in LDS, which half sides need: those few lead the range and get a
             // launch of their own -- on the chain stream where the push has one free --, the others follow as one launch, their
@@ -1601,7 +1720,7 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
         a.mode = mode | h->stream_mode;
         // what the side circuits move: they synthesise their input and write their final states
         for (size_t i = 0; i < n_split; ++i) {
-            const SplitInfo& sp = circs[eval_of(first + i)]->split;
+            const SplitInfo& sp = side_form(h, *circs[eval_of(first + i)]);
             const uint64_t bytes = ((uint64_t(1) << sp.n_virtual[0]) + (uint64_t(1) << sp.n_virtual[1])) * h->amp_bytes;
             h->prof.state_bytes += bytes;
             h->prof.moved_bytes += bytes;
@@ -1610,7 +1729,7 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
         }
         // (the fused ones: what their Gram matrices read and compute is part of that launch)
         for (size_t i = n_unfused; i < n_split; ++i) {
-            const SplitInfo& sp = circs[eval_of(first + i)]->split;
+            const SplitInfo& sp = side_form(h, *circs[eval_of(first + i)]);
             for (int s = 0; s < 2; ++s) {
                 const int side_bits = sp.n_virtual[s] - sp.n_keys;
                 const uint64_t moved = (uint64_t(1) << sp.n_virtual[s]) * h->amp_bytes + (uint64_t(8) << side_bits);
@@ -1816,7 +1935,9 @@ int eval_begin(qsv_t* h, const std::vector<Circuit*>& circs, const std::vector<i
         QSV_HIP(h, hipEventCreate(&h->batch.ev1));
         QSV_HIP(h, hipEventRecord(h->batch.ev0, h->stream));
     }
-    if ((rc = batch_layout(h, circs, n_params, split_rule(h, SplitUse::Expectation)))) return rc;
+    SplitRule rule = split_rule(h, SplitUse::Expectation);
+    rule.reduced = reduced_route(h);
+    if ((rc = batch_layout(h, circs, n_params, rule))) return rc;
     if (factor_terms_path(h) && h->batch.split_any &&
         (rc = ensure(h, h->d_fpart, std::max<size_t>(1, n_evals) * kFactorTermWaves * sizeof(double))))
         return rc;
@@ -1901,7 +2022,7 @@ size_t order_split_first(qsv_t* h, size_t first, size_t count, size_t* n_cont = 
         for (int cls = kMaxSplitKeys; cls >= 0; --cls)
             for (size_t j = 0; j < count; ++j) {
                 if (!b.split[first + j]) continue;
-                const SplitInfo& sp = b.circs[first + j]->split;
+                const SplitInfo& sp = side_form(h, *b.circs[first + j]);
                 if (sp.n_keys != cls || int(sp.fused) != fused || ((sp.side_r == 3) != (r == 3)) || int(sp.halves) != halved) continue;
                 hd[at] = tmp[j];
                 hd[P + at] = tmp2[j];
@@ -2139,14 +2260,14 @@ int eval_push(qsv_t* h, size_t first, size_t count, const double* values, const 
     if (h->chain_enabled && ways <= 2 && lane <= 1 && h->n_lane_streams >= 1 && n_split > 0 && n_split <= SG && factor_path(h) &&
         fused_route(h)) {
         size_t n_fused = 0;
-        for (size_t j = 0; j < n_split; ++j) n_fused += b.circs[b.eval_at[first + j]]->split.fused ? 1 : 0;
+        for (size_t j = 0; j < n_split; ++j) n_fused += side_form(h, *b.circs[b.eval_at[first + j]]).fused ? 1 : 0;
         b.chain_now = n_fused > 0 && n_fused < n_split;
         // (... or every split evaluation is of the first kind, too many for one launch with the sides' states in LDS, and some have
         // half sides, which need them there: those few get a launch of their own beside the others', run_group)
         size_t n_halved = 0;
-        for (size_t j = 0; j < n_split; ++j) n_halved += b.circs[b.eval_at[first + j]]->split.halves ? 1 : 0;
+        for (size_t j = 0; j < n_split; ++j) n_halved += side_form(h, *b.circs[b.eval_at[first + j]]).halves ? 1 : 0;
         size_t working = 0;
-        for (size_t j = 0; j < n_split; ++j) working += working_workgroups(b.circs[b.eval_at[first + j]]->split);
+        for (size_t j = 0; j < n_split; ++j) working += working_workgroups(side_form(h, *b.circs[b.eval_at[first + j]]));
         if (n_fused == n_split && n_halved > 0 && working > size_t(h->n_cus)) b.chain_now = true;
     }
     if (b.chain_now) {
@@ -2726,6 +2847,7 @@ int qsv_create(int n_qubits, int dtype, int device, const qsv_plan_config* cfg, 
     if (const char* env = getenv("QSV_SIDE_PREPARE")) h->side_prepare = atoi(env) != 0;
     if (const char* env = getenv("QSV_SIDE_DIAG")) h->side_diag = atoi(env) != 0;
     if (const char* env = getenv("QSV_SIDES_R3")) h->sides_r3 = atoi(env) != 0;
+    if (const char* env = getenv("QSV_FINAL_CONTROLS")) h->final_controls = atoi(env) != 0;
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) h->n_cus = cus;
@@ -3178,6 +3300,13 @@ int qsv_circuit_create_on_prefix(qsv_t* h, int prefix_id, int n_ops, const qsv_o
     return qsv_circuits_create_on_prefixes(h, 1, offsets, ops, &n_params, &prefix_id, out_circuit_id);
 }
 
+// Whether the one-launch route runs `c` on its reduced form under the operator set now: what run_group decides through side_form
+// (eval_begin lays a batch out for reduced sides where reduced_route holds); before an operator is set, what it would decide
+// under a quadratic one.
+static bool runs_reduced(const qsv_t* h, const Circuit& c) {
+    return c.split.fused && c.reduced.ok && (h->n_terms == 0 ? h->fused_factor && h->final_controls : reduced_route(h));
+}
+
 int qsv_circuit_cost(qsv_t* h, int circuit_id, qsv_circuit_cost_t* out) {
     if (!h) return QSV_E_ARG;
     if (!out) return fail(h, QSV_E_ARG, "out is null");
@@ -3189,8 +3318,9 @@ int qsv_circuit_cost(qsv_t* h, int circuit_id, qsv_circuit_cost_t* out) {
     // which way an expectation value of this circuit goes under the operator set now
     const double scale = std::ldexp(1.0, h->n - 20) * (h->dtype == QSV_F64 ? 1.0 : 0.5);
     if (split_rule(h, SplitUse::Expectation).takes(c)) {
-        const SplitInfo& sp = c.split;
-        const bool one_launch = sp.fused && h->fused_factor && (h->n_terms == 0 || factor_path(h));
+        const bool one_launch = c.split.fused && h->fused_factor && (h->n_terms == 0 || factor_path(h));
+        // (the one-launch route runs the reduced form of a circuit that has one: its sizes are what the launch costs)
+        const SplitInfo& sp = one_launch && runs_reduced(h, c) ? c.reduced : c.split;
         out->route = one_launch ? QSV_ROUTE_SPLIT_ONE_LAUNCH : QSV_ROUTE_SPLIT;
         out->n_keys = sp.n_keys;
         out->n_passes = std::max(sp.stats[0].n_passes, sp.stats[1].n_passes);
@@ -3228,7 +3358,7 @@ int qsv_circuit_cost(qsv_t* h, int circuit_id, qsv_circuit_cost_t* out) {
     return QSV_OK;
 }
 
-int qsv_circuit_form(qsv_t* h, int circuit_id, qsv_circuit_form_t* out) {
+static int circuit_form_of(qsv_t* h, int circuit_id, qsv_circuit_form_t* out, bool launched) {
     if (!h) return QSV_E_ARG;
     if (!out) return fail(h, QSV_E_ARG, "out is null");
     qsv_circuit_cost_t cost;
@@ -3241,10 +3371,12 @@ int qsv_circuit_form(qsv_t* h, int circuit_id, qsv_circuit_form_t* out) {
     *out = qsv_circuit_form_t{};
     out->route = cost.route;
     out->n_keys = cost.n_keys;
-    const SplitInfo& sp = c.split;
-    if (!sp.ok) return QSV_OK;
-    // (the side plans are indexed as find_split left them; the split block names which of them is X)
-    const uint32_t* blk = c.plan.words.data() + sp.off_block;
+    // (qsv_circuit_form: the FULL form, also of a circuit the one-launch route runs reduced: mask_x / mask_y and the keys both sides
+    // share are what every other consumer of the side states goes by.  qsv_circuit_launch_form: the side plans that route runs)
+    if (!c.split.ok) return QSV_OK;
+    const SplitInfo& sp = launched && cost.route == QSV_ROUTE_SPLIT_ONE_LAUNCH && runs_reduced(h, c) ? c.reduced : c.split;
+    // (the side plans are indexed as find_split left them; the split block names which of them is X -- in either form)
+    const uint32_t* blk = c.plan.words.data() + c.split.off_block;
     const int sx = (blk[kSplitFlags] & kSplitSwapXY) ? 1 : 0;
     for (int xy = 0; xy < 2; ++xy) {
         out->n_virtual[xy] = sp.n_virtual[xy == 0 ? sx : 1 - sx];
@@ -3258,6 +3390,10 @@ int qsv_circuit_form(qsv_t* h, int circuit_id, qsv_circuit_form_t* out) {
     out->mask_y = blk[kSplitMaskY];
     return QSV_OK;
 }
+
+int qsv_circuit_form(qsv_t* h, int circuit_id, qsv_circuit_form_t* out) { return circuit_form_of(h, circuit_id, out, false); }
+
+int qsv_circuit_launch_form(qsv_t* h, int circuit_id, qsv_circuit_form_t* out) { return circuit_form_of(h, circuit_id, out, true); }
 
 int qsv_eval_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
                       double* out) {
@@ -3382,7 +3518,7 @@ int qsv_eval_begin(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t*
         b.cur_ids.assign(circuit_ids, circuit_ids + n_evals);
         b.cur_counts.assign(param_counts, param_counts + n_evals);
         b.have_ids = true;
-        if (h->repeat_enabled && n_evals > 0 && b.snap_epoch == h->epoch && !h->profiling &&
+        if (h->repeat_enabled && n_evals > 0 && b.snap_epoch == h->epoch && !h->profiling && b.reduced == reduced_route(h) &&
             b.snap_ids == b.cur_ids && b.snap_counts == b.cur_counts && b.circs.size() == size_t(n_evals)) {
             // (A batch that ended without waiting may still be running.  Its kernels read the staging buffers: whoever WRITES
             // them waits for it first -- qsv_eval_push with host values, qsv_eval_staging --, and a batch whose values come from
@@ -5193,6 +5329,9 @@ int qsv_set_option(qsv_t* h, const char* name, int value) {
         h->fused_lds_table = value != 0;
     } else if (key == "side_prepare") {  // one-launch route: a side prepared from one staged read of its plan (same bits either way).  The next launch.
         h->side_prepare = value != 0;
+    } else if (key == "final_controls") {  // one-launch route: no key qubit for a final control's key on the control's side.  Circuits registered afterwards.
+        h->final_controls = value != 0;
+        h->epoch += 1;  // (a batch that repeats must be laid out again: which form it runs is decided there)
     } else if (key == "sides_r3") {  // one-launch route: sides with eight amplitudes per thread, three-key sides on two workgroups.  Circuits registered afterwards.
         h->sides_r3 = value != 0;
     } else if (key == "side_diag") {  // one-launch route: a side's values of D from a table of its own (one run) instead of gathered from D
@@ -5339,6 +5478,48 @@ int qsv_split_describe(int n_qubits, int n_ops, const qsv_op* ops, int max_side,
         for (size_t i = 0; i < sc.gates[s].size(); ++i) {
             const GateIn& g = sc.gates[s][i];
             const AngleSource& a = sc.angles[s][size_t(g.op)];
+            qsv_op o{};
+            o.kind = g.control < 0 ? QSV_OP_U : QSV_OP_CU3;
+            o.target = uint8_t(g.target);
+            o.control = g.control < 0 ? uint8_t(QSV_NO_CONTROL) : uint8_t(g.control);
+            o.p_theta = a.p_theta; o.p_phi = a.p_phi; o.p_lambda = a.p_lambda;
+            o.theta = a.theta; o.phi = a.phi; o.lambda = a.lambda;
+            outs[s][i] = o;
+        }
+    }
+    return sc.n_keys;
+}
+
+int qsv_split_describe_reduced(int n_qubits, int n_ops, const qsv_op* ops, int max_side, uint64_t* mask_a, qsv_op* ops_a,
+                               int capacity_a, int* n_ops_a, qsv_op* ops_b, int capacity_b, int* n_ops_b,
+                               uint32_t* simulated_keys, uint32_t* final_keys, int* key_bits, int* qubits) {
+    if (!mask_a || !n_ops_a || !n_ops_b || !simulated_keys || !final_keys || !key_bits || !qubits)
+        return fail(nullptr, QSV_E_ARG, "null output") - 100;
+    if (n_qubits < 1 || n_qubits > 32) return fail(nullptr, QSV_E_ARG, "n_qubits must be in [1, 32]") - 100;
+    if (validate_ops(nullptr, n_qubits, n_ops, ops, 1 << 30)) return QSV_E_ARG - 100;
+    std::vector<AngleSource> angles;
+    const std::vector<GateIn> gates = gates_of(ops, n_ops, &angles);
+    const SplitCircuits sc = find_split(n_qubits, gates, angles, max_side);
+    if (!sc.ok) return -1;
+    const ReducedSplit rs = reduce_final_controls(sc);
+    *mask_a = sc.mask[0];
+    qsv_op* outs[2] = {ops_a, ops_b};
+    const int caps[2] = {capacity_a, capacity_b};
+    int* counts[2] = {n_ops_a, n_ops_b};
+    for (int s = 0; s < 2; ++s) {
+        simulated_keys[s] = rs.simulated_keys[s];
+        final_keys[s] = rs.final_keys[s];
+        for (int j = 0; j < QSV_SPLIT_MAX_KEYS; ++j) key_bits[s * QSV_SPLIT_MAX_KEYS + j] = j < kMaxSplitKeys ? rs.key_bit[s][j] : -1;
+        // (the side's qubits in ascending order are the full form's local numbers)
+        std::vector<int> global;
+        for (int q = 0; q < n_qubits; ++q)
+            if (sc.mask[s] >> q & 1u) global.push_back(q);
+        for (int p = 0; p < 32; ++p) qubits[s * 32 + p] = p < sc.n_side[s] ? global[size_t(rs.qubit_of[s][size_t(p)])] : -1;
+        *counts[s] = int(rs.gates[s].size());
+        if (!outs[s] || caps[s] < *counts[s]) continue;
+        for (size_t i = 0; i < rs.gates[s].size(); ++i) {
+            const GateIn& g = rs.gates[s][i];
+            const AngleSource& a = rs.angles[s][size_t(g.op)];
             qsv_op o{};
             o.kind = g.control < 0 ? QSV_OP_U : QSV_OP_CU3;
             o.target = uint8_t(g.target);

@@ -437,4 +437,70 @@ SplitCircuits find_split(int n, const std::vector<GateIn>& all_gates, const std:
     return SplitCircuits{};
 }
 
+ReducedSplit reduce_final_controls(const SplitCircuits& full) {
+    ReducedSplit out;
+    if (!full.ok) return out;
+    const int nk = full.n_keys;
+    for (int s = 0; s < 2; ++s) {
+        const std::vector<GateIn>& fg = full.gates[s];
+        const std::vector<AngleSource>& fa = full.angles[s];
+        const int ns = full.n_side[s];
+        auto code = [&](const GateIn& g) { return fa[size_t(g.op)].p_theta; };
+        // ---- the keys whose control is final on this side ---------------------------------------------------------------
+        // (a projector triple CX(key -> c) P0(c) CX(key -> c) tells that c is the key's control and lies on this side; the
+        // gates of a side keep the circuit's order, and every gate that targets c is one of this side's)
+        std::vector<int> control_of(size_t(nk), -1);  // per final key: its control's local number in the full form
+        std::vector<char> skip(fg.size(), 0);         // gates the reduced circuit does without
+        uint32_t finals = 0;
+        for (size_t i = 0; i + 2 < fg.size(); ++i) {
+            const int j = fg[i].control - ns;
+            if (j < 0 || code(fg[i]) != kFixedX || code(fg[i + 1]) != kFixedProj0) continue;
+            const int c = fg[i].target;
+            bool later = false;
+            for (size_t l = i + 3; l < fg.size() && !later; ++l) later = fg[l].target == c;
+            if (later) continue;
+            finals |= 1u << j;
+            control_of[size_t(j)] = c;
+            skip[i] = skip[i + 1] = skip[i + 2] = 1;
+        }
+        for (size_t i = 0; i < fg.size(); ++i)  // (the (1, 1) start of a final key's qubit)
+            if (fg[i].target >= ns && (finals >> (fg[i].target - ns) & 1u)) skip[i] = 1;
+        out.final_keys[s] = finals;
+        out.simulated_keys[s] = ((1u << nk) - 1u) & ~finals;
+        out.n_virtual[s] = ns + __builtin_popcount(out.simulated_keys[s]);
+        out.any |= finals != 0;
+        // ---- the side's layout: other real qubits, final controls by key, simulated keys --------------------------------
+        std::vector<int> place(size_t(ns + nk), -1);  // full-form qubit -> reduced qubit
+        std::vector<char> is_final(size_t(ns), 0);
+        for (int j = 0; j < nk; ++j)
+            if (finals >> j & 1u) is_final[size_t(control_of[size_t(j)])] = 1;
+        int at = 0;
+        for (int q = 0; q < ns; ++q)
+            if (!is_final[size_t(q)]) {
+                place[size_t(q)] = at++;
+                out.qubit_of[s].push_back(q);
+            }
+        for (int j = 0; j < nk; ++j)
+            if (finals >> j & 1u) {
+                place[size_t(control_of[size_t(j)])] = at;
+                out.key_bit[s][j] = at++;
+                out.qubit_of[s].push_back(control_of[size_t(j)]);
+            }
+        for (int j = 0; j < nk; ++j)
+            if (!(finals >> j & 1u)) {
+                place[size_t(ns + j)] = at;
+                out.key_bit[s][j] = at++;
+            }
+        for (int j = nk; j < kMaxSplitKeys; ++j) out.key_bit[s][j] = -1;
+        // ---- the gates that are left, renumbered ---------------------------------------------------------------------------
+        for (size_t i = 0; i < fg.size(); ++i) {
+            if (skip[i]) continue;
+            out.angles[s].push_back(fa[size_t(fg[i].op)]);
+            out.gates[s].push_back(GateIn{place[size_t(fg[i].target)], fg[i].control < 0 ? -1 : place[size_t(fg[i].control)],
+                                          int(out.angles[s].size()) - 1});
+        }
+    }
+    return out;
+}
+
 }  // namespace qsv

@@ -58,4 +58,30 @@ SplitCircuits find_split(int n_qubits, const std::vector<GateIn>& gates, const s
 SplitCircuits find_split(int n_qubits, const std::vector<GateIn>& gates, const std::vector<AngleSource>& op_angles,
                          const std::vector<int>& max_sides, int max_keys = kMaxSplitKeys);
 
+// The REDUCED form of the same partition and keys.  A key's control c is FINAL when nothing targets c after the key's first
+// gate (only the last epoch of a control can be).  P_kappa(c) then commutes with everything that follows on c's side, so
+//
+//     a_kappa(x) = a(x) [x_c = kappa_j]
+//
+// with a(x) the state of the side's circuit WITHOUT the key: no key qubit, no (1, 1) start, no CX / P0 / CX.  The rows for
+// kappa_j = 0 / 1 are the two halves of the one state, Gram entries whose final-key bits differ are exactly zero and the others
+// are sums over half of x.  The target's side of the key is as in the full form.
+//
+// Layout of a reduced side: its real qubits that are no final controls in ascending order, then its final controls in
+// ascending order of their keys, then its simulated keys in ascending order -- so the restriction x_c = beta is a contiguous
+// half and (simulated keys, final-control bits) index the rows the way the keys do in the full form.
+struct ReducedSplit {
+    bool any = false;                // at least one side got smaller
+    uint32_t final_keys[2] = {0, 0};      // per side: the keys (bits of kappa) whose control is final on it
+    uint32_t simulated_keys[2] = {0, 0};  // per side: the keys it still simulates (the others)
+    int n_virtual[2] = {0, 0};            // n_side + popcount(simulated_keys)
+    int key_bit[2][kMaxSplitKeys];        // per side and key: its bit in the side's index (a key qubit's, or the final control's)
+    std::vector<int> qubit_of[2];         // per side: the full form's local qubit (0 .. n_side - 1) at each reduced real position
+    std::vector<GateIn> gates[2];
+    std::vector<AngleSource> angles[2];
+};
+
+// From the full form alone (the projector triples and (1, 1) starts are told by their fixed matrices).  Deterministic.
+ReducedSplit reduce_final_controls(const SplitCircuits& full);
+
 }  // namespace qsv
