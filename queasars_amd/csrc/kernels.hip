@@ -3905,9 +3905,17 @@ __global__ void __launch_bounds__(1024) factor_combine_kernel(const uint32_t* __
 // order and each wave's four row partials in order (factor_sum_partials' order); the imaginary part changes sign where the
 // simulated rows come in the other order; the weight of a real qubit is the weight of its position in the reduced side, and
 // the bit of a final control is the same for the whole block: the plain sum or nothing.
-__device__ __forceinline__ double factor_reduced_entry(const double* partial, const uint32_t* __restrict__ slots, uint32_t reduced,
-                                                       uint32_t n_keys, uint32_t bits, uint32_t waves_per_block, uint32_t w, uint32_t pi) {
-    const uint32_t n_final = reduced & 3u, n_sim = (reduced >> 2) & 3u, low_bits = bits - n_final;
+// In two steps, because a thread of the hand-off keeps its entry pi for every weight it stores (its indices are a multiple of
+// the entries apart): what pi alone decides -- the block of x, the entry of the simulated rows and its sign, or that the entry is
+// zero whatever the weight -- once per thread (factor_reduced_rows), the weight's slot and the sum once per value
+// (factor_reduced_value).  As one call per value this was most of a three-key reduced side's hand-off, 11.9 k cycles of the
+// first wave against 3.2 k for a two-key side on the full form (profiles/r16_free_halves.txt).  The same sums in the same order.
+struct ReducedRows {
+    uint32_t x_block, entry;
+    double sign;  // +-1; 0: the entry is zero (final-key bits differ)
+};
+__device__ __forceinline__ ReducedRows factor_reduced_rows(uint32_t reduced, uint32_t n_keys, uint32_t pi) {
+    const uint32_t n_final = reduced & 3u, n_sim = (reduced >> 2) & 3u;
     uint32_t ja, jb, part;
     if (n_keys == 1)
         split_entry_of<2>(pi, &ja, &jb, &part);
@@ -3922,7 +3930,7 @@ __device__ __forceinline__ double factor_reduced_entry(const double* partial, co
         rb |= (jb >> key & 1u) << r;
     }
     const uint32_t x_block = ra & ((1u << n_final) - 1u);
-    if (x_block != (rb & ((1u << n_final) - 1u))) return 0.0;
+    if (x_block != (rb & ((1u << n_final) - 1u))) return ReducedRows{0u, 0u, 0.0};
     const uint32_t sa = ra >> n_final, sb = rb >> n_final, J = 1u << n_sim;
     uint32_t entry = sa;
     double sign = 1.0;
@@ -3933,11 +3941,28 @@ __device__ __forceinline__ double factor_reduced_entry(const double* partial, co
         entry = J + 2u * o + (part - 1u);
         if (part == 2u && sa > sb) sign = -1.0;
     }
+    return ReducedRows{x_block, entry, sign};
+}
+// The reduced side's position of each local qubit of the full form, four bits each (the inverse of the side's two words of weight
+// slots, which name the local qubit at each position): the same for every value of a side, so worked out once -- on the scalar
+// unit, every operand is uniform -- instead of searched for per value.  A qubit no position names: position 0, as the search gave.
+__device__ __forceinline__ uint64_t factor_reduced_positions(uint32_t slots0, uint32_t slots1, uint32_t bits) {
+    uint64_t positions = 0;
+    for (uint32_t p = 0; p < bits; ++p) {
+        const uint32_t q = (p < 8u ? slots0 : slots1) >> (4u * (p & 7u)) & 15u;
+        positions = (positions & ~(uint64_t(15) << (4u * q))) | uint64_t(p) << (4u * q);
+    }
+    return positions;
+}
+// (a reduced side's block of x has at most kMaxWaves / 2 = 4 Gram waves: the reads of all of them go out together, the additions
+// keep the order of the loop over the block's waves)
+__device__ __forceinline__ double factor_reduced_value(const double* partial, const ReducedRows& rows, uint64_t positions, uint32_t reduced,
+                                                       uint32_t bits, uint32_t waves_per_block, uint32_t w) {
+    if (rows.sign == 0.0) return 0.0;
+    const uint32_t low_bits = bits - (reduced & 3u), x_block = rows.x_block;
     uint32_t weight = w;
     if (w >= 2u) {
-        uint32_t at = 0;  // the reduced side's position of the full form's local qubit w - 2
-        for (uint32_t p = 0; p < bits; ++p)
-            if ((slots[p >> 3] >> (4u * (p & 7u)) & 15u) == w - 2u) at = p;
+        const uint32_t at = uint32_t(positions >> (4u * (w - 2u))) & 15u;  // the reduced side's position of the full form's local qubit w - 2
         if (at < low_bits)
             weight = 2u + at;
         else if (x_block >> (at - low_bits) & 1u)
@@ -3945,11 +3970,20 @@ __device__ __forceinline__ double factor_reduced_entry(const double* partial, co
         else
             return 0.0;
     }
-    double v = 0.0;
-    for (uint32_t g = x_block * waves_per_block; g < (x_block + 1u) * waves_per_block; ++g)
+    constexpr uint32_t kMostWaves = 4;
+    const double* first = partial + (size_t(x_block * waves_per_block) * kFactorWeights + weight) * 64 + rows.entry;
+    double part[kMostWaves][4];
 #pragma unroll
-        for (uint32_t row = 0; row < 4; ++row) v += partial[(size_t(g) * kFactorWeights + weight) * 64 + row * 16 + entry];
-    return sign * v;
+    for (uint32_t g = 0; g < kMostWaves; ++g)
+#pragma unroll
+        for (uint32_t row = 0; row < 4; ++row) part[g][row] = g < waves_per_block ? first[size_t(g) * kFactorWeights * 64 + row * 16] : 0.0;
+    double v = 0.0;
+#pragma unroll
+    for (uint32_t g = 0; g < kMostWaves; ++g)
+#pragma unroll
+        for (uint32_t row = 0; row < 4; ++row)
+            if (g < waves_per_block) v += part[g][row];
+    return rows.sign * v;
 }
 
 // The two launches above as the tail of the kernel that ran the virtual circuits (pass_kernel, kModeFusedFactor): the side's
@@ -4149,12 +4183,28 @@ __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ p
     double* mine = slot + (size_t(xy) * kFactorSlices + hh) * kFactorWeights * 64;  // (a half side: slice h)
     // (write-through stores: the few hundred bytes the other side will read must not wait for a write-back of everything
     // this XCD's L2 holds dirty -- the side tables of sixteen workgroups; an agent-scope release did that: 46 us per launch)
-    for (uint32_t idx = tid; idx < (2u + bits) * NQ; idx += blockDim.x) {
-        const uint32_t w = idx / NQ, pi = idx % NQ;
-        const double v = n_final ? factor_reduced_entry(partial, sp + kSplitReducedSlots + 2u * xy, reduced, n_keys, bits, waves_per_block, w, pi)
-                                 : factor_sum_partials(partial, kWaves, w, pi, n_keys);
-        __hip_atomic_store(mine + w * 64 + pi, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    bool handed = false;
+    if constexpr (REDUCED) {
+        if (n_final) {
+            // (a reduced side: a thread's indices are blockDim.x apart, a multiple of the NQ entries, so its entry pi is one and the
+            // same for every weight it stores -- the rows it stands for are worked out once, factor_reduced_rows)
+            const uint32_t pi = tid & (NQ - 1u);
+            const ReducedRows rows = factor_reduced_rows(reduced, n_keys, pi);
+            const uint64_t positions = factor_reduced_positions(sp[kSplitReducedSlots + 2u * xy], sp[kSplitReducedSlots + 2u * xy + 1u], bits);
+            for (uint32_t idx = tid; idx < (2u + bits) * NQ; idx += blockDim.x) {
+                const uint32_t w = idx >> (2u * n_keys);
+                const double v = factor_reduced_value(partial, rows, positions, reduced, bits, waves_per_block, w);
+                __hip_atomic_store(mine + w * 64 + pi, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            handed = true;
+        }
     }
+    if (!handed)
+        for (uint32_t idx = tid; idx < (2u + bits) * NQ; idx += blockDim.x) {
+            const uint32_t w = idx / NQ, pi = idx % NQ;
+            const double v = factor_sum_partials(partial, kWaves, w, pi, n_keys);
+            __hip_atomic_store(mine + w * 64 + pi, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave, before the barrier the signalling lane joins
     __syncthreads();
     if (tid == 0) {
