@@ -757,6 +757,11 @@ int qsv_fitness_table_wait(const volatile uint64_t* own, int count, volatile int
  *                        the key's first gate; qsv_split_describe_reduced): the rows of that key are the two halves of the one state.
  *                        Only on that route; every other consumer of side states keeps the full form.  Other orders of the sums
  *                        (1e-10 apart).  Applies to circuits registered afterwards; QSV_FINAL_CONTROLS=0 in the environment.
+ *   "live_entries" 0|1   ... and a THREE-key evaluation with a side on that form hands off and combines only the LIVE entries of its
+ *                        sides' Gram tables (qsv_live_entries): an entry whose rows differ in a final-control key is an exact zero on
+ *                        the side that projects, and the combination multiplies entry by entry.  64 >> f values a weight instead of
+ *                        64, f the final-control keys of both sides; the same terms in the same order, the same bits.  Takes effect
+ *                        at the next launch (a recorded launch is dropped); QSV_LIVE_ENTRIES=0 in the environment.
  *   "side_prepare" 0|1   ... and a side whose plan qualifies (one pass, at most two tiles, its angle table, fold index and chain index
  *                        within 4096 plan words) is prepared from ONE staged read of its plan and parameters, and keeps its threads'
  *                        and tiles' factors in registers instead of handing them to itself through memory: the same expressions in
@@ -791,6 +796,17 @@ int qsv_fitness_table_wait(const volatile uint64_t* own, int count, volatile int
  * Returns QSV_E_ARG for an unknown name or a value out of range.
  */
 int qsv_set_option(qsv_t* h, const char* name, int value);
+
+/*
+ * The LIVE entries of a three-key evaluation's 8 x 8 Hermitian Gram tables on the one-launch route (option "live_entries"),
+ * without touching any device.  key_mask: the keys (bits of kappa, 0 .. 7) whose final control a side of the evaluation projects
+ * on.  Entry pi < 64 -- the 8 diagonal entries, then the real and the imaginary part of every pair of rows (ja, jb), ja < jb, in
+ * lexicographic order -- is live iff ja and jb agree on every key of the mask; every other entry is an exact zero on the side
+ * that projects, and adds nothing to the combination.  out_pi[r] receives the entry of live rank r, in ascending order, -1
+ * beyond; returns their number, 64 >> popcount(key_mask).  n_keys other than 3, a mask above 7 or a null pointer: QSV_E_ARG.
+ * Used by the CPU-side tests; the kernel asks the same function (csrc/kernels.hpp live_entry).
+ */
+int qsv_live_entries(int n_keys, unsigned key_mask, int* out_pi);
 
 /* Pushes of this handle, since it was created, that queued a kept layout's recorded launches ("replay_launches"). */
 long long qsv_replayed_pushes(const qsv_t* h);

@@ -291,6 +291,7 @@ SIGNATURES = {
     "qsv_set_option": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "qsv_fitness_table_wait": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int]),
     "qsv_replayed_pushes": (C.c_longlong, [_P]),
+    "qsv_live_entries": (C.c_int, [C.c_int, C.c_uint, C.POINTER(C.c_int)]),
     "qsv_set_profiling": (C.c_int, [_P, C.c_int]),
     "qsv_get_profile": (C.c_int, [_P, C.POINTER(QsvProfile)]),
     "qsv_bench_gate": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]),

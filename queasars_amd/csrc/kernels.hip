@@ -3580,6 +3580,18 @@ __device__ __forceinline__ double factor_pairing(const double* a, const double* 
         default: return factor_pairing_unrolled<8>(a, b);
     }
 }
+// The same for two three-key tables that hold their L LIVE entries only (kernels.hpp live_entry), in the entries' order: the 8
+// diagonal entries, then (L - 8) / 2 pairs.  factor_pairing_unrolled<8> with the terms left out that are exact zeros -- adding
+// one leaves the sum's bits as they were -- and the others in its order: the same bits.
+template <uint32_t L>
+__device__ __forceinline__ double factor_pairing_live(const double* a, const double* b) {
+    double t = 0.0;
+#pragma unroll
+    for (uint32_t j = 0; j < 8; ++j) t = fma(a[j], b[j], t);
+#pragma unroll
+    for (uint32_t e = 8; e < L; e += 2) t += 2.0 * fma(a[e], b[e], -a[e + 1] * b[e + 1]);
+    return t;
+}
 
 constexpr unsigned kFactorParts = 8;
 constexpr uint32_t kFactorSlices = kFactorParts / 2;
@@ -3936,8 +3948,7 @@ __device__ __forceinline__ ReducedRows factor_reduced_rows(uint32_t reduced, uin
     double sign = 1.0;
     if (sa != sb) {
         const uint32_t lo = sa < sb ? sa : sb, hi = sa < sb ? sb : sa;
-        uint32_t o = hi - lo - 1u;
-        for (uint32_t i = 0; i < lo; ++i) o += J - 1u - i;
+        const uint32_t o = hi - lo - 1u + lo * (2u * J - 1u - lo) / 2u;  // (the pairs of the rows below lo: J - 1, J - 2, ..)
         entry = J + 2u * o + (part - 1u);
         if (part == 2u && sa > sb) sign = -1.0;
     }
@@ -4174,6 +4185,27 @@ __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ p
             factor_side_body_pairs<real, 2, false>(tab, bits, mask, diag, wave < kWaves ? wave : 0xffffffu, step, stage, dstage_all + w * 64, sink, dq_pairs QSV_PSTAMP_ARGS);
 #endif
     }
+    // A three-key evaluation with a reduced side (kModeFusedLive): only the LIVE entries of a table are handed off and combined
+    // (kernels.hpp live_entry) -- 64 >> f of the 64, f the final-control keys of both sides; a side on the full form profits from
+    // its partner's zeros.  Lane r < L of every wave learns the entry of live rank r: the live lanes are counted by ballot, lane
+    // pi sends itself to the lane of its rank -- the others to the lanes behind, a permutation -- and the upper lanes fetch what
+    // lane r = lane mod L holds.  No LDS is written.  Here, ahead of the barrier the Gram sums end with: worked out before the
+    // sums, under the wait for the side's stores, the launch of all the population's circuits was 0.5 - 0.7 us LONGER although the
+    // three-key circuit alone was shorter (profiles/r17_live_entries.txt).
+    uint32_t live_log = 6u, live_pi = 0u;  // (6: the table goes out whole)
+    if constexpr (REDUCED) {
+        const uint32_t key_mask = n_keys == 3u && (a.mode & kModeFusedLive) ? live_key_mask(sp[kSplitReduced], sp[kSplitReduced + 1]) : 0u;
+        if (key_mask) {
+            const uint32_t lane = tid & 63u;
+            const bool live = live_entry(key_mask, lane, nullptr);
+            const uint64_t live_lanes = __ballot(live);
+            const uint32_t below = __builtin_amdgcn_mbcnt_hi(uint32_t(live_lanes >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(live_lanes), 0u));
+            live_log = 6u - uint32_t(__builtin_popcount(key_mask));
+            const uint32_t to = live ? below : (1u << live_log) + (lane - below);
+            const uint32_t ranked = uint32_t(__builtin_amdgcn_ds_permute(int(to << 2), int(lane)));
+            live_pi = uint32_t(__builtin_amdgcn_ds_bpermute(int((lane & ((1u << live_log) - 1u)) << 2), int(ranked)));
+        }
+    }
     __syncthreads();
     QSV_PSTAMP(1);  // Gram matrices
 #ifdef QSV_ABL_NO_HANDOFF  // (measurement: no hand-off between the sides, no combination)
@@ -4188,13 +4220,25 @@ __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ p
         if (n_final) {
             // (a reduced side: a thread's indices are blockDim.x apart, a multiple of the NQ entries, so its entry pi is one and the
             // same for every weight it stores -- the rows it stands for are worked out once, factor_reduced_rows)
-            const uint32_t pi = tid & (NQ - 1u);
-            const ReducedRows rows = factor_reduced_rows(reduced, n_keys, pi);
+            // (live entries only: a weight's L values lie at its start, in the entries' order; a thread keeps rank tid mod L, so the
+            // threads index live values alone and none of them walks over a dead entry)
+            const bool live_only = live_log < 6u;
+            const uint32_t at_log = live_only ? live_log : 2u * n_keys, at = tid & ((1u << at_log) - 1u);
+            const ReducedRows rows = factor_reduced_rows(reduced, n_keys, live_only ? live_pi : at);
             const uint64_t positions = factor_reduced_positions(sp[kSplitReducedSlots + 2u * xy], sp[kSplitReducedSlots + 2u * xy + 1u], bits);
-            for (uint32_t idx = tid; idx < (2u + bits) * NQ; idx += blockDim.x) {
-                const uint32_t w = idx >> (2u * n_keys);
+            for (uint32_t idx = tid; idx < (2u + bits) << at_log; idx += blockDim.x) {
+                const uint32_t w = idx >> at_log;
                 const double v = factor_reduced_value(partial, rows, positions, reduced, bits, waves_per_block, w);
-                __hip_atomic_store(mine + w * 64 + pi, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(mine + w * 64 + at, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            handed = true;
+        } else if (live_log < 6u) {
+            // (a side on the full form beside a reduced one: the same sums, of the live entries only, to the same places)
+            const uint32_t at = tid & ((1u << live_log) - 1u), pi = live_pi;
+            for (uint32_t idx = tid; idx < (2u + bits) << live_log; idx += blockDim.x) {
+                const uint32_t w = idx >> live_log;
+                const double v = factor_sum_partials(partial, kWaves, w, pi, n_keys);
+                __hip_atomic_store(mine + w * 64 + at, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             handed = true;
         }
@@ -4244,14 +4288,16 @@ __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ p
         // and a loop that stored each before asking for the next paid a memory round trip per value)
         constexpr uint32_t kMaxPerThread = (kFactorWeights * 64 + 255) / 256;
         double fetched[2][kMaxPerThread];
+        // (live entries only: the L values a weight's hand-off holds, to the start of the weight's row)
+        const uint32_t per_weight = REDUCED ? 1u << (live_log < 6u ? live_log : 2u * n_keys) : 1u << (2 * n_keys);
 #pragma unroll
         for (uint32_t s2 = 0; s2 < 2; ++s2)
 #pragma unroll
             for (uint32_t it = 0; it < kMaxPerThread; ++it) {
                 const uint32_t idx = tid + it * blockDim.x;
                 fetched[s2][it] = 0.0;
-                if (idx < (2u + side_bits[s2]) * NQ) {
-                    const double* entry = slot + size_t(s2) * kFactorSlices * kFactorWeights * 64 + (idx / NQ) * 64 + idx % NQ;
+                if (idx < (2u + side_bits[s2]) * per_weight) {
+                    const double* entry = slot + size_t(s2) * kFactorSlices * kFactorWeights * 64 + (idx / per_weight) * 64 + idx % per_weight;
                     fetched[s2][it] = __hip_atomic_load(entry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     // (half sides: the sums over the two halves of x, the lower first)
                     if (two_halves[s2])
@@ -4263,22 +4309,54 @@ __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ p
 #pragma unroll
             for (uint32_t it = 0; it < kMaxPerThread; ++it) {
                 const uint32_t idx = tid + it * blockDim.x;
-                if (idx < (2u + side_bits[s2]) * NQ)
-                    gram[size_t(s2) * kFactorWeights * kFactorPitch + (idx / NQ) * kFactorPitch + idx % NQ] = fetched[s2][it];
+                if (idx < (2u + side_bits[s2]) * per_weight)
+                    gram[size_t(s2) * kFactorWeights * kFactorPitch + (idx / per_weight) * kFactorPitch + idx % per_weight] = fetched[s2][it];
             }
     }
     __syncthreads();
     const double* g0 = gram;
     const double* g1 = gram + size_t(kFactorWeights) * kFactorPitch;
     double v = 0.0;
-    if (tid < bx * by) {
-        if (coupling != 0.0) v = 4.0 * coupling * factor_pairing(g0 + (2 + qa_i) * kFactorPitch, g1 + (2 + qb_i) * kFactorPitch, n_keys);
-    } else if (tid == bx * by) {
-        v = factor_pairing(g0 + kFactorPitch, g1, n_keys);  // D(x, 0)
-    } else if (tid == bx * by + 1) {
-        v = factor_pairing(g0, g1 + kFactorPitch, n_keys);  // D(0, y)
-    } else if (tid == bx * by + 2) {
-        v = -d00 * factor_pairing(g0, g1, n_keys);          // - D(0, 0) <psi|psi>
+    bool paired = false;
+    if constexpr (REDUCED) {
+        if (live_log < 6u) {
+            // (live entries: which two rows a thread pairs and what it scales the sum by first, then ONE pairing for its size --
+            // every product as below)
+            const double* pa = g0;
+            const double* pb = g1;
+            double scale = 1.0;
+            bool term = true;
+            if (tid < bx * by) {
+                term = coupling != 0.0;
+                pa = g0 + (2 + qa_i) * kFactorPitch;
+                pb = g1 + (2 + qb_i) * kFactorPitch;
+                scale = 4.0 * coupling;
+            } else if (tid == bx * by) {
+                pa = g0 + kFactorPitch;  // D(x, 0)
+            } else if (tid == bx * by + 1) {
+                pb = g1 + kFactorPitch;  // D(0, y)
+            } else if (tid == bx * by + 2) {
+                scale = -d00;            // - D(0, 0) <psi|psi>
+            } else {
+                term = false;
+            }
+            if (term) {
+                const double t = live_log == 5u ? factor_pairing_live<32>(pa, pb) : live_log == 4u ? factor_pairing_live<16>(pa, pb) : factor_pairing_live<8>(pa, pb);
+                v = scale * t;  // (scale 1: the sum's own bits)
+            }
+            paired = true;
+        }
+    }
+    if (!paired) {
+        if (tid < bx * by) {
+            if (coupling != 0.0) v = 4.0 * coupling * factor_pairing(g0 + (2 + qa_i) * kFactorPitch, g1 + (2 + qb_i) * kFactorPitch, n_keys);
+        } else if (tid == bx * by) {
+            v = factor_pairing(g0 + kFactorPitch, g1, n_keys);  // D(x, 0)
+        } else if (tid == bx * by + 1) {
+            v = factor_pairing(g0, g1 + kFactorPitch, n_keys);  // D(0, y)
+        } else if (tid == bx * by + 2) {
+            v = -d00 * factor_pairing(g0, g1, n_keys);          // - D(0, 0) <psi|psi>
+        }
     }
     // fixed-order sum over the first 256 threads (bx by + 3 <= 172 of them carry a term)
     double* red = reinterpret_cast<double*>(flag) + 1;

@@ -105,7 +105,52 @@ enum PassMode : uint32_t {
     kModeFusedReduced = 8192u, // (with kModeFusedFactor) at least one evaluation of the launch runs a side on the reduced split form
                                // (kSplitReduced above): the launch takes the instantiation whose tail reads those words.  A launch
                                // without the bit must hold no such side -- its tail never looks
+    kModeFusedLive = 16384u,   // (with kModeFusedReduced) a three-key evaluation with a reduced side hands off and combines only the LIVE
+                               // entries of its sides' tables (live_entry below).  The same bits either way; both workgroups of an
+                               // evaluation read the bit from the same launch, so they agree on the layout of the hand-off
 };
+// The LIVE entries of a three-key evaluation's Gram tables.  On the reduced form a side's entry (kappa, kappa') is exactly zero where
+// the rows differ in a bit of one of the side's final-control keys, and the combination multiplies the two sides' tables entry by
+// entry: an entry that is zero on either side adds an exact zero.  key_mask: the final-control keys of both sides (live_key_mask).
+// Entry pi < 64 of the 8 x 8 Hermitian form (kernels.hip split_entry_of: the 8 diagonal entries, then the real and the imaginary
+// part of every pair (ja, jb), ja < jb, in lexicographic order) is live iff its rows agree on every key of the mask; *rank_out (may
+// be null) receives the number of live entries below pi -- its place in the hand-off, which keeps the entries' order.  Of the 64
+// entries 64 >> popcount(key_mask) are live: the 8 diagonal ones always, and both parts of a pair or neither.
+// (straight-line, not split_entry_of's loop: every lane of a wave asks at once, on the launch's critical path.  Pair number o of
+// row ja starts at 7 + 6 + .. = ja (15 - ja) / 2)
+inline __host__ __device__ void live_entry_rows(uint32_t pi, uint32_t* ja_out, uint32_t* jb_out) {
+    uint32_t ja = pi, jb = pi;
+    if (pi >= 8u) {
+        const uint32_t o = (pi - 8u) >> 1;
+        ja = (o >= 7u) + (o >= 13u) + (o >= 18u) + (o >= 22u) + (o >= 25u) + (o >= 27u);
+        jb = ja + 1u + o - ja * (15u - ja) / 2u;
+    }
+    *ja_out = ja;
+    *jb_out = jb;
+}
+inline __host__ __device__ bool live_entry(uint32_t key_mask, uint32_t pi, uint32_t* rank_out) {
+    uint32_t ja, jb;
+    live_entry_rows(pi, &ja, &jb);
+    if (rank_out) {
+        uint32_t rank = 0;
+        for (uint32_t below = 0; below < pi; ++below) {
+            uint32_t a, b;
+            live_entry_rows(below, &a, &b);
+            rank += ((a ^ b) & key_mask) == 0u ? 1u : 0u;
+        }
+        *rank_out = rank;
+    }
+    return ((ja ^ jb) & key_mask) == 0u;
+}
+// ... and the mask: the keys whose final control a side of the evaluation projects on (the sides' words kSplitReduced above: the
+// first F row bits of a side's word are its final controls).  A side on the full form (word 0) names none.
+inline __host__ __device__ uint32_t live_key_mask(uint32_t reduced_x, uint32_t reduced_y) {
+    auto of_side = [](uint32_t word) {
+        const uint32_t n_final = word & 3u;
+        return (n_final > 0u ? 1u << (word >> 4 & 3u) : 0u) | (n_final > 1u ? 1u << (word >> 6 & 3u) : 0u) | (n_final > 2u ? 1u << (word >> 8 & 3u) : 0u);
+    };
+    return of_side(reduced_x) | of_side(reduced_y);
+}
 // The optional mask of a device-resident CVaR call (qsv.h: qsv_cvar_device): entry e / stride decides evaluation e (its out_index,
 // the caller's numbering), 0 = skipped.  flags == nullptr: every evaluation runs.  The flags are written by an EARLIER launch on
 // the same stream and are the same for every workgroup of an evaluation in every kernel of a call, so all of them take the same

@@ -288,6 +288,9 @@ struct qsv_handle {
     bool side_diag = true;             // (QSV_SIDE_DIAG=0: the sums gather from D itself, as before round 4)
     bool final_controls = true;        // one-launch route: a side simulates no key qubit for a key whose control on it is final (split.hpp,
                                        // reduce_final_controls); circuits registered afterwards.  QSV_FINAL_CONTROLS=0 / option "final_controls"
+    bool live_entries = true;          // one-launch route: a three-key evaluation with a reduced side hands off and combines only the live
+                                       // entries of its Gram tables (kernels.hpp kModeFusedLive); the next launch.  QSV_LIVE_ENTRIES=0 /
+                                       // option "live_entries"
     bool sides_r3 = true;              // one-launch route at 20 qubits: sides of up to twelve virtual qubits planned with EIGHT amplitudes per thread
                                        // (a gate phase is one wave's issue time over its own amplitudes: twice the waves, half the time),
                                        // three-key sides of thirteen as two workgroups each (kEvalHalves); circuits registered afterwards
@@ -1655,6 +1658,7 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
                 // (need >= kFusedFactorLdsBytes: room for the staged plan run behind prepare_eval's scratch)
                 if (p == 0 && (extra_mode & kModeFusedFactor) && h->side_prepare) a.mode |= kModeSidePrepare;
                 if (p == 0 && any_reduced) a.mode |= kModeFusedReduced;
+                if (p == 0 && any_reduced && h->live_entries) a.mode |= kModeFusedLive;
                 if (h->stamping) QSV_HIP(h, stamp(h, h->batch.launch_events[kind], true));
                 QSV_LAUNCH(h, launch_pass(h->dtype, r, h->cfg.xmode, dim3(grid_x, unsigned(hi - lo), 2), threads, need, ws(h), a));
                 record_pass(h, r, dim3(grid_x, unsigned(hi - lo), 2), threads, need, a);
@@ -2848,6 +2852,7 @@ int qsv_create(int n_qubits, int dtype, int device, const qsv_plan_config* cfg, 
     if (const char* env = getenv("QSV_SIDE_DIAG")) h->side_diag = atoi(env) != 0;
     if (const char* env = getenv("QSV_SIDES_R3")) h->sides_r3 = atoi(env) != 0;
     if (const char* env = getenv("QSV_FINAL_CONTROLS")) h->final_controls = atoi(env) != 0;
+    if (const char* env = getenv("QSV_LIVE_ENTRIES")) h->live_entries = atoi(env) != 0;
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) h->n_cus = cus;
@@ -5332,6 +5337,9 @@ int qsv_set_option(qsv_t* h, const char* name, int value) {
     } else if (key == "final_controls") {  // one-launch route: no key qubit for a final control's key on the control's side.  Circuits registered afterwards.
         h->final_controls = value != 0;
         h->epoch += 1;  // (a batch that repeats must be laid out again: which form it runs is decided there)
+    } else if (key == "live_entries") {  // one-launch route: three-key evaluations with a reduced side hand off live entries only (same bits either way)
+        // (a launch's mode carries it: the epoch moved above, so a recorded launch is dropped and the next push lays its launches out anew)
+        h->live_entries = value != 0;
     } else if (key == "sides_r3") {  // one-launch route: sides with eight amplitudes per thread, three-key sides on two workgroups.  Circuits registered afterwards.
         h->sides_r3 = value != 0;
     } else if (key == "side_diag") {  // one-launch route: a side's values of D from a table of its own (one run) instead of gathered from D
@@ -5363,6 +5371,19 @@ int qsv_set_profiling(qsv_t* h, int enabled) {
     h->epoch += 1;
     h->profiling = enabled != 0;
     return QSV_OK;
+}
+
+int qsv_live_entries(int n_keys, unsigned key_mask, int* out_pi) {
+    if (n_keys != 3 || key_mask > 7u || !out_pi) return QSV_E_ARG;
+    for (int i = 0; i < 64; ++i) out_pi[i] = -1;
+    int count = 0;
+    for (uint32_t pi = 0; pi < 64; ++pi) {
+        uint32_t rank = 0;
+        if (!live_entry(key_mask, pi, &rank)) continue;
+        out_pi[rank] = int(pi);  // (the entry's place in the hand-off)
+        ++count;
+    }
+    return count;
 }
 
 long long qsv_replayed_pushes(const qsv_t* h) {
