@@ -694,6 +694,28 @@ typedef struct qsv_adjoint_stats_t {
 } qsv_adjoint_stats_t;
 int qsv_adjoint_stats(const qsv_t* h, qsv_adjoint_stats_t* out);
 
+/*
+ * ENERGY VARIANCE: out_variances[e] = <psi_e| H_h^2 |psi_e> - <psi_e| H_h |psi_e>^2 and, where out_values is
+ * not NULL, out_values[e] = <psi_e| H_h |psi_e>, for n_evals (circuit, parameter vector) pairs laid out as in qsv_eval_circuits;
+ * H_h is the Hermitian part of the operator (what qsv_set_operator keeps).  Zero exactly on eigenstates of H_h; the spread of a
+ * diagonal cost over the state's distribution; Var / shots is the squared statistical error of a finite-shot estimator.
+ * Each launch group's circuits run their ordinary plans into state slots (no split route, as qsv_prefix_create runs them: the
+ * whole state is needed), then on the handle's stream one kernel forms every row lambda_i = (H_h psi)_i from the operator tables
+ * -- the diagonal table, and per x-mask group (w_re(i) - i w_im(i)) psi_(i ^ x) -- and reduces m1 = sum Re(conj(psi_i) lambda_i)
+ * and m2 = sum |lambda_i|^2 in fp64 without storing lambda, and a second one writes E = m1 and Var = m2 - m1 * m1.  The scratch
+ * (two doubles per evaluation and per workgroup of a launch group) is allocated on first need and grown by need.
+ * The values are RAW: no division by <psi|psi>, and Var is not clamped -- rounding may leave a tiny negative number.  One pass
+ * costs a cancellation of about eps * E^2 where Var << E^2 (fp64: 1e-12 at |E| = 100).
+ * Contract: an evaluation's two numbers are the same bits in any batch, at any position of a launch group and on every call
+ * (fixed-order sums, no floating-point atomics).  out_values agrees with qsv_eval_circuits to rounding, not bit for bit: it comes
+ * from another route.  The call lays a batch out as every batch call does, so a recorded batch ("replay_launches") is dropped
+ * and laid out again by the next qsv_eval_* call, which returns the bits it returned before.  Goes between batches.
+ * Errors: no operator set QSV_E_STATE; a batch open on this thread QSV_E_STATE; out_variances NULL with n_evals > 0 (or other
+ * bad arguments) QSV_E_ARG; a circuit on a kept state QSV_E_UNSUPPORTED; more than 28 qubits QSV_E_UNSUPPORTED; n_evals == 0 QSV_OK.
+ */
+int qsv_variance_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
+                          double* out_variances, double* out_values /* may be NULL */);
+
 /* ---- several observables per evaluation ---------------------------------------------------------- */
 
 /*
@@ -793,6 +815,8 @@ int qsv_fitness_table_wait(const volatile uint64_t* own, int count, volatile int
  *                        operator may hold more groups than the device's largest gridDim.y (hipDeviceAttributeMaxGridDimY, read
  *                        when the handle is created: the default, 0, and the largest value accepted).  More groups go in several
  *                        launches with the partial sums laid out as one launch lays them out: the same bits at any value
+ *   "time_moments" 0|1   qsv_variance_circuits brackets the two kernels of every launch group by HIP events on the handle's stream
+ *                        and leaves their summed device time in qsv_get_profile's expect_ms (measurements; the same bits)
  * Returns QSV_E_ARG for an unknown name or a value out of range.
  */
 int qsv_set_option(qsv_t* h, const char* name, int value);

@@ -1174,6 +1174,27 @@ class StatevectorDevice:
         self._check(self._lib.qsv_adjoint_stats(self._handle, C.byref(stats)))
         return {name: int(getattr(stats, name)) for name, _ in _lib.QsvAdjointStats._fields_}
 
+    # -- the operator's variance ------------------------------------------------------------------
+    def variances(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]]) -> tuple[np.ndarray, np.ndarray]:
+        """``(values, variances)`` of the operator set on the device, two float64 arrays with one entry per (circuit, parameter
+        vector) pair: ``<H>`` and ``<H^2> - <H>^2`` of the operator's Hermitian part, reduced on the device from the final state
+        (``qsv_variance_circuits``).  The variance is zero on eigenstates, the spread of a diagonal cost over
+        the state's distribution, and ``sqrt(variance / shots)`` the statistical error of a finite-shot estimate.  Raw numbers:
+        rounding may leave a variance a tiny bit below zero.  Deterministic; the values agree with :meth:`expectation_values`
+        to rounding.  A circuit on a kept state raises ``ValueError``."""
+        n = len(circuits)
+        if len(parameter_values) != n:
+            raise ValueError("circuits and parameter_values must have the same length")
+        values = np.zeros(n, dtype=np.float64)
+        variances = np.zeros(n, dtype=np.float64)
+        if n == 0:
+            return values, variances
+        ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
+        # (a refused circuit -- QSV_E_UNSUPPORTED: one on a kept state -- as a ValueError with the library's message)
+        self._check_gradient(self._lib.qsv_variance_circuits(
+            self._handle, n, _lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat), _lib.as_ptr(variances), _lib.as_ptr(values)))
+        return values, variances
+
     # -- several observables ---------------------------------------------------------------------
     MAX_OBSERVABLE_SETS = 16
 
@@ -1233,7 +1254,8 @@ class StatevectorDevice:
         """Switches of the handle (``qsv_set_option``): "split", "factor", "split_sampling" (0 / 1), "streams" (1 .. 4),
         "gradient_chunk" (shifted evaluations per chunk of a gradient call, 0 = the default), "max_grid_y" (x-mask groups or
         observable rows per launch, 0 = the device's largest gridDim.y), "repeat_layout" / "replay_launches" (0 / 1: a repeated batch
-        keeps its layout / queues its recorded launches again).
+        keeps its layout / queues its recorded launches again), "time_moments" (0 / 1: :meth:`variances` leaves the device time of
+        its two kernels in :meth:`profile`'s ``expect_ms``).
         A circuit keeps the form it was registered in; the cache of the previous batch is dropped."""
         self._check(self._lib.qsv_set_option(self._handle, name.encode(), int(value)))
         self._last_batch = None
@@ -1548,6 +1570,18 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         if self._precision > 0:
             values = values + self._rng.normal(0.0, self._precision, size=values.shape)
         return values.tolist()
+
+    def evaluate_variances(self, circuits: list[CircuitIR], parameter_values: list[list[float]], with_values: bool = False):
+        """``<H^2> - <H>^2`` of the evaluator's operator for every circuit (behind this evaluator's initial state), as a list
+        (:meth:`StatevectorDevice.variances`); with ``with_values`` the pair ``(values, variances)`` of two
+        lists, the values from the same pass over the state.  Exact numbers: ``estimator_precision`` adds no noise here, and no
+        random number is drawn."""
+        circuits = self._composed_list(circuits)
+        with self._device.operator_lock:
+            if self._device._operator is not self._operator:
+                self._device.set_operator(self._operator)
+            values, variances = self._device.variances(circuits, parameter_values)
+        return (values.tolist(), variances.tolist()) if with_values else variances.tolist()
 
     def evaluate_observables(
         self, circuits: list[CircuitIR], parameter_values: list[list[float]], operators: Sequence[PauliOperator]

@@ -2,6 +2,7 @@
 // fixed order -- per thread over its pairs, across a wave by a butterfly, across waves and workgroups in index order --, so an
 // evaluation's numbers depend on nothing but its circuit, its point and the operator.  No floating-point atomics.
 #include "adjoint.hpp"
+#include "operator_row.hpp"
 
 namespace qsv {
 
@@ -73,10 +74,7 @@ adjoint_prepare_kernel(const AdjEval* __restrict__ evals, const AdjGate* __restr
     m[28] = 0.0,  m[29] = 0.0,  m[30] = -ss * c,  m[31] = sc * c;
 }
 
-// lambda_i = D[i] psi_i + sum over x-mask groups of (w_re(i) - i w_im(i)) psi_(i ^ x), with w_re / w_im(i) the sums of
-// (-1)^popcount(i & z_k) coef_k over the group's terms with an even / odd number of Y factors (coef_k carries
-// (-1)^floor(ny / 2), as pauli_groups_kernel reads it): P_k psi = (-i)^ny (-1)^popcount(i & z) psi_(i ^ x).  The term tables are
-// read at wave-uniform addresses.
+// lambda = H_h psi, row by row (operator_row.hpp), and each workgroup's share of Re<psi|lambda>.
 template <typename real>
 __global__ void __launch_bounds__(kAdjointThreads)
 adjoint_apply_operator_kernel(const acx<real>* __restrict__ states, acx<real>* __restrict__ lambda, unsigned long long dim,
@@ -91,27 +89,8 @@ adjoint_apply_operator_kernel(const acx<real>* __restrict__ states, acx<real>* _
     const unsigned long long stride = (unsigned long long)gridDim.x * kAdjointThreads;
     for (unsigned long long i = (unsigned long long)blockIdx.x * kAdjointThreads + threadIdx.x; i < dim; i += stride) {
         const acx<real> a = st[i];
-        double l_re = 0.0, l_im = 0.0;
-        if (diag) {
-            const double d = diag[i];
-            l_re = d * double(a.re);
-            l_im = d * double(a.im);
-        }
-        for (int g = 0; g < n_groups; ++g) {
-            const PauliGroup gr = groups[g];
-            const acx<real> b = st[i ^ gr.x];
-            double w_re = 0.0, w_im = 0.0;
-            for (uint32_t k = gr.first; k < gr.first + gr.count; ++k) {
-                const bool minus = __popcll(i & term_z[k]) & 1;
-                const double c = minus ? -term_coef[k] : term_coef[k];
-                if (term_odd[k])
-                    w_im += c;
-                else
-                    w_re += c;
-            }
-            l_re += w_re * double(b.re) + w_im * double(b.im);
-            l_im += w_re * double(b.im) - w_im * double(b.re);
-        }
+        const OperatorRow row = operator_row(st, i, a, diag, n_groups, groups, term_z, term_coef, term_odd);
+        const double l_re = row.re, l_im = row.im;
         acc += double(a.re) * l_re + double(a.im) * l_im;
         store_amp(lm + i, acx<real>{real(l_re), real(l_im)}, streaming);
     }

@@ -19,6 +19,7 @@
 
 #include "../../include/qsv.h"
 #include "adjoint.hpp"
+#include "moments.hpp"
 #include "gradient.hpp"
 #include "value_cache.hpp"
 #include "kernels.hpp"
@@ -484,6 +485,9 @@ struct qsv_handle {
     DeviceBuffer d_adj_lambda, d_adj_tab, d_adj_mats, d_adj_partials, d_adj_epart, d_adj_base, d_adj_out, d_adj_values;
     const void* adj_checked[3] = {nullptr, nullptr, nullptr};  // qsv_adjoint_gradient_device's pointers last found to be this device's memory
     qsv_adjoint_stats_t adj_stats{};
+    // the operator's moments (qsv_variance_circuits; moments.hpp): the call's (E, Var) pairs by position | one launch group's partials
+    DeviceBuffer d_moments;
+    bool time_moments = false;  // option "time_moments": the device time of the two kernels goes to prof.expect_ms
     uint64_t host_waits = 0;  // times the host waited for a stream or an event (sync_streams and the few direct waits a batch can meet)
 
     // device-resident value caches (qsv_value_cache_create; value_cache.hpp)
@@ -2945,7 +2949,7 @@ void qsv_destroy(qsv_t* h) {
                             &h->d_states, &h->d_wtab, &h->d_side, &h->d_factor, &h->d_factor_count, &h->d_factor_big, &h->d_factor_big_count, &h->d_quad, &h->d_fterms, &h->d_fpart, &h->d_batch, &h->d_mats, &h->d_partials, &h->d_out, &h->d_scratch, &h->d_prefix, &h->d_sdiag,
                             &h->d_obs_partials, &h->d_obs_values, &h->d_grad_tab, &h->d_grad_rows, &h->d_grad_values, &h->d_grad_base,
                             &h->d_grad_out, &h->d_adj_lambda, &h->d_adj_tab, &h->d_adj_mats, &h->d_adj_partials, &h->d_adj_epart, &h->d_adj_base,
-                            &h->d_adj_out, &h->d_adj_values})
+                            &h->d_adj_out, &h->d_adj_values, &h->d_moments})
         if (b->ptr) (void)hipFree(b->ptr);
     for (auto& kv : h->obs_sets) free_observable_set(kv.second);
     for (auto& kv : h->value_caches) free_value_cache(kv.second);
@@ -5043,6 +5047,82 @@ int qsv_adjoint_stats(const qsv_t* h, qsv_adjoint_stats_t* out) {
     return QSV_OK;
 }
 
+// ---- the operator's variance (qsv.h: ENERGY VARIANCE; moments.hpp) -------------------------------------------------------------
+
+int qsv_variance_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
+                          double* out_variances, double* out_values) {
+    if (!h) return QSV_E_ARG;
+    if (h->batch_owner.load() == std::this_thread::get_id())
+        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_variance_circuits goes between batches)");
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets || !out_variances))) return fail(h, QSV_E_ARG, "bad arguments");
+    if (n_evals == 0) return QSV_OK;
+    if (h->n_terms == 0) return fail(h, QSV_E_STATE, "no operator set (call qsv_set_operator first)");
+    if (h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "the variance is available up to 28 qubits");
+    QSV_HIP(h, hipSetDevice(h->device));
+    BatchArgs args;
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args,
+                           "the variance of a circuit on a kept state is not built");
+    if (rc) return rc;
+    if (h->async_pending) {  // (the buffers below may still be read or written by a call that did not wait)
+        QSV_HIP(h, sync_streams(h));
+        h->async_pending = false;
+    }
+    // ordinary plans into state slots, never split: the whole state is needed (as qsv_prefix_create runs them)
+    const size_t n = size_t(n_evals);
+    const size_t G = std::max<size_t>(1, std::min(size_t(h->group), size_t(h->max_grid_y)));
+    const uint32_t blocks = moments_blocks(h->n);
+    // device scratch: the call's (E, Var) pairs by position | the partials of one launch group
+    const size_t out_bytes = (n * 2 * sizeof(double) + 63) / 64 * 64;
+    if ((rc = ensure(h, h->d_moments, out_bytes + std::min(G, n) * blocks * 2 * sizeof(double))) || (rc = ensure_host_out(h, 2 * n))) return rc;
+    double* const pairs = static_cast<double*>(h->d_moments.ptr);
+    double* const partials = reinterpret_cast<double*>(static_cast<char*>(h->d_moments.ptr) + out_bytes);
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> timed;  // (option "time_moments": the two kernels of every launch group)
+    struct DestroyEvents {
+        std::vector<std::pair<hipEvent_t, hipEvent_t>>& list;
+        ~DestroyEvents() {
+            for (auto& p : list) {
+                if (p.first) (void)hipEventDestroy(p.first);
+                if (p.second) (void)hipEventDestroy(p.second);
+            }
+        }
+    } destroy_events{timed};
+    auto moments = [&](size_t g0, size_t gc) -> int {
+        if (h->time_moments) {
+            timed.emplace_back(nullptr, nullptr);
+            QSV_HIP(h, hipEventCreate(&timed.back().first));
+            QSV_HIP(h, hipEventCreate(&timed.back().second));
+            QSV_HIP(h, hipEventRecord(timed.back().first, h->stream));
+        }
+        QSV_HIP(h, launch_operator_moments(h->dtype, h->d_states.ptr, h->n, int(gc),
+                                           h->has_diag_part ? static_cast<const double*>(h->d_diag.ptr) : nullptr, h->n_groups,
+                                           static_cast<const PauliGroup*>(h->d_groups.ptr), static_cast<const uint64_t*>(h->d_z.ptr),
+                                           static_cast<const double*>(h->d_cre.ptr), static_cast<const uint32_t*>(h->d_term_odd.ptr),
+                                           partials, h->stream));
+        QSV_HIP(h, launch_moments_combine(partials, blocks, int(gc), pairs + 2 * g0, h->stream));
+        if (h->time_moments) QSV_HIP(h, hipEventRecord(timed.back().second, h->stream));
+        return QSV_OK;
+    };
+    rc = run_to_states(h, args, StateRun{SplitRule{}, 1, G, false, 0, kModeSynthFirst | kModeFinalStore}, {}, moments);
+    if (rc) {  // nothing of a failed call may still be running
+        (void)sync_streams(h);
+        return rc;
+    }
+    QSV_HIP(h, hipMemcpyAsync(h->h_out, pairs, n * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QSV_HIP(h, sync_streams(h));
+    for (size_t j = 0; j < n; ++j) {
+        const size_t e = h->batch.eval_at[j];
+        if (out_values) out_values[e] = h->h_out[2 * j];
+        out_variances[e] = h->h_out[2 * j + 1];
+    }
+    for (const auto& p : timed) {
+        float ms = 0.0f;
+        QSV_HIP(h, hipEventElapsedTime(&ms, p.first, p.second));
+        h->prof.expect_ms += double(ms);
+    }
+    return QSV_OK;
+}
+
 int qsv_gradient_plan_create(qsv_t* h, int n_evals, const int* circuit_ids, int width, const int64_t* wrt_offsets, const int32_t* wrt,
                              int out_width, int* out_plan_id, int64_t* out_n_shifted) {
     if (!h) return QSV_E_ARG;
@@ -5359,6 +5439,8 @@ int qsv_set_option(qsv_t* h, const char* name, int value) {
     } else if (key == "gradient_chunk") {  // shifted evaluations per chunk of a gradient call (0: the default); the same bits at any value
         if (value < 0 || value > (1 << 20)) return fail(h, QSV_E_ARG, "gradient_chunk must be between 0 and 1048576");
         h->grad_chunk = value ? value : kGradientChunkRows;
+    } else if (key == "time_moments") {  // qsv_variance_circuits brackets its two kernels by events: qsv_get_profile's expect_ms (the same bits)
+        h->time_moments = value != 0;
     } else {
         return fail(h, QSV_E_ARG, "unknown option '" + key + "'");
     }

@@ -602,6 +602,8 @@ class EVQEResult:
     # first (None: not asked for), and -- under a diagonal operator -- bitstring -> the operator's value on it
     eigenstate: Optional[dict[str, float]] = None
     eigenstate_values: Optional[dict[str, float]] = None
+    # <H^2> - <H>^2 of the evaluator's operator at the best individual: zero on an eigenstate (None: not asked for)
+    eigenvalue_variance: Optional[float] = None
 
 
 # ---- the solver -----------------------------------------------------------------------------------------------
@@ -861,7 +863,7 @@ class EVQEMinimumEigensolver:
 
     # -- main loop ------------------------------------------------------------------------------------------
     def compute_minimum_eigenvalue(self, evaluator, search_evaluator=None, aux_operators=None,
-                                   eigenstate_states: Optional[int] = None) -> EVQEResult:
+                                   eigenstate_states: Optional[int] = None, eigenvalue_variance: bool = False) -> EVQEResult:
         """``search_evaluator``: a second evaluator of the SAME operator for the parameter searches alone -- a single-precision
         handle: the points a search compares differ by far more than 1e-6 (the reference's own tests run their searches on an
         estimator with precision 0.05, test/minimum_eigensolvers/evqe/solver.py:20-27), a layer search on kept states is bound
@@ -881,7 +883,12 @@ class EVQEMinimumEigensolver:
         which users decode the most probable states).  They go to ``result.eigenstate`` (bitstring -> probability, most
         probable first) and, when the evaluator's operator is diagonal, their values to ``result.eigenstate_values``.  Like the
         aux operators the call uses no random stream of the solver, is not counted in ``circuit_evaluations`` and is made by
-        every rank of a sharded run itself.  ``None``: no call, both stay ``None``."""
+        every rank of a sharded run itself.  ``None``: no call, both stay ``None``.
+
+        ``eigenvalue_variance``: after the run, one ``evaluator.evaluate_variances`` call at the best individual; the operator's
+        variance there, ``<H^2> - <H>^2`` (zero on an eigenstate; for a diagonal cost the spread over the individual's
+        distribution), goes to ``result.eigenvalue_variance``.  The same rules: no random stream of the solver, not counted in
+        ``circuit_evaluations``, made by every rank of a sharded run itself.  ``False``: no call, the field stays ``None``."""
         cfg = self.configuration
         searcher = evaluator if search_evaluator is None else search_evaluator
         if searcher.n_qubits != evaluator.n_qubits:
@@ -894,6 +901,8 @@ class EVQEMinimumEigensolver:
                     raise ValueError(f"an aux operator acts on {op.num_qubits} qubits, the evaluator on {evaluator.n_qubits}")
         if eigenstate_states is not None and getattr(evaluator, "statevector_device", None) is None:
             raise ValueError("eigenstate_states needs an evaluator with a statevector_device (a device evaluator)")
+        if eigenvalue_variance and not callable(getattr(evaluator, "evaluate_variances", None)):
+            raise ValueError("eigenvalue_variance needs an evaluator with evaluate_variances (an operator evaluator)")
         if cfg.termination_criterion is not None:
             cfg.termination_criterion.reset_state()
         population = EVQEPopulation.random_population(
@@ -964,6 +973,10 @@ class EVQEMinimumEigensolver:
             result.aux_operators_evaluated = self._evaluate_aux_operators(evaluator, result.best_individual, aux_operators)
         if eigenstate_states is not None:
             result.eigenstate, result.eigenstate_values = self._read_eigenstate(evaluator, result.best_individual, eigenstate_states)
+        if eigenvalue_variance:
+            best = result.best_individual
+            circuit = best.get_parameterized_quantum_circuit(shared=self.share_circuits)
+            result.eigenvalue_variance = float(evaluator.evaluate_variances([circuit], [list(best.parameter_values)])[0])
         return result
 
     def _read_eigenstate(self, evaluator, individual: EVQEIndividual, k: int):

@@ -103,9 +103,19 @@ class GpuEstimator(_EstimatorBase):
     Gaussian noise of that standard deviation (what an estimator's target precision means to the reference).
 
     One :class:`StatevectorDevice` per qubit count serves every operator (its tables are rebuilt when the operator
-    changes); operators are recognised by content, not identity, and at most ``max_operators`` evaluators are kept."""
+    changes); operators are recognised by content, not identity, and at most ``max_operators`` evaluators are kept.
 
-    def __init__(self, dtype: str = "fp64", device: int = 0, seed: Optional[int] = None, max_operators: int = 8):
+    ``shots=N`` (``None``, the default: nothing of the above changes) emulates the shot noise of ``N`` shots instead: every
+    entry of ``evs`` gets Gaussian noise of ITS OWN standard deviation ``sqrt(max(Var, 0) / N)``, with ``Var`` the observable's
+    variance in that entry's state, computed on the device (``OperatorCircuitEvaluator.evaluate_variances``).
+    ``data.stds`` holds those standard deviations in the shape of ``evs`` and ``metadata["shots"]`` is ``N``.  In this mode a
+    pub's own precision and the call's ``precision`` are ignored."""
+
+    def __init__(self, dtype: str = "fp64", device: int = 0, seed: Optional[int] = None, max_operators: int = 8,
+                 shots: Optional[int] = None):
+        if shots is not None and int(shots) <= 0:
+            raise ValueError("shots must be a positive number (or None: the precision's noise)")
+        self._shots = None if shots is None else int(shots)
         self._dtype, self._device_index, self._seed = dtype, device, seed
         self._rng = np.random.default_rng(seed)
         self._convert = _Converter()
@@ -139,8 +149,11 @@ class GpuEstimator(_EstimatorBase):
     def run(self, pubs: Iterable[Sequence[Any]], *, precision: Optional[float] = None) -> _Job:
         """A pub is (circuit, observables[, parameter values[, precision]]): observables one observable or a (nested) list or
         object array of them, parameter values one vector or an array of shape (..., n_params); ``evs`` has their broadcast
-        shape (:func:`pub_broadcast`).  A pub's own precision overrides ``precision``."""
+        shape (:func:`pub_broadcast`).  A pub's own precision overrides ``precision``; with ``shots`` set both are ignored (see
+        the class)."""
         pubs = [tuple(pub) for pub in pubs]
+        if self._shots is not None:
+            return self._run_with_shots(pubs)
         out: list[Any] = [None] * len(pubs)
         by_operator: dict[tuple, list[int]] = {}
         operators: dict[int, PauliOperator] = {}
@@ -181,6 +194,56 @@ class GpuEstimator(_EstimatorBase):
         dev = self._device(circuit.num_qubits)
         table = dev.observable_values([circuit] * len(layout.rows), [list(r) for r in layout.rows], ops)
         return table[layout.binding_index, np.asarray(observable_of, dtype=np.intp)[layout.observable_index]]
+
+    def _run_with_shots(self, pubs: list) -> _Job:
+        """``run`` with ``shots`` set: the exact values and the variances from the same calls -- single-observable pubs batched
+        per distinct operator, an array pub by :meth:`_array_pub_moments` --, then the noise, pub by pub in their order."""
+        moments: list[Any] = [None] * len(pubs)  # per pub: (exact values, variances), scalars or arrays of the pub's shape
+        by_operator: dict[tuple, list[int]] = {}
+        operators: dict[int, PauliOperator] = {}
+        for i, pub in enumerate(pubs):
+            values = pub[2] if len(pub) > 2 else None
+            if _is_observable_array(pub[1]) or (values is not None and np.ndim(values) > 1):
+                moments[i] = self._array_pub_moments(pub[0], pub[1], values)
+                continue
+            operators[i] = self._convert.operator(pub[1])
+            by_operator.setdefault(_operator_key(operators[i]), []).append(i)
+        for indices in by_operator.values():  # one batched call per distinct operator
+            evaluator = self._evaluator(operators[indices[0]])
+            circuits = [self._convert.circuit(pubs[i][0]) for i in indices]
+            values = [list(np.ravel(pubs[i][2])) if len(pubs[i]) > 2 and pubs[i][2] is not None else [] for i in indices]
+            exact, variances = evaluator.evaluate_variances(circuits, values, with_values=True)
+            for i, value, variance in zip(indices, exact, variances):
+                moments[i] = (value, variance)
+        results = []
+        for exact, variances in moments:
+            stds = np.sqrt(np.maximum(np.asarray(variances, dtype=np.float64), 0.0) / self._shots)
+            evs = np.asarray(exact, dtype=np.float64) + self._rng.normal(0.0, stds)
+            results.append(SimpleNamespace(data=SimpleNamespace(evs=np.asarray(evs), stds=stds),
+                                           metadata={"target_precision": 0.0, "shots": self._shots}))
+        return _Job(results)
+
+    def _array_pub_moments(self, circuit: Any, observables: Any, values: Any) -> tuple[np.ndarray, np.ndarray]:
+        """(exact values, variances) of one array pub, both of its broadcast shape: one ``evaluate_variances`` call per distinct
+        observable over the pub's distinct bindings, spread by :func:`pub_layout`'s indices."""
+        circuit = self._convert.circuit(circuit)
+        layout = pub_layout(observables, values)
+        ops, keys, observable_of = [], {}, []
+        for o in layout.observables:
+            op = self._convert.operator(o)
+            key = _operator_key(op)
+            if key not in keys:
+                keys[key] = len(ops)
+                ops.append(op)
+            observable_of.append(keys[key])
+        rows = [list(r) for r in layout.rows]
+        exact = np.zeros((len(rows), len(ops)))
+        variances = np.zeros((len(rows), len(ops)))
+        for m, op in enumerate(ops):
+            if rows:
+                exact[:, m], variances[:, m] = self._evaluator(op).evaluate_variances([circuit] * len(rows), rows, with_values=True)
+        column = np.asarray(observable_of, dtype=np.intp)[layout.observable_index]
+        return exact[layout.binding_index, column], variances[layout.binding_index, column]
 
 
 def pub_layout(observables: Any, values: Any) -> SimpleNamespace:
