@@ -1286,6 +1286,26 @@ size_t mat_doubles_of(const qsv_t* h, const Circuit& c, bool split, int side) {
                               sp.outer[side], sp.stats[side].n_passes);
 }
 
+// The partial sums and the counters of evaluations of four and five keys (launch_factor: factor_big_slot_doubles() doubles and
+// factor_big_slot_counters() counters per side-table slot), made when a handle first meets such an evaluation.  The counters
+// are zeroed, and waited for, before anything else is enqueued: the counters of EVERY slot are cleared here, and the next
+// push's chain -- on the other lane's stream, which does not wait for this one -- adds to those of its own slots.  Left to run
+// in stream order, a clear that came late (its stream still busy with this chain's virtual circuits) reset counters that
+// other chain had begun to add to: its evaluations of four and five keys were combined from incomplete partial sums, or not
+// at all -- a wrong value in the first batch of a handle.  `in_push`: called from inside a push, whose launch record the clear
+// (no kernel launch) spoils.
+int ensure_factor_big(qsv_t* h, hipStream_t stream, bool in_push) {
+    int rc = ensure(h, h->d_factor_big, factor_big_slot_doubles() * sizeof(double) * size_t(h->side_slots));
+    if (rc || h->d_factor_big_count.ptr) return rc;
+    const size_t cbytes = factor_big_slot_counters() * sizeof(uint32_t) * size_t(h->side_slots);
+    if ((rc = ensure(h, h->d_factor_big_count, cbytes))) return rc;
+    if (in_push) record_spoil(h);
+    QSV_HIP(h, hipMemsetAsync(h->d_factor_big_count.ptr, 0, cbytes, stream));
+    h->host_waits += 1;
+    QSV_HIP(h, hipStreamSynchronize(stream));
+    return QSV_OK;
+}
+
 // Whether a circuit runs as the two virtual circuits of its split form (split.hpp) in a call of one kind (split_rule):
 // `allow` -- what the virtual circuits leave is all the caller needs of the final state --, and no more cut keys than the
 // caller's kernels take (four and five keys: the factorised expectation under a quadratic operator only).  Otherwise the
@@ -1370,6 +1390,16 @@ int batch_layout(qsv_t* h, const std::vector<Circuit*>& circs, const std::vector
     }
     if (total_params >= (size_t(1) << 31) || total_mats >= (size_t(1) << 31))
         return fail(h, QSV_E_ARG, "batch too large");
+    // The counters of evaluations of four and five keys (run_group, launch_factor) are allocated and cleared here, before the
+    // batch's first push.  Left to the push, the clear -- no kernel launch -- spoiled the push's launch record, and a repeated
+    // push records nothing: the first batch of a handle that held such a circuit was never replayed while its layout was kept,
+    // where the same batch on a handle that had met one before was (tests/test_gpu_operator_walk.py).
+    if (b.split_any && !h->d_factor_big_count.ptr && h->side_slots > 0) {
+        int most_keys = 0;
+        for (size_t i = 0; i < n_evals; ++i)
+            if (b.split[i]) most_keys = std::max(most_keys, circs[i]->split.n_keys);
+        if (most_keys > 3 && (rc = ensure_factor_big(h, h->stream, false))) return rc;
+    }
     b.desc_bytes = ((sizeof(EvalDesc) * n_evals * (b.split_any ? 2 : 1) + 63) / 64) * 64;
     const size_t bytes = b.desc_bytes + (total_params + 1) * sizeof(double);
     if ((rc = ensure_host_batch(h, bytes))) return rc;
@@ -1816,21 +1846,9 @@ int run_group(qsv_t* h, const std::vector<Circuit*>& circs, size_t first, size_t
         int most_keys = 0;
         for (size_t i = 0; i < n_unfused; ++i) most_keys = std::max(most_keys, circs[eval_of(first + i)]->split.n_keys);
         if (most_keys > 3) {
-            int rc3 = ensure(h, h->d_factor_big, factor_big_slot_doubles() * sizeof(double) * size_t(h->side_slots));
+            // (batch_layout has made these buffers for every batch it laid out: a fallback, which spoils the push's record)
+            int rc3 = ensure_factor_big(h, ws(h), true);
             if (rc3) return rc3;
-            if (!h->d_factor_big_count.ptr) {
-                const size_t cbytes = factor_big_slot_counters() * sizeof(uint32_t) * size_t(h->side_slots);
-                if ((rc3 = ensure(h, h->d_factor_big_count, cbytes))) return rc3;
-                // Zeroed, and waited for, before anything else is enqueued: the counters of EVERY slot are cleared here, and the
-                // next push's chain -- on the other lane's stream, which does not wait for this one -- adds to those of its own
-                // slots.  Left to run in stream order, a clear that came late (its stream still busy with this chain's virtual
-                // circuits) reset counters that other chain had begun to add to: its evaluations of four and five keys were
-                // combined from incomplete partial sums, or not at all -- a wrong value in the first batch of a handle.
-                record_spoil(h);
-                QSV_HIP(h, hipMemsetAsync(h->d_factor_big_count.ptr, 0, cbytes, ws(h)));
-                h->host_waits += 1;
-                QSV_HIP(h, hipStreamSynchronize(ws(h)));
-            }
         }
         a.evals = batch_evals(h) + first;
         a.result_out = h->out_target ? h->out_target : h->h_out;
