@@ -743,6 +743,32 @@ int qsv_observables_destroy(qsv_t* h, int set_id);
 int qsv_eval_observables(qsv_t* h, int set_id, int n_evals, const int* circuit_ids, const int64_t* param_offsets,
                          const double* params, double* out);
 
+/*
+ * COVARIANCES: the second moments of a set's observables in each evaluation's state.  With lambda_m = O_m psi_e
+ * for the Hermitian part O_m of observable m (a set keeps the real parts of the coefficients),
+ *     out_values[e * M + m]        = E_m  = Re<psi_e|lambda_m>                     (where out_values is not NULL)
+ *     out_cov[(e * M + a) * M + b] = C_ab = Re<lambda_a|lambda_b> - E_a E_b = <{O_a, O_b}> / 2 - <O_a><O_b>,
+ * the full symmetric M x M matrix, row-major; C_aa is Var(O_a), and w^T C w the variance of sum_m w_m O_m.  Arguments are laid
+ * out as in qsv_eval_observables.  The call runs as qsv_variance_circuits runs: ordinary plans into state slots (no split route),
+ * then on the handle's stream one kernel per launch group that forms lambda_m(i) for 64 amplitudes and 16 observables at a time
+ * and accumulates Re(Lambda^H Lambda) per pair of 16-observable blocks on the fp64 matrix pipe, and one that adds the workgroups'
+ * partial tiles in ascending order, subtracts E_a E_b and mirrors the upper triangle.  Nothing state-sized is written; the scratch
+ * is allocated on first need and grown by need, and a launch group is made smaller where its partials would pass 64 MiB.
+ * The handle's operator is neither needed nor touched.  The numbers are RAW (no division by <psi|psi>, no clamping: rounding may
+ * leave a diagonal entry a tiny bit below zero) and out_cov[a][b] == out_cov[b][a] bit for bit.  Contract: an evaluation's numbers
+ * are the same bits in any batch, at any position of a launch group and on every call (fixed-order sums, no floating-point
+ * atomics).  out_values agrees with qsv_eval_observables to rounding, not bit for bit.  The call lays a batch out as every batch
+ * call does, so a recorded batch is dropped and laid out again by the next qsv_eval_* call, which returns the bits it returned
+ * before.  Goes between batches.
+ * Errors: unknown set QSV_E_ARG; out_cov NULL with n_evals > 0 (or other bad arguments) QSV_E_ARG; a batch open on this thread
+ * QSV_E_STATE; a circuit on a kept state QSV_E_UNSUPPORTED; more than 28 qubits QSV_E_UNSUPPORTED; a set of more than
+ * QSV_COVARIANCE_MAX_OBSERVABLES observables QSV_E_UNSUPPORTED; n_evals == 0 QSV_OK.
+ */
+#define QSV_COVARIANCE_MAX_OBSERVABLES 64
+int qsv_observables_covariance(qsv_t* h, int set_id, int n_evals, const int* circuit_ids, const int64_t* param_offsets,
+                               const double* params, double* out_values /* n_evals*M, may be NULL */,
+                               double* out_cov /* n_evals*M*M */);
+
 /* ---- sharded populations on one node ------------------------------------------------------------- */
 
 /*
@@ -815,8 +841,8 @@ int qsv_fitness_table_wait(const volatile uint64_t* own, int count, volatile int
  *                        operator may hold more groups than the device's largest gridDim.y (hipDeviceAttributeMaxGridDimY, read
  *                        when the handle is created: the default, 0, and the largest value accepted).  More groups go in several
  *                        launches with the partial sums laid out as one launch lays them out: the same bits at any value
- *   "time_moments" 0|1   qsv_variance_circuits brackets the two kernels of every launch group by HIP events on the handle's stream
- *                        and leaves their summed device time in qsv_get_profile's expect_ms (measurements; the same bits)
+ *   "time_moments" 0|1   qsv_variance_circuits and qsv_observables_covariance bracket the two kernels of every launch group by HIP
+ *                        events on the handle's stream and leave their summed device time in qsv_get_profile's expect_ms (measurements; the same bits)
  * Returns QSV_E_ARG for an unknown name or a value out of range.
  */
 int qsv_set_option(qsv_t* h, const char* name, int value);

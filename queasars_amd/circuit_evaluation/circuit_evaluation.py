@@ -1249,6 +1249,37 @@ class StatevectorDevice:
                                                     _lib.as_ptr(out)))
         return out
 
+    MAX_COVARIANCE_OBSERVABLES = 64  # (QSV_COVARIANCE_MAX_OBSERVABLES)
+
+    def observable_covariances(
+        self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]], operators: Sequence[PauliOperator]
+    ) -> tuple[np.ndarray, np.ndarray]:
+        """``(values, covariances)`` of ``operators`` in every (circuit, parameter vector) pair's state: a ``(n, M)`` and a
+        ``(n, M, M)`` float64 array, ``E_m = <O_m>`` and ``C_ab = <{O_a, O_b}> / 2 - <O_a><O_b>`` of the operators' Hermitian
+        parts, reduced on the device from the final state (``qsv_observables_covariance``).  ``C[i]`` is exactly
+        symmetric, its diagonal the operators' variances, and ``w @ C[i] @ w`` the variance of ``sum_m w_m O_m``.  Raw numbers:
+        rounding may leave a diagonal entry a tiny bit below zero.  Deterministic; does not use or change the operator set on
+        the device.  At most :attr:`MAX_COVARIANCE_OBSERVABLES` operators; a circuit on a kept state raises ``ValueError``."""
+        n = len(circuits)
+        if len(parameter_values) != n:
+            raise ValueError("circuits and parameter_values must have the same length")
+        operators = list(operators)
+        if not operators:
+            raise ValueError("at least one observable is needed")
+        m = len(operators)
+        if m > self.MAX_COVARIANCE_OBSERVABLES:
+            raise ValueError(f"covariances are available for at most {self.MAX_COVARIANCE_OBSERVABLES} observables, not {m}")
+        set_id = self._observable_set(operators)
+        values = np.zeros((n, m), dtype=np.float64)
+        covariances = np.zeros((n, m, m), dtype=np.float64)
+        if n == 0:
+            return values, covariances
+        ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
+        # (a refused circuit -- QSV_E_UNSUPPORTED: one on a kept state -- as a ValueError with the library's message)
+        self._check_gradient(self._lib.qsv_observables_covariance(
+            self._handle, set_id, n, _lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat), _lib.as_ptr(values), _lib.as_ptr(covariances)))
+        return values, covariances
+
     # -- measurement support ----------------------------------------------------------------------
     def set_option(self, name: str, value: int) -> None:
         """Switches of the handle (``qsv_set_option``): "split", "factor", "split_sampling" (0 / 1), "streams" (1 .. 4),
@@ -1595,6 +1626,18 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         if self._precision > 0:
             values = values + self._rng.normal(0.0, self._precision, size=values.shape)
         return values.tolist()
+
+    def evaluate_covariances(
+        self, circuits: list[CircuitIR], parameter_values: list[list[float]], operators: Sequence[PauliOperator], with_values: bool = False
+    ):
+        """The covariance matrices ``C_ab = <{O_a, O_b}> / 2 - <O_a><O_b>`` of ``operators`` for every circuit (behind this
+        evaluator's initial state), an ``(n, M, M)`` float64 array (:meth:`StatevectorDevice.observable_covariances`, DESIGN.md
+        4.14); with ``with_values`` the pair ``(values, covariances)``, the ``(n, M)`` values from the same pass over the state.
+        Exact numbers: ``estimator_precision`` adds no noise here, and no random number is drawn.  The evaluator's own operator
+        is neither used nor changed."""
+        circuits = self._composed_list(circuits)
+        values, covariances = self._device.observable_covariances(circuits, parameter_values, operators)
+        return (values, covariances) if with_values else covariances
 
     def _evaluate_device_matrix(self, circuits, matrix, ready: bool = False, out_device_pointer: int = 0, as_list: bool = False):
         pointer, width, event, remember = _device_matrix_arguments(self, circuits, matrix, ready)

@@ -20,6 +20,7 @@
 #include "../../include/qsv.h"
 #include "adjoint.hpp"
 #include "moments.hpp"
+#include "covariance.hpp"
 #include "gradient.hpp"
 #include "value_cache.hpp"
 #include "kernels.hpp"
@@ -108,6 +109,9 @@ struct ObservableSet {
     int n_rows = 0;
     int nb = 1;            // workgroups per row and state of pauli_terms_kernel
     DeviceBuffer d_rows, d_terms, d_split_terms, d_offsets, d_term_of, d_coef;
+    // what covariance_panels_kernel reads (covariance.hpp; sets of up to kCovMaxObservables only): each observable's terms grouped
+    // by x mask, in the caller's order within a group
+    DeviceBuffer d_cov_first, d_cov_groups, d_cov_terms;
 };
 
 }  // namespace
@@ -487,6 +491,9 @@ struct qsv_handle {
     qsv_adjoint_stats_t adj_stats{};
     // the operator's moments (qsv_variance_circuits; moments.hpp): the call's (E, Var) pairs by position | one launch group's partials
     DeviceBuffer d_moments;
+    // an observable set's second moments (qsv_observables_covariance; covariance.hpp): the call's values | covariances by position |
+    // one launch group's partials
+    DeviceBuffer d_cov;
     bool time_moments = false;  // option "time_moments": the device time of the two kernels goes to prof.expect_ms
     uint64_t host_waits = 0;  // times the host waited for a stream or an event (sync_streams and the few direct waits a batch can meet)
 
@@ -2714,7 +2721,8 @@ constexpr int64_t kMaxObsEntries = int64_t(1) << 24;
 constexpr size_t kObsScratchBytes = size_t(64) << 20;
 
 void free_observable_set(ObservableSet& s) {
-    for (DeviceBuffer* b : {&s.d_rows, &s.d_terms, &s.d_split_terms, &s.d_offsets, &s.d_term_of, &s.d_coef})
+    for (DeviceBuffer* b : {&s.d_rows, &s.d_terms, &s.d_split_terms, &s.d_offsets, &s.d_term_of, &s.d_coef, &s.d_cov_first, &s.d_cov_groups,
+                            &s.d_cov_terms})
         if (b->ptr) (void)hipFree(b->ptr);
     s = ObservableSet{};
 }
@@ -2967,7 +2975,7 @@ void qsv_destroy(qsv_t* h) {
                             &h->d_states, &h->d_wtab, &h->d_side, &h->d_factor, &h->d_factor_count, &h->d_factor_big, &h->d_factor_big_count, &h->d_quad, &h->d_fterms, &h->d_fpart, &h->d_batch, &h->d_mats, &h->d_partials, &h->d_out, &h->d_scratch, &h->d_prefix, &h->d_sdiag,
                             &h->d_obs_partials, &h->d_obs_values, &h->d_grad_tab, &h->d_grad_rows, &h->d_grad_values, &h->d_grad_base,
                             &h->d_grad_out, &h->d_adj_lambda, &h->d_adj_tab, &h->d_adj_mats, &h->d_adj_partials, &h->d_adj_epart, &h->d_adj_base,
-                            &h->d_adj_out, &h->d_adj_values, &h->d_moments})
+                            &h->d_adj_out, &h->d_adj_values, &h->d_moments, &h->d_cov})
         if (b->ptr) (void)hipFree(b->ptr);
     for (auto& kv : h->obs_sets) free_observable_set(kv.second);
     for (auto& kv : h->value_caches) free_value_cache(kv.second);
@@ -5329,6 +5337,40 @@ int qsv_observables_create(qsv_t* h, int n_observables, const int64_t* term_offs
         free_observable_set(s);
         return rc;
     }
+    if (uint32_t(n_observables) <= kCovMaxObservables) {  // qsv_observables_covariance's tables (covariance.hpp)
+        std::vector<uint32_t> cov_first(size_t(n_observables) + 1, 0);
+        std::vector<PauliGroup> cov_groups;
+        std::vector<CovTerm> cov_terms;
+        std::vector<int64_t> order;
+        for (int m = 0; m < n_observables; ++m) {
+            order.clear();
+            for (int64_t k = term_offsets[m]; k < term_offsets[m + 1]; ++k) order.push_back(k);
+            std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return x_mask[a] < x_mask[b]; });
+            bool any = false;
+            for (int64_t k : order) {
+                const uint64_t x = x_mask[k];
+                if (!any || cov_groups.back().x != x) {
+                    PauliGroup g{};
+                    g.x = x;
+                    g.first = uint32_t(cov_terms.size());
+                    g.pivot = x ? uint32_t(63 - __builtin_clzll(x)) : 0u;
+                    cov_groups.push_back(g);
+                    any = true;
+                }
+                cov_groups.back().count += 1;
+                const int ny = __builtin_popcountll(x & z_mask[k]);
+                const double c = ((ny >> 1) & 1) ? -coeff_re[k] : coeff_re[k];  // (-1)^{floor(ny/2)}
+                cov_terms.push_back(CovTerm{z_mask[k] | ((ny & 1) ? kCovOddY : uint64_t(0)), c});
+            }
+            cov_first[size_t(m) + 1] = uint32_t(cov_groups.size());
+        }
+        if ((rc = upload_bytes(h, s.d_cov_first, cov_first.data(), cov_first.size() * sizeof(uint32_t))) ||
+            (rc = upload_bytes(h, s.d_cov_groups, cov_groups.data(), cov_groups.size() * sizeof(PauliGroup))) ||
+            (rc = upload_bytes(h, s.d_cov_terms, cov_terms.data(), cov_terms.size() * sizeof(CovTerm)))) {
+            free_observable_set(s);
+            return rc;
+        }
+    }
     const int id = h->next_obs_id++;
     h->obs_sets.emplace(id, std::move(s));
     *out_set_id = id;
@@ -5359,6 +5401,86 @@ int qsv_eval_observables(qsv_t* h, int set_id, int n_evals, const int* circuit_i
     if (rc || n_evals == 0) return rc;
     QSV_HIP(h, hipSetDevice(h->device));
     return eval_observables_locked(h, set->second, args, out);
+}
+
+// ---- an observable set's second moments (qsv.h: COVARIANCES; covariance.hpp) -----------------------------------------------------
+
+int qsv_observables_covariance(qsv_t* h, int set_id, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
+                               double* out_values, double* out_cov) {
+    if (!h) return QSV_E_ARG;
+    if (h->batch_owner.load() == std::this_thread::get_id())
+        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_observables_covariance goes between batches)");
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets || !out_cov))) return fail(h, QSV_E_ARG, "bad arguments");
+    const auto found = h->obs_sets.find(set_id);
+    if (found == h->obs_sets.end()) return fail(h, QSV_E_ARG, "unknown observable set " + std::to_string(set_id));
+    const ObservableSet& set = found->second;
+    if (set.n_obs > kCovMaxObservables) return fail(h, QSV_E_UNSUPPORTED, "covariances are available for sets of up to 64 observables");
+    if (n_evals == 0) return QSV_OK;
+    if (h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "covariances are available up to 28 qubits");
+    QSV_HIP(h, hipSetDevice(h->device));
+    BatchArgs args;
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args,
+                           "the covariances of a circuit on a kept state are not built");
+    if (rc) return rc;
+    if (h->async_pending) {  // (the buffers below may still be read or written by a call that did not wait)
+        QSV_HIP(h, sync_streams(h));
+        h->async_pending = false;
+    }
+    // ordinary plans into state slots, never split, as qsv_variance_circuits runs them; a launch group's partials stay within
+    // the scratch limit of qsv_eval_observables
+    const size_t n = size_t(n_evals), M = set.n_obs;
+    const size_t per_eval = size_t(covariance_pairs(set.n_obs)) * covariance_blocks(h->n, set.n_obs) * kCovPartial * sizeof(double);
+    const size_t G = std::max<size_t>(1, std::min({size_t(h->group), size_t(h->max_grid_y), size_t(65535), kObsScratchBytes / per_eval}));
+    // device scratch: the call's values by position | its covariances by position | the partials of one launch group
+    const size_t out_count = n * (M + M * M), out_bytes = (out_count * sizeof(double) + 63) / 64 * 64;
+    if ((rc = ensure(h, h->d_cov, out_bytes + std::min(G, n) * per_eval)) || (rc = ensure_host_out(h, out_count))) return rc;
+    double* const values = static_cast<double*>(h->d_cov.ptr);
+    double* const cov = values + n * M;
+    double* const partials = reinterpret_cast<double*>(static_cast<char*>(h->d_cov.ptr) + out_bytes);
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> timed;  // (option "time_moments": the two kernels of every launch group)
+    struct DestroyEvents {
+        std::vector<std::pair<hipEvent_t, hipEvent_t>>& list;
+        ~DestroyEvents() {
+            for (auto& p : list) {
+                if (p.first) (void)hipEventDestroy(p.first);
+                if (p.second) (void)hipEventDestroy(p.second);
+            }
+        }
+    } destroy_events{timed};
+    auto moments = [&](size_t g0, size_t gc) -> int {
+        if (h->time_moments) {
+            timed.emplace_back(nullptr, nullptr);
+            QSV_HIP(h, hipEventCreate(&timed.back().first));
+            QSV_HIP(h, hipEventCreate(&timed.back().second));
+            QSV_HIP(h, hipEventRecord(timed.back().first, h->stream));
+        }
+        QSV_HIP(h, launch_covariance_panels(h->dtype, h->d_states.ptr, h->n, int(gc), set.n_obs, static_cast<const uint32_t*>(set.d_cov_first.ptr),
+                                            static_cast<const PauliGroup*>(set.d_cov_groups.ptr),
+                                            static_cast<const CovTerm*>(set.d_cov_terms.ptr), partials, h->stream));
+        QSV_HIP(h, launch_covariance_combine(partials, h->n, int(gc), set.n_obs, values + g0 * M, cov + g0 * M * M, h->stream));
+        if (h->time_moments) QSV_HIP(h, hipEventRecord(timed.back().second, h->stream));
+        return QSV_OK;
+    };
+    rc = run_to_states(h, args, StateRun{SplitRule{}, 1, G, false, 0, kModeSynthFirst | kModeFinalStore}, {}, moments);
+    if (rc) {  // nothing of a failed call may still be running
+        (void)sync_streams(h);
+        return rc;
+    }
+    QSV_HIP(h, hipMemcpyAsync(h->h_out, values, out_count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QSV_HIP(h, sync_streams(h));
+    const double* const h_cov = h->h_out + n * M;
+    for (size_t j = 0; j < n; ++j) {
+        const size_t e = h->batch.eval_at[j];
+        if (out_values) std::copy(h->h_out + j * M, h->h_out + (j + 1) * M, out_values + e * M);
+        std::copy(h_cov + j * M * M, h_cov + (j + 1) * M * M, out_cov + e * M * M);
+    }
+    for (const auto& p : timed) {
+        float ms = 0.0f;
+        QSV_HIP(h, hipEventElapsedTime(&ms, p.first, p.second));
+        h->prof.expect_ms += double(ms);
+    }
+    return QSV_OK;
 }
 
 int qsv_sample(qsv_t* h, int circuit_id, const double* params, int n_params, int shots, uint64_t seed,

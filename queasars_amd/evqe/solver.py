@@ -604,6 +604,11 @@ class EVQEResult:
     eigenstate_values: Optional[dict[str, float]] = None
     # <H^2> - <H>^2 of the evaluator's operator at the best individual: zero on an eigenstate (None: not asked for)
     eigenvalue_variance: Optional[float] = None
+    # the aux operators' covariance matrix at the best individual, C_ab = <{O_a, O_b}> / 2 - <O_a><O_b>, an (M, M) array in the aux
+    # operators' order (a dict's in list(aux_operators) order), and its diagonal, the variances, in the shape of
+    # aux_operators_evaluated (None: not asked for)
+    aux_operators_covariance: Optional[np.ndarray] = None
+    aux_operators_variance: Optional[Union[list[float], dict[Any, float]]] = None
 
 
 # ---- the solver -----------------------------------------------------------------------------------------------
@@ -863,7 +868,8 @@ class EVQEMinimumEigensolver:
 
     # -- main loop ------------------------------------------------------------------------------------------
     def compute_minimum_eigenvalue(self, evaluator, search_evaluator=None, aux_operators=None,
-                                   eigenstate_states: Optional[int] = None, eigenvalue_variance: bool = False) -> EVQEResult:
+                                   eigenstate_states: Optional[int] = None, eigenvalue_variance: bool = False,
+                                   aux_operators_covariance: bool = False) -> EVQEResult:
         """``search_evaluator``: a second evaluator of the SAME operator for the parameter searches alone -- a single-precision
         handle: the points a search compares differ by far more than 1e-6 (the reference's own tests run their searches on an
         estimator with precision 0.05, test/minimum_eigensolvers/evqe/solver.py:20-27), a layer search on kept states is bound
@@ -888,7 +894,14 @@ class EVQEMinimumEigensolver:
         ``eigenvalue_variance``: after the run, one ``evaluator.evaluate_variances`` call at the best individual; the operator's
         variance there, ``<H^2> - <H>^2`` (zero on an eigenstate; for a diagonal cost the spread over the individual's
         distribution), goes to ``result.eigenvalue_variance``.  The same rules: no random stream of the solver, not counted in
-        ``circuit_evaluations``, made by every rank of a sharded run itself.  ``False``: no call, the field stays ``None``."""
+        ``circuit_evaluations``, made by every rank of a sharded run itself.  ``False``: no call, the field stays ``None``.
+
+        ``aux_operators_covariance``: after the run, one ``evaluator.evaluate_covariances`` call at the best individual with the
+        aux operators; their covariance matrix there goes to ``result.aux_operators_covariance`` (an (M, M) array in the aux
+        operators' order, a dict's in ``list(aux_operators)`` order) and its diagonal, the variances, to
+        ``result.aux_operators_variance`` in the shape of ``aux_operators_evaluated``.  With the cost's parts as aux operators
+        ``w @ C @ w`` is the variance of any re-weighting of them.  The same rules as ``eigenvalue_variance``.  ``False``: no
+        call, both fields stay ``None``."""
         cfg = self.configuration
         searcher = evaluator if search_evaluator is None else search_evaluator
         if searcher.n_qubits != evaluator.n_qubits:
@@ -903,6 +916,11 @@ class EVQEMinimumEigensolver:
             raise ValueError("eigenstate_states needs an evaluator with a statevector_device (a device evaluator)")
         if eigenvalue_variance and not callable(getattr(evaluator, "evaluate_variances", None)):
             raise ValueError("eigenvalue_variance needs an evaluator with evaluate_variances (an operator evaluator)")
+        if aux_operators_covariance:
+            if aux_operators is None or len(aux_operators) == 0:
+                raise ValueError("aux_operators_covariance needs aux_operators")
+            if not callable(getattr(evaluator, "evaluate_covariances", None)):
+                raise ValueError("aux_operators_covariance needs an evaluator with evaluate_covariances (an operator evaluator)")
         if cfg.termination_criterion is not None:
             cfg.termination_criterion.reset_state()
         population = EVQEPopulation.random_population(
@@ -977,6 +995,15 @@ class EVQEMinimumEigensolver:
             best = result.best_individual
             circuit = best.get_parameterized_quantum_circuit(shared=self.share_circuits)
             result.eigenvalue_variance = float(evaluator.evaluate_variances([circuit], [list(best.parameter_values)])[0])
+        if aux_operators_covariance:
+            best = result.best_individual
+            names = list(aux_operators) if isinstance(aux_operators, dict) else None
+            operators = [aux_operators[k] for k in names] if names is not None else list(aux_operators)
+            circuit = best.get_parameterized_quantum_circuit(shared=self.share_circuits)
+            matrix = np.array(evaluator.evaluate_covariances([circuit], [list(best.parameter_values)], operators)[0], dtype=np.float64)
+            variances = [float(v) for v in np.diagonal(matrix)]
+            result.aux_operators_covariance = matrix
+            result.aux_operators_variance = dict(zip(names, variances)) if names is not None else variances
         return result
 
     def _read_eigenstate(self, evaluator, individual: EVQEIndividual, k: int):

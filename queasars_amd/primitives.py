@@ -109,12 +109,20 @@ class GpuEstimator(_EstimatorBase):
     entry of ``evs`` gets Gaussian noise of ITS OWN standard deviation ``sqrt(max(Var, 0) / N)``, with ``Var`` the observable's
     variance in that entry's state, computed on the device (``OperatorCircuitEvaluator.evaluate_variances``).
     ``data.stds`` holds those standard deviations in the shape of ``evs`` and ``metadata["shots"]`` is ``N``.  In this mode a
-    pub's own precision and the call's ``precision`` are ignored."""
+    pub's own precision and the call's ``precision`` are ignored.
+
+    ``joint_moments=True`` (with ``shots``; the default ``False`` leaves that route and its numbers as they are): an array pub
+    takes the values and the variances of all its distinct observables from ONE ``evaluate_covariances`` call over its distinct
+    bindings -- the diagonal of the observables' covariance matrix, DESIGN.md 4.14 -- instead of one evaluator and one pass over
+    the states per distinct observable.  The noise stays independent per entry; ``stds`` and ``metadata`` keep their form."""
 
     def __init__(self, dtype: str = "fp64", device: int = 0, seed: Optional[int] = None, max_operators: int = 8,
-                 shots: Optional[int] = None):
+                 shots: Optional[int] = None, joint_moments: bool = False):
         if shots is not None and int(shots) <= 0:
             raise ValueError("shots must be a positive number (or None: the precision's noise)")
+        if joint_moments and shots is None:
+            raise ValueError("joint_moments belongs to the shot noise: set shots")
+        self._joint_moments = bool(joint_moments)
         self._shots = None if shots is None else int(shots)
         self._dtype, self._device_index, self._seed = dtype, device, seed
         self._rng = np.random.default_rng(seed)
@@ -225,7 +233,8 @@ class GpuEstimator(_EstimatorBase):
 
     def _array_pub_moments(self, circuit: Any, observables: Any, values: Any) -> tuple[np.ndarray, np.ndarray]:
         """(exact values, variances) of one array pub, both of its broadcast shape: one ``evaluate_variances`` call per distinct
-        observable over the pub's distinct bindings, spread by :func:`pub_layout`'s indices."""
+        observable over the pub's distinct bindings -- with ``joint_moments`` one ``evaluate_covariances`` call for all of them --,
+        spread by :func:`pub_layout`'s indices."""
         circuit = self._convert.circuit(circuit)
         layout = pub_layout(observables, values)
         ops, keys, observable_of = [], {}, []
@@ -239,8 +248,16 @@ class GpuEstimator(_EstimatorBase):
         rows = [list(r) for r in layout.rows]
         exact = np.zeros((len(rows), len(ops)))
         variances = np.zeros((len(rows), len(ops)))
-        for m, op in enumerate(ops):
-            if rows:
+        if not rows:
+            pass
+        elif self._joint_moments:
+            evaluator, limit = self._evaluator(ops[0]), StatevectorDevice.MAX_COVARIANCE_OBSERVABLES
+            for m in range(0, len(ops), limit):  # (a set holds at most `limit` observables; only the diagonal is wanted)
+                part, cov = evaluator.evaluate_covariances([circuit] * len(rows), rows, ops[m:m + limit], with_values=True)
+                exact[:, m:m + limit] = part
+                variances[:, m:m + limit] = np.diagonal(cov, axis1=1, axis2=2)
+        else:
+            for m, op in enumerate(ops):
                 exact[:, m], variances[:, m] = self._evaluator(op).evaluate_variances([circuit] * len(rows), rows, with_values=True)
         column = np.asarray(observable_of, dtype=np.intp)[layout.observable_index]
         return exact[layout.binding_index, column], variances[layout.binding_index, column]
