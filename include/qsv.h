@@ -21,6 +21,12 @@
  *   - every function returns 0 on success, a negative QSV_E_* code otherwise; qsv_last_error() gives text
  *   - the caller owns every host array it passes in or receives results in; the library owns all device memory
  *   - a handle may be used from several host threads; calls on one handle are serialised internally
+ *   - between qsv_eval_begin and qsv_eval_end the calling thread holds the handle (other threads' calls wait for the end).  From
+ *     that thread, every call that takes the handle returns QSV_E_STATE -- "a batch is open on this handle (<function> goes
+ *     between batches)" -- and does nothing.  The exceptions are the calls that belong inside a batch: qsv_eval_push,
+ *     qsv_eval_push_device, qsv_eval_staging, qsv_eval_set_output, qsv_eval_suggested_pushes and qsv_eval_end; and those that
+ *     take no lock: qsv_destroy, qsv_last_error, qsv_n_qubits, qsv_group_size and the functions without a handle.  (A second
+ *     qsv_eval_begin is refused in its own words.)
  */
 #ifndef QSV_H
 #define QSV_H
@@ -710,7 +716,7 @@ int qsv_adjoint_stats(const qsv_t* h, qsv_adjoint_stats_t* out);
  * (fixed-order sums, no floating-point atomics).  out_values agrees with qsv_eval_circuits to rounding, not bit for bit: it comes
  * from another route.  The call lays a batch out as every batch call does, so a recorded batch ("replay_launches") is dropped
  * and laid out again by the next qsv_eval_* call, which returns the bits it returned before.  Goes between batches.
- * Errors: no operator set QSV_E_STATE; a batch open on this thread QSV_E_STATE; out_variances NULL with n_evals > 0 (or other
+ * Errors: no operator set QSV_E_STATE; out_variances NULL with n_evals > 0 (or other
  * bad arguments) QSV_E_ARG; a circuit on a kept state QSV_E_UNSUPPORTED; more than 28 qubits QSV_E_UNSUPPORTED; n_evals == 0 QSV_OK.
  */
 int qsv_variance_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
@@ -760,8 +766,7 @@ int qsv_eval_observables(qsv_t* h, int set_id, int n_evals, const int* circuit_i
  * atomics).  out_values agrees with qsv_eval_observables to rounding, not bit for bit.  The call lays a batch out as every batch
  * call does, so a recorded batch is dropped and laid out again by the next qsv_eval_* call, which returns the bits it returned
  * before.  Goes between batches.
- * Errors: unknown set QSV_E_ARG; out_cov NULL with n_evals > 0 (or other bad arguments) QSV_E_ARG; a batch open on this thread
- * QSV_E_STATE; a circuit on a kept state QSV_E_UNSUPPORTED; more than 28 qubits QSV_E_UNSUPPORTED; a set of more than
+ * Errors: unknown set QSV_E_ARG; out_cov NULL with n_evals > 0 (or other bad arguments) QSV_E_ARG; a circuit on a kept state QSV_E_UNSUPPORTED; more than 28 qubits QSV_E_UNSUPPORTED; a set of more than
  * QSV_COVARIANCE_MAX_OBSERVABLES observables QSV_E_UNSUPPORTED; n_evals == 0 QSV_OK.
  */
 #define QSV_COVARIANCE_MAX_OBSERVABLES 64

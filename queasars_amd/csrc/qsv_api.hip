@@ -358,7 +358,7 @@ struct qsv_handle {
     size_t h_stage_words = 0;
     double* h_out = nullptr;  // pinned
     bool repeat_device_descs = true;  // (QSV_REPEAT_DESCS=0: a repeated batch reads its descriptors from pinned memory again)
-    const double* dev_params_checked = nullptr;  // the last qsv_eval_push_device pointer found to be this device's memory
+    const void* dev_params_checked = nullptr;  // the last qsv_eval_push_device pointer found to be this device's memory
     double* out_target = nullptr;  // qsv_eval_set_output: device memory the open batch's results go to instead of h_out
     bool async_pending = false;    // a batch ended without waiting (qsv_eval_end with a device output): the staging buffers
                                    // may still be read by its kernels
@@ -599,6 +599,64 @@ int ensure(qsv_t* h, DeviceBuffer& b, size_t bytes) {
     QSV_HIP(h, hipMalloc(&b.ptr, want));
     b.bytes = want;
     return QSV_OK;
+}
+
+// ... and a reallocation counted where a call reports its own (qsv_gradient_stats, qsv_adjoint_stats)
+int ensure_counted(qsv_t* h, DeviceBuffer& b, size_t bytes, int64_t& counter) {
+    if (!(b.bytes >= bytes && b.ptr)) counter += 1;
+    return ensure(h, b, bytes);
+}
+
+// ---- what the entry points have in common (the entry layer) ------------------------------------------------------
+// Between qsv_eval_begin and qsv_eval_end the calling thread holds the handle's lock (batch_lock): an entry point that took it
+// again from that thread would wait for itself, so it refuses.
+int refuse_in_batch(qsv_t* h, const char* name) {
+    return fail(h, QSV_E_STATE, std::string("a batch is open on this handle (") + name + " goes between batches)");
+}
+
+// The opening: the one way an entry point takes the handle.  A handle, no batch of the calling thread's open on it, its lock
+// (held by `lock` until the caller returns) and, for a call that touches the device, its device.  The getters hand in a
+// const handle: fail only writes thread-locals, and the lock is mutable.
+int open_handle(const qsv_t* handle, const char* name, std::unique_lock<std::mutex>& lock, bool device) {
+    qsv_t* h = const_cast<qsv_t*>(handle);
+    if (!h) return QSV_E_ARG;
+    if (h->batch_owner.load() == std::this_thread::get_id()) return refuse_in_batch(h, name);
+    lock = std::unique_lock<std::mutex>(h->mu);
+    if (device) QSV_HIP(h, hipSetDevice(h->device));
+    return QSV_OK;
+}
+constexpr bool kHostOnly = false, kDevice = true;
+#define QSV_OPEN(h, name, device)                                               \
+    std::unique_lock<std::mutex> lock;                                          \
+    if (const int _open_rc = open_handle((h), (name), lock, (device))) return _open_rc
+
+// A batch that ended without waiting (async_pending) may still read or write the staging buffers and the scratch: whoever is
+// about to write them waits for it first.
+int wait_pending(qsv_t* h) {
+    if (h->async_pending) {
+        QSV_HIP(h, sync_streams(h));
+        h->async_pending = false;
+    }
+    return QSV_OK;
+}
+
+// given[i] (null: not looked at) is memory of the handle's device.  A search hands over the same buffers call after call: the
+// caller's cache remembers each, so that it is asked about once.
+int check_device_pointers(qsv_t* h, const void* const* given, const char* const* names, const void** cache, int count) {
+    for (int i = 0; i < count; ++i) {
+        if (!given[i] || given[i] == cache[i]) continue;
+        hipPointerAttribute_t attr{};
+        if (hipPointerGetAttributes(&attr, given[i]) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != h->device) {
+            (void)hipGetLastError();
+            return fail(h, QSV_E_ARG, std::string(names[i]) + " is not memory of this handle's device");
+        }
+        cache[i] = given[i];
+    }
+    return QSV_OK;
+}
+
+int too_few_values(qsv_t* h, int need, int64_t got) {
+    return fail(h, QSV_E_ARG, "circuit needs " + std::to_string(need) + " parameter values, got " + std::to_string(got));
 }
 
 int validate_ops(qsv_t* h, int n, int n_ops, const qsv_op* ops, int n_params) {
@@ -1337,10 +1395,7 @@ int batch_layout(qsv_t* h, const std::vector<Circuit*>& circs, const std::vector
     b.reduced = rule.reduced;
     b.record.entries.clear();  // (the launches of the layout that goes)
     b.record.usable = false;
-    if (h->async_pending) {  // the kernels of a batch that ended without waiting read the staging buffers written below
-        QSV_HIP(h, sync_streams(h));
-        h->async_pending = false;
-    }
+    if ((rc = wait_pending(h))) return rc;  // (the staging buffers are written below)
     {
         // ordinary plans that are needed now and do not exist yet (circuits registered in split form): scheduled on the
         // host's worker threads when there are several
@@ -1386,9 +1441,7 @@ int batch_layout(qsv_t* h, const std::vector<Circuit*>& circs, const std::vector
     b.eval_at.resize(n_evals);
     for (size_t i = 0; i < n_evals; ++i) b.eval_at[i] = uint32_t(i);
     for (size_t i = 0; i < n_evals; ++i) {
-        if (n_params[i] < circs[i]->n_params)
-            return fail(h, QSV_E_ARG, "circuit needs " + std::to_string(circs[i]->n_params) + " parameter values, got " +
-                                          std::to_string(n_params[i]));
+        if (n_params[i] < circs[i]->n_params) return too_few_values(h, circs[i]->n_params, n_params[i]);
         total_params += size_t(n_params[i]);
         const bool split = splits(circs[i]);
         b.split[i] = split;
@@ -2573,6 +2626,41 @@ int resolve_batch(qsv_t* h, size_t n, const int* circuit_ids, const int64_t* par
     return QSV_OK;
 }
 
+// The host forms of the gradient entry points hand the driver matrices.  pack_rows: the batch's parameter vectors as the rows
+// of one zero-filled row-major matrix `base`, as wide as the longest of them (at least one value; `even`: rounded up to an even
+// number of doubles), and out_width, the longest gradient request's -- evaluation e's is wrt_offsets[e + 1] - wrt_offsets[e]
+// entries (wrt_offsets null: one per parameter of its circuit).  unpack_rows: the first so many entries of each row of `rows`,
+// back to back into `out`.
+int pack_rows(qsv_t* h, const BatchArgs& args, const int64_t* wrt_offsets, const double* out, bool even, int64_t& width, int64_t& out_width,
+              std::vector<double>& base) {
+    const size_t n = args.circs.size();
+    auto row = [&](int64_t count) { return even ? (count + 1) / 2 * 2 : count; };
+    int64_t total_out = 0;
+    width = row(1);
+    out_width = 1;
+    for (size_t e = 0; e < n; ++e) {
+        width = std::max(width, row(args.n_params[e]));
+        const int64_t count = wrt_offsets ? wrt_offsets[e + 1] - wrt_offsets[e] : int64_t(args.circs[e]->n_params);
+        if (count < 0) return fail(h, QSV_E_ARG, "wrt_offsets must be non-decreasing");
+        out_width = std::max(out_width, count);
+        total_out += count;
+        if (args.n_params[e] < args.circs[e]->n_params) return too_few_values(h, args.circs[e]->n_params, args.n_params[e]);
+    }
+    if (total_out > 0 && !out) return fail(h, QSV_E_ARG, "out is null");
+    if (width > (1 << 24) || out_width > (1 << 24)) return fail(h, QSV_E_ARG, "too many parameters");
+    base.assign(n * size_t(width), 0.0);
+    for (size_t e = 0, cur = 0; e < n; cur += size_t(args.n_params[e]), ++e)
+        if (args.n_params[e]) std::memcpy(base.data() + e * size_t(width), args.values.data() + cur, size_t(args.n_params[e]) * sizeof(double));
+    return QSV_OK;
+}
+void unpack_rows(const BatchArgs& args, const int64_t* wrt_offsets, const std::vector<double>& rows, int64_t out_width, double* out) {
+    for (size_t e = 0, cur = 0; e < args.circs.size(); ++e) {
+        const size_t count = size_t(wrt_offsets ? wrt_offsets[e + 1] - wrt_offsets[e] : int64_t(args.circs[e]->n_params));
+        if (count) std::memcpy(out + cur, rows.data() + e * size_t(out_width), count * sizeof(double));
+        cur += count;
+    }
+}
+
 // One-shot evaluation: begin + one push + end.
 int eval_all(qsv_t* h, const BatchArgs& args, double* out) {
     if (args.circs.empty()) return QSV_OK;
@@ -2661,6 +2749,48 @@ int run_to_states(qsv_t* h, const BatchArgs& args, const StateRun& run, const Gr
     return rc ? rc : run_laid_out(h, args, run, lay, on_split, on_state);
 }
 
+// The frame of a consumer of WHOLE final states (qsv_variance_circuits, qsv_observables_covariance): ordinary plans into state
+// slots, never split (as qsv_prefix_create runs them), in launch groups of G; behind each group `launch`(first, count) queues
+// the consumer's kernels on the handle's stream, which leave their results by position in device memory at `results`.  Those
+// `count` doubles are in h_out when it returns, and batch.eval_at says whose they are; nothing of a failed call is still
+// running.  Option "time_moments": each group's kernels are bracketed by events, and their device time goes to prof.expect_ms.
+int run_whole_states(qsv_t* h, const BatchArgs& args, size_t G, const GroupFn& launch, const double* results, size_t count) {
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> timed;
+    struct DestroyEvents {
+        std::vector<std::pair<hipEvent_t, hipEvent_t>>& list;
+        ~DestroyEvents() {
+            for (auto& p : list) {
+                if (p.first) (void)hipEventDestroy(p.first);
+                if (p.second) (void)hipEventDestroy(p.second);
+            }
+        }
+    } destroy_events{timed};
+    auto group = [&](size_t g0, size_t gc) -> int {
+        if (h->time_moments) {
+            timed.emplace_back(nullptr, nullptr);
+            QSV_HIP(h, hipEventCreate(&timed.back().first));
+            QSV_HIP(h, hipEventCreate(&timed.back().second));
+            QSV_HIP(h, hipEventRecord(timed.back().first, h->stream));
+        }
+        if (const int rc = launch(g0, gc)) return rc;
+        if (h->time_moments) QSV_HIP(h, hipEventRecord(timed.back().second, h->stream));
+        return QSV_OK;
+    };
+    const int rc = run_to_states(h, args, StateRun{SplitRule{}, 1, G, false, 0, kModeSynthFirst | kModeFinalStore}, {}, group);
+    if (rc) {
+        (void)sync_streams(h);
+        return rc;
+    }
+    QSV_HIP(h, hipMemcpyAsync(h->h_out, results, count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QSV_HIP(h, sync_streams(h));
+    for (const auto& p : timed) {
+        float ms = 0.0f;
+        QSV_HIP(h, hipEventElapsedTime(&ms, p.first, p.second));
+        h->prof.expect_ms += double(ms);
+    }
+    return QSV_OK;
+}
+
 // What qsv_cvar_device has and the host forms of the sampler branch do not: the ids and row width its layout is remembered
 // by, and device memory for the results.  Such a call does not wait, so the next one that writes the staging buffer must
 // (batch_layout, async_pending) -- unless it is the same batch again, the next iteration of a search: then the layout the last
@@ -2707,8 +2837,7 @@ int run_single_to_state(qsv_t* h, int circuit_id, const double* params, int n_pa
     BatchArgs args;
     int rc = resolve_batch(h, 1, &circuit_id, offsets, params, args);
     if (!rc && n_params < 0)  // (a count, not offsets: refused as batch_layout refuses too few values)
-        rc = fail(h, QSV_E_ARG, "circuit needs " + std::to_string(args.circs[0]->n_params) + " parameter values, got " +
-                                    std::to_string(n_params));
+        rc = too_few_values(h, args.circs[0]->n_params, n_params);
     if (!rc) rc = run_to_states(h, args, StateRun{SplitRule{}, 1, 1, false, 0, kModeSynthFirst | kModeFinalStore}, {}, {});
     return rc;
 }
@@ -2998,10 +3127,8 @@ const char* qsv_last_error(const qsv_t* h) {
 }
 
 int qsv_set_stream(qsv_t* h, void* hip_stream) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_set_stream", kDevice);
     h->epoch += 1;
-    QSV_HIP(h, hipSetDevice(h->device));
     QSV_HIP(h, hipStreamSynchronize(h->stream));
     if (h->own_stream) {
         (void)hipStreamDestroy(h->stream);
@@ -3021,15 +3148,13 @@ int qsv_group_size(const qsv_t* h) { return h ? h->group : QSV_E_ARG; }
 
 int qsv_set_operator(qsv_t* h, int n_terms, const uint64_t* x_mask, const uint64_t* z_mask, const double* coeff_re,
                      const double* coeff_im) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_set_operator", kDevice);
     h->epoch += 1;
     if (n_terms < 1 || !x_mask || !z_mask || !coeff_re) return fail(h, QSV_E_ARG, "operator needs at least one term");
     (void)coeff_im;  // <P_k> is real for every Pauli string, so real(<H>) only needs the real parts
     const uint64_t limit = (uint64_t(1) << h->n) - 1;
     for (int k = 0; k < n_terms; ++k)
         if ((x_mask[k] | z_mask[k]) & ~limit) return fail(h, QSV_E_ARG, "Pauli term acts on a qubit >= n_qubits");
-    QSV_HIP(h, hipSetDevice(h->device));
     // ---- split into the diagonal part (x = 0) and x-mask groups of the rest -------------------------------
     std::vector<uint64_t> diag_z, off_z;
     std::vector<double> diag_c, off_c;
@@ -3145,7 +3270,7 @@ int qsv_circuit_create(qsv_t* h, int n_ops, const qsv_op* ops, int n_params, int
     std::string err;
     int rc = build_circuit(h, n_ops, ops, n_params, true, &c, &err);
     if (rc) return fail(h, rc, err);
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_circuit_create", kHostOnly);
     h->epoch += 1;
     *out_circuit_id = insert_circuit(h, std::move(c));
     return QSV_OK;
@@ -3164,15 +3289,14 @@ int qsv_circuits_create(qsv_t* h, int n_circuits, const int64_t* op_offsets, con
     }, built);
     for (int i = 0; i < n_circuits; ++i)
         if (built[size_t(i)].rc) return fail(h, built[size_t(i)].rc, built[size_t(i)].err + " (circuit " + std::to_string(i) + ")");
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_circuits_create", kHostOnly);
     h->epoch += 1;
     for (int i = 0; i < n_circuits; ++i) out_circuit_ids[i] = insert_circuit(h, std::move(built[size_t(i)].circuit));
     return QSV_OK;
 }
 
 int qsv_circuit_destroy(qsv_t* h, int circuit_id) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_circuit_destroy", kHostOnly);
     h->epoch += 1;
     auto it = h->circuits.find(circuit_id);
     if (it == h->circuits.end()) return fail(h, QSV_E_ARG, "unknown circuit id");
@@ -3188,13 +3312,9 @@ int qsv_circuit_destroy(qsv_t* h, int circuit_id) {
 
 int qsv_prefix_create(qsv_t* h, int n_states, const int* circuit_ids, const int64_t* param_offsets, const double* params,
                       int* out_prefix_ids) {
-    if (!h) return QSV_E_ARG;
-    if (h->batch_owner.load() == std::this_thread::get_id())
-        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_prefix_create goes between batches)");
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_prefix_create", kDevice);
     if (n_states < 0 || (n_states > 0 && (!circuit_ids || !param_offsets || !out_prefix_ids))) return fail(h, QSV_E_ARG, "bad arguments");
     if (n_states == 0) return QSV_OK;
-    QSV_HIP(h, hipSetDevice(h->device));
     const size_t n = size_t(n_states);
     BatchArgs args;
     int rc = resolve_batch(h, n, circuit_ids, param_offsets, params, args, "a kept state of a circuit that itself continues a kept state");
@@ -3277,9 +3397,8 @@ int qsv_prefix_create(qsv_t* h, int n_states, const int* circuit_ids, const int6
 int qsv_prefix_destroy(qsv_t* h, int n_states, const int* prefix_ids) {
     if (!h) return QSV_E_ARG;
     if (n_states < 0 || (n_states > 0 && !prefix_ids)) return fail(h, QSV_E_ARG, "bad arguments");
-    // (finalizers of host objects call this: it must not wait for a handle its own thread holds between begin and end)
-    if (h->batch_owner.load() == std::this_thread::get_id()) return fail(h, QSV_E_STATE, "a batch is open on this handle");
-    std::lock_guard<std::mutex> lock(h->mu);
+    // (finalizers of host objects call this: the opening keeps it from waiting for a handle its own thread holds between begin and end)
+    QSV_OPEN(h, "qsv_prefix_destroy", kHostOnly);
     int rc = QSV_OK;
     for (int i = 0; i < n_states; ++i) {
         auto it = h->prefixes.find(prefix_ids[i]);
@@ -3297,13 +3416,12 @@ int qsv_prefix_destroy(qsv_t* h, int n_states, const int* prefix_ids) {
 }
 
 int qsv_prefix_count(const qsv_t* h) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_prefix_count", kHostOnly);
     return int(h->prefixes.size());
 }
 
-int qsv_circuits_create_on_prefixes(qsv_t* h, int n_circuits, const int64_t* op_offsets, const qsv_op* ops, const int* n_params,
-                                    const int* prefix_ids, int* out_circuit_ids) {
+static int create_on_prefixes(qsv_t* h, const char* name, int n_circuits, const int64_t* op_offsets, const qsv_op* ops, const int* n_params,
+                              const int* prefix_ids, int* out_circuit_ids) {
     if (!h) return QSV_E_ARG;
     if (n_circuits < 0 || (n_circuits > 0 && (!op_offsets || !n_params || !prefix_ids || !out_circuit_ids)))
         return fail(h, QSV_E_ARG, "bad arguments");
@@ -3316,7 +3434,7 @@ int qsv_circuits_create_on_prefixes(qsv_t* h, int n_circuits, const int64_t* op_
     }, built);
     for (int i = 0; i < n_circuits; ++i)
         if (built[size_t(i)].rc) return fail(h, built[size_t(i)].rc, built[size_t(i)].err + " (circuit " + std::to_string(i) + ")");
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, name, kHostOnly);
     for (int i = 0; i < n_circuits; ++i) {
         auto it = h->prefixes.find(prefix_ids[i]);
         if (it == h->prefixes.end() || it->second.released) return fail(h, QSV_E_ARG, "unknown kept state " + std::to_string(prefix_ids[i]));
@@ -3330,9 +3448,14 @@ int qsv_circuits_create_on_prefixes(qsv_t* h, int n_circuits, const int64_t* op_
     return QSV_OK;
 }
 
+int qsv_circuits_create_on_prefixes(qsv_t* h, int n_circuits, const int64_t* op_offsets, const qsv_op* ops, const int* n_params,
+                                    const int* prefix_ids, int* out_circuit_ids) {
+    return create_on_prefixes(h, "qsv_circuits_create_on_prefixes", n_circuits, op_offsets, ops, n_params, prefix_ids, out_circuit_ids);
+}
+
 int qsv_circuit_create_on_prefix(qsv_t* h, int prefix_id, int n_ops, const qsv_op* ops, int n_params, int* out_circuit_id) {
     const int64_t offsets[2] = {0, n_ops};
-    return qsv_circuits_create_on_prefixes(h, 1, offsets, ops, &n_params, &prefix_id, out_circuit_id);
+    return create_on_prefixes(h, "qsv_circuit_create_on_prefix", 1, offsets, ops, &n_params, &prefix_id, out_circuit_id);
 }
 
 // Whether the one-launch route runs `c` on its reduced form under the operator set now: what run_group decides through side_form
@@ -3342,10 +3465,7 @@ static bool runs_reduced(const qsv_t* h, const Circuit& c) {
     return c.split.fused && c.reduced.ok && (h->n_terms == 0 ? h->fused_factor && h->final_controls : reduced_route(h));
 }
 
-int qsv_circuit_cost(qsv_t* h, int circuit_id, qsv_circuit_cost_t* out) {
-    if (!h) return QSV_E_ARG;
-    if (!out) return fail(h, QSV_E_ARG, "out is null");
-    std::lock_guard<std::mutex> lock(h->mu);
+static int circuit_cost_locked(qsv_t* h, int circuit_id, qsv_circuit_cost_t* out) {
     auto it = h->circuits.find(circuit_id);
     if (it == h->circuits.end()) return fail(h, QSV_E_ARG, "unknown circuit id");
     Circuit& c = it->second;
@@ -3393,16 +3513,21 @@ int qsv_circuit_cost(qsv_t* h, int circuit_id, qsv_circuit_cost_t* out) {
     return QSV_OK;
 }
 
+int qsv_circuit_cost(qsv_t* h, int circuit_id, qsv_circuit_cost_t* out) {
+    if (!h) return QSV_E_ARG;
+    if (!out) return fail(h, QSV_E_ARG, "out is null");
+    QSV_OPEN(h, "qsv_circuit_cost", kHostOnly);
+    return circuit_cost_locked(h, circuit_id, out);
+}
+
 static int circuit_form_of(qsv_t* h, int circuit_id, qsv_circuit_form_t* out, bool launched) {
     if (!h) return QSV_E_ARG;
     if (!out) return fail(h, QSV_E_ARG, "out is null");
+    QSV_OPEN(h, launched ? "qsv_circuit_launch_form" : "qsv_circuit_form", kHostOnly);
     qsv_circuit_cost_t cost;
-    int rc = qsv_circuit_cost(h, circuit_id, &cost);
+    int rc = circuit_cost_locked(h, circuit_id, &cost);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lock(h->mu);
-    auto it = h->circuits.find(circuit_id);
-    if (it == h->circuits.end()) return fail(h, QSV_E_ARG, "unknown circuit id");
-    const Circuit& c = it->second;
+    const Circuit& c = h->circuits.find(circuit_id)->second;
     *out = qsv_circuit_form_t{};
     out->route = cost.route;
     out->n_keys = cost.n_keys;
@@ -3432,11 +3557,9 @@ int qsv_circuit_launch_form(qsv_t* h, int circuit_id, qsv_circuit_form_t* out) {
 
 int qsv_eval_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
                       double* out) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_eval_circuits", kDevice);
     if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets || !out)))
         return fail(h, QSV_E_ARG, "bad arguments");
-    QSV_HIP(h, hipSetDevice(h->device));
     BatchArgs args;
     int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args);
     return rc ? rc : eval_all(h, args, out);
@@ -3514,6 +3637,8 @@ static void coalesce_lead(qsv_t* h, std::unique_lock<std::mutex>& lock, double w
 int qsv_eval_coalesced(qsv_t* h, int circuit_id, const double* params, int n_params, double window_us, double* out) {
     if (!h) return QSV_E_ARG;
     if (!out || n_params < 0 || (n_params > 0 && !params)) return fail(h, QSV_E_ARG, "bad arguments");
+    // (whoever collects the batch takes the handle's lock in coalesce_lead: refused here, before the request is queued)
+    if (h->batch_owner.load() == std::this_thread::get_id()) return refuse_in_batch(h, "qsv_eval_coalesced");
     qsv_handle::CoalesceRequest req;
     req.circuit_id = circuit_id;
     req.params = params;
@@ -3610,14 +3735,9 @@ int qsv_eval_push_device(qsv_t* h, int first, int count, const double* device_va
     if (!h->batch.open) return fail(h, QSV_E_STATE, "no open batch (call qsv_eval_begin first)");
     if (first < 0 || count < 0) return fail(h, QSV_E_ARG, "bad arguments");
     if (!device_values) return qsv_eval_push(h, first, count, nullptr);  // (only legal for evaluations without parameters)
-    if (device_values != h->dev_params_checked) {  // (an optimiser hands over the same buffer call after call: asked once)
-        hipPointerAttribute_t attr{};
-        if (hipPointerGetAttributes(&attr, device_values) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != h->device) {
-            (void)hipGetLastError();
-            return fail(h, QSV_E_ARG, "device_values is not memory of this handle's device");
-        }
-        h->dev_params_checked = device_values;
-    }
+    const void* const given = device_values;
+    static const char* const name = "device_values";
+    if (const int rc = check_device_pointers(h, &given, &name, &h->dev_params_checked, 1)) return rc;
     if (ready_event) {
         // whichever of the handle's streams runs a part of this push reads the values: all of them wait
         QSV_HIP(h, hipStreamWaitEvent(h->stream, static_cast<hipEvent_t>(ready_event), 0));
@@ -3631,30 +3751,15 @@ int qsv_eval_staging(qsv_t* h, int first, int count, double** values) {
     if (!h->batch.open) return fail(h, QSV_E_STATE, "no open batch (call qsv_eval_begin first)");
     const qsv_handle::Batch& b = h->batch;
     if (first < 0 || count < 0 || size_t(first) + size_t(count) > b.circs.size()) return fail(h, QSV_E_ARG, "range exceeds the batch");
-    if (h->async_pending) {  // (the caller is about to write where an unfinished batch's kernels may still read)
-        QSV_HIP(h, sync_streams(h));
-        h->async_pending = false;
-    }
+    if (const int rc = wait_pending(h)) return rc;  // (the caller is about to write the staging buffer)
     double* hp = reinterpret_cast<double*>(static_cast<char*>(h->h_batch) + b.desc_bytes);
     *values = hp + (count > 0 ? size_t(b.param_base[size_t(first)]) : 0);
     return QSV_OK;
 }
 
-// The opening the step entry points have in common: a handle and arguments, no batch of the calling thread's open on the
-// handle, the handle's lock (held by `lock` until the caller returns) and its device.
-static int step_begin(qsv_t* h, const void* args, const char* name, std::unique_lock<std::mutex>& lock) {
-    if (!h || !args) return QSV_E_ARG;
-    // (between qsv_eval_begin and qsv_eval_end the calling thread holds the handle: it would wait for itself)
-    if (h->batch_owner.load() == std::this_thread::get_id())
-        return fail(h, QSV_E_STATE, std::string("a batch is open on this handle (") + name + " goes between batches)");
-    lock = std::unique_lock<std::mutex>(h->mu);
-    QSV_HIP(h, hipSetDevice(h->device));
-    return QSV_OK;
-}
-
 int qsv_spsa_step(qsv_t* h, const qsv_spsa_step_args* in) {
-    std::unique_lock<std::mutex> lock;
-    if (const int rc = step_begin(h, in, "qsv_spsa_step", lock)) return rc;
+    if (!h || !in) return QSV_E_ARG;
+    QSV_OPEN(h, "qsv_spsa_step", kDevice);
     if (in->n_runs < 0 || in->width < 0 || !in->x || !in->active || !in->iterations) return fail(h, QSV_E_ARG, "bad arguments");
     if (in->values && !in->delta_accept) return fail(h, QSV_E_ARG, "values without the signs they were measured with");
     if (in->delta_propose && !in->points) return fail(h, QSV_E_ARG, "a proposal needs somewhere to go");
@@ -3666,8 +3771,8 @@ int qsv_spsa_step(qsv_t* h, const qsv_spsa_step_args* in) {
 }
 
 int qsv_nft_step(qsv_t* h, const qsv_nft_step_args* in) {
-    std::unique_lock<std::mutex> lock;
-    if (const int rc = step_begin(h, in, "qsv_nft_step", lock)) return rc;
+    if (!h || !in) return QSV_E_ARG;
+    QSV_OPEN(h, "qsv_nft_step", kDevice);
     if (in->n_runs < 0 || in->width < 0 || in->columns_stride < 1 || !in->x || !in->sizes || !in->columns || !in->recycled)
         return fail(h, QSV_E_ARG, "bad arguments");
     if (in->accept && !in->values) return fail(h, QSV_E_ARG, "an accept needs the values it fits");
@@ -3681,8 +3786,8 @@ int qsv_nft_step(qsv_t* h, const qsv_nft_step_args* in) {
 }
 
 int qsv_adam_step(qsv_t* h, const qsv_adam_step_args* in) {
-    std::unique_lock<std::mutex> lock;
-    if (const int rc = step_begin(h, in, "qsv_adam_step", lock)) return rc;
+    if (!h || !in) return QSV_E_ARG;
+    QSV_OPEN(h, "qsv_adam_step", kDevice);
     if (in->n_runs < 0 || in->width < 0 || in->grad_width < 0 || in->columns_stride < 1 || !in->x || !in->sizes || !in->columns || !in->m ||
         !in->v || !in->gradient || !in->active || !in->iterations)
         return fail(h, QSV_E_ARG, "bad arguments");
@@ -3730,9 +3835,7 @@ int qsv_eval_set_output(qsv_t* h, double* device_out) {
 }
 
 int qsv_eval_results_seen(qsv_t* h) {
-    if (!h) return QSV_E_ARG;
-    if (h->batch_owner.load() == std::this_thread::get_id()) return fail(h, QSV_E_STATE, "a batch is open");
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_eval_results_seen", kHostOnly);
     if (h->batch.open) return fail(h, QSV_E_STATE, "a batch is open");
     h->async_pending = false;
     return QSV_OK;
@@ -3754,11 +3857,9 @@ int qsv_eval_end(qsv_t* h, double* out_expectations) {
 
 int qsv_eval_batch(qsv_t* h, int n_evals, const int64_t* op_offsets, const qsv_op* ops, const int64_t* param_offsets,
                    const double* params, double* out) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_eval_batch", kDevice);
     if (n_evals < 0 || (n_evals > 0 && (!op_offsets || !param_offsets || !out)))
         return fail(h, QSV_E_ARG, "bad arguments");
-    QSV_HIP(h, hipSetDevice(h->device));
     // The cache of inline structures is bounded.  It is emptied only HERE, before any circuit of this call has been
     // looked up: evicting inside the loop below would free plans that earlier evaluations of the same call point at.
     if (h->inline_cache.size() > kInlineCacheLimit) {
@@ -3833,10 +3934,8 @@ int qsv_eval_batch(qsv_t* h, int n_evals, const int64_t* op_offsets, const qsv_o
 }
 
 int qsv_statevector(qsv_t* h, int circuit_id, const double* params, int n_params, double* out_re_im) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_statevector", kDevice);
     if (!out_re_im) return fail(h, QSV_E_ARG, "out is null");
-    QSV_HIP(h, hipSetDevice(h->device));
     int rc = run_single_to_state(h, circuit_id, params, n_params);
     if (rc) return rc;
     const uint64_t dim = uint64_t(1) << h->n;
@@ -3852,10 +3951,8 @@ int qsv_statevector(qsv_t* h, int circuit_id, const double* params, int n_params
 }
 
 int qsv_probabilities(qsv_t* h, int circuit_id, const double* params, int n_params, double* out_probs) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_probabilities", kDevice);
     if (!out_probs) return fail(h, QSV_E_ARG, "out is null");
-    QSV_HIP(h, hipSetDevice(h->device));
     int rc = run_single_to_state(h, circuit_id, params, n_params);
     if (rc) return rc;
     const uint64_t dim = uint64_t(1) << h->n;
@@ -3994,10 +4091,7 @@ static int exact_cvar_locked(qsv_t* h, const BatchArgs& args, double alpha, doub
     const uint64_t dim = uint64_t(1) << h->n;
     int rc;
     if (!h->order_valid) {
-        if (h->async_pending) {  // (it allocates: not beside a batch that ended without waiting)
-            QSV_HIP(h, sync_streams(h));
-            h->async_pending = false;
-        }
+        if ((rc = wait_pending(h))) return rc;  // (it allocates: not beside a batch that ended without waiting)
         if ((rc = ensure(h, h->d_order, dim * sizeof(uint32_t))) || (rc = ensure(h, h->d_sorted, dim * sizeof(double)))) return rc;
         QSV_HIP(h, sort_states_by_value(static_cast<const double*>(h->d_diag.ptr), dim, static_cast<uint32_t*>(h->d_order.ptr),
                                         static_cast<double*>(h->d_sorted.ptr), h->stream));
@@ -4098,11 +4192,9 @@ static int expectation_to_device(qsv_t* h, const BatchArgs& args, double* device
 
 int qsv_sample_batch(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
                      int shots, uint64_t seed, uint64_t* out_states, double* out_values) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_sample_batch", kDevice);
     if (n_evals < 0 || shots < 0 || (n_evals > 0 && shots > 0 && (!circuit_ids || !param_offsets || !out_states)))
         return fail(h, QSV_E_ARG, "bad arguments");
-    QSV_HIP(h, hipSetDevice(h->device));
     BatchArgs args;  // (no shots: only the ids are looked at)
     int rc = resolve_batch(h, size_t(n_evals), circuit_ids, shots ? param_offsets : nullptr, params, args, shots ? kNotSampled : nullptr);
     return rc ? rc : sample_batch_locked(h, args, shots, seed, out_states, out_values);
@@ -4110,13 +4202,11 @@ int qsv_sample_batch(qsv_t* h, int n_evals, const int* circuit_ids, const int64_
 
 int qsv_sample_cvar_batch(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
                           int shots, uint64_t seed, double alpha, double* out_cvar) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_sample_cvar_batch", kDevice);
     if (n_evals < 0 || shots < 1 || (n_evals > 0 && (!circuit_ids || !param_offsets || !out_cvar)))
         return fail(h, QSV_E_ARG, "bad arguments");
     if (!(alpha > 0.0) || alpha > 1.0) return fail(h, QSV_E_ARG, "alpha must be in (0, 1]");
     if (shots > kCvarMaxShots) return fail(h, QSV_E_ARG, "the device-side CVaR sorts at most 4096 samples per evaluation");
-    QSV_HIP(h, hipSetDevice(h->device));
     BatchArgs args;
     int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args, kNotSampled);
     return rc ? rc : sample_batch_locked(h, args, shots, seed, nullptr, nullptr, alpha, out_cvar);
@@ -4124,11 +4214,9 @@ int qsv_sample_cvar_batch(qsv_t* h, int n_evals, const int* circuit_ids, const i
 
 int qsv_exact_cvar_batch(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
                          double alpha, double* out_cvar) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_exact_cvar_batch", kDevice);
     if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets || !out_cvar))) return fail(h, QSV_E_ARG, "bad arguments");
     if (!(alpha > 0.0) || alpha > 1.0) return fail(h, QSV_E_ARG, "alpha must be in (0, 1]");
-    QSV_HIP(h, hipSetDevice(h->device));
     BatchArgs args;
     int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args, kNotSampled);
     return rc ? rc : exact_cvar_locked(h, args, alpha, out_cvar);
@@ -4182,13 +4270,11 @@ static int top_states_locked(qsv_t* h, const BatchArgs& args, int k, uint64_t* o
 
 int qsv_top_states(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params, int k,
                    uint64_t* out_states, double* out_probs, double* out_values) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_top_states", kDevice);
     if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets || !out_states || !out_probs))) return fail(h, QSV_E_ARG, "bad arguments");
     if (h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "the top states are available up to 28 qubits");
     if (k < 1 || k > int(kTopMaxStates) || uint64_t(k) > (uint64_t(1) << h->n))
         return fail(h, QSV_E_ARG, "k must be between 1 and min(" + std::to_string(kTopMaxStates) + ", 2^n)");
-    QSV_HIP(h, hipSetDevice(h->device));
     BatchArgs args;
     int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args,
                            "circuits on kept states have no top states (qsv_eval_* only)");
@@ -4197,32 +4283,19 @@ int qsv_top_states(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t*
 
 int qsv_cvar_device(qsv_t* h, int n_evals, const int* circuit_ids, int width, const double* device_values, void* ready_event,
                     int shots, uint64_t seed, double alpha, const uint8_t* device_active, int active_stride, double* device_out) {
-    if (!h) return QSV_E_ARG;
-    if (h->batch_owner.load() == std::this_thread::get_id())
-        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_cvar_device goes between batches)");
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_cvar_device", kDevice);
     if (n_evals < 0 || shots < 0 || width < 0 || (n_evals > 0 && (!circuit_ids || !device_out || (width > 0 && !device_values))))
         return fail(h, QSV_E_ARG, "bad arguments");
     if (device_active && active_stride < 1) return fail(h, QSV_E_ARG, "active_stride must be at least 1");
     if (!(alpha > 0.0) || alpha > 1.0) return fail(h, QSV_E_ARG, "alpha must be in (0, 1]");
     if (shots > kCvarMaxShots) return fail(h, QSV_E_ARG, "the device-side CVaR sorts at most 4096 samples per evaluation");
     if (n_evals == 0) return QSV_OK;
-    QSV_HIP(h, hipSetDevice(h->device));
-    // (a search hands over the same three buffers call after call: each is asked about once)
     const void* given[3] = {width > 0 ? device_values : nullptr, device_out, device_active};
     static const char* const names[3] = {"device_values", "device_out", "device_active"};
-    for (int i = 0; i < 3; ++i) {
-        if (!given[i] || given[i] == h->cvar_checked[i]) continue;
-        hipPointerAttribute_t attr{};
-        if (hipPointerGetAttributes(&attr, given[i]) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != h->device) {
-            (void)hipGetLastError();
-            return fail(h, QSV_E_ARG, std::string(names[i]) + " is not memory of this handle's device");
-        }
-        h->cvar_checked[i] = given[i];
-    }
-    BatchArgs args;
-    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, nullptr, nullptr, args, kNotSampled);
+    int rc = check_device_pointers(h, given, names, h->cvar_checked, 3);
     if (rc) return rc;
+    BatchArgs args;
+    if ((rc = resolve_batch(h, size_t(n_evals), circuit_ids, nullptr, nullptr, args, kNotSampled))) return rc;
     args.n_params.assign(size_t(n_evals), int64_t(width));
     args.device_values = width > 0 ? device_values : nullptr;
     // (all work of the call goes to the handle's stream -- run_laid_out --, so that is the stream that waits for the values)
@@ -4336,12 +4409,10 @@ static ValueCache* find_cache(qsv_t* h, int cache_id) {
 }
 
 int qsv_value_cache_create(qsv_t* h, int log2_slots, int log2_max_slots, int* out_cache_id) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_value_cache_create", kDevice);
     if (!out_cache_id) return fail(h, QSV_E_ARG, "out_cache_id is null");
     if (log2_slots < 1 || log2_max_slots < log2_slots || log2_max_slots > 30)
         return fail(h, QSV_E_ARG, "a value cache needs 1 <= log2_slots <= log2_max_slots <= 30");
-    QSV_HIP(h, hipSetDevice(h->device));
     ValueCache c;
     c.log2_slots = log2_slots;
     c.log2_max_slots = log2_max_slots;
@@ -4363,11 +4434,9 @@ int qsv_value_cache_create(qsv_t* h, int log2_slots, int log2_max_slots, int* ou
 }
 
 int qsv_value_cache_destroy(qsv_t* h, int cache_id) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_value_cache_destroy", kDevice);
     ValueCache* c = find_cache(h, cache_id);
     if (!c) return QSV_E_ARG;
-    QSV_HIP(h, hipSetDevice(h->device));
     QSV_HIP(h, sync_streams(h));
     free_value_cache(*c);
     h->value_caches.erase(cache_id);
@@ -4375,17 +4444,15 @@ int qsv_value_cache_destroy(qsv_t* h, int cache_id) {
 }
 
 int qsv_value_cache_clear(qsv_t* h, int cache_id) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_value_cache_clear", kDevice);
     ValueCache* c = find_cache(h, cache_id);
     if (!c) return QSV_E_ARG;
-    QSV_HIP(h, hipSetDevice(h->device));
     return cache_clear_locked(h, *c);
 }
 
 int qsv_value_cache_stats(const qsv_t* h, int cache_id, qsv_value_cache_stats_t* out) {
-    if (!h || !out) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    if (!out) return QSV_E_ARG;
+    QSV_OPEN(h, "qsv_value_cache_stats", kHostOnly);
     auto it = h->value_caches.find(cache_id);
     if (it == h->value_caches.end()) return QSV_E_ARG;
     const ValueCache& c = it->second;
@@ -4401,8 +4468,7 @@ int qsv_value_cache_stats(const qsv_t* h, int cache_id, qsv_value_cache_stats_t*
 
 int qsv_sample_lookup(qsv_t* h, int cache_id, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
                       int shots, uint64_t seed, int64_t* out_n_missing, const uint64_t** out_missing_states) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_sample_lookup", kDevice);
     if (n_evals < 0 || shots < 0 || !out_n_missing || !out_missing_states ||
         (n_evals > 0 && shots > 0 && (!circuit_ids || !param_offsets)))
         return fail(h, QSV_E_ARG, "bad arguments");
@@ -4414,7 +4480,6 @@ int qsv_sample_lookup(qsv_t* h, int cache_id, int n_evals, const int* circuit_id
         return fail(h, QSV_E_ARG, "one call's " + std::to_string(n_samples) + " samples do not fit into half of the cache's 2^" +
                                       std::to_string(c->log2_max_slots) + " slots");
     if (h->n >= 64) return fail(h, QSV_E_UNSUPPORTED, "value caches key on states of fewer than 64 qubits");
-    QSV_HIP(h, hipSetDevice(h->device));
     BatchArgs args;
     int rc = resolve_batch(h, size_t(n_evals), circuit_ids, shots ? param_offsets : nullptr, params, args, shots ? kNotSampled : nullptr);
     if (rc) return rc;
@@ -4473,8 +4538,7 @@ int qsv_sample_lookup(qsv_t* h, int cache_id, int n_evals, const int* circuit_id
 
 int qsv_sample_lookup_finish(qsv_t* h, int cache_id, int64_t n_values, const double* values, double alpha, double* out_cvar,
                              double* out_values) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_sample_lookup_finish", kDevice);
     ValueCache* c = find_cache(h, cache_id);
     if (!c) return QSV_E_ARG;
     if (!c->pending) return fail(h, QSV_E_STATE, "no lookup on this value cache waits for its values (qsv_sample_lookup comes first)");
@@ -4485,13 +4549,9 @@ int qsv_sample_lookup_finish(qsv_t* h, int cache_id, int64_t n_values, const dou
     if (out_cvar && (!(alpha > 0.0) || alpha > 1.0)) return fail(h, QSV_E_ARG, "alpha must be in (0, 1]");
     if (out_cvar && c->pending_shots > kCvarMaxShots)
         return fail(h, QSV_E_ARG, "the device-side CVaR sorts at most 4096 samples per evaluation");
-    QSV_HIP(h, hipSetDevice(h->device));
     const int64_t n_evals = c->pending_evals, n_samples = n_evals * c->pending_shots;
     int rc;
-    if (h->async_pending) {  // (the scratch and the result buffer are about to be written: a batch that ended without waiting may still use them)
-        QSV_HIP(h, sync_streams(h));
-        h->async_pending = false;
-    }
+    if ((rc = wait_pending(h))) return rc;  // (the scratch and the result buffer are about to be written)
     if (n_values > 0) {
         if ((rc = ensure_pinned(h, reinterpret_cast<void**>(&c->h_values), &c->h_values_bytes, size_t(n_values) * sizeof(double)))) return rc;
         std::memcpy(c->h_values, values, size_t(n_values) * sizeof(double));
@@ -4518,14 +4578,9 @@ int qsv_sample_lookup_finish(qsv_t* h, int cache_id, int64_t n_values, const dou
 // ---- parameter-shift gradients ---------------------------------------------------------------------------------------------
 
 // A device buffer that grows by doubling (the scratch matrix of the shifted rows: calls of growing size reallocate seldom).
-static int ensure_doubling(qsv_t* h, DeviceBuffer& b, size_t bytes, size_t most) {
+static int ensure_doubling(qsv_t* h, DeviceBuffer& b, size_t bytes, size_t most, int64_t& counter) {
     if (b.bytes >= bytes && b.ptr) return QSV_OK;
-    h->grad_stats.n_allocations += 1;
-    return ensure(h, b, std::max(bytes, std::min(2 * b.bytes, most)));
-}
-static int ensure_counted(qsv_t* h, DeviceBuffer& b, size_t bytes) {
-    if (!(b.bytes >= bytes && b.ptr)) h->grad_stats.n_allocations += 1;
-    return ensure(h, b, bytes);
+    return ensure_counted(h, b, std::max(bytes, std::min(2 * b.bytes, most)), counter);
 }
 
 // The base rows and the output of a gradient call, both in device memory.
@@ -4556,8 +4611,7 @@ static int gradient_tables(qsv_t* h, const std::vector<Circuit*>& circs, const i
     const double shifts[4] = {grad_shift1(), -grad_shift1(), grad_shift3(), -grad_shift3()};
     for (size_t e = 0; e < n_evals; ++e) {
         const Circuit& c = *circs[e];
-        if (base_width < c.n_params)
-            return fail(h, QSV_E_ARG, "circuit needs " + std::to_string(c.n_params) + " parameter values, got " + std::to_string(base_width));
+        if (base_width < c.n_params) return too_few_values(h, c.n_params, base_width);
         const int64_t first = wrt_offsets ? wrt_offsets[e] : 0, count = wrt_offsets ? wrt_offsets[e + 1] - first : int64_t(c.n_params);
         if (count < 0) return fail(h, QSV_E_ARG, "wrt_offsets must be non-decreasing");
         if (count > out_width)
@@ -4589,20 +4643,18 @@ static int gradient_chunks(qsv_t* h, const std::vector<Circuit*>& circs, const G
                            const GradEntry* d_entries, const int64_t* d_offsets, const GradCall& call, const int* plan_id) {
     const size_t n_evals = circs.size();
     int rc;
-    if ((rc = ensure_counted(h, h->d_grad_values, std::max<size_t>(1, T) * sizeof(double)))) return rc;
+    int64_t& allocations = h->grad_stats.n_allocations;
+    if ((rc = ensure_counted(h, h->d_grad_values, std::max<size_t>(1, T) * sizeof(double), allocations))) return rc;
     double* values = static_cast<double*>(h->d_grad_values.ptr);
     // the shifted rows: even width, so that every row starts on 16 bytes (an evaluation takes the first n_params of its row)
     const int width = (std::max(call.base_width, 1) + 1) / 2 * 2;
     const size_t row_bytes = size_t(width) * sizeof(double);
-    if (T > 0 && (rc = ensure_doubling(h, h->d_grad_rows, std::min(T, chunk) * row_bytes, chunk * row_bytes))) return rc;
+    if (T > 0 && (rc = ensure_doubling(h, h->d_grad_rows, std::min(T, chunk) * row_bytes, chunk * row_bytes, allocations))) return rc;
     double* matrix = static_cast<double*>(h->d_grad_rows.ptr);
     BatchArgs args;
     for (size_t t0 = 0; t0 < T; t0 += chunk) {
         const size_t tc = std::min(chunk, T - t0);
-        if (t0 > 0 && h->async_pending) {  // (the chunk before this one may still be reading the rows)
-            QSV_HIP(h, sync_streams(h));
-            h->async_pending = false;
-        }
+        if (t0 > 0 && (rc = wait_pending(h))) return rc;  // (the chunk before this one may still be reading the rows)
         QSV_HIP(h, launch_gradient_expand(call.base, call.base_stride, call.base_width, d_rows + t0, int64_t(tc), matrix, width, h->stream));
         args.circs.resize(tc);
         for (size_t t = 0; t < tc; ++t) args.circs[t] = circs[size_t(host_rows[t0 + t].base_row)];
@@ -4650,7 +4702,7 @@ static int gradient_locked(qsv_t* h, const std::vector<Circuit*>& circs, const i
         h->h_grad_tab_bytes = want;
         h->grad_stats.n_allocations += 1;
     }
-    if ((rc = ensure_doubling(h, h->d_grad_tab, tab_bytes, size_t(-1) / 4))) return rc;
+    if ((rc = ensure_doubling(h, h->d_grad_tab, tab_bytes, size_t(-1) / 4, h->grad_stats.n_allocations))) return rc;
     char* ht = static_cast<char*>(h->h_grad_tab);
     if (rows_bytes) std::memcpy(ht, rows.data(), rows_bytes);
     if (entries_bytes) std::memcpy(ht + rows_bytes, entries.data(), entries_bytes);
@@ -4678,36 +4730,19 @@ int qsv_gradient_describe(int n_ops, const qsv_op* ops, int n_params, int32_t* o
 
 int qsv_gradient_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
                           const int64_t* wrt_offsets, const int32_t* wrt, double* out, int64_t* out_n_shifted) {
-    if (!h) return QSV_E_ARG;
-    if (h->batch_owner.load() == std::this_thread::get_id())
-        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_gradient_circuits goes between batches)");
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_gradient_circuits", kDevice);
     if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets))) return fail(h, QSV_E_ARG, "bad arguments");
     if (out_n_shifted) *out_n_shifted = 0;
     if (n_evals == 0) return QSV_OK;
-    QSV_HIP(h, hipSetDevice(h->device));
     BatchArgs args;
     int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args);
     if (rc) return rc;
     // the base points as one matrix, a row per evaluation; the gradient rows as wide as the longest request
-    int64_t base_width = 1, out_width = 1, total_out = 0;
-    for (int e = 0; e < n_evals; ++e) {
-        base_width = std::max(base_width, args.n_params[size_t(e)]);
-        const int64_t count = wrt_offsets ? wrt_offsets[e + 1] - wrt_offsets[e] : int64_t(args.circs[size_t(e)]->n_params);
-        if (count < 0) return fail(h, QSV_E_ARG, "wrt_offsets must be non-decreasing");
-        out_width = std::max(out_width, count);
-        total_out += count;
-        if (args.n_params[size_t(e)] < args.circs[size_t(e)]->n_params)
-            return fail(h, QSV_E_ARG, "circuit needs " + std::to_string(args.circs[size_t(e)]->n_params) + " parameter values, got " +
-                                          std::to_string(args.n_params[size_t(e)]));
-    }
-    if (total_out > 0 && !out) return fail(h, QSV_E_ARG, "out is null");
-    if (base_width > (1 << 24) || out_width > (1 << 24)) return fail(h, QSV_E_ARG, "too many parameters");
-    std::vector<double> base(size_t(n_evals) * size_t(base_width), 0.0);
-    for (size_t e = 0, cur = 0; e < size_t(n_evals); cur += size_t(args.n_params[e]), ++e)
-        if (args.n_params[e]) std::memcpy(base.data() + e * size_t(base_width), args.values.data() + cur, size_t(args.n_params[e]) * sizeof(double));
-    if ((rc = ensure_counted(h, h->d_grad_base, base.size() * sizeof(double)))) return rc;
-    if ((rc = ensure_counted(h, h->d_grad_out, size_t(n_evals) * size_t(out_width) * sizeof(double)))) return rc;
+    int64_t base_width, out_width;
+    std::vector<double> base;
+    if ((rc = pack_rows(h, args, wrt_offsets, out, false, base_width, out_width, base))) return rc;
+    if ((rc = ensure_counted(h, h->d_grad_base, base.size() * sizeof(double), h->grad_stats.n_allocations))) return rc;
+    if ((rc = ensure_counted(h, h->d_grad_out, size_t(n_evals) * size_t(out_width) * sizeof(double), h->grad_stats.n_allocations))) return rc;
     // (`base` outlives the copy: every path below waits for the stream before it returns)
     QSV_HIP(h, hipMemcpyAsync(h->d_grad_base.ptr, base.data(), base.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     const GradCall call{static_cast<const double*>(h->d_grad_base.ptr), base_width, int(base_width), static_cast<double*>(h->d_grad_out.ptr),
@@ -4721,39 +4756,23 @@ int qsv_gradient_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const i
     QSV_HIP(h, hipMemcpyAsync(rows.data(), h->d_grad_out.ptr, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     QSV_HIP(h, sync_streams(h));
     h->async_pending = false;
-    for (size_t e = 0, cur = 0; e < size_t(n_evals); ++e) {
-        const size_t count = size_t(wrt_offsets ? wrt_offsets[e + 1] - wrt_offsets[e] : int64_t(args.circs[e]->n_params));
-        if (count) std::memcpy(out + cur, rows.data() + e * size_t(out_width), count * sizeof(double));
-        cur += count;
-    }
+    unpack_rows(args, wrt_offsets, rows, out_width, out);
     return QSV_OK;
 }
 
 int qsv_gradient_device(qsv_t* h, int n_evals, const int* circuit_ids, int width, const double* device_values, void* ready_event,
                         const int64_t* wrt_offsets, const int32_t* wrt, int out_width, double* device_out, int64_t* out_n_shifted) {
-    if (!h) return QSV_E_ARG;
-    if (h->batch_owner.load() == std::this_thread::get_id())
-        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_gradient_device goes between batches)");
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_gradient_device", kDevice);
     if (n_evals < 0 || width < 0 || out_width < 0 || (n_evals > 0 && (!circuit_ids || (out_width > 0 && !device_out) || (width > 0 && !device_values))))
         return fail(h, QSV_E_ARG, "bad arguments");
     if (out_n_shifted) *out_n_shifted = 0;
     if (n_evals == 0) return QSV_OK;
-    QSV_HIP(h, hipSetDevice(h->device));
     const void* given[2] = {width > 0 ? device_values : nullptr, out_width > 0 ? device_out : nullptr};
     static const char* const names[2] = {"device_values", "device_out"};
-    for (int i = 0; i < 2; ++i) {  // (a search hands over the same buffers call after call: each is asked about once)
-        if (!given[i] || given[i] == h->grad_checked[i]) continue;
-        hipPointerAttribute_t attr{};
-        if (hipPointerGetAttributes(&attr, given[i]) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != h->device) {
-            (void)hipGetLastError();
-            return fail(h, QSV_E_ARG, std::string(names[i]) + " is not memory of this handle's device");
-        }
-        h->grad_checked[i] = given[i];
-    }
-    BatchArgs args;
-    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, nullptr, nullptr, args);
+    int rc = check_device_pointers(h, given, names, h->grad_checked, 2);
     if (rc) return rc;
+    BatchArgs args;
+    if ((rc = resolve_batch(h, size_t(n_evals), circuit_ids, nullptr, nullptr, args))) return rc;
     if (ready_event) QSV_HIP(h, hipStreamWaitEvent(h->stream, static_cast<hipEvent_t>(ready_event), 0));
     const GradCall call{device_values, int64_t(width), width, device_out, out_width};
     rc = gradient_locked(h, args.circs, circuit_ids, wrt_offsets, wrt, call, out_n_shifted);
@@ -4762,8 +4781,8 @@ int qsv_gradient_device(qsv_t* h, int n_evals, const int* circuit_ids, int width
 }
 
 int qsv_gradient_stats(const qsv_t* h, qsv_gradient_stats_t* out) {
-    if (!h || !out) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    if (!out) return QSV_E_ARG;
+    QSV_OPEN(h, "qsv_gradient_stats", kHostOnly);
     *out = h->grad_stats;
     out->scratch_bytes = int64_t(h->d_grad_tab.bytes + h->d_grad_rows.bytes + h->d_grad_values.bytes + h->d_grad_base.bytes + h->d_grad_out.bytes);
     return QSV_OK;
@@ -4798,11 +4817,6 @@ struct AdjCall {
     double* out_values;
 };
 
-static int ensure_adjoint(qsv_t* h, DeviceBuffer& b, size_t bytes) {
-    if (!(b.bytes >= bytes && b.ptr)) h->adj_stats.n_allocations += 1;
-    return ensure(h, b, bytes);
-}
-
 // What both entry points run with the lock held: the call's tables, the forward run group by group, and behind each group the H
 // application, the runs and the combination on the handle's stream.  Returns without waiting.
 static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, const int64_t* wrt_offsets, const int32_t* wrt,
@@ -4826,8 +4840,7 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
     uint32_t max_gates = 0;
     for (size_t e = 0; e < n_evals; ++e) {
         const Circuit& c = *args.circs[e];
-        if (call.width < c.n_params)
-            return fail(h, QSV_E_ARG, "circuit needs " + std::to_string(c.n_params) + " parameter values, got " + std::to_string(call.width));
+        if (call.width < c.n_params) return too_few_values(h, c.n_params, call.width);
         const int64_t first = wrt_offsets ? wrt_offsets[e] : 0, count = wrt_offsets ? wrt_offsets[e + 1] - first : int64_t(c.n_params);
         if (count < 0) return fail(h, QSV_E_ARG, "wrt_offsets must be non-decreasing");
         if (count > call.out_width)
@@ -4925,10 +4938,11 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
     const size_t gc_max = std::min(G, n_evals);
     const uint64_t dim = uint64_t(1) << h->n;
     const uint32_t blocks = adjoint_blocks(h->n), op_blocks = adjoint_op_blocks(h->n);
-    if ((rc = ensure_adjoint(h, h->d_adj_tab, tab_bytes)) || (rc = ensure_adjoint(h, h->d_adj_lambda, gc_max * dim * h->amp_bytes)) ||
-        (rc = ensure_adjoint(h, h->d_adj_mats, gc_max * std::max<size_t>(1, max_gates) * kAdjointMatDoubles * sizeof(double))) ||
-        (rc = ensure_adjoint(h, h->d_adj_partials, gc_max * 3 * std::max<size_t>(1, max_gates) * blocks * sizeof(double))) ||
-        (rc = ensure_adjoint(h, h->d_adj_epart, gc_max * op_blocks * sizeof(double))))
+    int64_t& allocations = h->adj_stats.n_allocations;
+    if ((rc = ensure_counted(h, h->d_adj_tab, tab_bytes, allocations)) || (rc = ensure_counted(h, h->d_adj_lambda, gc_max * dim * h->amp_bytes, allocations)) ||
+        (rc = ensure_counted(h, h->d_adj_mats, gc_max * std::max<size_t>(1, max_gates) * kAdjointMatDoubles * sizeof(double), allocations)) ||
+        (rc = ensure_counted(h, h->d_adj_partials, gc_max * 3 * std::max<size_t>(1, max_gates) * blocks * sizeof(double), allocations)) ||
+        (rc = ensure_counted(h, h->d_adj_epart, gc_max * op_blocks * sizeof(double), allocations)))
         return rc;
     // (lay_out_states has waited for whatever an earlier call without a wait left running: nothing reads the old tables)
     QSV_HIP(h, hipMemcpy(h->d_adj_tab.ptr, blob.data(), tab_bytes, hipMemcpyHostToDevice));
@@ -4966,40 +4980,21 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
 
 int qsv_adjoint_gradient_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
                                   const int64_t* wrt_offsets, const int32_t* wrt, double* out, double* out_values) {
-    if (!h) return QSV_E_ARG;
-    if (h->batch_owner.load() == std::this_thread::get_id())
-        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_adjoint_gradient_circuits goes between batches)");
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_adjoint_gradient_circuits", kDevice);
     if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets))) return fail(h, QSV_E_ARG, "bad arguments");
     if (n_evals == 0) return QSV_OK;
-    QSV_HIP(h, hipSetDevice(h->device));
     BatchArgs packed;
     int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, packed, "adjoint gradients of a circuit on a kept state are not built");
     if (rc) return rc;
     // the points as one matrix, a row per evaluation (rows of an even number of doubles); the gradient rows as wide as the longest request
-    int64_t width = 2, out_width = 1, total_out = 0;
-    for (int e = 0; e < n_evals; ++e) {
-        width = std::max(width, (packed.n_params[size_t(e)] + 1) / 2 * 2);
-        const int64_t count = wrt_offsets ? wrt_offsets[e + 1] - wrt_offsets[e] : int64_t(packed.circs[size_t(e)]->n_params);
-        if (count < 0) return fail(h, QSV_E_ARG, "wrt_offsets must be non-decreasing");
-        out_width = std::max(out_width, count);
-        total_out += count;
-        if (packed.n_params[size_t(e)] < packed.circs[size_t(e)]->n_params)
-            return fail(h, QSV_E_ARG, "circuit needs " + std::to_string(packed.circs[size_t(e)]->n_params) + " parameter values, got " +
-                                          std::to_string(packed.n_params[size_t(e)]));
-    }
-    if (total_out > 0 && !out) return fail(h, QSV_E_ARG, "out is null");
-    if (width > (1 << 24) || out_width > (1 << 24)) return fail(h, QSV_E_ARG, "too many parameters");
-    std::vector<double> base(size_t(n_evals) * size_t(width), 0.0);
-    for (size_t e = 0, cur = 0; e < size_t(n_evals); cur += size_t(packed.n_params[e]), ++e)
-        if (packed.n_params[e]) std::memcpy(base.data() + e * size_t(width), packed.values.data() + cur, size_t(packed.n_params[e]) * sizeof(double));
-    if (h->async_pending) {  // (the buffers below may still be read or written by a call that did not wait)
-        QSV_HIP(h, sync_streams(h));
-        h->async_pending = false;
-    }
-    if ((rc = ensure_adjoint(h, h->d_adj_base, base.size() * sizeof(double))) ||
-        (rc = ensure_adjoint(h, h->d_adj_out, size_t(n_evals) * size_t(out_width) * sizeof(double))) ||
-        (rc = ensure_adjoint(h, h->d_adj_values, size_t(n_evals) * sizeof(double))))
+    int64_t width, out_width;
+    std::vector<double> base;
+    if ((rc = pack_rows(h, packed, wrt_offsets, out, true, width, out_width, base))) return rc;
+    if ((rc = wait_pending(h))) return rc;  // (the buffers below may still be read or written by a call that did not wait)
+    int64_t& allocations = h->adj_stats.n_allocations;
+    if ((rc = ensure_counted(h, h->d_adj_base, base.size() * sizeof(double), allocations)) ||
+        (rc = ensure_counted(h, h->d_adj_out, size_t(n_evals) * size_t(out_width) * sizeof(double), allocations)) ||
+        (rc = ensure_counted(h, h->d_adj_values, size_t(n_evals) * sizeof(double), allocations)))
         return rc;
     QSV_HIP(h, hipMemcpy(h->d_adj_base.ptr, base.data(), base.size() * sizeof(double), hipMemcpyHostToDevice));
     BatchArgs args;
@@ -5019,39 +5014,23 @@ int qsv_adjoint_gradient_circuits(qsv_t* h, int n_evals, const int* circuit_ids,
     QSV_HIP(h, hipMemcpyAsync(values.data(), h->d_adj_values.ptr, values.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     QSV_HIP(h, sync_streams(h));
     h->async_pending = false;
-    for (size_t e = 0, cur = 0; e < size_t(n_evals); ++e) {
-        const size_t count = size_t(wrt_offsets ? wrt_offsets[e + 1] - wrt_offsets[e] : int64_t(packed.circs[e]->n_params));
-        if (count) std::memcpy(out + cur, rows.data() + e * size_t(out_width), count * sizeof(double));
-        cur += count;
-    }
+    unpack_rows(packed, wrt_offsets, rows, out_width, out);
     if (out_values) std::memcpy(out_values, values.data(), values.size() * sizeof(double));
     return QSV_OK;
 }
 
 int qsv_adjoint_gradient_device(qsv_t* h, int n_evals, const int* circuit_ids, int width, const double* device_values, void* ready_event,
                                 const int64_t* wrt_offsets, const int32_t* wrt, int out_width, double* device_out, double* device_out_values) {
-    if (!h) return QSV_E_ARG;
-    if (h->batch_owner.load() == std::this_thread::get_id())
-        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_adjoint_gradient_device goes between batches)");
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_adjoint_gradient_device", kDevice);
     if (n_evals < 0 || width < 0 || out_width < 0 || (n_evals > 0 && (!circuit_ids || (out_width > 0 && !device_out) || (width > 0 && !device_values))))
         return fail(h, QSV_E_ARG, "bad arguments");
     if (n_evals == 0) return QSV_OK;
-    QSV_HIP(h, hipSetDevice(h->device));
     const void* given[3] = {width > 0 ? device_values : nullptr, out_width > 0 ? device_out : nullptr, device_out_values};
     static const char* const names[3] = {"device_values", "device_out", "device_out_values"};
-    for (int i = 0; i < 3; ++i) {  // (a search hands over the same buffers call after call: each is asked about once)
-        if (!given[i] || given[i] == h->adj_checked[i]) continue;
-        hipPointerAttribute_t attr{};
-        if (hipPointerGetAttributes(&attr, given[i]) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != h->device) {
-            (void)hipGetLastError();
-            return fail(h, QSV_E_ARG, std::string(names[i]) + " is not memory of this handle's device");
-        }
-        h->adj_checked[i] = given[i];
-    }
-    BatchArgs args;
-    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, nullptr, nullptr, args, "adjoint gradients of a circuit on a kept state are not built");
+    int rc = check_device_pointers(h, given, names, h->adj_checked, 3);
     if (rc) return rc;
+    BatchArgs args;
+    if ((rc = resolve_batch(h, size_t(n_evals), circuit_ids, nullptr, nullptr, args, "adjoint gradients of a circuit on a kept state are not built"))) return rc;
     args.n_params.assign(size_t(n_evals), int64_t(width));
     args.device_values = width > 0 ? device_values : nullptr;
     if (ready_event) QSV_HIP(h, hipStreamWaitEvent(h->stream, static_cast<hipEvent_t>(ready_event), 0));
@@ -5065,8 +5044,8 @@ int qsv_adjoint_gradient_device(qsv_t* h, int n_evals, const int* circuit_ids, i
 }
 
 int qsv_adjoint_stats(const qsv_t* h, qsv_adjoint_stats_t* out) {
-    if (!h || !out) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    if (!out) return QSV_E_ARG;
+    QSV_OPEN(h, "qsv_adjoint_stats", kHostOnly);
     *out = h->adj_stats;
     out->scratch_bytes = int64_t(h->d_adj_lambda.bytes + h->d_adj_tab.bytes + h->d_adj_mats.bytes + h->d_adj_partials.bytes + h->d_adj_epart.bytes +
                                  h->d_adj_base.bytes + h->d_adj_out.bytes + h->d_adj_values.bytes);
@@ -5077,24 +5056,16 @@ int qsv_adjoint_stats(const qsv_t* h, qsv_adjoint_stats_t* out) {
 
 int qsv_variance_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
                           double* out_variances, double* out_values) {
-    if (!h) return QSV_E_ARG;
-    if (h->batch_owner.load() == std::this_thread::get_id())
-        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_variance_circuits goes between batches)");
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_variance_circuits", kDevice);
     if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets || !out_variances))) return fail(h, QSV_E_ARG, "bad arguments");
     if (n_evals == 0) return QSV_OK;
     if (h->n_terms == 0) return fail(h, QSV_E_STATE, "no operator set (call qsv_set_operator first)");
     if (h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "the variance is available up to 28 qubits");
-    QSV_HIP(h, hipSetDevice(h->device));
     BatchArgs args;
     int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args,
                            "the variance of a circuit on a kept state is not built");
     if (rc) return rc;
-    if (h->async_pending) {  // (the buffers below may still be read or written by a call that did not wait)
-        QSV_HIP(h, sync_streams(h));
-        h->async_pending = false;
-    }
-    // ordinary plans into state slots, never split: the whole state is needed (as qsv_prefix_create runs them)
+    if ((rc = wait_pending(h))) return rc;  // (the buffers below may still be read or written by a call that did not wait)
     const size_t n = size_t(n_evals);
     const size_t G = std::max<size_t>(1, std::min(size_t(h->group), size_t(h->max_grid_y)));
     const uint32_t blocks = moments_blocks(h->n);
@@ -5103,61 +5074,29 @@ int qsv_variance_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const i
     if ((rc = ensure(h, h->d_moments, out_bytes + std::min(G, n) * blocks * 2 * sizeof(double))) || (rc = ensure_host_out(h, 2 * n))) return rc;
     double* const pairs = static_cast<double*>(h->d_moments.ptr);
     double* const partials = reinterpret_cast<double*>(static_cast<char*>(h->d_moments.ptr) + out_bytes);
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> timed;  // (option "time_moments": the two kernels of every launch group)
-    struct DestroyEvents {
-        std::vector<std::pair<hipEvent_t, hipEvent_t>>& list;
-        ~DestroyEvents() {
-            for (auto& p : list) {
-                if (p.first) (void)hipEventDestroy(p.first);
-                if (p.second) (void)hipEventDestroy(p.second);
-            }
-        }
-    } destroy_events{timed};
     auto moments = [&](size_t g0, size_t gc) -> int {
-        if (h->time_moments) {
-            timed.emplace_back(nullptr, nullptr);
-            QSV_HIP(h, hipEventCreate(&timed.back().first));
-            QSV_HIP(h, hipEventCreate(&timed.back().second));
-            QSV_HIP(h, hipEventRecord(timed.back().first, h->stream));
-        }
         QSV_HIP(h, launch_operator_moments(h->dtype, h->d_states.ptr, h->n, int(gc),
                                            h->has_diag_part ? static_cast<const double*>(h->d_diag.ptr) : nullptr, h->n_groups,
                                            static_cast<const PauliGroup*>(h->d_groups.ptr), static_cast<const uint64_t*>(h->d_z.ptr),
                                            static_cast<const double*>(h->d_cre.ptr), static_cast<const uint32_t*>(h->d_term_odd.ptr),
                                            partials, h->stream));
         QSV_HIP(h, launch_moments_combine(partials, blocks, int(gc), pairs + 2 * g0, h->stream));
-        if (h->time_moments) QSV_HIP(h, hipEventRecord(timed.back().second, h->stream));
         return QSV_OK;
     };
-    rc = run_to_states(h, args, StateRun{SplitRule{}, 1, G, false, 0, kModeSynthFirst | kModeFinalStore}, {}, moments);
-    if (rc) {  // nothing of a failed call may still be running
-        (void)sync_streams(h);
-        return rc;
-    }
-    QSV_HIP(h, hipMemcpyAsync(h->h_out, pairs, n * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    QSV_HIP(h, sync_streams(h));
+    if ((rc = run_whole_states(h, args, G, moments, pairs, 2 * n))) return rc;
     for (size_t j = 0; j < n; ++j) {
         const size_t e = h->batch.eval_at[j];
         if (out_values) out_values[e] = h->h_out[2 * j];
         out_variances[e] = h->h_out[2 * j + 1];
-    }
-    for (const auto& p : timed) {
-        float ms = 0.0f;
-        QSV_HIP(h, hipEventElapsedTime(&ms, p.first, p.second));
-        h->prof.expect_ms += double(ms);
     }
     return QSV_OK;
 }
 
 int qsv_gradient_plan_create(qsv_t* h, int n_evals, const int* circuit_ids, int width, const int64_t* wrt_offsets, const int32_t* wrt,
                              int out_width, int* out_plan_id, int64_t* out_n_shifted) {
-    if (!h) return QSV_E_ARG;
-    if (h->batch_owner.load() == std::this_thread::get_id())
-        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_gradient_plan_create goes between batches)");
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_gradient_plan_create", kDevice);
     if (n_evals < 0 || width < 0 || out_width < 0 || !out_plan_id || (n_evals > 0 && !circuit_ids)) return fail(h, QSV_E_ARG, "bad arguments");
     if (out_n_shifted) *out_n_shifted = 0;
-    QSV_HIP(h, hipSetDevice(h->device));
     BatchArgs args;
     int rc = resolve_batch(h, size_t(n_evals), circuit_ids, nullptr, nullptr, args);
     if (rc) return rc;
@@ -5197,32 +5136,20 @@ int qsv_gradient_plan_create(qsv_t* h, int n_evals, const int* circuit_ids, int 
 }
 
 int qsv_gradient_plan_run(qsv_t* h, int plan_id, const double* device_values, void* ready_event, double* device_out) {
-    if (!h) return QSV_E_ARG;
-    if (h->batch_owner.load() == std::this_thread::get_id())
-        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_gradient_plan_run goes between batches)");
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_gradient_plan_run", kDevice);
     const auto it = h->grad_plans.find(plan_id);
     if (it == h->grad_plans.end()) return fail(h, QSV_E_ARG, "unknown gradient plan " + std::to_string(plan_id));
     qsv_handle::GradientPlan& plan = it->second;
     const size_t n_evals = plan.ids.size();
     if (n_evals > 0 && ((plan.out_width > 0 && !device_out) || (plan.width > 0 && !device_values))) return fail(h, QSV_E_ARG, "bad arguments");
     if (n_evals == 0) return QSV_OK;
-    QSV_HIP(h, hipSetDevice(h->device));
     const void* given[2] = {plan.width > 0 ? device_values : nullptr, plan.out_width > 0 ? device_out : nullptr};
     static const char* const names[2] = {"device_values", "device_out"};
-    for (int i = 0; i < 2; ++i) {  // (as qsv_gradient_device: each buffer is asked about once)
-        if (!given[i] || given[i] == h->grad_checked[i]) continue;
-        hipPointerAttribute_t attr{};
-        if (hipPointerGetAttributes(&attr, given[i]) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != h->device) {
-            (void)hipGetLastError();
-            return fail(h, QSV_E_ARG, std::string(names[i]) + " is not memory of this handle's device");
-        }
-        h->grad_checked[i] = given[i];
-    }
+    int rc = check_device_pointers(h, given, names, h->grad_checked, 2);  // (the cache of qsv_gradient_device)
+    if (rc) return rc;
     if (h->n_terms == 0) return fail(h, QSV_E_STATE, "no operator set (call qsv_set_operator first)");
     BatchArgs args;
-    int rc = resolve_batch(h, n_evals, plan.ids.data(), nullptr, nullptr, args);
-    if (rc) return rc;
+    if ((rc = resolve_batch(h, n_evals, plan.ids.data(), nullptr, nullptr, args))) return rc;
     const uint64_t waits_before = h->host_waits;
     if (ready_event) QSV_HIP(h, hipStreamWaitEvent(h->stream, static_cast<hipEvent_t>(ready_event), 0));
     const size_t T = plan.rows.size();
@@ -5243,13 +5170,9 @@ int qsv_gradient_plan_run(qsv_t* h, int plan_id, const double* device_values, vo
 }
 
 int qsv_gradient_plan_destroy(qsv_t* h, int plan_id) {
-    if (!h) return QSV_E_ARG;
-    if (h->batch_owner.load() == std::this_thread::get_id())
-        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_gradient_plan_destroy goes between batches)");
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_gradient_plan_destroy", kDevice);
     const auto it = h->grad_plans.find(plan_id);
     if (it == h->grad_plans.end()) return fail(h, QSV_E_ARG, "unknown gradient plan " + std::to_string(plan_id));
-    QSV_HIP(h, hipSetDevice(h->device));
     QSV_HIP(h, sync_streams(h));  // (a run's kernels may still read the tables)
     h->async_pending = false;
     if (h->plan_snap.plan_id == plan_id) h->plan_snap.epoch = 0;
@@ -5259,8 +5182,8 @@ int qsv_gradient_plan_destroy(qsv_t* h, int plan_id) {
 }
 
 int qsv_gradient_plan_stats(const qsv_t* h, int plan_id, qsv_gradient_plan_stats_t* out) {
-    if (!h || !out) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    if (!out) return QSV_E_ARG;
+    QSV_OPEN(h, "qsv_gradient_plan_stats", kHostOnly);
     const auto it = h->grad_plans.find(plan_id);
     if (it == h->grad_plans.end()) return QSV_E_ARG;
     *out = it->second.stats;
@@ -5269,9 +5192,8 @@ int qsv_gradient_plan_stats(const qsv_t* h, int plan_id, qsv_gradient_plan_stats
 
 int qsv_observables_create(qsv_t* h, int n_observables, const int64_t* term_offsets, const uint64_t* x_mask, const uint64_t* z_mask,
                            const double* coeff_re, const double* coeff_im, int* out_set_id) {
-    if (!h) return QSV_E_ARG;
     (void)coeff_im;  // <P_k> is real for every Pauli string: real(<O_m>) only needs the real parts (as qsv_set_operator)
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_observables_create", kDevice);
     if (n_observables < 1 || uint32_t(n_observables) > kMaxObservables || !term_offsets || !out_set_id)
         return fail(h, QSV_E_ARG, "an observable set needs 1 .. 65536 observables, their term offsets and an output");
     const int64_t first = term_offsets[0], n_entries = term_offsets[n_observables] - first;
@@ -5317,7 +5239,6 @@ int qsv_observables_create(qsv_t* h, int n_observables, const int64_t* term_offs
         term_of[size_t(k)] = uint32_t(at - strings.begin());
         coef[size_t(k)] = coeff_re[first + k];
     }
-    QSV_HIP(h, hipSetDevice(h->device));
     ObservableSet s;
     s.n_obs = uint32_t(n_observables);
     s.n_terms = T;
@@ -5378,11 +5299,9 @@ int qsv_observables_create(qsv_t* h, int n_observables, const int64_t* term_offs
 }
 
 int qsv_observables_destroy(qsv_t* h, int set_id) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_observables_destroy", kDevice);
     auto it = h->obs_sets.find(set_id);
     if (it == h->obs_sets.end()) return fail(h, QSV_E_ARG, "unknown observable set " + std::to_string(set_id));
-    QSV_HIP(h, hipSetDevice(h->device));
     QSV_HIP(h, sync_streams(h));
     free_observable_set(it->second);
     h->obs_sets.erase(it);
@@ -5391,15 +5310,13 @@ int qsv_observables_destroy(qsv_t* h, int set_id) {
 
 int qsv_eval_observables(qsv_t* h, int set_id, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
                          double* out) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_eval_observables", kDevice);
     if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets || !out))) return fail(h, QSV_E_ARG, "bad arguments");
     auto set = h->obs_sets.find(set_id);
     if (set == h->obs_sets.end()) return fail(h, QSV_E_ARG, "unknown observable set " + std::to_string(set_id));
     BatchArgs args;
     int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args);
     if (rc || n_evals == 0) return rc;
-    QSV_HIP(h, hipSetDevice(h->device));
     return eval_observables_locked(h, set->second, args, out);
 }
 
@@ -5407,10 +5324,7 @@ int qsv_eval_observables(qsv_t* h, int set_id, int n_evals, const int* circuit_i
 
 int qsv_observables_covariance(qsv_t* h, int set_id, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
                                double* out_values, double* out_cov) {
-    if (!h) return QSV_E_ARG;
-    if (h->batch_owner.load() == std::this_thread::get_id())
-        return fail(h, QSV_E_STATE, "a batch is open on this handle (qsv_observables_covariance goes between batches)");
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_observables_covariance", kDevice);
     if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets || !out_cov))) return fail(h, QSV_E_ARG, "bad arguments");
     const auto found = h->obs_sets.find(set_id);
     if (found == h->obs_sets.end()) return fail(h, QSV_E_ARG, "unknown observable set " + std::to_string(set_id));
@@ -5418,17 +5332,12 @@ int qsv_observables_covariance(qsv_t* h, int set_id, int n_evals, const int* cir
     if (set.n_obs > kCovMaxObservables) return fail(h, QSV_E_UNSUPPORTED, "covariances are available for sets of up to 64 observables");
     if (n_evals == 0) return QSV_OK;
     if (h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "covariances are available up to 28 qubits");
-    QSV_HIP(h, hipSetDevice(h->device));
     BatchArgs args;
     int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args,
                            "the covariances of a circuit on a kept state are not built");
     if (rc) return rc;
-    if (h->async_pending) {  // (the buffers below may still be read or written by a call that did not wait)
-        QSV_HIP(h, sync_streams(h));
-        h->async_pending = false;
-    }
-    // ordinary plans into state slots, never split, as qsv_variance_circuits runs them; a launch group's partials stay within
-    // the scratch limit of qsv_eval_observables
+    if ((rc = wait_pending(h))) return rc;  // (the buffers below may still be read or written by a call that did not wait)
+    // (a launch group's partials stay within the scratch limit of qsv_eval_observables)
     const size_t n = size_t(n_evals), M = set.n_obs;
     const size_t per_eval = size_t(covariance_pairs(set.n_obs)) * covariance_blocks(h->n, set.n_obs) * kCovPartial * sizeof(double);
     const size_t G = std::max<size_t>(1, std::min({size_t(h->group), size_t(h->max_grid_y), size_t(65535), kObsScratchBytes / per_eval}));
@@ -5438,57 +5347,27 @@ int qsv_observables_covariance(qsv_t* h, int set_id, int n_evals, const int* cir
     double* const values = static_cast<double*>(h->d_cov.ptr);
     double* const cov = values + n * M;
     double* const partials = reinterpret_cast<double*>(static_cast<char*>(h->d_cov.ptr) + out_bytes);
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> timed;  // (option "time_moments": the two kernels of every launch group)
-    struct DestroyEvents {
-        std::vector<std::pair<hipEvent_t, hipEvent_t>>& list;
-        ~DestroyEvents() {
-            for (auto& p : list) {
-                if (p.first) (void)hipEventDestroy(p.first);
-                if (p.second) (void)hipEventDestroy(p.second);
-            }
-        }
-    } destroy_events{timed};
     auto moments = [&](size_t g0, size_t gc) -> int {
-        if (h->time_moments) {
-            timed.emplace_back(nullptr, nullptr);
-            QSV_HIP(h, hipEventCreate(&timed.back().first));
-            QSV_HIP(h, hipEventCreate(&timed.back().second));
-            QSV_HIP(h, hipEventRecord(timed.back().first, h->stream));
-        }
         QSV_HIP(h, launch_covariance_panels(h->dtype, h->d_states.ptr, h->n, int(gc), set.n_obs, static_cast<const uint32_t*>(set.d_cov_first.ptr),
                                             static_cast<const PauliGroup*>(set.d_cov_groups.ptr),
                                             static_cast<const CovTerm*>(set.d_cov_terms.ptr), partials, h->stream));
         QSV_HIP(h, launch_covariance_combine(partials, h->n, int(gc), set.n_obs, values + g0 * M, cov + g0 * M * M, h->stream));
-        if (h->time_moments) QSV_HIP(h, hipEventRecord(timed.back().second, h->stream));
         return QSV_OK;
     };
-    rc = run_to_states(h, args, StateRun{SplitRule{}, 1, G, false, 0, kModeSynthFirst | kModeFinalStore}, {}, moments);
-    if (rc) {  // nothing of a failed call may still be running
-        (void)sync_streams(h);
-        return rc;
-    }
-    QSV_HIP(h, hipMemcpyAsync(h->h_out, values, out_count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    QSV_HIP(h, sync_streams(h));
+    if ((rc = run_whole_states(h, args, G, moments, values, out_count))) return rc;
     const double* const h_cov = h->h_out + n * M;
     for (size_t j = 0; j < n; ++j) {
         const size_t e = h->batch.eval_at[j];
         if (out_values) std::copy(h->h_out + j * M, h->h_out + (j + 1) * M, out_values + e * M);
         std::copy(h_cov + j * M * M, h_cov + (j + 1) * M * M, out_cov + e * M * M);
     }
-    for (const auto& p : timed) {
-        float ms = 0.0f;
-        QSV_HIP(h, hipEventElapsedTime(&ms, p.first, p.second));
-        h->prof.expect_ms += double(ms);
-    }
     return QSV_OK;
 }
 
 int qsv_sample(qsv_t* h, int circuit_id, const double* params, int n_params, int shots, uint64_t seed,
                uint64_t* out_states) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_sample", kDevice);
     if (shots < 0 || n_params < 0 || (shots > 0 && !out_states)) return fail(h, QSV_E_ARG, "bad arguments");
-    QSV_HIP(h, hipSetDevice(h->device));
     const int64_t offsets[2] = {0, n_params};
     BatchArgs args;
     int rc = resolve_batch(h, 1, &circuit_id, offsets, params, args, shots ? kNotSampled : nullptr);
@@ -5524,7 +5403,7 @@ int qsv_fitness_table_wait(const volatile uint64_t* own, int count, volatile int
 int qsv_set_option(qsv_t* h, const char* name, int value) {
     if (!h) return QSV_E_ARG;
     if (!name) return fail(h, QSV_E_ARG, "option name is null");
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_set_option", kHostOnly);
     h->epoch += 1;
     const std::string key(name);
     if (key == "split") {
@@ -5588,8 +5467,7 @@ int qsv_set_option(qsv_t* h, const char* name, int value) {
 }
 
 int qsv_set_profiling(qsv_t* h, int enabled) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_set_profiling", kHostOnly);
     h->epoch += 1;
     h->profiling = enabled != 0;
     return QSV_OK;
@@ -5609,14 +5487,13 @@ int qsv_live_entries(int n_keys, unsigned key_mask, int* out_pi) {
 }
 
 long long qsv_replayed_pushes(const qsv_t* h) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_replayed_pushes", kHostOnly);
     return (long long)h->replayed_pushes;
 }
 
 int qsv_get_profile(const qsv_t* h, qsv_profile* out) {
-    if (!h || !out) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    if (!out) return QSV_E_ARG;
+    QSV_OPEN(h, "qsv_get_profile", kHostOnly);
     *out = h->prof;
     return QSV_OK;
 }
@@ -5624,7 +5501,6 @@ int qsv_get_profile(const qsv_t* h, qsv_profile* out) {
 static int bench_ops_locked(qsv_t* h, int n_ops, const qsv_op* ops, int reps, double* out_ms_per_rep,
                             int* out_n_passes) {
     if (!out_ms_per_rep || reps < 1) return fail(h, QSV_E_ARG, "bad arguments");
-    QSV_HIP(h, hipSetDevice(h->device));
     int id = 0;
     // no folding: the gates must really be applied to the resident state
     int rc = register_circuit(h, n_ops, ops, 0, &id, /*fold=*/false);
@@ -5678,8 +5554,7 @@ static int bench_ops_locked(qsv_t* h, int n_ops, const qsv_op* ops, int reps, do
 }
 
 int qsv_bench_ops(qsv_t* h, int n_ops, const qsv_op* ops, int reps, double* out_ms_per_rep, int* out_n_passes) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_bench_ops", kDevice);
     for (int i = 0; i < n_ops; ++i)
         if (ops && ops[i].kind != QSV_OP_ID && (ops[i].p_theta >= 0 || ops[i].p_phi >= 0 || ops[i].p_lambda >= 0))
             return fail(h, QSV_E_ARG, "qsv_bench_ops needs bound (literal) angles");
@@ -5688,8 +5563,7 @@ int qsv_bench_ops(qsv_t* h, int n_ops, const qsv_op* ops, int reps, double* out_
 
 int qsv_bench_gate(qsv_t* h, int target, int control, double theta, double phi, double lambda, int reps,
                    double* out_ms_per_sweep) {
-    if (!h) return QSV_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
+    QSV_OPEN(h, "qsv_bench_gate", kDevice);
     if (target < 0 || target >= h->n || control >= h->n) return fail(h, QSV_E_ARG, "qubit out of range");
     qsv_op op{};
     op.kind = control >= 0 ? QSV_OP_CU3 : QSV_OP_U;
