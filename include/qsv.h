@@ -774,6 +774,34 @@ int qsv_observables_covariance(qsv_t* h, int set_id, int n_evals, const int* cir
                                const double* params, double* out_values /* n_evals*M, may be NULL */,
                                double* out_cov /* n_evals*M*M */);
 
+/* ---- two states at a time -------------------------------------------------------------------------- */
+
+/*
+ * OVERLAPS: the final states psi_e of n_evals (circuit, parameter vector) pairs, laid out as in
+ * qsv_eval_circuits, against n_states kept states phi_k (qsv_prefix_create), named by prefix_ids in any order, repeats allowed:
+ *     out_overlaps[(e * n_states + k) * 2 + {0, 1}] = S_ek = <phi_k|psi_e> = sum_i conj(phi_k[i]) psi_e[i]   (re, im)
+ *     out_elements[(e * n_states + k) * 2 + {0, 1}] = T_ek = <phi_k|H_h|psi_e>                               (with_operator != 0)
+ * with H_h the Hermitian part qsv_set_operator keeps; out_elements is required iff with_operator is set and not looked at
+ * otherwise, and the handle's operator is read only then.  The call runs as qsv_variance_circuits runs: ordinary plans into state
+ * slots (no split route), then on the handle's stream one kernel per launch group that takes 64 amplitudes of 16 kept states and
+ * 16 evaluations at a time, forms (H_h psi_e)(i) for them where asked, and accumulates the 16 x 16 complex tiles on the fp64
+ * matrix pipe, and one that adds the workgroups' partial tiles in ascending order.  Nothing state-sized is written and the
+ * kept-state buffer is only read; the scratch is allocated on first need and grown by need, and a launch group is made smaller
+ * where its partial tiles would pass 64 MiB.  The numbers are RAW: no division by norms.  Contract: an evaluation's row is the
+ * same bits in any batch, at any position of a launch group and on every call, and a kept state's column the same bits at any
+ * position of prefix_ids -- a repeated id gives two identical columns (fixed-order sums, no floating-point atomics).  The call
+ * lays a batch out as every batch call does, so a recorded batch is dropped and laid out again by the next qsv_eval_* call, which
+ * returns the bits it returned before.  Goes between batches.
+ * Errors: out_overlaps NULL, out_elements NULL where with_operator is set, prefix_ids NULL, n_states < 1 (or other bad arguments)
+ * QSV_E_ARG; an unknown or released kept state QSV_E_ARG; n_states > QSV_OVERLAP_MAX_STATES QSV_E_UNSUPPORTED; more than 28 qubits
+ * QSV_E_UNSUPPORTED; an evaluated circuit on a kept state QSV_E_UNSUPPORTED; with_operator and no operator set QSV_E_STATE;
+ * n_evals == 0 QSV_OK.
+ */
+#define QSV_OVERLAP_MAX_STATES 64
+int qsv_overlap_circuits(qsv_t* h, int n_states, const int* prefix_ids, int with_operator, int n_evals, const int* circuit_ids,
+                         const int64_t* param_offsets, const double* params, double* out_overlaps /* [n_evals][n_states][2] */,
+                         double* out_elements /* the same shape; required iff with_operator */);
+
 /* ---- sharded populations on one node ------------------------------------------------------------- */
 
 /*

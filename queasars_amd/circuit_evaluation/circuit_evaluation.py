@@ -1280,6 +1280,49 @@ class StatevectorDevice:
             self._handle, set_id, n, _lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat), _lib.as_ptr(values), _lib.as_ptr(covariances)))
         return values, covariances
 
+    # -- two states at a time -----------------------------------------------------------------------
+    MAX_OVERLAP_STATES = 64  # (QSV_OVERLAP_MAX_STATES)
+
+    def overlaps(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]], kept_states: Sequence[KeptState],
+                 with_operator: bool = False):
+        """``S[i, k] = <phi_k|psi_i>`` of every (circuit, parameter vector) pair's final state psi_i against every kept state
+        phi_k (:meth:`keep_states`): a complex128 ``(n, K)`` array, reduced on the device from the states where they are
+        (``qsv_overlap_circuits``).  With ``with_operator`` the pair ``(S, T)``, ``T[i, k] = <phi_k|H|psi_i>``
+        for the Hermitian part of the operator set on the device.  Raw numbers: nothing is divided by a norm.  Deterministic: a
+        row depends on its circuit and point alone, a column on its kept state alone.  More than
+        :attr:`MAX_OVERLAP_STATES` kept states are served in blocks of that many, one library call each.  A kept state of
+        another device, or a released one, and a circuit that itself continues a kept state raise ``ValueError``."""
+        n = len(circuits)
+        if len(parameter_values) != n:
+            raise ValueError("circuits and parameter_values must have the same length")
+        kept_states = list(kept_states)
+        if not kept_states:
+            raise ValueError("at least one kept state is needed")
+        for kept in kept_states:
+            if not isinstance(kept, KeptState):
+                raise ValueError("kept_states must hold KeptState objects (StatevectorDevice.keep_states)")
+            if kept._serial != self._serial or kept._id < 0:
+                raise ValueError("a kept state is not kept on this device (or was released)")
+        if any(c._kept_state is not None for c in circuits):
+            raise ValueError("the overlaps of a circuit that itself continues a kept state are not supported")
+        k_all = len(kept_states)
+        overlaps = np.zeros((n, k_all), dtype=np.complex128)
+        elements = np.zeros((n, k_all), dtype=np.complex128) if with_operator else None
+        if n > 0:
+            ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
+            for k0 in range(0, k_all, self.MAX_OVERLAP_STATES):
+                block = np.asarray([kept._id for kept in kept_states[k0:k0 + self.MAX_OVERLAP_STATES]], dtype=np.int32)
+                s = np.zeros((n, len(block)), dtype=np.complex128)
+                t = np.zeros((n, len(block)), dtype=np.complex128) if with_operator else None
+                # (a refusal with QSV_E_UNSUPPORTED as a ValueError with the library's message)
+                self._check_gradient(self._lib.qsv_overlap_circuits(
+                    self._handle, len(block), _lib.as_ptr(block), int(bool(with_operator)), n, _lib.as_ptr(ids), _lib.as_ptr(offsets),
+                    _lib.as_ptr(flat), _lib.as_ptr(s), _lib.as_ptr(t) if with_operator else None))
+                overlaps[:, k0:k0 + len(block)] = s
+                if with_operator:
+                    elements[:, k0:k0 + len(block)] = t
+        return (overlaps, elements) if with_operator else overlaps
+
     # -- measurement support ----------------------------------------------------------------------
     def set_option(self, name: str, value: int) -> None:
         """Switches of the handle (``qsv_set_option``): "split", "factor", "split_sampling" (0 / 1), "streams" (1 .. 4),
@@ -1638,6 +1681,46 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         circuits = self._composed_list(circuits)
         values, covariances = self._device.observable_covariances(circuits, parameter_values, operators)
         return (values, covariances) if with_values else covariances
+
+    def evaluate_overlaps(self, circuits: list[CircuitIR], parameter_values: list[list[float]], kept_states: Sequence[KeptState],
+                          with_operator: bool = False):
+        """``S[i, k] = <phi_k|psi_i>`` of every circuit's final state (behind this evaluator's initial state) against the kept
+        states (:meth:`keep_states`), a complex128 ``(n, K)`` array (:meth:`StatevectorDevice.overlaps`); with
+        ``with_operator`` the pair ``(S, T)``, ``T[i, k] = <phi_k|H|psi_i>`` for the evaluator's operator.  Exact numbers:
+        ``estimator_precision`` adds no noise here, and no random number is drawn."""
+        if len(parameter_values) != len(circuits):
+            raise ValueError("circuits and parameter_values must have the same length")
+        circuits = self._composed_list(circuits)
+        if not with_operator:
+            return self._device.overlaps(circuits, parameter_values, kept_states)
+        with self._device.operator_lock:
+            if self._device._operator is not self._operator:
+                self._device.set_operator(self._operator)
+            return self._device.overlaps(circuits, parameter_values, kept_states, with_operator=True)
+
+    def evaluate_subspace_matrices(self, circuits: list[CircuitIR], parameter_values: list[list[float]]):
+        """``(S, H)`` of the circuits' final states among themselves: ``S[i, j] = <psi_i|psi_j>`` and ``H[i, j] =
+        <psi_i|H|psi_j>`` for the evaluator's operator, two complex128 ``(n, n)`` arrays -- what a subspace diagonalisation of
+        the states needs (``evqe.subspace.lowest_subspace_eigenvalue``).  The states are kept with :meth:`keep_states` in blocks
+        of 64, the whole batch is evaluated against each block, and the block is released.  Raw numbers: the matrices are
+        Hermitian to rounding only and are not symmetrised.  Exact, as :meth:`evaluate_overlaps`."""
+        n = len(circuits)
+        if len(parameter_values) != n:
+            raise ValueError("circuits and parameter_values must have the same length")
+        s = np.zeros((n, n), dtype=np.complex128)
+        h = np.zeros((n, n), dtype=np.complex128)
+        block = StatevectorDevice.MAX_OVERLAP_STATES
+        for k0 in range(0, n, block):
+            kept = self.keep_states(circuits[k0:k0 + block], parameter_values[k0:k0 + block])
+            try:
+                # S[j, k] = <phi_k|psi_j>: column k belongs to the kept state, so row i of the result is kept state i
+                s_block, t_block = self.evaluate_overlaps(circuits, parameter_values, kept, with_operator=True)
+            finally:
+                for state in kept:
+                    state.release()
+            s[k0:k0 + len(kept), :] = s_block.T
+            h[k0:k0 + len(kept), :] = t_block.T
+        return s, h
 
     def _evaluate_device_matrix(self, circuits, matrix, ready: bool = False, out_device_pointer: int = 0, as_list: bool = False):
         pointer, width, event, remember = _device_matrix_arguments(self, circuits, matrix, ready)

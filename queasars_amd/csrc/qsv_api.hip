@@ -21,6 +21,7 @@
 #include "adjoint.hpp"
 #include "moments.hpp"
 #include "covariance.hpp"
+#include "overlap.hpp"
 #include "gradient.hpp"
 #include "value_cache.hpp"
 #include "kernels.hpp"
@@ -494,6 +495,9 @@ struct qsv_handle {
     // an observable set's second moments (qsv_observables_covariance; covariance.hpp): the call's values | covariances by position |
     // one launch group's partials
     DeviceBuffer d_cov;
+    // overlaps against kept states (qsv_overlap_circuits; overlap.hpp): the call's S by position | its T by position | one launch
+    // group's partial tiles
+    DeviceBuffer d_overlap;
     bool time_moments = false;  // option "time_moments": the device time of the two kernels goes to prof.expect_ms
     uint64_t host_waits = 0;  // times the host waited for a stream or an event (sync_streams and the few direct waits a batch can meet)
 
@@ -2749,7 +2753,7 @@ int run_to_states(qsv_t* h, const BatchArgs& args, const StateRun& run, const Gr
     return rc ? rc : run_laid_out(h, args, run, lay, on_split, on_state);
 }
 
-// The frame of a consumer of WHOLE final states (qsv_variance_circuits, qsv_observables_covariance): ordinary plans into state
+// The frame of a consumer of WHOLE final states (qsv_variance_circuits, qsv_observables_covariance, qsv_overlap_circuits): ordinary plans into state
 // slots, never split (as qsv_prefix_create runs them), in launch groups of G; behind each group `launch`(first, count) queues
 // the consumer's kernels on the handle's stream, which leave their results by position in device memory at `results`.  Those
 // `count` doubles are in h_out when it returns, and batch.eval_at says whose they are; nothing of a failed call is still
@@ -3104,7 +3108,7 @@ void qsv_destroy(qsv_t* h) {
                             &h->d_states, &h->d_wtab, &h->d_side, &h->d_factor, &h->d_factor_count, &h->d_factor_big, &h->d_factor_big_count, &h->d_quad, &h->d_fterms, &h->d_fpart, &h->d_batch, &h->d_mats, &h->d_partials, &h->d_out, &h->d_scratch, &h->d_prefix, &h->d_sdiag,
                             &h->d_obs_partials, &h->d_obs_values, &h->d_grad_tab, &h->d_grad_rows, &h->d_grad_values, &h->d_grad_base,
                             &h->d_grad_out, &h->d_adj_lambda, &h->d_adj_tab, &h->d_adj_mats, &h->d_adj_partials, &h->d_adj_epart, &h->d_adj_base,
-                            &h->d_adj_out, &h->d_adj_values, &h->d_moments, &h->d_cov})
+                            &h->d_adj_out, &h->d_adj_values, &h->d_moments, &h->d_cov, &h->d_overlap})
         if (b->ptr) (void)hipFree(b->ptr);
     for (auto& kv : h->obs_sets) free_observable_set(kv.second);
     for (auto& kv : h->value_caches) free_value_cache(kv.second);
@@ -5360,6 +5364,63 @@ int qsv_observables_covariance(qsv_t* h, int set_id, int n_evals, const int* cir
         const size_t e = h->batch.eval_at[j];
         if (out_values) std::copy(h->h_out + j * M, h->h_out + (j + 1) * M, out_values + e * M);
         std::copy(h_cov + j * M * M, h_cov + (j + 1) * M * M, out_cov + e * M * M);
+    }
+    return QSV_OK;
+}
+
+// ---- overlaps and operator matrix elements against kept states (qsv.h: OVERLAPS; overlap.hpp) -------------------------------------
+
+int qsv_overlap_circuits(qsv_t* h, int n_states, const int* prefix_ids, int with_operator, int n_evals, const int* circuit_ids,
+                         const int64_t* param_offsets, const double* params, double* out_overlaps, double* out_elements) {
+    QSV_OPEN(h, "qsv_overlap_circuits", kDevice);
+    if (n_states < 1) return fail(h, QSV_E_ARG, "n_states must be at least 1");
+    if (n_states > int(kOvlMaxStates)) return fail(h, QSV_E_UNSUPPORTED, "n_states: overlaps are available against up to 64 kept states per call");
+    if (!prefix_ids) return fail(h, QSV_E_ARG, "prefix_ids is null");
+    if (n_evals < 0) return fail(h, QSV_E_ARG, "n_evals is negative");
+    if (n_evals > 0 && (!circuit_ids || !param_offsets)) return fail(h, QSV_E_ARG, "circuit_ids or param_offsets is null");
+    if (n_evals > 0 && !out_overlaps) return fail(h, QSV_E_ARG, "out_overlaps is null");
+    if (n_evals > 0 && with_operator && !out_elements) return fail(h, QSV_E_ARG, "out_elements is null (required with with_operator)");
+    // (the register's size is the handle's own: asked before the kept states, which such a handle need not hold)
+    if (n_evals > 0 && h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "overlaps are available up to 28 qubits, this handle has " + std::to_string(h->n));
+    const size_t K = size_t(n_states);
+    OverlapRefs refs{};
+    for (size_t k = 0; k < K; ++k) {
+        const auto it = h->prefixes.find(prefix_ids[k]);
+        if (it == h->prefixes.end() || it->second.released) return fail(h, QSV_E_ARG, "unknown kept state " + std::to_string(prefix_ids[k]));
+        refs.slot[k] = it->second.slot;
+    }
+    if (n_evals == 0) return QSV_OK;
+    if (with_operator && h->n_terms == 0) return fail(h, QSV_E_STATE, "with_operator: no operator set (call qsv_set_operator first)");
+    BatchArgs args;
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args,
+                           "circuit_ids: the overlaps of a circuit on a kept state are not built");
+    if (rc) return rc;
+    if ((rc = wait_pending(h))) return rc;  // (the buffers below may still be read or written by a call that did not wait)
+    const size_t n = size_t(n_evals);
+    const bool op = with_operator != 0;
+    const size_t G = overlap_group(h->n, K, op, std::max<size_t>(1, std::min(size_t(h->group), size_t(h->max_grid_y))));
+    // device scratch: the call's S by position | its T by position | the partial tiles of one launch group
+    const size_t tile_count = n * K * 2, out_count = op ? 2 * tile_count : tile_count, out_bytes = (out_count * sizeof(double) + 63) / 64 * 64;
+    if ((rc = ensure(h, h->d_overlap, out_bytes + overlap_partial_bytes(h->n, K, op, std::min(G, n)))) || (rc = ensure_host_out(h, out_count)))
+        return rc;
+    double* const d_s = static_cast<double*>(h->d_overlap.ptr);
+    double* const d_t = op ? d_s + tile_count : nullptr;
+    double* const partials = reinterpret_cast<double*>(static_cast<char*>(h->d_overlap.ptr) + out_bytes);
+    auto tiles = [&](size_t g0, size_t gc) -> int {
+        QSV_HIP(h, launch_overlap_panels(h->dtype, h->d_states.ptr, h->d_prefix.ptr, refs, uint32_t(K), h->n, int(gc),
+                                         op && h->has_diag_part ? static_cast<const double*>(h->d_diag.ptr) : nullptr, op ? h->n_groups : -1,
+                                         static_cast<const PauliGroup*>(h->d_groups.ptr), static_cast<const uint64_t*>(h->d_z.ptr),
+                                         static_cast<const double*>(h->d_cre.ptr), static_cast<const uint32_t*>(h->d_term_odd.ptr),
+                                         partials, h->stream));
+        QSV_HIP(h, launch_overlap_combine(partials, h->n, int(gc), uint32_t(K), d_s + g0 * K * 2, op ? d_t + g0 * K * 2 : nullptr, h->stream));
+        return QSV_OK;
+    };
+    if ((rc = run_whole_states(h, args, G, tiles, d_s, out_count))) return rc;
+    const size_t row = K * 2;
+    for (size_t j = 0; j < n; ++j) {
+        const size_t e = h->batch.eval_at[j];
+        std::copy(h->h_out + j * row, h->h_out + (j + 1) * row, out_overlaps + e * row);
+        if (op) std::copy(h->h_out + tile_count + j * row, h->h_out + tile_count + (j + 1) * row, out_elements + e * row);
     }
     return QSV_OK;
 }

@@ -609,6 +609,13 @@ class EVQEResult:
     # aux_operators_evaluated (None: not asked for)
     aux_operators_covariance: Optional[np.ndarray] = None
     aux_operators_variance: Optional[Union[list[float], dict[Any, float]]] = None
+    # the subspace refinement over the best individual and the last scored generation (None: not asked for): the lowest
+    # generalised eigenvalue of (H, S) over the picked states, its coefficients over them (c^H S c = 1), the number of
+    # directions of S that were kept, and S itself, the picked states' overlap matrix as the device returned it, best individual first
+    subspace_eigenvalue: Optional[float] = None
+    subspace_coefficients: Optional[np.ndarray] = None
+    subspace_rank: Optional[int] = None
+    subspace_overlaps: Optional[np.ndarray] = None
 
 
 # ---- the solver -----------------------------------------------------------------------------------------------
@@ -869,7 +876,8 @@ class EVQEMinimumEigensolver:
     # -- main loop ------------------------------------------------------------------------------------------
     def compute_minimum_eigenvalue(self, evaluator, search_evaluator=None, aux_operators=None,
                                    eigenstate_states: Optional[int] = None, eigenvalue_variance: bool = False,
-                                   aux_operators_covariance: bool = False) -> EVQEResult:
+                                   aux_operators_covariance: bool = False, subspace_states: Optional[int] = None,
+                                   subspace_rcond: Optional[float] = None) -> EVQEResult:
         """``search_evaluator``: a second evaluator of the SAME operator for the parameter searches alone -- a single-precision
         handle: the points a search compares differ by far more than 1e-6 (the reference's own tests run their searches on an
         estimator with precision 0.05, test/minimum_eigensolvers/evqe/solver.py:20-27), a layer search on kept states is bound
@@ -901,7 +909,22 @@ class EVQEMinimumEigensolver:
         operators' order, a dict's in ``list(aux_operators)`` order) and its diagonal, the variances, to
         ``result.aux_operators_variance`` in the shape of ``aux_operators_evaluated``.  With the cost's parts as aux operators
         ``w @ C @ w`` is the variance of any re-weighting of them.  The same rules as ``eigenvalue_variance``.  ``False``: no
-        call, both fields stay ``None``."""
+        call, both fields stay ``None``.
+
+        ``subspace_states``: after the run, diagonalise the operator in the span of up to that many (at most 64) states the run
+        already has -- the best individual first, then the individuals of the last scored generation in ascending value, one
+        that repeats an earlier pick's structure and parameter values skipped -- from one
+        ``evaluator.evaluate_subspace_matrices`` call: S_ij = <psi_i|psi_j> and H_ij = <psi_i|H|psi_j> on the device (DESIGN.md
+        4.15).  The lowest generalised eigenvalue of (H, S) (``evqe.subspace.lowest_subspace_eigenvalue``) goes to
+        ``result.subspace_eigenvalue``: a variational upper bound that is never above ``result.eigenvalue`` beyond rounding,
+        for no new circuit and no optimiser step.  Its coefficients over the picked states, the number of directions of S that
+        were kept and S itself go to ``result.subspace_coefficients``, ``subspace_rank`` and ``subspace_overlaps``.
+        ``subspace_rcond``: directions of S with eigenvalues below that times the largest are dropped; ``None`` means 1e-8 on
+        an fp64 evaluator (entries of S carry up to 1e-11, so eigenvalues of a 64 x 64 S below about 6e-10 are noise: ten times
+        that) and 1e-4 on an fp32 one (entries to about 2e-6, by the same argument).  The eigenvalue's error grows as (entry
+        error) * sum_k|c_k| / s_min_kept, c_k the operator's coefficients and s_min_kept the smallest kept eigenvalue of S.  The
+        same rules as ``eigenvalue_variance``: no random stream of the solver, not counted in ``circuit_evaluations``, made by
+        every rank of a sharded run itself.  ``None``: no call, the four fields stay ``None``."""
         cfg = self.configuration
         searcher = evaluator if search_evaluator is None else search_evaluator
         if searcher.n_qubits != evaluator.n_qubits:
@@ -921,6 +944,16 @@ class EVQEMinimumEigensolver:
                 raise ValueError("aux_operators_covariance needs aux_operators")
             if not callable(getattr(evaluator, "evaluate_covariances", None)):
                 raise ValueError("aux_operators_covariance needs an evaluator with evaluate_covariances (an operator evaluator)")
+        if subspace_states is not None:
+            if not 1 <= int(subspace_states) <= 64:
+                raise ValueError("subspace_states must be between 1 and 64")
+            if not callable(getattr(evaluator, "evaluate_subspace_matrices", None)):
+                raise ValueError("subspace_states needs an evaluator with evaluate_subspace_matrices (an operator evaluator)")
+            if subspace_rcond is not None and not subspace_rcond > 0:
+                raise ValueError("subspace_rcond must be positive")
+        elif subspace_rcond is not None:
+            raise ValueError("subspace_rcond needs subspace_states")
+        last_scored: Optional[tuple] = None  # (individuals, values) of the last scored generation
         if cfg.termination_criterion is not None:
             cfg.termination_criterion.reset_state()
         population = EVQEPopulation.random_population(
@@ -961,6 +994,8 @@ class EVQEMinimumEigensolver:
             else:
                 values = evaluator.evaluate_circuits(circuits, [list(ind.parameter_values) for ind in population.individuals])
             evaluations[-1] += len(values)
+            if subspace_states is not None:
+                last_scored = (tuple(population.individuals), [float(v) for v in values])
             best = int(np.argmin(values))
             if values[best] < result.eigenvalue:
                 result.eigenvalue, result.best_individual = values[best], population.individuals[best]
@@ -1004,7 +1039,40 @@ class EVQEMinimumEigensolver:
             variances = [float(v) for v in np.diagonal(matrix)]
             result.aux_operators_covariance = matrix
             result.aux_operators_variance = dict(zip(names, variances)) if names is not None else variances
+        if subspace_states is not None:
+            self._refine_in_subspace(evaluator, result, last_scored, int(subspace_states), subspace_rcond)
         return result
+
+    def _refine_in_subspace(self, evaluator, result: EVQEResult, last_scored, k: int, rcond: Optional[float]) -> None:
+        """The subspace fields of ``result``: picks the states, one ``evaluate_subspace_matrices`` call, the host's
+        diagonalisation."""
+        from queasars_amd.evqe.subspace import lowest_subspace_eigenvalue
+
+        picks = [result.best_individual]
+        if last_scored is not None:
+            individuals, values = last_scored
+            picks += [individuals[i] for i in sorted(range(len(values)), key=lambda i: (values[i], i))]
+        chosen: list[EVQEIndividual] = []
+        seen = set()
+        for individual in picks:
+            key = (individual.layers, tuple(float(v) for v in individual.parameter_values))
+            if key in seen:
+                continue
+            seen.add(key)
+            chosen.append(individual)
+            if len(chosen) == k:
+                break
+        if rcond is None:
+            device = getattr(evaluator, "statevector_device", None)
+            rcond = 1e-4 if getattr(device, "dtype", "fp64") == "fp32" else 1e-8
+        circuits = [ind.get_parameterized_quantum_circuit(shared=self.share_circuits) for ind in chosen]
+        overlaps, elements = evaluator.evaluate_subspace_matrices(circuits, [list(ind.parameter_values) for ind in chosen])
+        overlaps = np.asarray(overlaps, dtype=np.complex128)
+        eigenvalue, coefficients, rank, _ = lowest_subspace_eigenvalue(overlaps, elements, rcond)
+        result.subspace_eigenvalue = eigenvalue
+        result.subspace_coefficients = coefficients
+        result.subspace_rank = rank
+        result.subspace_overlaps = overlaps
 
     def _read_eigenstate(self, evaluator, individual: EVQEIndividual, k: int):
         """The ``k`` most probable basis states of ``individual`` and, where the evaluator knows them, their values: one
