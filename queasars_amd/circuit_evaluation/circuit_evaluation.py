@@ -174,6 +174,86 @@ def _pack_doubles(vectors: Sequence[Sequence[float]], total: int) -> np.ndarray:
     return np.frombuffer(packed, dtype=np.float64)
 
 
+def _same_length(n_circuits: int, n_vectors: int) -> int:
+    """The size of a batch of ``n_circuits`` circuits and ``n_vectors`` parameter vectors (or matrix rows): one each."""
+    if n_vectors != n_circuits:
+        raise ValueError("circuits and parameter_values must have the same length")
+    return n_circuits
+
+
+def _pointer(what) -> Optional[C.c_void_p]:
+    """An array, or an address given as an integer, as the library takes a pointer; ``None`` for None and for 0."""
+    if isinstance(what, np.ndarray):
+        return _lib.as_ptr(what)
+    return C.c_void_p(what) if what else None
+
+
+def _wrt_per_circuit(n: int, wrt) -> Optional[list]:
+    """``wrt`` of a gradient call over ``n`` circuits -- None (every parameter of each circuit), one sequence of parameter
+    indices for all circuits, or one sequence per circuit -- as one entry per circuit, or None."""
+    if wrt is None:
+        return None
+    wrt = list(wrt)
+    if all(np.ndim(w) == 0 for w in wrt):
+        return [wrt] * n
+    if len(wrt) != n:
+        raise ValueError("wrt must be None, one list of parameter indices, or one list per circuit")
+    return wrt
+
+
+def _struct_dict(raw: C.Structure) -> dict:
+    """The fields of one of the library's statistics structs by name (an array field as a list)."""
+    out = {}
+    for name, _ in raw._fields_:
+        value = getattr(raw, name)
+        out[name] = list(value) if hasattr(value, "__len__") else value
+    return out
+
+
+class _HostBatch:
+    """The opening of a host batch method of :class:`StatevectorDevice`: the length check when it is made, ``n`` for the
+    method's own checks and its empty result, and :meth:`arguments` -- what the library's batch entry points take -- once the
+    method is about to call.  The packed arrays live as long as this object: keep it over the call."""
+
+    __slots__ = ("n", "_source", "_arrays")
+
+    def __init__(self, device: "StatevectorDevice", circuits, parameter_values):
+        self.n = _same_length(len(circuits), len(parameter_values))
+        self._source = (device, circuits, parameter_values)
+
+    def arguments(self) -> tuple:
+        """``(n, circuit ids, parameter offsets, packed values)``; three ``None`` for the pointers of an empty batch."""
+        if self.n == 0:
+            return 0, None, None, None
+        device, circuits, parameter_values = self._source
+        self._arrays = device._batch_arguments(circuits, parameter_values)
+        return (self.n, *map(_lib.as_ptr, self._arrays))
+
+
+class _OperatorInstalled:
+    """:meth:`StatevectorDevice.with_operator`.  (A class, not a generator behind ``contextlib.contextmanager``: the guard is on
+    the path of every evaluation, and entering one of those costs about a microsecond.)"""
+
+    __slots__ = ("_device", "_operator")
+
+    def __init__(self, device: "StatevectorDevice", operator: PauliOperator):
+        self._device, self._operator = device, operator
+
+    def __enter__(self) -> "StatevectorDevice":
+        device = self._device
+        device.operator_lock.acquire()
+        try:
+            if device._operator is not self._operator:
+                device.set_operator(self._operator)
+        except BaseException:
+            device.operator_lock.release()
+            raise
+        return device
+
+    def __exit__(self, *exc) -> None:
+        self._device.operator_lock.release()
+
+
 def _make_gone(dead: list, watched: dict):
     """Callback of the weak references StatevectorDevice._watch creates: queue the dead circuit's id for destruction."""
 
@@ -239,19 +319,13 @@ class DeviceValueCache:
     def lookup(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]], shots: int, seed: int) -> np.ndarray:
         """Draws the samples :meth:`StatevectorDevice.sample_batch` draws for the same arguments and returns the distinct
         states among them (over the whole batch) that the table did not hold, in no particular order (``uint64``)."""
-        n = len(circuits)
-        if len(parameter_values) != n:
-            raise ValueError("circuits and parameter_values must have the same length")
         owner = self._owner
-        if n and shots:
-            ids, offsets, flat = owner._batch_arguments(circuits, parameter_values)
-            arguments = (_lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat))
-        else:
-            arguments = (None, None, None)
+        batch = _HostBatch(owner, circuits, parameter_values)
+        arguments = batch.arguments() if shots else (batch.n, None, None, None)  # (no shots: nothing is packed)
         n_missing, states = C.c_int64(0), C.c_void_p()
-        self._check(owner._lib.qsv_sample_lookup(owner._handle, self._id, n, *arguments, int(shots), C.c_uint64(seed & (2**64 - 1)),
+        self._check(owner._lib.qsv_sample_lookup(owner._handle, self._id, *arguments, int(shots), C.c_uint64(seed & (2**64 - 1)),
                                                  C.byref(n_missing), C.byref(states)))
-        self._shape = (n, int(shots))
+        self._shape = (batch.n, int(shots))
         if n_missing.value == 0:
             return np.empty(0, dtype=np.uint64)
         # (the library's pinned list is good until the finish; a copy is good for as long as the caller likes)
@@ -282,7 +356,7 @@ class DeviceValueCache:
         """``entries``, ``slots``, ``samples_looked_up``, ``hits``, ``new_entries``, ``rehashes``, ``clears``."""
         raw = _lib.QsvValueCacheStats()
         self._check(self._owner._lib.qsv_value_cache_stats(self._owner._handle, self._id, C.byref(raw)))
-        return {name: int(getattr(raw, name)) for name, _ in raw._fields_}
+        return _struct_dict(raw)
 
     def close(self) -> None:
         """Free the table (idempotent; the device's own end frees it as well)."""
@@ -315,9 +389,8 @@ class DeviceGradientPlan:
         wrt_offsets, wrt_flat, _counts = owner._wrt_arguments(self._circuits, wrt)
         out, n_shifted = C.c_int(-1), C.c_int64(0)
         owner._check_gradient(owner._lib.qsv_gradient_plan_create(
-            owner._handle, n, _lib.as_ptr(ids) if n else None, int(width),
-            _lib.as_ptr(wrt_offsets) if wrt_offsets is not None else None, _lib.as_ptr(wrt_flat) if wrt_flat is not None else None,
-            int(out_width), C.byref(out), C.byref(n_shifted)))
+            owner._handle, n, _pointer(ids), int(width), _pointer(wrt_offsets), _pointer(wrt_flat), int(out_width), C.byref(out),
+            C.byref(n_shifted)))
         self._id = int(out.value)
         #: circuit evaluations one :meth:`run` queues
         self.n_shifted = int(n_shifted.value)
@@ -332,8 +405,7 @@ class DeviceGradientPlan:
             raise RuntimeError("the gradient plan is closed")
         owner.last_gradient_evaluations = 0
         owner._check_gradient(owner._lib.qsv_gradient_plan_run(
-            owner._handle, self._id, C.c_void_p(matrix_ptr) if matrix_ptr else None, C.c_void_p(event) if event else None,
-            C.c_void_p(out_ptr) if out_ptr else None))
+            owner._handle, self._id, _pointer(matrix_ptr), _pointer(event), _pointer(out_ptr)))
         owner.last_gradient_evaluations = self.n_shifted
         return self.n_shifted
 
@@ -345,7 +417,7 @@ class DeviceGradientPlan:
             raise RuntimeError("the gradient plan is closed")
         raw = _lib.QsvGradientPlanStats()
         owner._check(owner._lib.qsv_gradient_plan_stats(owner._handle, self._id, C.byref(raw)))
-        return {name: int(getattr(raw, name)) for name, _ in raw._fields_}
+        return _struct_dict(raw)
 
     def close(self) -> None:
         """Free the tables (idempotent; waits for the handle's stream.  The device's own end frees them as well)."""
@@ -479,6 +551,12 @@ class StatevectorDevice:
         )
         self._operator = operator
 
+    def with_operator(self, operator: PauliOperator) -> "_OperatorInstalled":
+        """``with device.with_operator(op): ...``: ``operator_lock`` is held over the block and ``op`` is the operator set on
+        the device, installed first if another one was.  Evaluators share a device, so "is it my operator? else set it" and
+        the evaluation are one critical section: this is the only way anything that reads the device's operator gets there."""
+        return _OperatorInstalled(self, operator)
+
     # -- circuits -------------------------------------------------------------------------------
     def circuit_id(self, circuit: CircuitIR) -> int:
         """Register ``circuit`` on this device once; later calls return the cached id."""
@@ -564,9 +642,7 @@ class StatevectorDevice:
         """Run every (circuit, parameter vector) pair from |0..0> once and keep its final state resident
         (``qsv_prefix_create``): circuits made with ``CircuitIR.continue_from(state)`` then start there.  What a layer search
         does with everything in front of the searched layer (reference: mutation.py:57-59)."""
-        n = len(circuits)
-        if len(parameter_values) != n:
-            raise ValueError("circuits and parameter_values must have the same length")
+        n = _same_length(len(circuits), len(parameter_values))
         if n == 0:
             return []
         if any(c._kept_state is not None for c in circuits):
@@ -898,20 +974,13 @@ class StatevectorDevice:
         """``shots`` measured basis states per (circuit, parameter vector) pair, sampled on the device:
         ``states[i, s]``.  With ``with_values`` (diagonal operator set on the device) also ``values[i, s]``, the
         operator's value on each sample, gathered from the device-resident diagonal table."""
-        n = len(circuits)
-        if len(parameter_values) != n:
-            raise ValueError("circuits and parameter_values must have the same length")
-        states = np.empty((n, int(shots)), dtype=np.uint64)
-        values = np.empty((n, int(shots)), dtype=np.float64) if with_values else None
-        if n == 0 or shots == 0:
+        batch = _HostBatch(self, circuits, parameter_values)
+        states = np.empty((batch.n, int(shots)), dtype=np.uint64)
+        values = np.empty((batch.n, int(shots)), dtype=np.float64) if with_values else None
+        if batch.n == 0 or shots == 0:
             return states, values
-        ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
-        self._check(
-            self._lib.qsv_sample_batch(
-                self._handle, n, _lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat), int(shots),
-                C.c_uint64(seed & (2**64 - 1)), _lib.as_ptr(states), _lib.as_ptr(values) if with_values else None,
-            )
-        )
+        self._check(self._lib.qsv_sample_batch(self._handle, *batch.arguments(), int(shots), C.c_uint64(seed & (2**64 - 1)),
+                                               _lib.as_ptr(states), _pointer(values)))
         return states, values
 
     #: most samples per evaluation the device-side CVaR sorts (csrc/kernels.hpp kCvarMaxShots)
@@ -923,19 +992,12 @@ class StatevectorDevice:
         """CVaR_alpha of the (diagonal) operator over ``shots`` samples per (circuit, parameter vector) pair, sampled,
         valued and sorted on the device (``qsv_sample_cvar_batch``): the same samples :meth:`sample_batch` draws for
         ``seed``, but only one number per pair comes back."""
-        n = len(circuits)
-        if len(parameter_values) != n:
-            raise ValueError("circuits and parameter_values must have the same length")
-        if n == 0:
+        batch = _HostBatch(self, circuits, parameter_values)
+        if batch.n == 0:
             return []
-        ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
-        out = np.empty(n, dtype=np.float64)
-        self._check(
-            self._lib.qsv_sample_cvar_batch(
-                self._handle, n, _lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat), int(shots),
-                C.c_uint64(seed & (2**64 - 1)), float(alpha), _lib.as_ptr(out),
-            )
-        )
+        out = np.empty(batch.n, dtype=np.float64)
+        self._check(self._lib.qsv_sample_cvar_batch(self._handle, *batch.arguments(), int(shots), C.c_uint64(seed & (2**64 - 1)),
+                                                    float(alpha), _lib.as_ptr(out)))
         return out.tolist()
 
     def value_cache(self, log2_slots: int = 16, log2_max_slots: int = 24) -> DeviceValueCache:
@@ -947,15 +1009,11 @@ class StatevectorDevice:
         """CVaR_alpha of the (diagonal) operator under the EXACT output distribution of every (circuit, parameter vector)
         pair (``qsv_exact_cvar_batch``): what the reference's accumulation loop returns for a measured distribution that
         equals the exact one (expectation_calculation.py:14-32), stopping rule and tie order included.  Deterministic."""
-        n = len(circuits)
-        if len(parameter_values) != n:
-            raise ValueError("circuits and parameter_values must have the same length")
-        if n == 0:
+        batch = _HostBatch(self, circuits, parameter_values)
+        if batch.n == 0:
             return []
-        ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
-        out = np.empty(n, dtype=np.float64)
-        self._check(self._lib.qsv_exact_cvar_batch(self._handle, n, _lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat),
-                                                   float(alpha), _lib.as_ptr(out)))
+        out = np.empty(batch.n, dtype=np.float64)
+        self._check(self._lib.qsv_exact_cvar_batch(self._handle, *batch.arguments(), float(alpha), _lib.as_ptr(out)))
         return out.tolist()
 
     #: most states per evaluation :meth:`top_states` selects (csrc/kernels.hpp kTopMaxStates)
@@ -969,24 +1027,17 @@ class StatevectorDevice:
         descending, basis-state index ascending, ``probabilities[i, j]``, and with ``with_values`` (diagonal operator set on
         the device) ``values[i, j]``, the operator's value on each state.  ``1 <= k <= min(MAX_TOP_STATES, 2**n_qubits)``.
         Deterministic; only ``k`` entries per pair cross PCIe, not the ``2**n_qubits`` of :meth:`probabilities`."""
-        n = len(circuits)
-        if len(parameter_values) != n:
-            raise ValueError("circuits and parameter_values must have the same length")
+        batch = _HostBatch(self, circuits, parameter_values)
         k = int(k)
         if not 1 <= k <= min(self.MAX_TOP_STATES, 1 << self._n_qubits):
             raise ValueError(f"k must be between 1 and min({self.MAX_TOP_STATES}, 2**n_qubits), got {k}")
-        states = np.empty((n, k), dtype=np.uint64)
-        probabilities = np.empty((n, k), dtype=np.float64)
-        values = np.empty((n, k), dtype=np.float64) if with_values else None
-        if n == 0:
+        states = np.empty((batch.n, k), dtype=np.uint64)
+        probabilities = np.empty((batch.n, k), dtype=np.float64)
+        values = np.empty((batch.n, k), dtype=np.float64) if with_values else None
+        if batch.n == 0:
             return states, probabilities, values
-        ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
-        self._check(
-            self._lib.qsv_top_states(
-                self._handle, n, _lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat), k,
-                _lib.as_ptr(states), _lib.as_ptr(probabilities), _lib.as_ptr(values) if with_values else None,
-            )
-        )
+        self._check(self._lib.qsv_top_states(self._handle, *batch.arguments(), k, _lib.as_ptr(states), _lib.as_ptr(probabilities),
+                                             _pointer(values)))
         return states, probabilities, values
 
     def cvar_of_device_parameters(
@@ -1023,9 +1074,8 @@ class StatevectorDevice:
         ids, _need, _total = self._batch_metadata(circuits)
         self._check(
             self._lib.qsv_cvar_device(
-                self._handle, n, _lib.as_ptr(ids), int(width), C.c_void_p(matrix_ptr) if width else None,
-                C.c_void_p(event) if event else None, int(shots), C.c_uint64(seed & (2**64 - 1)), float(alpha),
-                C.c_void_p(active_ptr) if active_ptr else None, int(active_stride), C.c_void_p(out_ptr),
+                self._handle, n, _lib.as_ptr(ids), int(width), _pointer(matrix_ptr if width else 0), _pointer(event), int(shots),
+                C.c_uint64(seed & (2**64 - 1)), float(alpha), _pointer(active_ptr), int(active_stride), C.c_void_p(out_ptr),
             )
         )
 
@@ -1041,13 +1091,9 @@ class StatevectorDevice:
         """(wrt offsets, wrt indices, entries per circuit) of a gradient call.  ``wrt``: None (every parameter of each circuit),
         one sequence of parameter indices for all circuits, or one sequence per circuit."""
         n = len(circuits)
+        wrt = _wrt_per_circuit(n, wrt)
         if wrt is None:
             return None, None, np.fromiter((c.num_parameters for c in circuits), dtype=np.int64, count=n)
-        wrt = list(wrt)
-        if all(np.ndim(w) == 0 for w in wrt):
-            wrt = [wrt] * n
-        elif len(wrt) != n:
-            raise ValueError("wrt must be None, one list of parameter indices, or one list per circuit")
         counts = np.fromiter((len(w) for w in wrt), dtype=np.int64, count=n)
         offsets = np.zeros(n + 1, dtype=np.int64)
         np.cumsum(counts, out=offsets[1:])
@@ -1063,23 +1109,40 @@ class StatevectorDevice:
         :meth:`expectation_values` at the shifted points; the base points cross PCIe once, the shifted ones never exist on the
         host.  :attr:`last_gradient_evaluations` is the number of circuit evaluations the call ran.  A requested parameter
         that more than one angle slot reads raises ``ValueError``."""
-        n = len(circuits)
-        if len(parameter_values) != n:
-            raise ValueError("circuits and parameter_values must have the same length")
+        n_shifted = C.c_int64(0)
+        gradients = self._host_gradients(self._lib.qsv_gradient_circuits, circuits, parameter_values, wrt, C.byref(n_shifted))
+        self.last_gradient_evaluations = int(n_shifted.value)
+        return gradients
+
+    def _host_gradients(self, function, circuits, parameter_values, wrt, trailing) -> list[np.ndarray]:
+        """What :meth:`gradients` and :meth:`adjoint_gradients` share: ``function`` is the library's entry point, ``trailing``
+        its last argument.  Leaves :attr:`last_gradient_evaluations` at 0: what the call ran is the caller's to say."""
+        batch = _HostBatch(self, circuits, parameter_values)
         self.last_gradient_evaluations = 0
-        if n == 0:
+        if batch.n == 0:
             return []
-        ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
+        arguments = batch.arguments()
         wrt_offsets, wrt_flat, counts = self._wrt_arguments(circuits, wrt)
         out = np.zeros(max(1, int(counts.sum())), dtype=np.float64)
-        n_shifted = C.c_int64(0)
-        self._check_gradient(self._lib.qsv_gradient_circuits(
-            self._handle, n, _lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat),
-            _lib.as_ptr(wrt_offsets) if wrt_offsets is not None else None, _lib.as_ptr(wrt_flat) if wrt_flat is not None else None,
-            _lib.as_ptr(out), C.byref(n_shifted)))
-        self.last_gradient_evaluations = int(n_shifted.value)
+        self._check_gradient(function(self._handle, *arguments, _pointer(wrt_offsets), _pointer(wrt_flat), _lib.as_ptr(out), trailing))
         ends = np.cumsum(counts)
         return [out[int(e - c): int(e)].copy() for c, e in zip(counts, ends)]
+
+    def _device_gradients(self, function, circuits, matrix_ptr: int, width: int, event: int, out_ptr: int, out_width: int, wrt,
+                          trailing) -> None:
+        """What :meth:`gradients_of_device_parameters` and :meth:`adjoint_gradients_of_device_parameters` share, as
+        :meth:`_host_gradients` (an empty batch is no call)."""
+        n = len(circuits)
+        self.last_gradient_evaluations = 0
+        if n == 0:
+            return
+        if width < 0 or (width > 0 and not matrix_ptr) or out_width < 0 or (out_width > 0 and not out_ptr):
+            raise ValueError("matrix_ptr / width / out_ptr / out_width do not describe a matrix and its gradients")
+        ids, _need, _total = self._batch_metadata(circuits)
+        wrt_offsets, wrt_flat, _counts = self._wrt_arguments(circuits, wrt)
+        self._check_gradient(function(
+            self._handle, n, _lib.as_ptr(ids), int(width), _pointer(matrix_ptr if width else 0), _pointer(event),
+            _pointer(wrt_offsets), _pointer(wrt_flat), int(out_width), _pointer(out_ptr if out_width else 0), trailing))
 
     def gradients_of_device_parameters(self, circuits: Sequence[CircuitIR], matrix_ptr: int, width: int, event: int, out_ptr: int,
                                        out_width: int, wrt=None) -> int:
@@ -1088,20 +1151,9 @@ class StatevectorDevice:
         memory: row i of the ``len(circuits) x out_width`` matrix at ``out_ptr``, zeros behind its entries
         (``qsv_gradient_device``).  Queued on the handle's stream and not waited for.  ``event`` as in
         :meth:`cvar_of_device_parameters`.  Returns the number of circuit evaluations queued."""
-        n = len(circuits)
-        self.last_gradient_evaluations = 0
-        if n == 0:
-            return 0
-        if width < 0 or (width > 0 and not matrix_ptr) or out_width < 0 or (out_width > 0 and not out_ptr):
-            raise ValueError("matrix_ptr / width / out_ptr / out_width do not describe a matrix and its gradients")
-        ids, _need, _total = self._batch_metadata(circuits)
-        wrt_offsets, wrt_flat, _counts = self._wrt_arguments(circuits, wrt)
         n_shifted = C.c_int64(0)
-        self._check_gradient(self._lib.qsv_gradient_device(
-            self._handle, n, _lib.as_ptr(ids), int(width), C.c_void_p(matrix_ptr) if width else None,
-            C.c_void_p(event) if event else None, _lib.as_ptr(wrt_offsets) if wrt_offsets is not None else None,
-            _lib.as_ptr(wrt_flat) if wrt_flat is not None else None, int(out_width), C.c_void_p(out_ptr) if out_width else None,
-            C.byref(n_shifted)))
+        self._device_gradients(self._lib.qsv_gradient_device, circuits, matrix_ptr, width, event, out_ptr, out_width, wrt,
+                               C.byref(n_shifted))
         self.last_gradient_evaluations = int(n_shifted.value)
         return self.last_gradient_evaluations
 
@@ -1116,7 +1168,7 @@ class StatevectorDevice:
         allocated or grown since the device was created, and its size."""
         stats = _lib.QsvGradientStats()
         self._check(self._lib.qsv_gradient_stats(self._handle, C.byref(stats)))
-        return {name: int(getattr(stats, name)) for name, _ in _lib.QsvGradientStats._fields_}
+        return _struct_dict(stats)
 
     # -- adjoint gradients ------------------------------------------------------------------------
     def adjoint_gradients(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]], wrt=None,
@@ -1126,23 +1178,9 @@ class StatevectorDevice:
         there.  A parameter that several angle slots read gets the sum over them (parameter shift refuses it).  With
         ``return_values`` also the expectation values, a by-product of the sweep: ``(gradients, values)``.
         :attr:`last_gradient_evaluations` counts ONE per (circuit, point)."""
-        n = len(circuits)
-        if len(parameter_values) != n:
-            raise ValueError("circuits and parameter_values must have the same length")
-        self.last_gradient_evaluations = 0
-        if n == 0:
-            return ([], np.zeros(0)) if return_values else []
-        ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
-        wrt_offsets, wrt_flat, counts = self._wrt_arguments(circuits, wrt)
-        out = np.zeros(max(1, int(counts.sum())), dtype=np.float64)
-        values = np.zeros(n, dtype=np.float64)
-        self._check_gradient(self._lib.qsv_adjoint_gradient_circuits(
-            self._handle, n, _lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat),
-            _lib.as_ptr(wrt_offsets) if wrt_offsets is not None else None, _lib.as_ptr(wrt_flat) if wrt_flat is not None else None,
-            _lib.as_ptr(out), _lib.as_ptr(values)))
-        self.last_gradient_evaluations = n
-        ends = np.cumsum(counts)
-        gradients = [out[int(e - c): int(e)].copy() for c, e in zip(counts, ends)]
+        values = np.zeros(len(circuits), dtype=np.float64)
+        gradients = self._host_gradients(self._lib.qsv_adjoint_gradient_circuits, circuits, parameter_values, wrt, _lib.as_ptr(values))
+        self.last_gradient_evaluations = len(gradients)
         return (gradients, values) if return_values else gradients
 
     def adjoint_gradients_of_device_parameters(self, circuits: Sequence[CircuitIR], matrix_ptr: int, width: int, event: int, out_ptr: int,
@@ -1151,28 +1189,17 @@ class StatevectorDevice:
         (``qsv_adjoint_gradient_device``): points read from and gradients left in device memory, queued on the handle's stream,
         not waited for.  ``values_ptr``: device memory for ``len(circuits)`` expectation values, or 0.  Returns
         ``len(circuits)``, the evaluations counted."""
-        n = len(circuits)
-        self.last_gradient_evaluations = 0
-        if n == 0:
-            return 0
-        if width < 0 or (width > 0 and not matrix_ptr) or out_width < 0 or (out_width > 0 and not out_ptr):
-            raise ValueError("matrix_ptr / width / out_ptr / out_width do not describe a matrix and its gradients")
-        ids, _need, _total = self._batch_metadata(circuits)
-        wrt_offsets, wrt_flat, _counts = self._wrt_arguments(circuits, wrt)
-        self._check_gradient(self._lib.qsv_adjoint_gradient_device(
-            self._handle, n, _lib.as_ptr(ids), int(width), C.c_void_p(matrix_ptr) if width else None,
-            C.c_void_p(event) if event else None, _lib.as_ptr(wrt_offsets) if wrt_offsets is not None else None,
-            _lib.as_ptr(wrt_flat) if wrt_flat is not None else None, int(out_width), C.c_void_p(out_ptr) if out_width else None,
-            C.c_void_p(values_ptr) if values_ptr else None))
-        self.last_gradient_evaluations = n
-        return n
+        self._device_gradients(self._lib.qsv_adjoint_gradient_device, circuits, matrix_ptr, width, event, out_ptr, out_width, wrt,
+                               _pointer(values_ptr))
+        self.last_gradient_evaluations = len(circuits)
+        return self.last_gradient_evaluations
 
     def adjoint_stats(self) -> dict:
         """``qsv_adjoint_stats``: the last adjoint call's swept gates, run-kernel launches and state sweeps, the adjoint scratch's
         size and how often it was allocated or grown since the device was created."""
         stats = _lib.QsvAdjointStats()
         self._check(self._lib.qsv_adjoint_stats(self._handle, C.byref(stats)))
-        return {name: int(getattr(stats, name)) for name, _ in _lib.QsvAdjointStats._fields_}
+        return _struct_dict(stats)
 
     # -- the operator's variance ------------------------------------------------------------------
     def variances(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]]) -> tuple[np.ndarray, np.ndarray]:
@@ -1182,17 +1209,13 @@ class StatevectorDevice:
         the state's distribution, and ``sqrt(variance / shots)`` the statistical error of a finite-shot estimate.  Raw numbers:
         rounding may leave a variance a tiny bit below zero.  Deterministic; the values agree with :meth:`expectation_values`
         to rounding.  A circuit on a kept state raises ``ValueError``."""
-        n = len(circuits)
-        if len(parameter_values) != n:
-            raise ValueError("circuits and parameter_values must have the same length")
-        values = np.zeros(n, dtype=np.float64)
-        variances = np.zeros(n, dtype=np.float64)
-        if n == 0:
+        batch = _HostBatch(self, circuits, parameter_values)
+        values = np.zeros(batch.n, dtype=np.float64)
+        variances = np.zeros(batch.n, dtype=np.float64)
+        if batch.n == 0:
             return values, variances
-        ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
         # (a refused circuit -- QSV_E_UNSUPPORTED: one on a kept state -- as a ValueError with the library's message)
-        self._check_gradient(self._lib.qsv_variance_circuits(
-            self._handle, n, _lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat), _lib.as_ptr(variances), _lib.as_ptr(values)))
+        self._check_gradient(self._lib.qsv_variance_circuits(self._handle, *batch.arguments(), _lib.as_ptr(variances), _lib.as_ptr(values)))
         return values, variances
 
     # -- several observables ---------------------------------------------------------------------
@@ -1234,19 +1257,15 @@ class StatevectorDevice:
     ) -> np.ndarray:
         """``real(<psi_i|O_m|psi_i>)`` for every (circuit, parameter vector) pair i and operator m, a ``(len(circuits),
         len(operators))`` array (``qsv_eval_observables``).  Does not use or change the operator set on the device."""
-        n = len(circuits)
-        if len(parameter_values) != n:
-            raise ValueError("circuits and parameter_values must have the same length")
+        batch = _HostBatch(self, circuits, parameter_values)
         operators = list(operators)
         if not operators:
             raise ValueError("at least one observable is needed")
         set_id = self._observable_set(operators)
-        if n == 0:
+        if batch.n == 0:
             return np.zeros((0, len(operators)), dtype=np.float64)
-        ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
-        out = np.empty((n, len(operators)), dtype=np.float64)
-        self._check(self._lib.qsv_eval_observables(self._handle, set_id, n, _lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat),
-                                                    _lib.as_ptr(out)))
+        out = np.empty((batch.n, len(operators)), dtype=np.float64)
+        self._check(self._lib.qsv_eval_observables(self._handle, set_id, *batch.arguments(), _lib.as_ptr(out)))
         return out
 
     MAX_COVARIANCE_OBSERVABLES = 64  # (QSV_COVARIANCE_MAX_OBSERVABLES)
@@ -1260,9 +1279,7 @@ class StatevectorDevice:
         symmetric, its diagonal the operators' variances, and ``w @ C[i] @ w`` the variance of ``sum_m w_m O_m``.  Raw numbers:
         rounding may leave a diagonal entry a tiny bit below zero.  Deterministic; does not use or change the operator set on
         the device.  At most :attr:`MAX_COVARIANCE_OBSERVABLES` operators; a circuit on a kept state raises ``ValueError``."""
-        n = len(circuits)
-        if len(parameter_values) != n:
-            raise ValueError("circuits and parameter_values must have the same length")
+        batch = _HostBatch(self, circuits, parameter_values)
         operators = list(operators)
         if not operators:
             raise ValueError("at least one observable is needed")
@@ -1270,14 +1287,13 @@ class StatevectorDevice:
         if m > self.MAX_COVARIANCE_OBSERVABLES:
             raise ValueError(f"covariances are available for at most {self.MAX_COVARIANCE_OBSERVABLES} observables, not {m}")
         set_id = self._observable_set(operators)
-        values = np.zeros((n, m), dtype=np.float64)
-        covariances = np.zeros((n, m, m), dtype=np.float64)
-        if n == 0:
+        values = np.zeros((batch.n, m), dtype=np.float64)
+        covariances = np.zeros((batch.n, m, m), dtype=np.float64)
+        if batch.n == 0:
             return values, covariances
-        ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
         # (a refused circuit -- QSV_E_UNSUPPORTED: one on a kept state -- as a ValueError with the library's message)
         self._check_gradient(self._lib.qsv_observables_covariance(
-            self._handle, set_id, n, _lib.as_ptr(ids), _lib.as_ptr(offsets), _lib.as_ptr(flat), _lib.as_ptr(values), _lib.as_ptr(covariances)))
+            self._handle, set_id, *batch.arguments(), _lib.as_ptr(values), _lib.as_ptr(covariances)))
         return values, covariances
 
     # -- two states at a time -----------------------------------------------------------------------
@@ -1292,9 +1308,8 @@ class StatevectorDevice:
         row depends on its circuit and point alone, a column on its kept state alone.  More than
         :attr:`MAX_OVERLAP_STATES` kept states are served in blocks of that many, one library call each.  A kept state of
         another device, or a released one, and a circuit that itself continues a kept state raise ``ValueError``."""
-        n = len(circuits)
-        if len(parameter_values) != n:
-            raise ValueError("circuits and parameter_values must have the same length")
+        batch = _HostBatch(self, circuits, parameter_values)
+        n = batch.n
         kept_states = list(kept_states)
         if not kept_states:
             raise ValueError("at least one kept state is needed")
@@ -1309,15 +1324,14 @@ class StatevectorDevice:
         overlaps = np.zeros((n, k_all), dtype=np.complex128)
         elements = np.zeros((n, k_all), dtype=np.complex128) if with_operator else None
         if n > 0:
-            ids, offsets, flat = self._batch_arguments(circuits, parameter_values)
+            arguments = batch.arguments()
             for k0 in range(0, k_all, self.MAX_OVERLAP_STATES):
                 block = np.asarray([kept._id for kept in kept_states[k0:k0 + self.MAX_OVERLAP_STATES]], dtype=np.int32)
                 s = np.zeros((n, len(block)), dtype=np.complex128)
                 t = np.zeros((n, len(block)), dtype=np.complex128) if with_operator else None
                 # (a refusal with QSV_E_UNSUPPORTED as a ValueError with the library's message)
                 self._check_gradient(self._lib.qsv_overlap_circuits(
-                    self._handle, len(block), _lib.as_ptr(block), int(bool(with_operator)), n, _lib.as_ptr(ids), _lib.as_ptr(offsets),
-                    _lib.as_ptr(flat), _lib.as_ptr(s), _lib.as_ptr(t) if with_operator else None))
+                    self._handle, len(block), _lib.as_ptr(block), int(bool(with_operator)), *arguments, _lib.as_ptr(s), _pointer(t)))
                 overlaps[:, k0:k0 + len(block)] = s
                 if with_operator:
                     elements[:, k0:k0 + len(block)] = t
@@ -1342,11 +1356,7 @@ class StatevectorDevice:
     def profile(self) -> dict:
         prof = _lib.QsvProfile()
         self._check(self._lib.qsv_get_profile(self._handle, C.byref(prof)))
-        out = {}
-        for name, ctype in prof._fields_:
-            value = getattr(prof, name)
-            out[name] = list(value) if hasattr(value, "__len__") else value
-        return out
+        return _struct_dict(prof)
 
     def replayed_pushes(self) -> int:
         """Pushes of this handle so far that queued a kept layout's recorded launches again (``qsv_replayed_pushes``; option
@@ -1412,6 +1422,18 @@ class _ComposedCircuits:
             self._entries[key] = (weakref.ref(circuit, lambda _r, k=key: entries.pop(k, None)), circuit._version, composed)
         return composed
 
+    def get_all(self, circuits: list) -> list:
+        """:meth:`get` of every circuit, composed anew at every call; ``circuits`` itself where there is no initial state."""
+        if self._initial is None:
+            return circuits
+        return [self.get(c) for c in circuits]
+
+
+def _present_pairs(circuits, parameter_values) -> tuple[list, list]:
+    """``(circuits, parameter_values)`` without the pairs of which either half is None (the reference skips those)."""
+    pairs = [(c, p) for c, p in zip(circuits, parameter_values) if c is not None and p is not None]
+    return [c for c, _ in pairs], [p for _, p in pairs]
+
 
 def _check_initial_state(initial_state_circuit: Optional[CircuitIR], n_qubits: int, what: str) -> None:
     if initial_state_circuit is not None and initial_state_circuit.num_qubits != n_qubits:
@@ -1421,29 +1443,67 @@ def _check_initial_state(initial_state_circuit: Optional[CircuitIR], n_qubits: i
         )
 
 
-def _composed_list(evaluator, circuits: list) -> list:
-    """``circuits`` behind the evaluator's initial state, kept by IDENTITY of the list: the device-to-device methods are called
-    with the same list object iteration after iteration, and the library keys its batch layout on the composed circuits.  (One
-    list is kept: a caller that alternates between two composes at every change.)"""
-    if evaluator._initial_state_circuit is None:
-        return circuits
-    kept = evaluator._composed_lists
-    if kept is None or kept[0] is not circuits:
-        kept = evaluator._composed_lists = (circuits, [evaluator._composed.get(c) for c in circuits])
-    return kept[1]
+class _OperatorEvaluator(BaseCircuitEvaluator):
+    """What the two operator evaluators share: the device (theirs alone, or one that several evaluators use), the operator
+    and the only way to it, and the circuits behind the initial state."""
 
+    def __init__(self, operator: PauliOperator, initial_state_circuit: Optional[CircuitIR], dtype: str, device: int,
+                 statevector_device: Optional["StatevectorDevice"]):
+        self._operator = operator
+        self._initial_state_circuit = initial_state_circuit
+        self._device = statevector_device or StatevectorDevice(operator.num_qubits, dtype=dtype, device=device)
+        with self._device.operator_lock:
+            self._device.set_operator(operator)
+        self._composed = _ComposedCircuits(initial_state_circuit)
+        self._composed_lists = None  # (_behind_initial_state: the last list of circuits kept by identity, and its composition)
+        self._last_matrix = None     # (_device_matrix_arguments)
 
-def _evaluator_top_states(evaluator, circuits: list, parameter_values: list, k: int):
-    """:meth:`StatevectorDevice.top_states` for an operator evaluator's circuits: behind its initial state, and with the
-    operator's values (else ``None``) when its operator is diagonal -- set on the shared device inside the operator lock, as
-    every evaluation does."""
-    circuits = [evaluator._composed.get(c) for c in circuits]
-    device = evaluator._device
-    with device.operator_lock:
-        with_values = evaluator._operator.is_diagonal()
-        if with_values and device._operator is not evaluator._operator:
-            device.set_operator(evaluator._operator)
-        return device.top_states(circuits, parameter_values, k, with_values=with_values)
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["_last_matrix"] = None     # (a weak reference to a tensor of this process does not travel)
+        state["_composed_lists"] = None  # (a cache travels empty, as _ComposedCircuits does)
+        return state
+
+    @property
+    def n_qubits(self) -> int:
+        return self._operator.num_qubits
+
+    @property
+    def statevector_device(self) -> StatevectorDevice:
+        return self._device
+
+    def _own_operator(self):
+        """:meth:`StatevectorDevice.with_operator` for this evaluator's operator: around everything that reads it there."""
+        return _OperatorInstalled(self._device, self._operator)
+
+    def _behind_initial_state(self, circuits: list, same_list_every_call: bool = False) -> list:
+        """``circuits`` behind the evaluator's initial state.  Composed per call (:meth:`_ComposedCircuits.get_all`, which
+        knows a circuit by identity and version), so a list changed in place is seen.  ``same_list_every_call`` is for the
+        device-to-device methods alone, whose docstrings ask for the same list object iteration after iteration: the composed
+        list is kept by IDENTITY of the caller's list and handed out again as the same object.  (One list is kept: a caller
+        that alternates between two composes at every change.)"""
+        if not same_list_every_call or self._initial_state_circuit is None:
+            return self._composed.get_all(circuits)
+        kept = self._composed_lists
+        if kept is None or kept[0] is not circuits:
+            kept = self._composed_lists = (circuits, self._composed.get_all(circuits))
+        return kept[1]
+
+    def top_states(self, circuits: list, parameter_values: list, k: int):
+        """:meth:`StatevectorDevice.top_states` for the evaluator's circuits: behind its initial state, and with the
+        operator's values (else ``None``) when its operator is diagonal -- only then is it installed on the shared device."""
+        circuits = self._behind_initial_state(circuits)
+        with_values = self._operator.is_diagonal()
+        with self._own_operator() if with_values else self._device.operator_lock:
+            return self._device.top_states(circuits, parameter_values, k, with_values=with_values)
+
+    @staticmethod
+    def _torch_sees_a_gpu() -> bool:
+        try:
+            import torch
+        except ImportError:
+            return False
+        return torch.cuda.is_available()
 
 
 def _is_device_matrix(tensor, n_rows: int, device, width: Optional[int] = None) -> bool:
@@ -1477,27 +1537,31 @@ def _device_matrix_arguments(evaluator, circuits, matrix, ready: bool):
             raise ValueError("a device-resident parameter matrix must be a contiguous 2-D float64 tensor")
         if matrix.device.index != evaluator._device.device_index:
             raise ValueError("the parameter matrix lives on another device than the evaluator")
-    if shape[0] != len(circuits):
+    if shape[0] != len(circuits):  # (_same_length, written out: every call of the benchmark's step comes through here)
         raise ValueError("circuits and parameter_values must have the same length")
     if _has_none(circuits):
         raise ValueError("a device-resident parameter matrix cannot skip circuits (None entries)")
-    event, marker = 0, None
-    if seen:
-        ready = True
-    stream = None if ready else torch.cuda.current_stream(matrix.device)
-    if stream is not None and not stream.query():
-        # (whatever produces the matrix was queued on the tensor's current stream and has not finished: the handle's
-        # streams wait for it.  An idle stream -- the usual case -- costs one query instead of an event and four waits.)
-        # (an event of this call's own: evaluators are shared by threads, whose tensors may come from different streams)
-        marker = torch.cuda.Event()
-        marker.record(stream)
-        event = marker.cuda_event
+    marker = None if ready or seen else _ready_event(matrix)
 
     def remember(_marker=marker):  # (holds the event until the call that waits for it has been made)
         if not seen:
             evaluator._last_matrix = (weakref.ref(owner), stamp)
 
-    return stamp[1], stamp[3], event, remember
+    return stamp[1], stamp[3], marker.cuda_event if marker is not None else 0, remember
+
+
+def _ready_event(matrix):
+    """A recorded event after which whatever was queued on ``matrix``'s current stream has finished, for the handle's streams
+    to wait for; None when that stream is idle -- the usual case, which costs one query instead of an event and four waits.
+    (An event of the call's own: evaluators are shared by threads, whose tensors may come from different streams.)"""
+    import torch
+
+    stream = torch.cuda.current_stream(matrix.device)
+    if stream.query():
+        return None
+    marker = torch.cuda.Event()
+    marker.record(stream)
+    return marker
 
 
 class EvaluatorGradientPlan:
@@ -1517,21 +1581,12 @@ class EvaluatorGradientPlan:
         """Gradients at the rows of ``matrix`` into ``out`` -- tensors of the shapes the plan was made for, on the stream of the
         evaluator's handle --, queued and not waited for.  ``ready=False``: ``matrix`` is being written on the tensor's current
         stream, which is not the handle's; the handle's stream waits for it.  Returns the circuit evaluations queued."""
-        import torch
-
         evaluator, plan = self._evaluator, self._plan
         for tensor, width in ((matrix, plan.width), (out, plan.out_width)):
             if not _is_device_matrix(tensor, self._n, self._where, width):
                 raise ValueError("matrix and out must be the contiguous float64 device tensors of the shapes the plan was made for")
-        marker = None
-        if not ready:
-            stream = torch.cuda.current_stream(matrix.device)
-            if not stream.query():
-                marker = torch.cuda.Event()
-                marker.record(stream)
-        with evaluator._device.operator_lock:
-            if evaluator._device._operator is not evaluator._operator:
-                evaluator._device.set_operator(evaluator._operator)
+        marker = None if ready else _ready_event(matrix)
+        with evaluator._own_operator():
             try:
                 return plan.run(matrix.data_ptr() if plan.width else 0, marker.cuda_event if marker is not None else 0,
                                 out.data_ptr() if plan.out_width else 0)
@@ -1557,7 +1612,7 @@ def _has_shared_parameter(circuit: CircuitIR) -> bool:
     return len(np.unique(slots)) != len(slots)
 
 
-class OperatorCircuitEvaluator(BaseCircuitEvaluator):
+class OperatorCircuitEvaluator(_OperatorEvaluator):
     """Exact expectation values of ``operator`` on the GPU (estimator branch of the reference).
 
     :param operator: observable; if it is not hermitian the imaginary part of the result is dropped
@@ -1594,29 +1649,11 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         _check_initial_state(initial_state_circuit, operator.num_qubits, "the amount of qubits in the given operator")
         if initial_state_circuit is not None and initial_state_circuit.num_parameters:
             raise ValueError("The initial state circuit must not have free parameters!")
-        self._operator = operator
         self._precision = float(estimator_precision)
-        self._initial_state_circuit = initial_state_circuit
         self._rng = np.random.default_rng(seed)
-        self._device = statevector_device or StatevectorDevice(operator.num_qubits, dtype=dtype, device=device)
-        if self._device.n_qubits != operator.num_qubits:
+        if statevector_device is not None and statevector_device.n_qubits != operator.num_qubits:
             raise ValueError("statevector_device was created for a different number of qubits")
-        with self._device.operator_lock:
-            self._device.set_operator(operator)
-        self._composed = _ComposedCircuits(initial_state_circuit)
-        self._composed_lists = None
-        self._last_matrix = None
-
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state["_last_matrix"] = None  # (a weak reference to a tensor of this process)
-        return state
-
-    def _with_initial_state(self, circuit: CircuitIR) -> CircuitIR:
-        return self._composed.get(circuit)
-
-    _composed_list = _composed_list
-    top_states = _evaluator_top_states
+        super().__init__(operator, initial_state_circuit, dtype, device, statevector_device)
 
     def evaluate_circuits(self, circuits: list[CircuitIR], parameter_values: list[list[float]]) -> list[float]:
         """``parameter_values`` may also be a 2-D float64 tensor in THIS device's memory (anything with ``is_cuda`` /
@@ -1626,11 +1663,11 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         pointer -- has to be complete when it is handed over.)"""
         matrix = parameter_values if getattr(parameter_values, "is_cuda", False) else None
         if matrix is None and (_has_none(circuits) or _has_none(parameter_values)):
-            pairs = [(c, p) for c, p in zip(circuits, parameter_values) if c is not None and p is not None]
-            circuits, parameter_values = [c for c, _ in pairs], [p for _, p in pairs]
+            circuits, parameter_values = _present_pairs(circuits, parameter_values)
         if self._initial_state_circuit is not None:
-            circuits = [self._with_initial_state(c) for c in circuits]
-        # evaluators may share one device: "is it my operator? else set it" and the evaluation are one critical section
+            circuits = self._behind_initial_state(circuits)
+        # The guard (StatevectorDevice.with_operator), written out in this one method: it is the benchmark's route, and behind
+        # the guard object the headline's median was 1.2 % lower (0.5 us of a 38 us step; profiles/r22_python_layer.txt).
         with self._device.operator_lock:
             if self._device._operator is not self._operator:
                 self._device.set_operator(self._operator)
@@ -1650,10 +1687,8 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         (:meth:`StatevectorDevice.variances`); with ``with_values`` the pair ``(values, variances)`` of two
         lists, the values from the same pass over the state.  Exact numbers: ``estimator_precision`` adds no noise here, and no
         random number is drawn."""
-        circuits = self._composed_list(circuits)
-        with self._device.operator_lock:
-            if self._device._operator is not self._operator:
-                self._device.set_operator(self._operator)
+        circuits = self._behind_initial_state(circuits)
+        with self._own_operator():
             values, variances = self._device.variances(circuits, parameter_values)
         return (values.tolist(), variances.tolist()) if with_values else variances.tolist()
 
@@ -1663,9 +1698,7 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         """``real(<psi_i|O_m|psi_i>)`` of every circuit (behind this evaluator's initial state) and observable, one row per
         circuit (:meth:`StatevectorDevice.observable_values`); with ``estimator_precision > 0`` each value gets its own Gaussian
         noise, as in :meth:`evaluate_circuits`.  The evaluator's own operator is neither used nor changed."""
-        if self._initial_state_circuit is not None:
-            circuits = [self._with_initial_state(c) for c in circuits]
-        values = self._device.observable_values(circuits, parameter_values, operators)
+        values = self._device.observable_values(self._behind_initial_state(circuits), parameter_values, operators)
         if self._precision > 0:
             values = values + self._rng.normal(0.0, self._precision, size=values.shape)
         return values.tolist()
@@ -1678,8 +1711,7 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         4.14); with ``with_values`` the pair ``(values, covariances)``, the ``(n, M)`` values from the same pass over the state.
         Exact numbers: ``estimator_precision`` adds no noise here, and no random number is drawn.  The evaluator's own operator
         is neither used nor changed."""
-        circuits = self._composed_list(circuits)
-        values, covariances = self._device.observable_covariances(circuits, parameter_values, operators)
+        values, covariances = self._device.observable_covariances(self._behind_initial_state(circuits), parameter_values, operators)
         return (values, covariances) if with_values else covariances
 
     def evaluate_overlaps(self, circuits: list[CircuitIR], parameter_values: list[list[float]], kept_states: Sequence[KeptState],
@@ -1688,14 +1720,11 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         states (:meth:`keep_states`), a complex128 ``(n, K)`` array (:meth:`StatevectorDevice.overlaps`); with
         ``with_operator`` the pair ``(S, T)``, ``T[i, k] = <phi_k|H|psi_i>`` for the evaluator's operator.  Exact numbers:
         ``estimator_precision`` adds no noise here, and no random number is drawn."""
-        if len(parameter_values) != len(circuits):
-            raise ValueError("circuits and parameter_values must have the same length")
-        circuits = self._composed_list(circuits)
+        _same_length(len(circuits), len(parameter_values))
+        circuits = self._behind_initial_state(circuits)
         if not with_operator:
             return self._device.overlaps(circuits, parameter_values, kept_states)
-        with self._device.operator_lock:
-            if self._device._operator is not self._operator:
-                self._device.set_operator(self._operator)
+        with self._own_operator():
             return self._device.overlaps(circuits, parameter_values, kept_states, with_operator=True)
 
     def evaluate_subspace_matrices(self, circuits: list[CircuitIR], parameter_values: list[list[float]]):
@@ -1704,9 +1733,7 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         the states needs (``evqe.subspace.lowest_subspace_eigenvalue``).  The states are kept with :meth:`keep_states` in blocks
         of 64, the whole batch is evaluated against each block, and the block is released.  Raw numbers: the matrices are
         Hermitian to rounding only and are not symmetrised.  Exact, as :meth:`evaluate_overlaps`."""
-        n = len(circuits)
-        if len(parameter_values) != n:
-            raise ValueError("circuits and parameter_values must have the same length")
+        n = _same_length(len(circuits), len(parameter_values))
         s = np.zeros((n, n), dtype=np.complex128)
         h = np.zeros((n, n), dtype=np.complex128)
         block = StatevectorDevice.MAX_OVERLAP_STATES
@@ -1733,11 +1760,8 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         complete already (the caller synchronised, or it has not changed since an earlier call): no event is recorded."""
         if self._precision > 0:
             raise ValueError("estimator_precision > 0 is emulated on the host: use evaluate_circuits")
-        if self._initial_state_circuit is not None:
-            circuits = [self._with_initial_state(c) for c in circuits]
-        with self._device.operator_lock:
-            if self._device._operator is not self._operator:
-                self._device.set_operator(self._operator)
+        circuits = self._behind_initial_state(circuits)
+        with self._own_operator():
             return self._evaluate_device_matrix(circuits, matrix, ready)
 
     #: circuit evaluations the last :meth:`evaluate_gradients` / :meth:`evaluate_gradients_device_to_device` call ran (a circuit
@@ -1755,11 +1779,8 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         :attr:`last_gradient_evaluations` counts the circuit evaluations the call ran (one per circuit the sweep took)."""
         if self._precision > 0:
             raise ValueError("estimator_precision > 0 is emulated on the host: gradients are exact")
-        if self._initial_state_circuit is not None:
-            circuits = [self._with_initial_state(c) for c in circuits]
-        with self._device.operator_lock:
-            if self._device._operator is not self._operator:
-                self._device.set_operator(self._operator)
+        circuits = self._behind_initial_state(circuits)
+        with self._own_operator():
             if self.gradient_method == "parameter_shift":
                 try:
                     return self._device.gradients(circuits, parameter_values, wrt)
@@ -1775,17 +1796,21 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         return [i for i, c in enumerate(circuits)
                 if self._device.circuit_cost(c)["route"] == "gate passes" or _has_shared_parameter(c)]
 
-    @staticmethod
-    def _wrt_per_circuit(n: int, wrt):
-        """``wrt`` of a gradient call as one entry per circuit (None: every parameter)."""
-        if wrt is None:
-            return [None] * n
-        wrt = list(wrt)
-        if all(np.ndim(w) == 0 for w in wrt):
-            return [wrt] * n
-        if len(wrt) != n:
-            raise ValueError("wrt must be None, one list of parameter indices, or one list per circuit")
-        return wrt
+    def _parts_by_method(self, circuits, wrt) -> tuple[tuple, tuple]:
+        """A gradient call's batch split by method (operator lock held): ``(rows, circuits, wrt)`` of the part that goes to the
+        adjoint sweep and of the part that goes to parameter shift -- ``rows`` the places in the caller's batch, ``wrt`` one list
+        of parameter indices per circuit of the part, or None for every parameter."""
+        per_circuit = _wrt_per_circuit(len(circuits), wrt)
+        sweep = self._adjoint_rows(circuits)
+        taken = set(sweep)
+        shift = [i for i in range(len(circuits)) if i not in taken]
+
+        def part(rows):
+            part_wrt = None if per_circuit is None else [
+                list(range(circuits[i].num_parameters)) if per_circuit[i] is None else per_circuit[i] for i in rows]
+            return rows, [circuits[i] for i in rows], part_wrt
+
+        return part(sweep), part(shift)
 
     def _gradients_by_method(self, circuits, parameter_values, wrt) -> list[np.ndarray]:
         """``evaluate_gradients`` for "adjoint" and "auto": the batch split by method, the rows put back in the caller's order
@@ -1794,23 +1819,18 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         self.last_gradient_evaluations = 0
         if n == 0:
             return []
-        per_circuit = self._wrt_per_circuit(n, wrt)
-        sweep = self._adjoint_rows(circuits)
-        taken = set(sweep)
-        shift = [i for i in range(n) if i not in taken]
+        sweep, shift = self._parts_by_method(circuits, wrt)
         out: list = [None] * n
         evaluations = 0
         counts = [1] * n
-        for i in shift:
-            terms = circuits[i].gradient_terms()
-            counts[i] = sum(max(0, terms[p]) for p in (range(len(terms)) if per_circuit[i] is None else per_circuit[i]))
+        for i, circuit, indices in zip(shift[0], shift[1], shift[2] or [None] * n):
+            terms = circuit.gradient_terms()
+            counts[i] = sum(max(0, terms[p]) for p in (range(len(terms)) if indices is None else indices))
         self.last_gradient_evaluation_counts = counts
-        for rows, method in ((sweep, self._device.adjoint_gradients), (shift, self._device.gradients)):
+        for (rows, part_circuits, part_wrt), method in ((sweep, self._device.adjoint_gradients), (shift, self._device.gradients)):
             if not rows:
                 continue
-            part_wrt = None if wrt is None else [
-                list(range(circuits[i].num_parameters)) if per_circuit[i] is None else per_circuit[i] for i in rows]
-            part = method([circuits[i] for i in rows], [parameter_values[i] for i in rows], part_wrt)
+            part = method(part_circuits, [parameter_values[i] for i in rows], part_wrt)
             evaluations += self._device.last_gradient_evaluations
             for i, row in zip(rows, part):
                 out[i] = row
@@ -1825,7 +1845,7 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
 
         if self._precision > 0:
             raise ValueError("estimator_precision > 0 is emulated on the host")
-        circuits = self._composed_list(circuits)
+        circuits = self._behind_initial_state(circuits, same_list_every_call=True)
         pointer, width, event, remember = _device_matrix_arguments(self, circuits, matrix, ready=True)
         n = len(circuits)
         if not _is_device_matrix(out, n, matrix.device):
@@ -1833,9 +1853,7 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         _offsets, _flat, counts = StatevectorDevice._wrt_arguments(circuits, wrt)
         if n and int(counts.max()) > out.shape[1]:
             raise ValueError(f"the output has rows of {out.shape[1]} entries, a circuit's gradient has {int(counts.max())}")
-        with self._device.operator_lock:
-            if self._device._operator is not self._operator:
-                self._device.set_operator(self._operator)
+        with self._own_operator():
             if self.gradient_method == "parameter_shift":
                 try:
                     self._device.gradients_of_device_parameters(circuits, pointer, width, event, out.data_ptr(), out.shape[1], wrt)
@@ -1855,28 +1873,23 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         self.last_gradient_evaluations = 0
         if n == 0:
             return
-        sweep = self._adjoint_rows(circuits)
-        if len(sweep) == n:
+        sweep, shift = self._parts_by_method(circuits, wrt)
+        if not shift[0]:
             self._device.adjoint_gradients_of_device_parameters(circuits, pointer, width, event, out.data_ptr(), out.shape[1], wrt)
             self.last_gradient_evaluations = n
             return
-        if not sweep:
+        if not sweep[0]:
             self._device.gradients_of_device_parameters(circuits, pointer, width, event, out.data_ptr(), out.shape[1], wrt)
             self.last_gradient_evaluations = self._device.last_gradient_evaluations
             return
-        per_circuit = self._wrt_per_circuit(n, wrt)
-        taken = set(sweep)
-        shift = [i for i in range(n) if i not in taken]
         evaluations = 0
-        for rows, method in ((sweep, self._device.adjoint_gradients_of_device_parameters),
-                             (shift, self._device.gradients_of_device_parameters)):
+        for (rows, part_circuits, part_wrt), method in ((sweep, self._device.adjoint_gradients_of_device_parameters),
+                                                        (shift, self._device.gradients_of_device_parameters)):
             index = torch.tensor(rows, dtype=torch.int64, device=matrix.device)
             points = matrix.index_select(0, index).contiguous()
             part = torch.zeros((len(rows), out.shape[1]), dtype=torch.float64, device=matrix.device)
-            part_wrt = None if wrt is None else [
-                list(range(circuits[i].num_parameters)) if per_circuit[i] is None else per_circuit[i] for i in rows]
             torch.cuda.synchronize(matrix.device)  # (the gathered points are complete)
-            method([circuits[i] for i in rows], points.data_ptr(), int(points.shape[1]), 0, part.data_ptr(), int(part.shape[1]), part_wrt)
+            method(part_circuits, points.data_ptr(), int(points.shape[1]), 0, part.data_ptr(), int(part.shape[1]), part_wrt)
             evaluations += self._device.last_gradient_evaluations
             torch.cuda.synchronize(matrix.device)  # (... and so are the part's rows)
             out.index_copy_(0, index, part)
@@ -1891,8 +1904,7 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
 
         if self._precision > 0:
             raise ValueError("estimator_precision > 0 is emulated on the host")
-        if self._initial_state_circuit is not None:
-            circuits = [self._with_initial_state(c) for c in circuits]
+        circuits = self._behind_initial_state(circuits)
         n = len(circuits)
         for name, tensor in (("matrix", matrix), ("out", out)):
             if not _is_device_matrix(tensor, n, torch.device("cuda", self._device.device_index)):
@@ -1902,9 +1914,7 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         _offsets, _flat, counts = StatevectorDevice._wrt_arguments(circuits, wrt)
         if n and int(counts.max()) > out.shape[1]:
             raise ValueError(f"the output has rows of {out.shape[1]} entries, a circuit's gradient has {int(counts.max())}")
-        with self._device.operator_lock:
-            if self._device._operator is not self._operator:
-                self._device.set_operator(self._operator)
+        with self._own_operator():
             plan = self._device.gradient_plan(circuits, int(matrix.shape[1]), int(out.shape[1]), wrt)
         return EvaluatorGradientPlan(self, plan, n)
 
@@ -1912,9 +1922,7 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         """The final states of the (circuit, parameter vector) pairs -- behind this evaluator's initial state, if it has one --
         kept resident on the device (:meth:`StatevectorDevice.keep_states`); circuits made with
         ``CircuitIR.continue_from(state)`` are then evaluated from there by every method of this class."""
-        if self._initial_state_circuit is not None:
-            circuits = [self._with_initial_state(c) for c in circuits]
-        return self._device.keep_states(circuits, parameter_values)
+        return self._device.keep_states(self._behind_initial_state(circuits), parameter_values)
 
     def forget_circuits(self) -> None:
         """:meth:`StatevectorDevice.forget_last_batch`, and this evaluator's own memory of its last list of circuits."""
@@ -1923,11 +1931,8 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
 
     def circuit_costs(self, circuits: list[CircuitIR]) -> list[dict]:
         """:meth:`StatevectorDevice.circuit_cost` of every circuit as this evaluator would run it (its operator set)."""
-        if self._initial_state_circuit is not None:
-            circuits = [self._with_initial_state(c) for c in circuits]
-        with self._device.operator_lock:
-            if self._device._operator is not self._operator:
-                self._device.set_operator(self._operator)
+        circuits = self._behind_initial_state(circuits)
+        with self._own_operator():
             self._device._register_many([c for c in circuits if self._device._serial not in c._registered])
             return [self._device.circuit_cost(c) for c in circuits]
 
@@ -1938,13 +1943,7 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
     def device_resident_search_possible(self) -> bool:
         """Can an optimiser keep its points and values in this evaluator's device memory (:meth:`evaluate_device_to_device`)?
         Only the exact estimator: noise is emulated on the host."""
-        if self._precision > 0:
-            return False
-        try:
-            import torch
-        except ImportError:
-            return False
-        return torch.cuda.is_available()
+        return self._precision <= 0 and self._torch_sees_a_gpu()
 
     def evaluate_device_to_device(self, circuits: list[CircuitIR], matrix, out) -> None:
         """Parameter values from a device matrix (one row per circuit), expectation values into the device tensor ``out``
@@ -1954,10 +1953,8 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         state and its device-side ids are kept by identity)."""
         if self._precision > 0:
             raise ValueError("estimator_precision > 0 is emulated on the host")
-        circuits = self._composed_list(circuits)
-        with self._device.operator_lock:
-            if self._device._operator is not self._operator:
-                self._device.set_operator(self._operator)
+        circuits = self._behind_initial_state(circuits, same_list_every_call=True)
+        with self._own_operator():
             self._evaluate_device_matrix(circuits, matrix, ready=True, out_device_pointer=out.data_ptr())
 
     def evaluate_circuits_to_device(self, circuits: list[CircuitIR], parameter_values: list[list[float]], device_pointer: int) -> bool:
@@ -1967,24 +1964,13 @@ class OperatorCircuitEvaluator(BaseCircuitEvaluator):
         matrix = parameter_values if getattr(parameter_values, "is_cuda", False) else None
         if self._precision > 0 or _has_none(circuits) or (matrix is None and _has_none(parameter_values)):
             return False
-        if self._initial_state_circuit is not None:
-            circuits = [self._with_initial_state(c) for c in circuits]
-        with self._device.operator_lock:
-            if self._device._operator is not self._operator:
-                self._device.set_operator(self._operator)
+        circuits = self._behind_initial_state(circuits)
+        with self._own_operator():
             if matrix is not None:
                 self._evaluate_device_matrix(circuits, matrix, out_device_pointer=device_pointer)
             else:
                 self._device.expectation_values_to_device(circuits, parameter_values, device_pointer)
         return True
-
-    @property
-    def n_qubits(self) -> int:
-        return self._operator.num_qubits
-
-    @property
-    def statevector_device(self) -> StatevectorDevice:
-        return self._device
 
 
 def measure_quasi_distributions(
@@ -2063,7 +2049,7 @@ def _cvar_of_sample_matrix(values: np.ndarray, alpha: float) -> list[float]:
     return (total / mass).tolist()
 
 
-class OperatorSamplerCircuitEvaluator(BaseCircuitEvaluator):
+class OperatorSamplerCircuitEvaluator(_OperatorEvaluator):
     """Expectation / CVaR_alpha of a diagonal operator from ``sampler_shots`` measurements (reference [94-161]).
 
     ``sampler_shots=None`` (not in the reference, whose samplers always draw): the same quantity for the EXACT output
@@ -2090,32 +2076,12 @@ class OperatorSamplerCircuitEvaluator(BaseCircuitEvaluator):
         if alpha <= 0 or 1 < alpha:
             raise ValueError("alpha must be in the range (0, 1]!")
         _check_initial_state(initial_state_circuit, operator.num_qubits, "the amount of qubits in the given operator")
-        self._operator = operator
         if sampler_shots is not None and int(sampler_shots) < 1:
             raise ValueError("sampler_shots must be a positive number of shots, or None for the exact distribution!")
         self._shots = None if sampler_shots is None else int(sampler_shots)
         self._alpha = float(alpha)
-        self._initial_state_circuit = initial_state_circuit
         self._rng = np.random.default_rng(seed)
-        self._device = statevector_device or StatevectorDevice(operator.num_qubits, dtype=dtype, device=device)
-        with self._device.operator_lock:
-            self._device.set_operator(operator)
-        self._composed = _ComposedCircuits(initial_state_circuit)
-        self._last_matrix = None     # (_device_matrix_arguments)
-        self._composed_lists = None  # (evaluate_device_to_device: the last list of circuits behind the initial state)
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state["_last_matrix"] = None  # (a weak reference to a tensor does not travel)
-        state["_composed_lists"] = None
-        return state
-
-    @property
-    def statevector_device(self) -> StatevectorDevice:
-        return self._device
-
-    _composed_list = _composed_list
-    top_states = _evaluator_top_states
+        super().__init__(operator, initial_state_circuit, dtype, device, statevector_device)
 
     #: what ``device_resident_search=None`` of the solver's configuration means for this evaluator (evqe/solver.py): the host
     #: driver, as before the device search could take it -- ``True`` opts in
@@ -2127,11 +2093,7 @@ class OperatorSamplerCircuitEvaluator(BaseCircuitEvaluator):
         the host sorts the sample values."""
         if self._shots is not None and self._shots > StatevectorDevice.MAX_CVAR_SHOTS:
             return False
-        try:
-            import torch
-        except ImportError:
-            return False
-        return torch.cuda.is_available()
+        return self._torch_sees_a_gpu()
 
     def evaluate_device_to_device(self, circuits: list[CircuitIR], matrix, out, active=None, active_stride: int = 1) -> None:
         """Parameter values from a device matrix (one row per circuit), this evaluator's values -- what
@@ -2147,7 +2109,7 @@ class OperatorSamplerCircuitEvaluator(BaseCircuitEvaluator):
 
         if self._shots is not None and self._shots > StatevectorDevice.MAX_CVAR_SHOTS:
             raise ValueError(f"more than {StatevectorDevice.MAX_CVAR_SHOTS} shots are sorted on the host: use evaluate_circuits")
-        circuits = self._composed_list(circuits)
+        circuits = self._behind_initial_state(circuits, same_list_every_call=True)
         pointer, width, event, remember = _device_matrix_arguments(self, circuits, matrix, ready=True)
         n = len(circuits)
         if out.dtype != torch.float64 or out.numel() < n or not out.is_contiguous() or out.device != matrix.device:
@@ -2161,9 +2123,7 @@ class OperatorSamplerCircuitEvaluator(BaseCircuitEvaluator):
                 raise ValueError("the mask must be a contiguous uint8 or bool tensor on the matrix's device that covers every circuit")
             active_ptr = active.data_ptr()
         seed = int(self._rng.integers(0, 2**63 - 1))
-        with self._device.operator_lock:
-            if self._device._operator is not self._operator:
-                self._device.set_operator(self._operator)
+        with self._own_operator():
             # (sampler_shots=None with alpha = 1 is the expectation value, as in evaluate_circuits: the library takes that route)
             self._device.cvar_of_device_parameters(circuits, pointer, width, event, self._shots or 0, seed, self._alpha,
                                                    out.data_ptr(), active_ptr, active_stride)
@@ -2172,18 +2132,17 @@ class OperatorSamplerCircuitEvaluator(BaseCircuitEvaluator):
     def evaluate_circuits(self, circuits: list[CircuitIR], parameter_values: list[list[float]]) -> list[float]:
         """Samples every circuit on the device, gathers each sample's operator value from the device-resident diagonal
         table and takes the CVaR there as well (up to 4096 shots; beyond that the host sorts the values)."""
-        pairs = [(self._composed.get(c), p) for c, p in zip(circuits, parameter_values) if c is not None and p is not None]
+        circuits, parameter_values = _present_pairs(circuits, parameter_values)
+        circuits = self._behind_initial_state(circuits)
         seed = int(self._rng.integers(0, 2**63 - 1))
-        with self._device.operator_lock:
-            if self._device._operator is not self._operator:
-                self._device.set_operator(self._operator)
+        with self._own_operator():
             if self._shots is None:
                 if np.isclose(self._alpha, 1):  # (the reference takes the plain mean there: the expectation value)
-                    return self._device.expectation_values([c for c, _ in pairs], [p for _, p in pairs]).tolist()
-                return self._device.exact_cvar_batch([c for c, _ in pairs], [p for _, p in pairs], self._alpha)
+                    return self._device.expectation_values(circuits, parameter_values).tolist()
+                return self._device.exact_cvar_batch(circuits, parameter_values, self._alpha)
             if self._shots <= StatevectorDevice.MAX_CVAR_SHOTS:
-                return self._device.sample_cvar_batch([c for c, _ in pairs], [p for _, p in pairs], self._shots, seed, self._alpha)
-            _, values = self._device.sample_batch([c for c, _ in pairs], [p for _, p in pairs], self._shots, seed, with_values=True)
+                return self._device.sample_cvar_batch(circuits, parameter_values, self._shots, seed, self._alpha)
+            _, values = self._device.sample_batch(circuits, parameter_values, self._shots, seed, with_values=True)
         return _cvar_of_sample_matrix(values, self._alpha)
 
     def evaluate_observables(
@@ -2201,8 +2160,8 @@ class OperatorSamplerCircuitEvaluator(BaseCircuitEvaluator):
                 raise ValueError("The sampler branch needs a diagonal (I/Z only) operator!")
             if op.num_qubits != self.n_qubits:
                 raise ValueError(f"an observable acts on {op.num_qubits} qubits, the evaluator on {self.n_qubits}")
-        pairs = [(self._composed.get(c), p) for c, p in zip(circuits, parameter_values) if c is not None and p is not None]
-        circs, values = [c for c, _ in pairs], [p for _, p in pairs]
+        circs, values = _present_pairs(circuits, parameter_values)
+        circs = self._behind_initial_state(circs)
         if self._shots is None:
             if np.isclose(self._alpha, 1):
                 return self._device.observable_values(circs, values, operators).tolist()
@@ -2221,10 +2180,6 @@ class OperatorSamplerCircuitEvaluator(BaseCircuitEvaluator):
         states, _ = self._device.sample_batch(circs, values, self._shots, seed)
         columns = [_cvar_of_sample_matrix(_diagonal_values(op, states), self._alpha) for op in operators]
         return np.asarray(columns, dtype=np.float64).reshape(len(operators), len(circs)).T.tolist()
-
-    @property
-    def n_qubits(self) -> int:
-        return self._operator.num_qubits
 
 
 def _ascending(missing: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
@@ -2298,7 +2253,8 @@ class BitstringCircuitEvaluator(BaseCircuitEvaluator):
         return None if self._value_cache is None else self._value_cache.stats()
 
     def evaluate_circuits(self, circuits: list[CircuitIR], parameter_values: list[list[float]]) -> list[float]:
-        circuits = [None if c is None else self._composed.get(c) for c in circuits]
+        circuits, parameter_values = _present_pairs(circuits, parameter_values)
+        circuits = self._composed.get_all(circuits)
         seed = int(self._rng.integers(0, 2**63 - 1))
         if self._use_value_cache:
             return self._evaluate_through_cache(circuits, parameter_values, seed)
@@ -2308,13 +2264,12 @@ class BitstringCircuitEvaluator(BaseCircuitEvaluator):
         ]
 
     def _evaluate_through_cache(self, circuits, parameter_values, seed: int) -> list[float]:
-        pairs = [(c, p) for c, p in zip(circuits, parameter_values) if c is not None and p is not None]
         # (measure_quasi_distributions seeds a generator with the evaluator's draw and samples with ITS first draw)
         seed = int(np.random.default_rng(seed).integers(0, 2**63 - 1))
         if self._value_cache is None:
             self._value_cache = self._device.value_cache()
         cache = self._value_cache
-        missing = cache.lookup([c for c, _ in pairs], [p for _, p in pairs], self._shots, seed)
+        missing = cache.lookup(circuits, parameter_values, self._shots, seed)
         ordered, order = _ascending(missing)
         self._last_scored = 0
         n = self.n_qubits
