@@ -4,7 +4,9 @@
 E = Re<psi|H|psi>, psi = U_G .. U_1 |0..0> (oracle.statevector_oracle.simulate), H_h the Hermitian part of H applied term by
 term.  psi_G = psi, lambda_G = H_h psi; for g = G .. 1: psi_(g-1) = U_g^dagger psi_g, every angle slot of gate g that reads a
 parameter adds 2 Re<lambda_g| dU_g/d(slot) |psi_(g-1)> to that parameter's entry (cu3: the derivative's control-0 block is
-zero), then lambda_(g-1) = U_g^dagger lambda_g.  id gates and literal angles add nothing."""
+zero), then lambda_(g-1) = U_g^dagger lambda_g.  id gates and literal angles add nothing.
+
+For larger registers see tests/factorised_reference.py: product circuits whose gradients factorise block by block."""
 
 from __future__ import annotations
 
