@@ -396,6 +396,8 @@ struct qsv_handle {
         std::vector<int64_t> cur_counts, snap_counts;
         uint64_t snap_epoch = 0;
         size_t snap_n_split = 0;
+        int snap_ways = 0;         // `ways` of the push that laid the kept layout out and slotted its descriptors (eval_push)
+        bool pinned_descs = false; // this push repeats that layout over fewer lanes: its kernels read the pinned descriptors (descs_base)
         bool have_ids = false;     // cur_ids / cur_counts describe THIS batch (it came through qsv_eval_begin)
         bool repeat = false;       // this batch reuses the previous batch's layout (descriptors as its one push left them)
         bool whole_push = false;   // this batch was pushed in one piece
@@ -1285,8 +1287,13 @@ const void* ship_base(const qsv_t* h) { return h->bar_ship ? h->d_ship : h->h_ba
 // where the kernels read the descriptors of the current batch from: a batch that repeats the one before it (same layout, kept:
 // qsv_eval_begin) finds them in the device copy that batch's kernels left -- one PCIe round trip less at the start of every
 // workgroup
+// -- unless it runs over FEWER lanes than the push that laid the batch out (qsv_eval_set_output behind a call that waited): the
+// device copy's slots are that push's, an evaluation's position modulo its lanes' share of the slots, and a launch group of
+// this push, which spans a larger share, would hold two evaluations per slot.  Such a push reads the pinned descriptors, where
+// eval_push has just written its own slots.  (Over more lanes the groups are smaller and the kept slots distinct within each.)
 const EvalDesc* descs_base(const qsv_t* h) {
-    if (h->batch.repeat && !h->bar_ship && h->repeat_device_descs) return static_cast<const EvalDesc*>(h->d_batch.ptr);
+    if (h->batch.repeat && !h->bar_ship && h->repeat_device_descs && !h->batch.pinned_descs)
+        return static_cast<const EvalDesc*>(h->d_batch.ptr);
     return static_cast<const EvalDesc*>(ship_base(h));
 }
 // where the kernels of the current push read parameter values from: the pinned staging buffer, or the caller's device memory
@@ -2264,6 +2271,7 @@ int eval_push(qsv_t* h, size_t first, size_t count, const double* values, const 
             h->stamping = false;
             h->batch.dev_params = nullptr;  // (a property of the push: other paths lay batches out and ship them too)
             h->batch.record.recording = false;
+            h->batch.pinned_descs = false;
             h->timing.in_push = false;
         }
     } guard{h};
@@ -2287,6 +2295,7 @@ int eval_push(qsv_t* h, size_t first, size_t count, const double* values, const 
     // values would be)
     b.dev_params = device_values && count > 0 ? device_values - b.param_base[first] : nullptr;
     const bool whole = first == 0 && count == b.circs.size();
+    b.pinned_descs = b.repeat && b.ways < b.snap_ways;
     qsv_handle::Batch::LaunchRecord& rec = b.record;
     // (a record is made, and used, only where nothing but the call's own pointers can differ from one call to the next: no mask,
     // no per-launch events, descriptors that the kernels read where the host left them)
@@ -2307,6 +2316,7 @@ int eval_push(qsv_t* h, size_t first, size_t count, const double* values, const 
     if (b.whole_push) {
         b.snap_n_split = n_split;
         b.snap_n_cont = n_cont;
+        if (!b.repeat) b.snap_ways = b.ways;
     }
     // Slots.  Ordinary evaluations: G states are resident together; on one stream the slot of an evaluation is its
     // position mod G and the stream orders every reuse; with several streams each push takes its stream's share of the
@@ -2436,7 +2446,10 @@ int eval_push(qsv_t* h, size_t first, size_t count, const double* values, const 
         // This push's evaluations are reduced on the push's own stream, straight into the pinned result buffer: no
         // cross-stream join in front of one final reduction (the join alone cost 15-30 us at the end of every call).
         QSV_HIP(h, stamp(h, b.exp_events, true));
-        h->work = n_split > 0 && factor_path(h) ? plain_stream : lane_stream;
+        // (on the stream that wrote the partial sums it reads: the ordinary evaluations' -- the auxiliary stream in a mixed
+        // batch, ALSO in a push of that batch that holds no split evaluation itself; off the factor path the split evaluations
+        // leave partial sums too, and then the batch has no auxiliary stream: plain_stream is the lane's)
+        h->work = plain_stream;
         LaunchEntry* e = record_entry(h, LaunchEntry::Reduce, ws(h));
         if (n_split > 0 && factor_path(h)) {  // (the split evaluations' results are already there: the others, by descriptor)
             QSV_LAUNCH(h, launch_reduce_partials(static_cast<const double*>(h->d_partials.ptr), partials_per_state(h),

@@ -38,8 +38,8 @@ def assert_same_bits(got, want, what=""):
 class ShiftedValues:
     """``evaluate_circuits`` at every shifted point of the FULL gradient of a population, computed once and shared: any
     ``wrt`` selects its values from these (an evaluation's value does not depend on its batch).  One ``evaluate_circuits``
-    call per circuit: the reference is then a few hundred evaluations of ONE structure, the calling pattern the existing
-    tests hold ``evaluate_circuits`` to."""
+    call per circuit: a few hundred evaluations of ONE structure, a reference that shares no batch with what it is compared
+    to.  (One call over all of them holds the same bits: tests/test_gpu_large_batches.py compares that call with these.)"""
 
     def __init__(self, evaluator, circuits, params):
         self.circuits, self.params = circuits, params
