@@ -802,6 +802,34 @@ int qsv_overlap_circuits(qsv_t* h, int n_states, const int* prefix_ids, int with
                          const int64_t* param_offsets, const double* params, double* out_overlaps /* [n_evals][n_states][2] */,
                          double* out_elements /* the same shape; required iff with_operator */);
 
+/* ---- a few qubits of a state ------------------------------------------------------------------------ */
+
+/*
+ * REDUCED DENSITY MATRICES: rho_A = Tr_rest |psi_e><psi_e| of the final states psi_e of n_evals (circuit,
+ * parameter vector) pairs, laid out as in qsv_eval_circuits, for n_subsets qubit subsets A_s = subset_qubits[subset_offsets[s] ..
+ * subset_offsets[s + 1]) of k_s = 1 .. QSV_RDM_MAX_QUBITS distinct qubits each, in the caller's order: bit j of a row index a is
+ * the value of the subset's j-th qubit.
+ *     out[e * R + off_s + 2 * (a * 2^k_s + a') + {0, 1}] = rho_s[a][a'] = sum_b psi_e(a, b) conj psi_e(a', b)   (re, im)
+ * with off_s the sum of 2 * 4^k over the subsets before s and R that sum over all of them.  The matrices are raw: not divided
+ * by |psi|^2.  The call runs as qsv_variance_circuits runs: ordinary plans into state slots (no split route), then on the handle's
+ * stream one kernel per launch group and run of subsets that walks each state in blocks of the subset's qubits and the six lowest
+ * others and accumulates 16 x 16 tiles on the fp64 matrix pipe, and a second that adds the workgroups' tiles in ascending order.
+ * No operator is read: the call works on a handle that has none.  rho is Hermitian to the bit, its diagonal's imaginary parts are
+ * 0.0, and the matrix of an (evaluation, subset) is the same bits in any batch, at any position of a launch group and of the
+ * subset list, whatever other subsets the call names -- a repeated subset gives two identical blocks (fixed-order sums, no
+ * floating-point atomics).  Every sum is fp64, also on an fp32 handle.  The call lays a batch out as every batch call does, so a
+ * recorded batch is dropped and laid out again by the next qsv_eval_* call, which returns the bits it returned before.  Goes
+ * between batches.
+ * Errors: out, subset_offsets or subset_qubits NULL, n_subsets < 1, an empty subset, a qubit out of range or named twice in one
+ * subset, n_evals < 0 QSV_E_ARG; more than QSV_RDM_MAX_QUBITS qubits in a subset, more than QSV_RDM_MAX_SUBSETS subsets, more
+ * than 28 qubits, an evaluated circuit on a kept state QSV_E_UNSUPPORTED; n_evals == 0 QSV_OK once the subsets were checked.
+ */
+#define QSV_RDM_MAX_QUBITS 4
+#define QSV_RDM_MAX_SUBSETS 1024
+int qsv_reduced_density_circuits(qsv_t* h, int n_subsets, const int32_t* subset_offsets /* n_subsets + 1 */,
+                                 const int32_t* subset_qubits, int n_evals, const int* circuit_ids,
+                                 const int64_t* param_offsets, const double* params, double* out);
+
 /* ---- sharded populations on one node ------------------------------------------------------------- */
 
 /*

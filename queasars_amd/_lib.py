@@ -288,6 +288,7 @@ SIGNATURES = {
     "qsv_variance_circuits": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
     "qsv_observables_covariance": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "qsv_overlap_circuits": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "qsv_reduced_density_circuits": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P]),
     "qsv_observables_create": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.POINTER(C.c_int)]),
     "qsv_observables_destroy": (C.c_int, [_P, C.c_int]),
     "qsv_eval_observables": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),

@@ -1337,6 +1337,49 @@ class StatevectorDevice:
                     elements[:, k0:k0 + len(block)] = t
         return (overlaps, elements) if with_operator else overlaps
 
+    # -- a few qubits of a state ----------------------------------------------------------------------
+    MAX_RDM_QUBITS = 4      # (QSV_RDM_MAX_QUBITS)
+    MAX_RDM_SUBSETS = 1024  # (QSV_RDM_MAX_SUBSETS)
+
+    def reduced_density_matrices(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]],
+                                 subsets: Sequence[Sequence[int]]) -> list[np.ndarray]:
+        """The reduced density matrices ``rho_A = Tr_rest |psi_i><psi_i|`` of every (circuit, parameter vector) pair's final
+        state on every qubit subset A of ``subsets``: a list with one complex128 ``(n, 2**k, 2**k)`` array per subset, reduced on
+        the device from the states where they are (``qsv_reduced_density_circuits``).  A subset names 1 to
+        :attr:`MAX_RDM_QUBITS` distinct qubits, in the caller's order: bit j of a row index is the value of the subset's j-th
+        qubit.  Raw numbers: nothing is divided by a norm.  Each matrix is Hermitian to the bit and depends on its circuit,
+        point and subset alone.  Reads no operator.  More than :attr:`MAX_RDM_SUBSETS` subsets are served in runs of that
+        many, one library call each.  A circuit that continues a kept state raises ``ValueError``."""
+        batch = _HostBatch(self, circuits, parameter_values)
+        n = batch.n
+        subsets = [[int(q) for q in subset] for subset in subsets]
+        if not subsets:
+            raise ValueError("at least one subset of qubits is needed")
+        for subset in subsets:
+            if not 1 <= len(subset) <= self.MAX_RDM_QUBITS:
+                raise ValueError(f"a subset names 1 to {self.MAX_RDM_QUBITS} qubits, not {len(subset)}")
+            if len(set(subset)) != len(subset) or not all(0 <= q < self._n_qubits for q in subset):
+                raise ValueError(f"a subset names distinct qubits below {self._n_qubits}, not {subset}")
+        if any(c._kept_state is not None for c in circuits):
+            raise ValueError("the reduced density matrices of a circuit that continues a kept state are not supported")
+        result = [np.zeros((n, 1 << len(subset), 1 << len(subset)), dtype=np.complex128) for subset in subsets]
+        if n > 0:
+            arguments = batch.arguments()
+            for s0 in range(0, len(subsets), self.MAX_RDM_SUBSETS):
+                run = subsets[s0:s0 + self.MAX_RDM_SUBSETS]
+                offsets = np.zeros(len(run) + 1, dtype=np.int32)
+                np.cumsum([len(subset) for subset in run], out=offsets[1:])
+                qubits = np.asarray([q for subset in run for q in subset], dtype=np.int32)
+                starts = np.zeros(len(run) + 1, dtype=np.int64)  # (in complex entries of an evaluation's row)
+                np.cumsum([4 ** len(subset) for subset in run], out=starts[1:])
+                out = np.zeros((n, int(starts[-1])), dtype=np.complex128)
+                # (a refusal with QSV_E_UNSUPPORTED as a ValueError with the library's message)
+                self._check_gradient(self._lib.qsv_reduced_density_circuits(
+                    self._handle, len(run), _lib.as_ptr(offsets), _lib.as_ptr(qubits), *arguments, _lib.as_ptr(out)))
+                for j, subset in enumerate(run):
+                    result[s0 + j][...] = out[:, starts[j]:starts[j + 1]].reshape(n, 1 << len(subset), 1 << len(subset))
+        return result
+
     # -- measurement support ----------------------------------------------------------------------
     def set_option(self, name: str, value: int) -> None:
         """Switches of the handle (``qsv_set_option``): "split", "factor", "split_sampling" (0 / 1), "streams" (1 .. 4),
@@ -1726,6 +1769,17 @@ class OperatorCircuitEvaluator(_OperatorEvaluator):
             return self._device.overlaps(circuits, parameter_values, kept_states)
         with self._own_operator():
             return self._device.overlaps(circuits, parameter_values, kept_states, with_operator=True)
+
+    def reduced_density_matrices(self, circuits: list[CircuitIR], parameter_values: list[list[float]],
+                                 subsets: Sequence[Sequence[int]]) -> list[np.ndarray]:
+        """The reduced density matrices of every circuit's final state (behind this evaluator's initial state) on the qubit
+        subsets ``subsets``: one complex128 ``(n, 2**k, 2**k)`` array per subset
+        (:meth:`StatevectorDevice.reduced_density_matrices`; ``queasars_amd.entanglement`` turns them into
+        entropies, mutual information and marginal distributions).  Pairs of which either half is None are dropped.  Exact
+        numbers: no noise is added and no random number is drawn.  The evaluator's own operator is neither used nor changed."""
+        _same_length(len(circuits), len(parameter_values))
+        circuits, parameter_values = _present_pairs(circuits, parameter_values)
+        return self._device.reduced_density_matrices(self._behind_initial_state(circuits), parameter_values, subsets)
 
     def evaluate_subspace_matrices(self, circuits: list[CircuitIR], parameter_values: list[list[float]]):
         """``(S, H)`` of the circuits' final states among themselves: ``S[i, j] = <psi_i|psi_j>`` and ``H[i, j] =

@@ -22,6 +22,7 @@
 #include "moments.hpp"
 #include "covariance.hpp"
 #include "overlap.hpp"
+#include "reduced_density.hpp"
 #include "gradient.hpp"
 #include "value_cache.hpp"
 #include "kernels.hpp"
@@ -500,6 +501,9 @@ struct qsv_handle {
     // overlaps against kept states (qsv_overlap_circuits; overlap.hpp): the call's S by position | its T by position | one launch
     // group's partial tiles
     DeviceBuffer d_overlap;
+    // reduced density matrices (qsv_reduced_density_circuits; reduced_density.hpp): the call's subset table | its matrices by
+    // position | one launch's partial tiles
+    DeviceBuffer d_rdm;
     bool time_moments = false;  // option "time_moments": the device time of the two kernels goes to prof.expect_ms
     uint64_t host_waits = 0;  // times the host waited for a stream or an event (sync_streams and the few direct waits a batch can meet)
 
@@ -3121,7 +3125,7 @@ void qsv_destroy(qsv_t* h) {
                             &h->d_states, &h->d_wtab, &h->d_side, &h->d_factor, &h->d_factor_count, &h->d_factor_big, &h->d_factor_big_count, &h->d_quad, &h->d_fterms, &h->d_fpart, &h->d_batch, &h->d_mats, &h->d_partials, &h->d_out, &h->d_scratch, &h->d_prefix, &h->d_sdiag,
                             &h->d_obs_partials, &h->d_obs_values, &h->d_grad_tab, &h->d_grad_rows, &h->d_grad_values, &h->d_grad_base,
                             &h->d_grad_out, &h->d_adj_lambda, &h->d_adj_tab, &h->d_adj_mats, &h->d_adj_partials, &h->d_adj_epart, &h->d_adj_base,
-                            &h->d_adj_out, &h->d_adj_values, &h->d_moments, &h->d_cov, &h->d_overlap})
+                            &h->d_adj_out, &h->d_adj_values, &h->d_moments, &h->d_cov, &h->d_overlap, &h->d_rdm})
         if (b->ptr) (void)hipFree(b->ptr);
     for (auto& kv : h->obs_sets) free_observable_set(kv.second);
     for (auto& kv : h->value_caches) free_value_cache(kv.second);
@@ -5435,6 +5439,67 @@ int qsv_overlap_circuits(qsv_t* h, int n_states, const int* prefix_ids, int with
         std::copy(h->h_out + j * row, h->h_out + (j + 1) * row, out_overlaps + e * row);
         if (op) std::copy(h->h_out + tile_count + j * row, h->h_out + tile_count + (j + 1) * row, out_elements + e * row);
     }
+    return QSV_OK;
+}
+
+// ---- reduced density matrices of qubit subsets (qsv.h: REDUCED DENSITY MATRICES; reduced_density.hpp) ----------------------------
+
+int qsv_reduced_density_circuits(qsv_t* h, int n_subsets, const int32_t* subset_offsets, const int32_t* subset_qubits, int n_evals,
+                                 const int* circuit_ids, const int64_t* param_offsets, const double* params, double* out) {
+    QSV_OPEN(h, "qsv_reduced_density_circuits", kDevice);
+    if (n_subsets < 1) return fail(h, QSV_E_ARG, "n_subsets must be at least 1");
+    if (n_subsets > int(kRdmMaxSubsets)) return fail(h, QSV_E_UNSUPPORTED, "n_subsets: reduced density matrices are available for up to 1024 subsets per call");
+    if (!subset_offsets || !subset_qubits) return fail(h, QSV_E_ARG, "subset_offsets or subset_qubits is null");
+    if (n_evals < 0) return fail(h, QSV_E_ARG, "n_evals is negative");
+    if (n_evals > 0 && (!circuit_ids || !param_offsets)) return fail(h, QSV_E_ARG, "circuit_ids or param_offsets is null");
+    if (n_evals > 0 && !out) return fail(h, QSV_E_ARG, "out is null");
+    // (the register's size is asked before anything is built or uploaded)
+    if (h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "reduced density matrices are available up to 28 qubits, this handle has " + std::to_string(h->n));
+    const size_t S = size_t(n_subsets);
+    std::vector<RdmSubset> table(S);
+    size_t R = 0;  // doubles of an evaluation's row of the output
+    for (size_t s = 0; s < S; ++s) {
+        const int64_t k = int64_t(subset_offsets[s + 1]) - int64_t(subset_offsets[s]);
+        const std::string name = "subset " + std::to_string(s);
+        if (subset_offsets[s] < 0 || k < 0) return fail(h, QSV_E_ARG, "subset_offsets must start at or above 0 and not fall (" + name + ")");
+        if (k == 0) return fail(h, QSV_E_ARG, name + " is empty");
+        if (k > int64_t(kRdmMaxQubits)) return fail(h, QSV_E_UNSUPPORTED, name + " has " + std::to_string(k) + " qubits: reduced density matrices are available for up to 4");
+        const int32_t* q = subset_qubits + subset_offsets[s];
+        for (int64_t j = 0; j < k; ++j) {
+            if (q[j] < 0 || q[j] >= h->n) return fail(h, QSV_E_ARG, name + ": qubit " + std::to_string(q[j]) + " is out of range");
+            for (int64_t i = 0; i < j; ++i)
+                if (q[i] == q[j]) return fail(h, QSV_E_ARG, name + " names qubit " + std::to_string(q[j]) + " twice");
+        }
+        rdm_subset(h->n, q, uint32_t(k), uint32_t(R), table[s]);
+        R += size_t(2) << (2 * k);
+    }
+    if (n_evals == 0) return QSV_OK;
+    BatchArgs args;
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args,
+                           "circuit_ids: the reduced density matrices of a circuit on a kept state are not built");
+    if (rc) return rc;
+    if ((rc = wait_pending(h))) return rc;  // (the buffers below may still be read or written by a call that did not wait)
+    const size_t n = size_t(n_evals);
+    const size_t G = rdm_group(h->n, std::max<size_t>(1, std::min(size_t(h->group), size_t(h->max_grid_y))));
+    // device scratch: the subset table | the call's matrices by position | the partial tiles of one launch
+    const size_t table_bytes = S * sizeof(RdmSubset), out_count = n * R, out_bytes = (out_count * sizeof(double) + 63) / 64 * 64;
+    const size_t most = std::min(G, n), run = std::min(S, rdm_subset_run(h->n, most));
+    const size_t partial_bytes = most * run * rdm_blocks(h->n) * kRdmPartial * sizeof(double);
+    if ((rc = ensure(h, h->d_rdm, table_bytes + out_bytes + partial_bytes)) || (rc = ensure_host_out(h, out_count))) return rc;
+    const RdmSubset* const d_table = static_cast<const RdmSubset*>(h->d_rdm.ptr);
+    double* const d_out = reinterpret_cast<double*>(static_cast<char*>(h->d_rdm.ptr) + table_bytes);
+    double* const partials = reinterpret_cast<double*>(static_cast<char*>(h->d_rdm.ptr) + table_bytes + out_bytes);
+    QSV_HIP(h, hipMemcpy(h->d_rdm.ptr, table.data(), table_bytes, hipMemcpyHostToDevice));
+    auto tiles = [&](size_t g0, size_t gc) -> int {
+        for (size_t s0 = 0; s0 < S; s0 += run) {
+            const uint32_t sc = uint32_t(std::min(run, S - s0));
+            QSV_HIP(h, launch_rdm_panels(h->dtype, h->d_states.ptr, h->n, int(gc), d_table + s0, sc, partials, h->stream));
+            QSV_HIP(h, launch_rdm_combine(partials, h->n, int(gc), d_table + s0, sc, R, d_out + g0 * R, h->stream));
+        }
+        return QSV_OK;
+    };
+    if ((rc = run_whole_states(h, args, G, tiles, d_out, out_count))) return rc;
+    for (size_t j = 0; j < n; ++j) std::copy(h->h_out + j * R, h->h_out + (j + 1) * R, out + size_t(h->batch.eval_at[j]) * R);
     return QSV_OK;
 }
 

@@ -616,6 +616,10 @@ class EVQEResult:
     subspace_coefficients: Optional[np.ndarray] = None
     subspace_rank: Optional[int] = None
     subspace_overlaps: Optional[np.ndarray] = None
+    # the best individual's single-qubit entanglement entropies, (n_qubits,), and the mutual information between every two
+    # qubits, (n_qubits, n_qubits), symmetric with a zero diagonal, both in bits (None: not asked for)
+    qubit_entropies: Optional[np.ndarray] = None
+    mutual_information: Optional[np.ndarray] = None
 
 
 # ---- the solver -----------------------------------------------------------------------------------------------
@@ -877,7 +881,7 @@ class EVQEMinimumEigensolver:
     def compute_minimum_eigenvalue(self, evaluator, search_evaluator=None, aux_operators=None,
                                    eigenstate_states: Optional[int] = None, eigenvalue_variance: bool = False,
                                    aux_operators_covariance: bool = False, subspace_states: Optional[int] = None,
-                                   subspace_rcond: Optional[float] = None) -> EVQEResult:
+                                   subspace_rcond: Optional[float] = None, qubit_correlations: bool = False) -> EVQEResult:
         """``search_evaluator``: a second evaluator of the SAME operator for the parameter searches alone -- a single-precision
         handle: the points a search compares differ by far more than 1e-6 (the reference's own tests run their searches on an
         estimator with precision 0.05, test/minimum_eigensolvers/evqe/solver.py:20-27), a layer search on kept states is bound
@@ -924,7 +928,13 @@ class EVQEMinimumEigensolver:
         that) and 1e-4 on an fp32 one (entries to about 2e-6, by the same argument).  The eigenvalue's error grows as (entry
         error) * sum_k|c_k| / s_min_kept, c_k the operator's coefficients and s_min_kept the smallest kept eigenvalue of S.  The
         same rules as ``eigenvalue_variance``: no random stream of the solver, not counted in ``circuit_evaluations``, made by
-        every rank of a sharded run itself.  ``None``: no call, the four fields stay ``None``."""
+        every rank of a sharded run itself.  ``None``: no call, the four fields stay ``None``.
+
+        ``qubit_correlations``: after the run, one ``evaluator.reduced_density_matrices`` call at the best individual over all
+        single qubits and pairs; every qubit's entanglement entropy with the rest goes to
+        ``result.qubit_entropies`` and the mutual information between every two qubits to ``result.mutual_information``, both
+        in bits (``queasars_amd.entanglement``): where the evolved entanglers act, and whether the state is a basis state.
+        The same rules as ``eigenvalue_variance``.  ``False``: no call, both fields stay ``None``."""
         cfg = self.configuration
         searcher = evaluator if search_evaluator is None else search_evaluator
         if searcher.n_qubits != evaluator.n_qubits:
@@ -944,6 +954,8 @@ class EVQEMinimumEigensolver:
                 raise ValueError("aux_operators_covariance needs aux_operators")
             if not callable(getattr(evaluator, "evaluate_covariances", None)):
                 raise ValueError("aux_operators_covariance needs an evaluator with evaluate_covariances (an operator evaluator)")
+        if qubit_correlations and not callable(getattr(evaluator, "reduced_density_matrices", None)):
+            raise ValueError("qubit_correlations needs an evaluator with reduced_density_matrices (an operator evaluator)")
         if subspace_states is not None:
             if not 1 <= int(subspace_states) <= 64:
                 raise ValueError("subspace_states must be between 1 and 64")
@@ -1041,6 +1053,13 @@ class EVQEMinimumEigensolver:
             result.aux_operators_variance = dict(zip(names, variances)) if names is not None else variances
         if subspace_states is not None:
             self._refine_in_subspace(evaluator, result, last_scored, int(subspace_states), subspace_rcond)
+        if qubit_correlations:
+            from queasars_amd.entanglement import mutual_information
+
+            best = result.best_individual
+            circuit = best.get_parameterized_quantum_circuit(shared=self.share_circuits)
+            entropies, information = mutual_information(evaluator, [circuit], [list(best.parameter_values)], with_entropies=True)
+            result.qubit_entropies, result.mutual_information = entropies[0], information[0]
         return result
 
     def _refine_in_subspace(self, evaluator, result: EVQEResult, last_scored, k: int, rcond: Optional[float]) -> None:
