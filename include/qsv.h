@@ -830,6 +830,47 @@ int qsv_reduced_density_circuits(qsv_t* h, int n_subsets, const int32_t* subset_
                                  const int32_t* subset_qubits, int n_evals, const int* circuit_ids,
                                  const int64_t* param_offsets, const double* params, double* out);
 
+/* ---- the geometry of a circuit's parameters ---------------------------------------------------------- */
+
+/*
+ * FUBINI-STUDY METRIC (a quarter of the quantum Fisher information): for n_evals (circuit, parameter vector)
+ * pairs laid out as in qsv_eval_circuits,
+ *     out[e * W * W + i * W + j] = G_ij = Re<d_i psi|d_j psi> - <d_i psi|psi><psi|d_j psi>,   W = out_width,
+ * over the requested parameters of evaluation e: wrt[wrt_offsets[e] .. wrt_offsets[e + 1]), or every parameter of its circuit
+ * where wrt_offsets is NULL (qsv_adjoint_gradient_circuits' rules); zeros behind an evaluation's entries.  A parameter several
+ * angle slots read gets the sum over them, a parameter no gate reads a zero row and column; id gates and literal angles add
+ * nothing.  The call runs as qsv_adjoint_gradient_circuits runs -- ordinary plans into state slots (no split route), then on the
+ * handle's stream the adjoint sweep's runs (qsv_adjoint_describe, over the WHOLE circuit) --, but what it carries backwards
+ * beside psi is one derivative state per requested angle slot, born at its gate as dU/d(slot) psi_(g-1); behind the sweep one
+ * kernel forms the real Gram matrix of these columns and i psi on the fp64 matrix pipe and a second adds the workgroups' tiles
+ * in ascending order, subtracts b b^T (b = Im<psi|xi>) and sums slots into parameters.  No operator is read: the call works on a
+ * handle that has none.  Every sum is fp64, also on an fp32 handle.  G is symmetric to the bit; an evaluation's matrix is the
+ * same bits in any batch and at any position of a launch group, and the matrix of a wrt subset is, bit for bit, that submatrix of
+ * the full one (fixed-order sums, no floating-point atomics; the sweep does not stop early for a subset -- what it would leave
+ * un-swept changes the last bits of every sum).  Scratch: (columns + 2) states per evaluation of a launch group, as wide as the
+ * call's largest evaluation, allocated on first need, grown by need and bounded by option "metric_scratch_mib": the launch group
+ * shrinks to what fits.  Goes between batches.
+ * Errors: out NULL with n_evals > 0, a wrt index outside the circuit's parameters, out_width smaller than an evaluation's
+ * entries, n_evals < 0 QSV_E_ARG; more than 28 qubits, a circuit on a kept state, one evaluation's columns beyond the scratch
+ * bound (qsv_last_error names how many fit) QSV_E_UNSUPPORTED; n_evals == 0 QSV_OK.
+ */
+int qsv_metric_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
+                        const int64_t* wrt_offsets /* NULL: every parameter of each circuit */, const int32_t* wrt, int out_width,
+                        double* out /* host: [n_evals][out_width][out_width] */);
+/* Counters of the last metric call: columns carried (summed over its evaluations), launches of the run kernel and of the Gram
+ * kernel; with option "time_moments" on, the device time of those launches in milliseconds (0.0 otherwise); the scratch's present
+ * size in device memory and how often it was allocated or grown since the handle was created. */
+typedef struct qsv_metric_stats_t {
+    int64_t n_columns;
+    int64_t n_run_launches;
+    int64_t n_gram_launches;
+    int64_t scratch_bytes;
+    int64_t n_allocations;
+    double run_ms;
+    double gram_ms;
+} qsv_metric_stats_t;
+int qsv_metric_stats(const qsv_t* h, qsv_metric_stats_t* out);
+
 /* ---- sharded populations on one node ------------------------------------------------------------- */
 
 /*
@@ -903,7 +944,10 @@ int qsv_fitness_table_wait(const volatile uint64_t* own, int count, volatile int
  *                        when the handle is created: the default, 0, and the largest value accepted).  More groups go in several
  *                        launches with the partial sums laid out as one launch lays them out: the same bits at any value
  *   "time_moments" 0|1   qsv_variance_circuits and qsv_observables_covariance bracket the two kernels of every launch group by HIP
- *                        events on the handle's stream and leave their summed device time in qsv_get_profile's expect_ms (measurements; the same bits)
+ *                        events on the handle's stream and leave their summed device time in qsv_get_profile's expect_ms (measurements; the same bits);
+ *                        qsv_metric_circuits brackets its run launches and its Gram kernels: qsv_metric_stats' run_ms / gram_ms
+ *   "metric_scratch_mib" 1..1048576  most device memory, in MiB, that qsv_metric_circuits' scratch of derivative states may take
+ *                        (default 8192); the same bits at any value
  * Returns QSV_E_ARG for an unknown name or a value out of range.
  */
 int qsv_set_option(qsv_t* h, const char* name, int value);

@@ -204,6 +204,20 @@ class QsvAdjointStats(C.Structure):
     ]
 
 
+class QsvMetricStats(C.Structure):
+    """``qsv_metric_stats_t`` of include/qsv.h."""
+
+    _fields_ = [
+        ("n_columns", C.c_int64),
+        ("n_run_launches", C.c_int64),
+        ("n_gram_launches", C.c_int64),
+        ("scratch_bytes", C.c_int64),
+        ("n_allocations", C.c_int64),
+        ("run_ms", C.c_double),
+        ("gram_ms", C.c_double),
+    ]
+
+
 class QsvValueCacheStats(C.Structure):
     """``qsv_value_cache_stats_t`` of include/qsv.h."""
 
@@ -289,6 +303,8 @@ SIGNATURES = {
     "qsv_observables_covariance": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "qsv_overlap_circuits": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "qsv_reduced_density_circuits": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P]),
+    "qsv_metric_circuits": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P]),
+    "qsv_metric_stats": (C.c_int, [_P, C.POINTER(QsvMetricStats)]),
     "qsv_observables_create": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.POINTER(C.c_int)]),
     "qsv_observables_destroy": (C.c_int, [_P, C.c_int]),
     "qsv_eval_observables": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),

@@ -1380,13 +1380,44 @@ class StatevectorDevice:
                     result[s0 + j][...] = out[:, starts[j]:starts[j + 1]].reshape(n, 1 << len(subset), 1 << len(subset))
         return result
 
+    # -- the geometry of a circuit's parameters -------------------------------------------------------
+    def metric_tensors(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]], wrt=None) -> list[np.ndarray]:
+        """The Fubini-Study metric ``G_ij = Re<d_i psi|d_j psi> - <d_i psi|psi><psi|d_j psi>`` of every (circuit, parameter
+        vector) pair -- a quarter of the quantum Fisher information --, from one reverse sweep that carries a derivative state
+        per requested angle slot and a real Gram matrix of them on the device (``qsv_metric_circuits``): one
+        float64 ``(P, P)`` array per circuit over the parameters ``wrt`` names (as in :meth:`gradients`; None: every
+        parameter).  A parameter several angle slots read gets the sum over them, one no gate reads a zero row and column.
+        Symmetric to the bit; depends on its circuit and point alone; the matrix of a ``wrt`` subset is that submatrix of
+        the full one, bit for bit.  Reads no operator.  A circuit that continues a kept state, or columns beyond option
+        "metric_scratch_mib", raise ``ValueError``."""
+        batch = _HostBatch(self, circuits, parameter_values)
+        if batch.n == 0:
+            return []
+        if any(c._kept_state is not None for c in circuits):
+            raise ValueError("the metric of a circuit that continues a kept state is not supported")
+        arguments = batch.arguments()
+        wrt_offsets, wrt_flat, counts = self._wrt_arguments(circuits, wrt)
+        width = max(1, int(counts.max()))
+        out = np.zeros((batch.n, width, width), dtype=np.float64)
+        self._check_gradient(self._lib.qsv_metric_circuits(
+            self._handle, *arguments, _pointer(wrt_offsets), _pointer(wrt_flat), width, _lib.as_ptr(out)))
+        return [out[e, :int(c), :int(c)].copy() for e, c in enumerate(counts)]
+
+    def metric_stats(self) -> dict:
+        """``qsv_metric_stats``: the last :meth:`metric_tensors` call's columns and launches of the run and Gram kernels (with
+        option "time_moments" their device time in ms), the metric scratch's size and how often it was allocated or grown."""
+        stats = _lib.QsvMetricStats()
+        self._check(self._lib.qsv_metric_stats(self._handle, C.byref(stats)))
+        return _struct_dict(stats)
+
     # -- measurement support ----------------------------------------------------------------------
     def set_option(self, name: str, value: int) -> None:
         """Switches of the handle (``qsv_set_option``): "split", "factor", "split_sampling" (0 / 1), "streams" (1 .. 4),
         "gradient_chunk" (shifted evaluations per chunk of a gradient call, 0 = the default), "max_grid_y" (x-mask groups or
         observable rows per launch, 0 = the device's largest gridDim.y), "repeat_layout" / "replay_launches" (0 / 1: a repeated batch
         keeps its layout / queues its recorded launches again), "time_moments" (0 / 1: :meth:`variances` leaves the device time of
-        its two kernels in :meth:`profile`'s ``expect_ms``).
+        its two kernels in :meth:`profile`'s ``expect_ms``, :meth:`metric_tensors` that of its run launches and Gram kernels in
+        :meth:`metric_stats`), "metric_scratch_mib" (most device memory, in MiB, for :meth:`metric_tensors`' derivative states).
         A circuit keeps the form it was registered in; the cache of the previous batch is dropped."""
         self._check(self._lib.qsv_set_option(self._handle, name.encode(), int(value)))
         self._last_batch = None
@@ -1539,6 +1570,15 @@ class _OperatorEvaluator(BaseCircuitEvaluator):
         with_values = self._operator.is_diagonal()
         with self._own_operator() if with_values else self._device.operator_lock:
             return self._device.top_states(circuits, parameter_values, k, with_values=with_values)
+
+    def metric_tensors(self, circuits: list[CircuitIR], parameter_values: list[list[float]], wrt=None) -> list[np.ndarray]:
+        """The Fubini-Study metric (a quarter of the quantum Fisher information) of every circuit's parameters at its point,
+        behind this evaluator's initial state: one float64 ``(P, P)`` array per circuit over the parameters ``wrt`` names
+        (:meth:`StatevectorDevice.metric_tensors`).  The initial state has no parameters, so the indices are
+        the circuit's own.  Exact numbers: no noise is added and no random number is drawn.  The evaluator's own operator is
+        neither used nor changed."""
+        _same_length(len(circuits), len(parameter_values))
+        return self._device.metric_tensors(self._behind_initial_state(circuits), parameter_values, wrt)
 
     @staticmethod
     def _torch_sees_a_gpu() -> bool:

@@ -23,6 +23,7 @@
 #include "covariance.hpp"
 #include "overlap.hpp"
 #include "reduced_density.hpp"
+#include "metric.hpp"
 #include "gradient.hpp"
 #include "value_cache.hpp"
 #include "kernels.hpp"
@@ -504,6 +505,11 @@ struct qsv_handle {
     // reduced density matrices (qsv_reduced_density_circuits; reduced_density.hpp): the call's subset table | its matrices by
     // position | one launch's partial tiles
     DeviceBuffer d_rdm;
+    // the Fubini-Study metric (qsv_metric_circuits; metric.hpp): one launch group's psi buffers and derivative states | the call's
+    // tables | the group's gate matrices | one Gram launch's partial tiles | the points | the call's matrices
+    DeviceBuffer d_met_scratch, d_met_tab, d_met_mats, d_met_partials, d_met_base, d_met_out;
+    int metric_scratch_mib = 8192;  // option "metric_scratch_mib": the bound of d_met_scratch
+    qsv_metric_stats_t met_stats{};
     bool time_moments = false;  // option "time_moments": the device time of the two kernels goes to prof.expect_ms
     uint64_t host_waits = 0;  // times the host waited for a stream or an event (sync_streams and the few direct waits a batch can meet)
 
@@ -3125,7 +3131,8 @@ void qsv_destroy(qsv_t* h) {
                             &h->d_states, &h->d_wtab, &h->d_side, &h->d_factor, &h->d_factor_count, &h->d_factor_big, &h->d_factor_big_count, &h->d_quad, &h->d_fterms, &h->d_fpart, &h->d_batch, &h->d_mats, &h->d_partials, &h->d_out, &h->d_scratch, &h->d_prefix, &h->d_sdiag,
                             &h->d_obs_partials, &h->d_obs_values, &h->d_grad_tab, &h->d_grad_rows, &h->d_grad_values, &h->d_grad_base,
                             &h->d_grad_out, &h->d_adj_lambda, &h->d_adj_tab, &h->d_adj_mats, &h->d_adj_partials, &h->d_adj_epart, &h->d_adj_base,
-                            &h->d_adj_out, &h->d_adj_values, &h->d_moments, &h->d_cov, &h->d_overlap, &h->d_rdm})
+                            &h->d_adj_out, &h->d_adj_values, &h->d_moments, &h->d_cov, &h->d_overlap, &h->d_rdm,
+                            &h->d_met_scratch, &h->d_met_tab, &h->d_met_mats, &h->d_met_partials, &h->d_met_base, &h->d_met_out})
         if (b->ptr) (void)hipFree(b->ptr);
     for (auto& kv : h->obs_sets) free_observable_set(kv.second);
     for (auto& kv : h->value_caches) free_value_cache(kv.second);
@@ -5503,6 +5510,269 @@ int qsv_reduced_density_circuits(qsv_t* h, int n_subsets, const int32_t* subset_
     return QSV_OK;
 }
 
+// ---- the Fubini-Study metric (qsv.h: FUBINI-STUDY METRIC; metric.hpp) --------------------------------------------------------------
+
+int qsv_metric_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
+                        const int64_t* wrt_offsets, const int32_t* wrt, int out_width, double* out) {
+    QSV_OPEN(h, "qsv_metric_circuits", kDevice);
+    if (n_evals < 0) return fail(h, QSV_E_ARG, "n_evals is negative");
+    if (n_evals == 0) return QSV_OK;
+    if (!circuit_ids || !param_offsets) return fail(h, QSV_E_ARG, "circuit_ids or param_offsets is null");
+    if (!out) return fail(h, QSV_E_ARG, "out is null");
+    if (out_width < 1) return fail(h, QSV_E_ARG, "out_width must be at least 1");
+    // (the register's size is asked before anything is built or uploaded)
+    if (h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "the metric is available up to 28 qubits, this handle has " + std::to_string(h->n));
+    BatchArgs packed;
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, packed, "circuit_ids: the metric of a circuit on a kept state is not built");
+    if (rc) return rc;
+    int64_t width, longest;
+    std::vector<double> base;
+    if ((rc = pack_rows(h, packed, wrt_offsets, out, true, width, longest, base))) return rc;
+    const size_t n = size_t(n_evals), W = size_t(out_width);
+    h->met_stats.n_columns = h->met_stats.n_run_launches = h->met_stats.n_gram_launches = 0;
+    h->met_stats.run_ms = h->met_stats.gram_ms = 0.0;
+
+    // ---- the tables: per distinct circuit the adjoint sweep's gates and runs of the WHOLE circuit and the slots that read each
+    // parameter; per evaluation its columns (the requested slots in the sweep's order) and its entries
+    struct CircuitTables {
+        uint32_t gate_base, run_base, n_runs, n_gates;
+        std::vector<std::vector<uint32_t>> readers;  // per parameter: 3 * (swept gate) + slot, ascending -- the latest gate first
+    };
+    std::unordered_map<const Circuit*, CircuitTables> tables;
+    std::vector<AdjGate> gates;
+    std::vector<AdjRunDesc> runs;
+    std::vector<MetCol> cols;
+    std::vector<MetEntry> entries;
+    std::vector<uint32_t> entry_cols;
+    std::vector<MetEval> by_eval(n);
+    uint32_t max_gates = 0, max_cols = 0;
+    for (size_t e = 0; e < n; ++e) {
+        const Circuit& c = *packed.circs[e];
+        const int64_t first = wrt_offsets ? wrt_offsets[e] : 0, count = wrt_offsets ? wrt_offsets[e + 1] - first : int64_t(c.n_params);
+        if (count > int64_t(W))
+            return fail(h, QSV_E_ARG, "out_width " + std::to_string(out_width) + " is too small for " + std::to_string(count) + " parameters");
+        if (count > 0 && wrt_offsets && !wrt) return fail(h, QSV_E_ARG, "wrt is null");
+        for (int64_t j = 0; wrt_offsets && j < count; ++j)
+            if (wrt[first + j] < 0 || wrt[first + j] >= c.n_params)
+                return fail(h, QSV_E_ARG, "wrt index " + std::to_string(wrt[first + j]) + " is outside the " + std::to_string(c.n_params) +
+                                              " parameters of circuit " + std::to_string(circuit_ids[e]));
+        auto it = tables.find(&c);
+        if (it == tables.end()) {
+            CircuitTables t;
+            AdjointPlan plan;
+            if (adjoint_plan(h->n, int(c.ops.size()), c.ops.data(), c.n_params, -1, nullptr, &plan))
+                return fail(h, QSV_E_ARG, "circuit " + std::to_string(circuit_ids[e]) + " cannot be planned for the adjoint sweep");
+            t.gate_base = uint32_t(gates.size());
+            t.run_base = uint32_t(runs.size());
+            t.n_runs = uint32_t(plan.runs.size());
+            t.n_gates = uint32_t(plan.gates.size());
+            t.readers.resize(size_t(c.n_params));
+            for (const AdjointRun& r : plan.runs) {
+                runs.push_back(AdjRunDesc{r.mask, uint32_t(r.first_gate), uint32_t(r.n_gates)});
+                for (int32_t g = r.first_gate; g < r.first_gate + r.n_gates; ++g) {
+                    const qsv_op& o = c.ops[size_t(plan.gates[size_t(g)])];
+                    auto tile_bit = [&](int q) { return uint8_t(__builtin_popcountll(r.mask & ((uint64_t(1) << q) - 1))); };
+                    AdjGate ag{};
+                    ag.kind = o.kind;
+                    ag.tpos = tile_bit(o.target);
+                    ag.cpos = o.kind == QSV_OP_CU3 ? tile_bit(o.control) : uint8_t(QSV_NO_CONTROL);
+                    const int32_t p[3] = {o.p_theta, o.p_phi, o.p_lambda};
+                    const double lit[3] = {o.theta, o.phi, o.lambda};
+                    for (int s = 0; s < 3; ++s) {
+                        ag.p[s] = p[s] >= 0 ? p[s] : -1;
+                        ag.lit[s] = lit[s];
+                        if (p[s] >= 0) t.readers[size_t(p[s])].push_back(uint32_t(3 * g + s));
+                    }
+                    gates.push_back(ag);
+                }
+            }
+            it = tables.emplace(&c, std::move(t)).first;
+        }
+        const CircuitTables& t = it->second;
+        // the columns: every slot that reads a requested parameter, once, in birth order (the sweep's: ascending 3 * gate + slot)
+        std::vector<uint32_t> born;
+        for (int64_t j = 0; j < count; ++j) {
+            const std::vector<uint32_t>& r = t.readers[size_t(wrt_offsets ? int64_t(wrt[first + j]) : j)];
+            born.insert(born.end(), r.begin(), r.end());
+        }
+        std::sort(born.begin(), born.end());
+        born.erase(std::unique(born.begin(), born.end()), born.end());
+        MetEval& ev = by_eval[e];
+        ev = MetEval{t.gate_base, t.run_base, born.empty() ? 0u : t.n_runs, t.n_gates, uint32_t(e), uint32_t(cols.size()), uint32_t(born.size()),
+                     uint32_t(entries.size()), uint32_t(count), 0};
+        for (uint32_t s : born) cols.push_back(MetCol{s});
+        // an entry's columns in ascending (gate, slot) order of the CIRCUIT: the sweep's gates backwards, a gate's slots forwards
+        for (int64_t j = 0; j < count; ++j) {
+            std::vector<uint32_t> r = t.readers[size_t(wrt_offsets ? int64_t(wrt[first + j]) : j)];
+            std::sort(r.begin(), r.end(), [](uint32_t a, uint32_t b) { return a / 3 != b / 3 ? a / 3 > b / 3 : a < b; });
+            entries.push_back(MetEntry{uint32_t(entry_cols.size()), uint32_t(r.size())});
+            for (uint32_t s : r) entry_cols.push_back(uint32_t(std::lower_bound(born.begin(), born.end(), s) - born.begin()));
+        }
+        max_gates = std::max(max_gates, t.n_gates);
+        max_cols = std::max(max_cols, uint32_t(born.size()));
+        h->met_stats.n_columns += int64_t(born.size());
+    }
+    if (max_cols + 1 > 65535u) return fail(h, QSV_E_UNSUPPORTED, "the metric is available for up to 65534 columns per evaluation");
+
+    // ---- the launch group: what the scratch bound leaves of the handle's
+    const uint64_t dim = uint64_t(1) << h->n;
+    const size_t stride = size_t(max_cols) + kMetricPsiBuffers, state_bytes = size_t(dim) * h->amp_bytes, eval_bytes = stride * state_bytes;
+    const size_t bound = size_t(h->metric_scratch_mib) << 20;
+    if (eval_bytes > bound) {
+        const size_t fit = bound / state_bytes;
+        return fail(h, QSV_E_UNSUPPORTED, "an evaluation of this call has " + std::to_string(max_cols) + " columns; \"metric_scratch_mib\" " +
+                                              std::to_string(h->metric_scratch_mib) + " leaves room for " +
+                                              std::to_string(fit > kMetricPsiBuffers ? fit - kMetricPsiBuffers : 0) + " at " + std::to_string(h->n) + " qubits");
+    }
+    const size_t G = std::max<size_t>(1, std::min({size_t(h->group), size_t(65535), bound / eval_bytes}));
+    // the Gram kernel's partial tiles: so many evaluations per launch that they stay within 64 MiB (one always runs)
+    const uint32_t max_pairs = metric_pairs(max_cols), gram_blocks = metric_gram_blocks(h->n);
+    const size_t eval_partials = size_t(max_pairs) * gram_blocks * kMetTile * sizeof(double);
+    const size_t gram_group = std::max<size_t>(1, std::min(G, (size_t(64) << 20) / eval_partials));
+
+    if ((rc = wait_pending(h))) return rc;  // (the buffers below may still be read or written by a call that did not wait)
+    int64_t& allocations = h->met_stats.n_allocations;
+    if ((rc = ensure_counted(h, h->d_met_base, base.size() * sizeof(double), allocations)) ||
+        (rc = ensure_counted(h, h->d_met_out, n * W * W * sizeof(double), allocations)))
+        return rc;
+    QSV_HIP(h, hipMemcpy(h->d_met_base.ptr, base.data(), base.size() * sizeof(double), hipMemcpyHostToDevice));
+    BatchArgs args;
+    args.circs = packed.circs;
+    args.values.assign(1, 0.0);
+    args.n_params.assign(n, width);
+    args.device_values = static_cast<const double*>(h->d_met_base.ptr);
+
+    // ---- the forward run's layout (ordinary plans into state slots, never split: as qsv_adjoint_gradient_circuits runs them)
+    const StateRun run{SplitRule{}, 1, G, false, 0, kModeSynthFirst | kModeFinalStore};
+    BatchRelease release{h};
+    StateLayout lay;
+    h->prof = qsv_profile{};
+    if ((rc = lay_out_states(h, args, run, lay))) return rc;
+    std::vector<MetEval> evals(n);
+    std::vector<AdjEval> adj_evals(n);  // what launch_adjoint_prepare reads of an evaluation
+    for (size_t j = 0; j < n; ++j) {
+        evals[j] = by_eval[h->batch.eval_at[j]];
+        adj_evals[j] = AdjEval{evals[j].gate_base, evals[j].run_base, evals[j].n_runs, evals[j].n_runs ? evals[j].n_gates : 0u, evals[j].row, 0};
+    }
+    // one blob, every part a multiple of 8 bytes: [gates][runs][evaluations][... as the adjoint sweep's][columns][entries][entry columns]
+    auto padded = [](size_t bytes) { return (bytes + 7) / 8 * 8; };
+    const size_t off_gates = 0, off_runs = off_gates + gates.size() * sizeof(AdjGate), off_evals = off_runs + runs.size() * sizeof(AdjRunDesc),
+                 off_adj = off_evals + evals.size() * sizeof(MetEval), off_cols = off_adj + adj_evals.size() * sizeof(AdjEval),
+                 off_entries = off_cols + padded(cols.size() * sizeof(MetCol)), off_ecols = off_entries + entries.size() * sizeof(MetEntry),
+                 tab_bytes = off_ecols + padded(entry_cols.size() * sizeof(uint32_t));
+    std::vector<char> blob(tab_bytes, 0);
+    auto put = [&](size_t off, const void* src, size_t bytes) {
+        if (bytes) std::memcpy(blob.data() + off, src, bytes);
+    };
+    put(off_gates, gates.data(), gates.size() * sizeof(AdjGate));
+    put(off_runs, runs.data(), runs.size() * sizeof(AdjRunDesc));
+    put(off_evals, evals.data(), evals.size() * sizeof(MetEval));
+    put(off_adj, adj_evals.data(), adj_evals.size() * sizeof(AdjEval));
+    put(off_cols, cols.data(), cols.size() * sizeof(MetCol));
+    put(off_entries, entries.data(), entries.size() * sizeof(MetEntry));
+    put(off_ecols, entry_cols.data(), entry_cols.size() * sizeof(uint32_t));
+    const size_t gc_max = std::min(G, n);
+    if ((rc = ensure_counted(h, h->d_met_tab, tab_bytes, allocations)) || (rc = ensure_counted(h, h->d_met_scratch, gc_max * eval_bytes, allocations)) ||
+        (rc = ensure_counted(h, h->d_met_mats, gc_max * std::max<size_t>(1, max_gates) * kAdjointMatDoubles * sizeof(double), allocations)) ||
+        (rc = ensure_counted(h, h->d_met_partials, std::min(gram_group, gc_max) * eval_partials, allocations)))
+        return rc;
+    // (lay_out_states has waited for whatever an earlier call without a wait left running: nothing reads the old tables)
+    QSV_HIP(h, hipMemcpy(h->d_met_tab.ptr, blob.data(), tab_bytes, hipMemcpyHostToDevice));
+    const char* dt = static_cast<const char*>(h->d_met_tab.ptr);
+    const AdjGate* d_gates = reinterpret_cast<const AdjGate*>(dt + off_gates);
+    const AdjRunDesc* d_runs = reinterpret_cast<const AdjRunDesc*>(dt + off_runs);
+    const MetEval* d_evals = reinterpret_cast<const MetEval*>(dt + off_evals);
+    const AdjEval* d_adj = reinterpret_cast<const AdjEval*>(dt + off_adj);
+    const MetCol* d_cols = reinterpret_cast<const MetCol*>(dt + off_cols);
+    const MetEntry* d_entries = reinterpret_cast<const MetEntry*>(dt + off_entries);
+    const uint32_t* d_ecols = reinterpret_cast<const uint32_t*>(dt + off_ecols);
+    double* mats = static_cast<double*>(h->d_met_mats.ptr);
+    double* partials = static_cast<double*>(h->d_met_partials.ptr);
+    double* d_out = static_cast<double*>(h->d_met_out.ptr);
+    char* scratch = static_cast<char*>(h->d_met_scratch.ptr);
+    const bool streaming = h->stream_mode != 0;
+    // option "time_moments": the run launches and the Gram kernels of every group between events of their own
+    struct Timed {
+        hipEvent_t t0 = nullptr, t1 = nullptr;
+        bool gram = false;
+    };
+    std::vector<Timed> timed;
+    struct DestroyEvents {
+        std::vector<Timed>& list;
+        ~DestroyEvents() {
+            for (Timed& t : list) {
+                if (t.t0) (void)hipEventDestroy(t.t0);
+                if (t.t1) (void)hipEventDestroy(t.t1);
+            }
+        }
+    } destroy_events{timed};
+    auto mark = [&](bool begin, bool gram) -> int {
+        if (!h->time_moments) return QSV_OK;
+        if (begin) {
+            timed.emplace_back();
+            timed.back().gram = gram;
+            QSV_HIP(h, hipEventCreate(&timed.back().t0));
+            QSV_HIP(h, hipEventCreate(&timed.back().t1));
+            QSV_HIP(h, hipEventRecord(timed.back().t0, h->stream));
+        } else {
+            QSV_HIP(h, hipEventRecord(timed.back().t1, h->stream));
+        }
+        return QSV_OK;
+    };
+    auto sweep = [&](size_t g0, size_t gc) -> int {
+        uint32_t most_runs = 0, group_cols = 0;
+        for (size_t j = g0; j < g0 + gc; ++j) {
+            most_runs = std::max(most_runs, evals[j].n_runs);
+            group_cols = std::max(group_cols, evals[j].n_cols);
+        }
+        int rc2;
+        if (most_runs > 0) {
+            QSV_HIP(h, launch_adjoint_prepare(d_adj + g0, int(gc), d_gates, max_gates, args.device_values, width, mats, h->stream));
+            if ((rc2 = mark(true, false))) return rc2;
+            for (uint32_t r = 0; r < most_runs; ++r) {
+                QSV_HIP(h, launch_metric_run(h->dtype, h->d_states.ptr, scratch, stride, h->n, int(gc), group_cols, r, d_evals + g0, d_runs, d_gates,
+                                             d_cols, mats, max_gates, streaming, h->stream));
+                h->met_stats.n_run_launches += 1;
+            }
+            if ((rc2 = mark(false, false)) || (rc2 = mark(true, true))) return rc2;
+        }
+        for (size_t c0 = 0; c0 < gc; c0 += gram_group) {
+            const size_t cc = std::min(gram_group, gc - c0);
+            if (most_runs > 0) {
+                // (the pair numbering is the call's -- max_cols --, the grid too: pairs past an evaluation's own leave at once)
+                QSV_HIP(h, launch_metric_gram(h->dtype, scratch + c0 * eval_bytes, stride, h->n, int(cc), max_cols, d_evals + g0 + c0, partials, h->stream));
+                h->met_stats.n_gram_launches += 1;
+            }
+            QSV_HIP(h, launch_metric_combine(d_evals + g0 + c0, int(cc), d_entries, d_ecols, partials, max_pairs, gram_blocks, out_width, d_out, h->stream));
+        }
+        if (most_runs > 0 && (rc2 = mark(false, true))) return rc2;
+        return QSV_OK;
+    };
+    rc = run_laid_out(h, args, run, lay, {}, sweep);
+    if (rc) {
+        (void)sync_streams(h);
+        return rc;
+    }
+    QSV_HIP(h, hipMemcpyAsync(out, d_out, n * W * W * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QSV_HIP(h, sync_streams(h));
+    h->async_pending = false;
+    for (const Timed& t : timed) {
+        float ms = 0.0f;
+        QSV_HIP(h, hipEventElapsedTime(&ms, t.t0, t.t1));
+        (t.gram ? h->met_stats.gram_ms : h->met_stats.run_ms) += double(ms);
+    }
+    return QSV_OK;
+}
+
+int qsv_metric_stats(const qsv_t* h, qsv_metric_stats_t* out) {
+    if (!out) return QSV_E_ARG;
+    QSV_OPEN(h, "qsv_metric_stats", kHostOnly);
+    *out = h->met_stats;
+    out->scratch_bytes = int64_t(h->d_met_scratch.bytes + h->d_met_tab.bytes + h->d_met_mats.bytes + h->d_met_partials.bytes + h->d_met_base.bytes +
+                                 h->d_met_out.bytes);
+    return QSV_OK;
+}
+
 int qsv_sample(qsv_t* h, int circuit_id, const double* params, int n_params, int shots, uint64_t seed,
                uint64_t* out_states) {
     QSV_OPEN(h, "qsv_sample", kDevice);
@@ -5599,6 +5869,9 @@ int qsv_set_option(qsv_t* h, const char* name, int value) {
         h->grad_chunk = value ? value : kGradientChunkRows;
     } else if (key == "time_moments") {  // qsv_variance_circuits brackets its two kernels by events: qsv_get_profile's expect_ms (the same bits)
         h->time_moments = value != 0;
+    } else if (key == "metric_scratch_mib") {  // the bound of qsv_metric_circuits' scratch of derivative states; the same bits at any value
+        if (value < 1 || value > (1 << 20)) return fail(h, QSV_E_ARG, "metric_scratch_mib must be between 1 and 1048576");
+        h->metric_scratch_mib = value;
     } else {
         return fail(h, QSV_E_ARG, "unknown option '" + key + "'");
     }

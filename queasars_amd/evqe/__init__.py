@@ -24,5 +24,6 @@ from queasars_amd.evqe.solver import (  # noqa: F401,E402
     EVQEMinimumEigensolver,
     EVQEMinimumEigensolverConfiguration,
     EVQEResult,
+    NaturalGradient,
     SPSATerminationChecker,
 )

@@ -281,10 +281,73 @@ class _AdamRun:
         self.done = t >= cfg.maxiter or float(np.linalg.norm(update)) < cfg.tol
 
 
+@dataclass
+class NaturalGradient:
+    """Quantum natural gradient descent (Stokes, Izaac, Killoran and Carleo, "Quantum Natural Gradient", Quantum 4, 269, 2020):
+    ``x <- x - learning_rate * solve(G + regularization * I, g)`` with g the evaluator's analytic gradient
+    (``evaluate_gradients``) and G the Fubini-Study metric of the run's free parameters (``metric_tensors``).
+    ``regularization`` must be positive: G is singular wherever an angle does nothing to the state (lambda of a ``u`` on
+    |0>).  A run stops after ``maxiter`` iterations, or when the norm of an update falls below ``tol``.  Deterministic: the
+    seed of ``new_run`` is not used.  ``nfev`` counts what the gradient cost, as :class:`Adam`'s does; the metric call of an
+    iteration is one more sweep per run and is not counted."""
+
+    maxiter: int = 33
+    learning_rate: float = 0.1
+    regularization: float = 1e-3
+    tol: float = 0.0
+
+    #: a driver must hand these runs to ``evaluate_gradients`` and ``metric_tensors`` (_minimize_batched)
+    needs_gradients = True
+    needs_metric = True
+
+    def __post_init__(self):
+        if not self.regularization > 0:
+            raise ValueError("regularization must be positive: the metric is singular wherever an angle does nothing")
+
+    @property
+    def n_circuit_evaluations(self) -> int:
+        """As :attr:`Adam.n_circuit_evaluations`."""
+        return 2 * self.maxiter
+
+    def n_circuit_evaluations_for(self, n_qubits: int) -> int:
+        """As :meth:`Adam.n_circuit_evaluations_for`: the gradient's shifted evaluations of the largest layer."""
+        return self.maxiter * (6 * n_qubits + 8 * (n_qubits // 2))
+
+    def new_run(self, x0: Sequence[float], seed: Optional[int]) -> "_NaturalGradientRun":
+        return _NaturalGradientRun(self, x0)
+
+
+class _NaturalGradientRun:
+    """State of one natural-gradient minimisation; the driver advances many of them in lock-step
+    (:func:`_minimize_natural_gradient`)."""
+
+    def __init__(self, config: NaturalGradient, x0: Sequence[float]):
+        self.config = config
+        self.x = np.asarray(x0, dtype=np.float64).copy()
+        self.nfev = 0
+        self.iteration = 0
+        self.done = self.x.size == 0 or config.maxiter <= 0
+        self.embed = None  # (as _SPSARun.embed)
+
+    def accept_gradient_and_metric(self, gradient: np.ndarray, metric: np.ndarray, n_evaluations: int) -> None:
+        cfg = self.config
+        g = np.asarray(gradient, dtype=np.float64)
+        m = np.asarray(metric, dtype=np.float64)
+        self.nfev += int(n_evaluations)
+        self.iteration += 1
+        update = cfg.learning_rate * np.linalg.solve(m + cfg.regularization * np.eye(g.size), g)
+        self.x = self.x - update
+        self.done = self.iteration >= cfg.maxiter or float(np.linalg.norm(update)) < cfg.tol
+
+
 def _require_gradients(evaluator, optimizer) -> None:
-    """An optimiser that needs gradients (:class:`Adam`) with an evaluator that has none: said before anything runs."""
+    """An optimiser that needs gradients (:class:`Adam`) with an evaluator that has none: said before anything runs; likewise
+    one that needs the metric (:class:`NaturalGradient`)."""
     if getattr(optimizer, "needs_gradients", False) and not callable(getattr(evaluator, "evaluate_gradients", None)):
         raise ValueError(f"{type(optimizer).__name__} needs an evaluator with evaluate_gradients (OperatorCircuitEvaluator); "
+                         f"{type(evaluator).__name__} has none")
+    if getattr(optimizer, "needs_metric", False) and not callable(getattr(evaluator, "metric_tensors", None)):
+        raise ValueError(f"{type(optimizer).__name__} needs an evaluator with metric_tensors (a device evaluator); "
                          f"{type(evaluator).__name__} has none")
 
 
@@ -318,6 +381,33 @@ def _minimize_adam(evaluator, jobs: list) -> None:
             raise RuntimeError(f"the evaluator ran {reported} shifted evaluations, the shift plans say {counted}")
         for (_, run), gradient in zip(active, gradients):
             run.accept_gradient(gradient, cost[id(run)])
+        active = [job for job in active if not job[1].done]
+
+
+def _minimize_natural_gradient(evaluator, jobs: list) -> None:
+    """:func:`_minimize_batched` for :class:`NaturalGradient` runs: ONE ``evaluate_gradients`` and ONE ``metric_tensors`` call
+    per iteration for all running jobs, each run differentiated by its free parameters only.  ``nfev`` as in
+    :func:`_minimize_adam`: the shift plans' counts, or what an evaluator with another ``gradient_method`` reports."""
+    _require_gradients(evaluator, jobs[0][1].config)
+    wrt, cost = {}, {}
+    for circuit, run in jobs:
+        positions = _positions(run).tolist()
+        terms = circuit.gradient_terms()
+        wrt[id(run)] = positions
+        cost[id(run)] = sum(max(0, terms[p]) for p in positions)
+    active = [job for job in jobs if not job[1].done]
+    while active:
+        circuits = [circuit for circuit, _ in active]
+        params = [_full_point(run, run.x).tolist() for _, run in active]
+        requested = [wrt[id(run)] for _, run in active]
+        gradients = evaluator.evaluate_gradients(circuits, params, requested)
+        if getattr(evaluator, "gradient_method", "parameter_shift") != "parameter_shift":
+            spent = list(evaluator.last_gradient_evaluation_counts)
+        else:
+            spent = [cost[id(run)] for _, run in active]
+        metrics = evaluator.metric_tensors(circuits, params, requested)
+        for (_, run), gradient, metric, n in zip(active, gradients, metrics, spent):
+            run.accept_gradient_and_metric(gradient, metric, n)
         active = [job for job in active if not job[1].done]
 
 
@@ -491,8 +581,11 @@ def _minimize_batched(evaluator, jobs: list, on_device: Optional[bool] = False) 
         if not _searched_on_device(evaluator, active, on_device):
             _minimize_adam(evaluator, jobs)
         return
-    if any(isinstance(job[1], _AdamRun) for job in jobs):
-        raise ValueError("Adam runs cannot share a search with runs of another optimiser")
+    if jobs and all(isinstance(job[1], _NaturalGradientRun) for job in jobs):
+        _minimize_natural_gradient(evaluator, jobs)  # (on the host: a device-resident form is not built)
+        return
+    if any(isinstance(job[1], (_AdamRun, _NaturalGradientRun)) for job in jobs):
+        raise ValueError("Adam and NaturalGradient runs cannot share a search with runs of another optimiser")
     if active and isinstance(active[0][1], _NFTRun) and _searched_on_device(evaluator, active, on_device):
         return
     while active:
@@ -620,6 +713,10 @@ class EVQEResult:
     # qubits, (n_qubits, n_qubits), symmetric with a zero diagonal, both in bits (None: not asked for)
     qubit_entropies: Optional[np.ndarray] = None
     mutual_information: Optional[np.ndarray] = None
+    # the Fubini-Study metric of ALL the best individual's parameters at its point, (P, P) in circuit order, and the number of its
+    # eigenvalues above 1e-10 (fp64) or 1e-5 (fp32): how many directions of parameter space move the state (None: not asked for)
+    parameter_metric: Optional[np.ndarray] = None
+    parameter_metric_rank: Optional[int] = None
 
 
 # ---- the solver -----------------------------------------------------------------------------------------------
@@ -881,7 +978,8 @@ class EVQEMinimumEigensolver:
     def compute_minimum_eigenvalue(self, evaluator, search_evaluator=None, aux_operators=None,
                                    eigenstate_states: Optional[int] = None, eigenvalue_variance: bool = False,
                                    aux_operators_covariance: bool = False, subspace_states: Optional[int] = None,
-                                   subspace_rcond: Optional[float] = None, qubit_correlations: bool = False) -> EVQEResult:
+                                   subspace_rcond: Optional[float] = None, qubit_correlations: bool = False,
+                                   parameter_metric: bool = False) -> EVQEResult:
         """``search_evaluator``: a second evaluator of the SAME operator for the parameter searches alone -- a single-precision
         handle: the points a search compares differ by far more than 1e-6 (the reference's own tests run their searches on an
         estimator with precision 0.05, test/minimum_eigensolvers/evqe/solver.py:20-27), a layer search on kept states is bound
@@ -934,7 +1032,13 @@ class EVQEMinimumEigensolver:
         single qubits and pairs; every qubit's entanglement entropy with the rest goes to
         ``result.qubit_entropies`` and the mutual information between every two qubits to ``result.mutual_information``, both
         in bits (``queasars_amd.entanglement``): where the evolved entanglers act, and whether the state is a basis state.
-        The same rules as ``eigenvalue_variance``.  ``False``: no call, both fields stay ``None``."""
+        The same rules as ``eigenvalue_variance``.  ``False``: no call, both fields stay ``None``.
+
+        ``parameter_metric``: after the run, one ``evaluator.metric_tensors`` call at the best individual; the
+        Fubini-Study metric of all its parameters, in the circuit's parameter order, goes to ``result.parameter_metric`` and
+        the number of its eigenvalues above 1e-10 (1e-5 on an fp32 evaluator) to ``result.parameter_metric_rank``: how many
+        directions of the individual's parameter space change the state at all.  The same rules as ``eigenvalue_variance``.
+        ``False``: no call, both fields stay ``None``."""
         cfg = self.configuration
         searcher = evaluator if search_evaluator is None else search_evaluator
         if searcher.n_qubits != evaluator.n_qubits:
@@ -956,6 +1060,8 @@ class EVQEMinimumEigensolver:
                 raise ValueError("aux_operators_covariance needs an evaluator with evaluate_covariances (an operator evaluator)")
         if qubit_correlations and not callable(getattr(evaluator, "reduced_density_matrices", None)):
             raise ValueError("qubit_correlations needs an evaluator with reduced_density_matrices (an operator evaluator)")
+        if parameter_metric and not callable(getattr(evaluator, "metric_tensors", None)):
+            raise ValueError("parameter_metric needs an evaluator with metric_tensors (a device evaluator)")
         if subspace_states is not None:
             if not 1 <= int(subspace_states) <= 64:
                 raise ValueError("subspace_states must be between 1 and 64")
@@ -1060,6 +1166,14 @@ class EVQEMinimumEigensolver:
             circuit = best.get_parameterized_quantum_circuit(shared=self.share_circuits)
             entropies, information = mutual_information(evaluator, [circuit], [list(best.parameter_values)], with_entropies=True)
             result.qubit_entropies, result.mutual_information = entropies[0], information[0]
+        if parameter_metric:
+            best = result.best_individual
+            circuit = best.get_parameterized_quantum_circuit(shared=self.share_circuits)
+            metric = np.array(evaluator.metric_tensors([circuit], [list(best.parameter_values)])[0], dtype=np.float64)
+            device = getattr(evaluator, "statevector_device", None)
+            floor = 1e-5 if getattr(device, "dtype", "fp64") == "fp32" else 1e-10
+            result.parameter_metric = metric
+            result.parameter_metric_rank = int((np.linalg.eigvalsh(metric) > floor).sum()) if metric.size else 0
         return result
 
     def _refine_in_subspace(self, evaluator, result: EVQEResult, last_scored, k: int, rcond: Optional[float]) -> None:

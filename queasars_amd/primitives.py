@@ -439,3 +439,40 @@ class GpuStateFidelity:
                     state.release()
         fidelities = [float(abs(overlaps[i, k]) ** 2) for i, k in zip(first_at, second_at)]
         return _Job(SimpleNamespace(fidelities=fidelities, raw_fidelities=list(fidelities), metadata=[{} for _ in fidelities]))
+
+
+class GpuQFI:
+    """``run(circuits, parameter_values).result().qfis``: the quantum Fisher information matrices ``4 G`` of parametrised
+    circuits at the given points, G the Fubini-Study metric, in the call shape of Qiskit Algorithms' ``QFI`` (duck-typed, as
+    the other front ends are; a single circuit and a single value vector are accepted as lists of one).  ``parameters``: per
+    circuit the parameter INDICES (in the circuit's parameter order) to differentiate by, or None for all.  The metric is
+    formed on the device from one reverse sweep per circuit (``StatevectorDevice.metric_tensors``); no
+    statevector leaves it.  Circuits of different widths go to a device each."""
+
+    def __init__(self, dtype: str = "fp64", device: int = 0, statevector_device: Optional[StatevectorDevice] = None):
+        self._dtype, self._device_index = dtype, device
+        self._convert = _Converter()
+        self._devices: dict[int, StatevectorDevice] = {}
+        if statevector_device is not None:
+            self._devices[statevector_device.n_qubits] = statevector_device
+
+    _device = GpuStateFidelity._device
+
+    def run(self, circuits: Any, parameter_values: Any = None, parameters: Any = None) -> _Job:
+        circuits, values = GpuStateFidelity._as_lists(circuits, parameter_values)
+        irs = [self._convert.circuit(c) for c in circuits]
+        for ir, row in zip(irs, values):
+            if len(row) != ir.num_parameters:
+                raise ValueError(f"a circuit has {ir.num_parameters} parameters, {len(row)} values were given")
+        if parameters is not None and len(parameters) != len(irs):
+            raise ValueError(f"{len(irs)} circuits but {len(parameters)} parameter lists")
+        wrt = None if parameters is None else [list(range(ir.num_parameters)) if p is None else [int(i) for i in p]
+                                               for ir, p in zip(irs, parameters)]
+        qfis: list = [None] * len(irs)
+        for width in sorted({ir.n_qubits for ir in irs}):
+            rows = [i for i, ir in enumerate(irs) if ir.n_qubits == width]
+            metrics = self._device(width).metric_tensors([irs[i] for i in rows], [values[i] for i in rows],
+                                                         None if wrt is None else [wrt[i] for i in rows])
+            for i, metric in zip(rows, metrics):
+                qfis[i] = 4.0 * metric
+        return _Job(SimpleNamespace(qfis=qfis, metadata=[{} for _ in qfis]))
