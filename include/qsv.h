@@ -701,6 +701,44 @@ typedef struct qsv_adjoint_stats_t {
 int qsv_adjoint_stats(const qsv_t* h, qsv_adjoint_stats_t* out);
 
 /*
+ * DEFLATED COSTS: values and gradients of the variational-deflation cost
+ *     C_e = <psi_e|H_h|psi_e> + sum_k betas[k] |<phi_k|psi_e>|^2
+ * against n_states kept states phi_k (qsv_prefix_create; prefix_ids in any order, repeats allowed, at most
+ * QSV_OVERLAP_MAX_STATES).  The gradient is the adjoint sweep's with another seed: lambda_G = H_h psi_e + sum_k betas[k] c_ek phi_k
+ * with c_ek = <phi_k|psi_e>, for which Re<psi_e|lambda_G> = C_e; planner, runs, combination and every contract of the adjoint
+ * entry points carry over.  Per launch group, on the handle's stream: lambda = H_h psi, the overlap panels and their
+ * ascending-order reduction (qsv_overlap_circuits' kernels; c stays in device memory), one kernel that adds the rank-n_states
+ * update to lambda on the fp64 matrix pipe (the sum over k ascending in the position of prefix_ids, fp64 also on an fp32 handle),
+ * the runs, the combination, and the penalties added to E in ascending k.  A launch group in which no evaluation has a gate to
+ * sweep -- a call whose wrt counts are all 0: the value-only call -- does not run the update.
+ *     out          the gradient rows, as qsv_adjoint_gradient_circuits packs them
+ *     out_values   (may be NULL) C_e          out_energies (may be NULL) E_e = <psi_e|H_h|psi_e>
+ *     out_overlaps (may be NULL) [n_evals][n_states][2]: c_ek (re, im), the bits qsv_overlap_circuits returns
+ * Contract: n_states == 0 returns, bit for bit, what qsv_adjoint_gradient_circuits returns; an evaluation's row, value, energy
+ * and overlaps are the same bits in any batch, at any position of a launch group, from either entry point and on every call; the
+ * entries of a wrt subset are the bits of the full gradient.  Scratch growth is counted in qsv_adjoint_stats, and the update is
+ * one more state sweep per evaluation of a group that runs it.
+ * Errors: no operator set QSV_E_STATE; prefix_ids or betas NULL with n_states > 0, a non-finite beta, an unknown or released kept
+ * state, and the adjoint call's wrt and out_width errors QSV_E_ARG; n_states > QSV_OVERLAP_MAX_STATES, more than 28 qubits, a
+ * circuit on a kept state QSV_E_UNSUPPORTED; a batch open on this thread QSV_E_STATE; n_evals == 0 QSV_OK.
+ */
+int qsv_deflated_gradient_circuits(qsv_t* h, int n_states, const int* prefix_ids, const double* betas /* n_states doubles */,
+                                   int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
+                                   const int64_t* wrt_offsets /* NULL: every parameter of each circuit */, const int32_t* wrt,
+                                   double* out, double* out_values /* may be NULL */, double* out_energies /* may be NULL */,
+                                   double* out_overlaps /* may be NULL */);
+/*
+ * The same with the points READ FROM and the rows LEFT IN device memory: qsv_adjoint_gradient_device's layout, ready_event and
+ * stream contract (queued on the handle's stream, not waited for; nothing crosses to the host between the forward run and the
+ * sweep).  prefix_ids and betas are host memory.  device_out_values / device_out_energies: n_evals doubles; device_out_overlaps:
+ * n_evals * n_states * 2 doubles; each may be NULL.
+ */
+int qsv_deflated_gradient_device(qsv_t* h, int n_states, const int* prefix_ids, const double* betas, int n_evals, const int* circuit_ids,
+                                 int width, const double* device_values, void* ready_event, const int64_t* wrt_offsets, const int32_t* wrt,
+                                 int out_width, double* device_out, double* device_out_values /* may be NULL */,
+                                 double* device_out_energies /* may be NULL */, double* device_out_overlaps /* may be NULL */);
+
+/*
  * ENERGY VARIANCE: out_variances[e] = <psi_e| H_h^2 |psi_e> - <psi_e| H_h |psi_e>^2 and, where out_values is
  * not NULL, out_values[e] = <psi_e| H_h |psi_e>, for n_evals (circuit, parameter vector) pairs laid out as in qsv_eval_circuits;
  * H_h is the Hermitian part of the operator (what qsv_set_operator keeps).  Zero exactly on eigenstates of H_h; the spread of a

@@ -299,6 +299,8 @@ SIGNATURES = {
     "qsv_adjoint_gradient_circuits": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "qsv_adjoint_gradient_device": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P]),
     "qsv_adjoint_stats": (C.c_int, [_P, C.POINTER(QsvAdjointStats)]),
+    "qsv_deflated_gradient_circuits": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "qsv_deflated_gradient_device": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
     "qsv_variance_circuits": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
     "qsv_observables_covariance": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "qsv_overlap_circuits": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),

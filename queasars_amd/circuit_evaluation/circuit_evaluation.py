@@ -1201,6 +1201,70 @@ class StatevectorDevice:
         self._check(self._lib.qsv_adjoint_stats(self._handle, C.byref(stats)))
         return _struct_dict(stats)
 
+    # -- deflated costs against kept states ---------------------------------------------------------
+    def _deflation_arguments(self, kept_states, betas) -> tuple[np.ndarray, np.ndarray]:
+        """(kept-state ids, weights) of a deflated call as the library takes them: every state kept on THIS device
+        (:meth:`_kept_id`), one finite weight each, at most :attr:`MAX_OVERLAP_STATES`."""
+        kept_states = list(kept_states)
+        for kept in kept_states:
+            if not isinstance(kept, KeptState):
+                raise ValueError("kept_states must hold KeptState objects (StatevectorDevice.keep_states)")
+        ids = np.asarray([self._kept_id(kept) for kept in kept_states], dtype=np.int32).reshape(-1)
+        weights = np.ascontiguousarray(np.asarray(betas, dtype=np.float64).reshape(-1))
+        if len(weights) != len(ids):
+            raise ValueError("betas must hold one weight per kept state")
+        if not np.all(np.isfinite(weights)):
+            raise ValueError("betas must be finite")
+        if len(ids) > self.MAX_OVERLAP_STATES:
+            raise ValueError(f"a deflated cost takes at most {self.MAX_OVERLAP_STATES} kept states")
+        return ids, weights
+
+    def deflated_gradients(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]],
+                           kept_states: Sequence[KeptState], betas: Sequence[float], wrt=None, with_values: bool = False,
+                           with_overlaps: bool = False):
+        """Gradients of the deflated (VQD) cost ``C_i = <psi_i|H|psi_i> + sum_k betas[k] |<phi_k|psi_i>|^2`` against the kept
+        states phi_k, from the adjoint sweep with the deflated seed (``qsv_deflated_gradient_circuits``): one
+        1-D array per circuit, ``wrt`` as in :meth:`gradients` -- an empty ``wrt`` is the value-only call, which sweeps
+        nothing.  ``with_values``: also ``(costs, energies)``, two float64 arrays (C and ``<H>`` alone); ``with_overlaps``:
+        also the complex128 ``(n, K)`` array of ``<phi_k|psi_i>``, the bits :meth:`overlaps` returns.  The result is the
+        gradients alone, or a tuple ``(gradients[, costs, energies][, overlaps])``.  With no kept state it is
+        :meth:`adjoint_gradients`, bit for bit."""
+        ids, weights = self._deflation_arguments(kept_states, betas)
+        n, k = len(circuits), len(ids)
+        values = np.zeros(n, dtype=np.float64)
+        energies = np.zeros(n, dtype=np.float64)
+        overlaps = np.zeros((n, k), dtype=np.complex128)
+        entry = self._lib.qsv_deflated_gradient_circuits
+
+        def function(handle, *rest):
+            return entry(handle, k, _pointer(ids) if k else None, _pointer(weights) if k else None, *rest[:-1], *rest[-1])
+
+        trailing = (_lib.as_ptr(values), _lib.as_ptr(energies), _lib.as_ptr(overlaps) if with_overlaps and k else None)
+        gradients = self._host_gradients(function, circuits, parameter_values, wrt, trailing)
+        self.last_gradient_evaluations = len(gradients)
+        out = (gradients,) + ((values, energies) if with_values else ()) + ((overlaps,) if with_overlaps else ())
+        return out if len(out) > 1 else gradients
+
+    def deflated_gradients_of_device_parameters(self, circuits: Sequence[CircuitIR], matrix_ptr: int, width: int, event: int,
+                                                out_ptr: int, out_width: int, kept_states: Sequence[KeptState],
+                                                betas: Sequence[float], wrt=None, values_ptr: int = 0, energies_ptr: int = 0,
+                                                overlaps_ptr: int = 0) -> int:
+        """:meth:`deflated_gradients` with the layout and the contract of :meth:`gradients_of_device_parameters`
+        (``qsv_deflated_gradient_device``): points read from and gradients left in device memory, queued on the handle's
+        stream, not waited for.  ``values_ptr`` / ``energies_ptr``: device memory for ``len(circuits)`` doubles each,
+        ``overlaps_ptr`` for ``len(circuits) * K * 2``, or 0.  Returns ``len(circuits)``, the evaluations counted."""
+        ids, weights = self._deflation_arguments(kept_states, betas)
+        k = len(ids)
+        entry = self._lib.qsv_deflated_gradient_device
+
+        def function(handle, *rest):
+            return entry(handle, k, _pointer(ids) if k else None, _pointer(weights) if k else None, *rest[:-1], *rest[-1])
+
+        self._device_gradients(function, circuits, matrix_ptr, width, event, out_ptr, out_width, wrt,
+                               (_pointer(values_ptr), _pointer(energies_ptr), _pointer(overlaps_ptr)))
+        self.last_gradient_evaluations = len(circuits)
+        return self.last_gradient_evaluations
+
     # -- the operator's variance ------------------------------------------------------------------
     def variances(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]]) -> tuple[np.ndarray, np.ndarray]:
         """``(values, variances)`` of the operator set on the device, two float64 arrays with one entry per (circuit, parameter
@@ -1545,6 +1609,14 @@ class _OperatorEvaluator(BaseCircuitEvaluator):
     @property
     def statevector_device(self) -> StatevectorDevice:
         return self._device
+
+    @property
+    def operator(self) -> PauliOperator:
+        return self._operator
+
+    @property
+    def initial_state_circuit(self) -> Optional[CircuitIR]:
+        return self._initial_state_circuit
 
     def _own_operator(self):
         """:meth:`StatevectorDevice.with_operator` for this evaluator's operator: around everything that reads it there."""
@@ -2065,6 +2137,105 @@ class OperatorCircuitEvaluator(_OperatorEvaluator):
             else:
                 self._device.expectation_values_to_device(circuits, parameter_values, device_pointer)
         return True
+
+
+class DeflatedOperatorCircuitEvaluator(_OperatorEvaluator):
+    """The deflated (VQD) cost ``C = <psi|H|psi> + sum_k betas[k] |<phi_k|psi>|^2`` of ``operator`` against ``kept_states``
+    (``keep_states`` of an evaluator or device: the states found so far), exact, on the GPU.  Its minimum
+    over states is the lowest eigenvalue whose eigenvector the kept states do not span, so a search on it finds the next
+    eigenstate (:func:`queasars_amd.evqe.deflation.compute_eigenvalues`).
+
+    :param kept_states: :class:`KeptState` objects of ONE device, which becomes this evaluator's device (``device`` and
+        ``dtype`` are used only where there is none to take it from); at most 64
+    :param betas: one weight per kept state; ``None``: 2 * sum_k |c_k| over the operator's coefficients for every kept state --
+        at least the operator's spectral width, so the deflated minimum is the next eigenvalue whatever the gap
+    :param initial_state_circuit: as :class:`OperatorCircuitEvaluator`
+
+    ``evaluate_circuits`` gives the cost (a value-only call: nothing is swept), ``evaluate_gradients`` its exact gradient by
+    the adjoint sweep with the deflated seed (there is no parameter-shift form), ``evaluate_deflation_terms`` what was paid to
+    which kept state.  Circuits that continue a kept state are refused."""
+
+    MAX_KEPT_STATES = 64  # (StatevectorDevice.MAX_OVERLAP_STATES)
+    #: what the solver's host drivers read: every circuit is differentiated by one sweep
+    gradient_method = "adjoint"
+    last_gradient_evaluations = 0
+    last_gradient_evaluation_counts: list = []
+
+    def __init__(
+        self,
+        operator: PauliOperator,
+        kept_states: Sequence[KeptState],
+        betas: Optional[Sequence[float]] = None,
+        initial_state_circuit: Optional[CircuitIR] = None,
+        dtype: str = "fp64",
+        device: int = 0,
+        statevector_device: Optional[StatevectorDevice] = None,
+    ):
+        if not isinstance(operator, PauliOperator):
+            raise ValueError("The operator must be a PauliOperator!")
+        _check_initial_state(initial_state_circuit, operator.num_qubits, "the amount of qubits in the given operator")
+        if initial_state_circuit is not None and initial_state_circuit.num_parameters:
+            raise ValueError("The initial state circuit must not have free parameters!")
+        kept_states = list(kept_states)
+        for kept in kept_states:
+            if not isinstance(kept, KeptState):
+                raise ValueError("kept_states must hold KeptState objects (keep_states)")
+        if statevector_device is None and kept_states:
+            statevector_device = kept_states[0]._owner()
+        if statevector_device is not None and statevector_device.n_qubits != operator.num_qubits:
+            raise ValueError("the kept states' device was created for a different number of qubits")
+        if betas is None:
+            betas = [2.0 * float(np.abs(operator.coeffs).sum())] * len(kept_states)
+        betas = [float(b) for b in betas]
+        if len(betas) != len(kept_states):
+            raise ValueError("betas must hold one weight per kept state")
+        super().__init__(operator, initial_state_circuit, dtype, device, statevector_device)
+        for kept in kept_states:
+            self._device._kept_id(kept)  # (every kept state is this device's, and alive)
+        self._kept_states = kept_states
+        self._betas = betas
+
+    @property
+    def kept_states(self) -> list:
+        return list(self._kept_states)
+
+    @property
+    def betas(self) -> list:
+        return list(self._betas)
+
+    def _deflated(self, circuits, parameter_values, wrt, **options):
+        """One :meth:`StatevectorDevice.deflated_gradients` call: behind the initial state, the operator under the guard."""
+        if _has_none(circuits) or _has_none(parameter_values):
+            circuits, parameter_values = _present_pairs(circuits, parameter_values)
+        _same_length(len(circuits), len(parameter_values))
+        circuits = self._behind_initial_state(circuits)
+        with self._own_operator():
+            return self._device.deflated_gradients(circuits, parameter_values, self._kept_states, self._betas, wrt, **options)
+
+    def evaluate_circuits(self, circuits: list[CircuitIR], parameter_values: list[list[float]]) -> list[float]:
+        """The deflated cost of every circuit: the forward run, H psi and the overlaps -- no gate is swept."""
+        _gradients, costs, _energies = self._deflated(circuits, parameter_values, [], with_values=True)
+        return costs.tolist()
+
+    def evaluate_gradients(self, circuits: list[CircuitIR], parameter_values: list[list[float]], wrt=None) -> list[np.ndarray]:
+        """Exact gradients of :meth:`evaluate_circuits`: one 1-D array per circuit, ``wrt`` as in
+        :meth:`OperatorCircuitEvaluator.evaluate_gradients`.  :attr:`last_gradient_evaluations` counts one per circuit."""
+        gradients = self._deflated(circuits, parameter_values, wrt)
+        self.last_gradient_evaluations = len(gradients)
+        self.last_gradient_evaluation_counts = [1] * len(gradients)
+        return gradients
+
+    def evaluate_deflation_terms(self, circuits: list[CircuitIR], parameter_values: list[list[float]]):
+        """``(energies, overlaps)``: ``<psi_i|H|psi_i>`` alone as a float64 array, and the complex128 ``(n, K)`` array of
+        ``<phi_k|psi_i>`` -- the cost is ``energies[i] + sum_k betas[k] * abs(overlaps[i, k]) ** 2``."""
+        _gradients, _costs, energies, overlaps = self._deflated(circuits, parameter_values, [], with_values=True, with_overlaps=True)
+        return energies, overlaps
+
+    #: a search on the deflated cost runs the host drivers (DESIGN.md 4.18: not built)
+    device_resident_search_by_default = False
+
+    def device_resident_search_possible(self) -> bool:
+        return False
 
 
 def measure_quasi_distributions(

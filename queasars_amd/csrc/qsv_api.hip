@@ -24,6 +24,7 @@
 #include "overlap.hpp"
 #include "reduced_density.hpp"
 #include "metric.hpp"
+#include "deflation.hpp"
 #include "gradient.hpp"
 #include "value_cache.hpp"
 #include "kernels.hpp"
@@ -494,6 +495,10 @@ struct qsv_handle {
     DeviceBuffer d_adj_lambda, d_adj_tab, d_adj_mats, d_adj_partials, d_adj_epart, d_adj_base, d_adj_out, d_adj_values;
     const void* adj_checked[3] = {nullptr, nullptr, nullptr};  // qsv_adjoint_gradient_device's pointers last found to be this device's memory
     qsv_adjoint_stats_t adj_stats{};
+    // deflated costs (qsv_deflated_gradient_circuits / qsv_deflated_gradient_device; deflation.hpp): one launch group's overlaps by
+    // position | its partial tiles; the host form's energies | overlaps.  Counted with the adjoint scratch (adj_stats).
+    DeviceBuffer d_defl, d_defl_out;
+    const void* defl_checked[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // qsv_deflated_gradient_device's pointers
     // the operator's moments (qsv_variance_circuits; moments.hpp): the call's (E, Var) pairs by position | one launch group's partials
     DeviceBuffer d_moments;
     // an observable set's second moments (qsv_observables_covariance; covariance.hpp): the call's values | covariances by position |
@@ -3131,7 +3136,7 @@ void qsv_destroy(qsv_t* h) {
                             &h->d_states, &h->d_wtab, &h->d_side, &h->d_factor, &h->d_factor_count, &h->d_factor_big, &h->d_factor_big_count, &h->d_quad, &h->d_fterms, &h->d_fpart, &h->d_batch, &h->d_mats, &h->d_partials, &h->d_out, &h->d_scratch, &h->d_prefix, &h->d_sdiag,
                             &h->d_obs_partials, &h->d_obs_values, &h->d_grad_tab, &h->d_grad_rows, &h->d_grad_values, &h->d_grad_base,
                             &h->d_grad_out, &h->d_adj_lambda, &h->d_adj_tab, &h->d_adj_mats, &h->d_adj_partials, &h->d_adj_epart, &h->d_adj_base,
-                            &h->d_adj_out, &h->d_adj_values, &h->d_moments, &h->d_cov, &h->d_overlap, &h->d_rdm,
+                            &h->d_adj_out, &h->d_adj_values, &h->d_defl, &h->d_defl_out, &h->d_moments, &h->d_cov, &h->d_overlap, &h->d_rdm,
                             &h->d_met_scratch, &h->d_met_tab, &h->d_met_mats, &h->d_met_partials, &h->d_met_base, &h->d_met_out})
         if (b->ptr) (void)hipFree(b->ptr);
     for (auto& kv : h->obs_sets) free_observable_set(kv.second);
@@ -4844,12 +4849,25 @@ struct AdjCall {
     int out_width;
     double* out_values;
 };
+// The deflated cost's extension of the sweep's seed: lambda_G = H_h psi + sum_k betas[k] c_k phi_k against the
+// kept states `refs`, c_k = <phi_k|psi> from the overlap panels.  With it AdjCall::out_values receives the cost
+// E + sum_k betas[k] |c_k|^2; out_energies (E) and out_overlaps ([row][k][2]) are device memory and may be null.  `timed`
+// (may be null): under option "time_moments" the deflate kernel of every group between events of its own.
+struct AdjSeed {
+    uint32_t n_refs = 0;
+    OverlapRefs refs{};
+    const double* betas = nullptr;  // host memory
+    double* out_energies = nullptr;
+    double* out_overlaps = nullptr;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>>* timed = nullptr;
+};
 
 // What both entry points run with the lock held: the call's tables, the forward run group by group, and behind each group the H
 // application, the runs and the combination on the handle's stream.  Returns without waiting.
 static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, const int64_t* wrt_offsets, const int32_t* wrt,
-                          const AdjCall& call) {
+                          const AdjCall& call, const AdjSeed* seed = nullptr) {
     const size_t n_evals = args.circs.size();
+    const size_t K = seed ? size_t(seed->n_refs) : 0;
     if (h->n_terms == 0) return fail(h, QSV_E_STATE, "no operator set (call qsv_set_operator first)");
     h->adj_stats.n_gates = h->adj_stats.n_runs = h->adj_stats.n_state_sweeps = 0;
     // ---- the tables: per distinct circuit its swept gates, runs and the slots that read each parameter; per evaluation its entries
@@ -4935,7 +4953,9 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
     if (n_evals == 0) return QSV_OK;
 
     // ---- the forward run's layout (ordinary plans into state slots, never split: as qsv_prefix_create runs them)
-    const size_t G = std::max<size_t>(1, std::min<size_t>(size_t(h->group), 4096));
+    // (against kept states the group is the overlap panels' where that is smaller: their partial tiles stay under 64 MiB)
+    const size_t G_sweep = std::max<size_t>(1, std::min<size_t>(size_t(h->group), 4096));
+    const size_t G = K ? overlap_group(h->n, K, false, std::min(G_sweep, size_t(std::max(1, h->max_grid_y)))) : G_sweep;
     const StateRun run{SplitRule{}, 1, G, false, 0, kModeSynthFirst | kModeFinalStore};
     BatchRelease release{h};
     StateLayout lay;
@@ -4948,11 +4968,12 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
         const CircuitTables& t = tables.at(args.circs[e]);
         evals[j] = AdjEval{t.gate_base, t.run_base, eval_runs[e], eval_gates[e], uint32_t(e), 0};
     }
-    // one blob: [gates][runs][entries][entry offsets][slots, padded to 8 bytes][evaluations by position]
+    // one blob: [gates][runs][entries][entry offsets][slots, padded to 8 bytes][evaluations by position][the seed's betas]
     auto padded = [](size_t bytes) { return (bytes + 7) / 8 * 8; };
     const size_t off_gates = 0, off_runs = off_gates + gates.size() * sizeof(AdjGate), off_entries = off_runs + runs.size() * sizeof(AdjRunDesc),
                  off_offsets = off_entries + entries.size() * sizeof(AdjEntry), off_slots = off_offsets + entry_offsets.size() * sizeof(int64_t),
-                 off_evals = off_slots + padded(slots.size() * sizeof(uint32_t)), tab_bytes = off_evals + evals.size() * sizeof(AdjEval);
+                 off_evals = off_slots + padded(slots.size() * sizeof(uint32_t)), off_betas = off_evals + evals.size() * sizeof(AdjEval),
+                 tab_bytes = off_betas + K * sizeof(double);
     std::vector<char> blob(tab_bytes, 0);
     auto put = [&](size_t off, const void* src, size_t bytes) {
         if (bytes) std::memcpy(blob.data() + off, src, bytes);
@@ -4963,6 +4984,7 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
     put(off_offsets, entry_offsets.data(), entry_offsets.size() * sizeof(int64_t));
     put(off_slots, slots.data(), slots.size() * sizeof(uint32_t));
     put(off_evals, evals.data(), evals.size() * sizeof(AdjEval));
+    if (K) put(off_betas, seed->betas, K * sizeof(double));
     const size_t gc_max = std::min(G, n_evals);
     const uint64_t dim = uint64_t(1) << h->n;
     const uint32_t blocks = adjoint_blocks(h->n), op_blocks = adjoint_op_blocks(h->n);
@@ -4972,6 +4994,9 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
         (rc = ensure_counted(h, h->d_adj_partials, gc_max * 3 * std::max<size_t>(1, max_gates) * blocks * sizeof(double), allocations)) ||
         (rc = ensure_counted(h, h->d_adj_epart, gc_max * op_blocks * sizeof(double), allocations)))
         return rc;
+    // the seed's scratch: the group's overlaps by position | the panels' partial tiles
+    const size_t ovl_bytes = (gc_max * K * 2 * sizeof(double) + 63) / 64 * 64;
+    if (K && (rc = ensure_counted(h, h->d_defl, ovl_bytes + overlap_partial_bytes(h->n, K, false, gc_max), allocations))) return rc;
     // (lay_out_states has waited for whatever an earlier call without a wait left running: nothing reads the old tables)
     QSV_HIP(h, hipMemcpy(h->d_adj_tab.ptr, blob.data(), tab_bytes, hipMemcpyHostToDevice));
     const char* dt = static_cast<const char*>(h->d_adj_tab.ptr);
@@ -4981,6 +5006,11 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
     const int64_t* d_offsets = reinterpret_cast<const int64_t*>(dt + off_offsets);
     const uint32_t* d_slots = reinterpret_cast<const uint32_t*>(dt + off_slots);
     const AdjEval* d_evals = reinterpret_cast<const AdjEval*>(dt + off_evals);
+    const double* d_betas = reinterpret_cast<const double*>(dt + off_betas);
+    double* d_ovl = static_cast<double*>(h->d_defl.ptr);
+    double* ovl_partials = K ? reinterpret_cast<double*>(static_cast<char*>(h->d_defl.ptr) + ovl_bytes) : nullptr;
+    // E goes where the caller wants it apart from the cost; the cost is written behind it by the seed's finishing kernel
+    double* const d_energies = seed && seed->out_energies ? seed->out_energies : call.out_values;
     double* mats = static_cast<double*>(h->d_adj_mats.ptr);
     double* partials = static_cast<double*>(h->d_adj_partials.ptr);
     double* e_partials = static_cast<double*>(h->d_adj_epart.ptr);
@@ -4994,13 +5024,36 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
                                                  streaming, e_partials, h->stream));
         uint32_t most_runs = 0;
         for (size_t j = g0; j < g0 + gc; ++j) most_runs = std::max(most_runs, evals[j].n_runs);
+        if (K) {
+            // c = Phi^H Psi while the states are still the final ones (the runs rewrite them), then -- where a gate is swept at all --
+            // lambda += sum_k beta_k c_k phi_k
+            QSV_HIP(h, launch_overlap_panels(h->dtype, h->d_states.ptr, h->d_prefix.ptr, seed->refs, uint32_t(K), h->n, int(gc), nullptr, -1,
+                                             nullptr, nullptr, nullptr, nullptr, ovl_partials, h->stream));
+            QSV_HIP(h, launch_overlap_combine(ovl_partials, h->n, int(gc), uint32_t(K), d_ovl, nullptr, h->stream));
+            if (most_runs > 0) {
+                const bool timing = h->time_moments && seed->timed;
+                if (timing) {
+                    seed->timed->emplace_back(nullptr, nullptr);
+                    QSV_HIP(h, hipEventCreate(&seed->timed->back().first));
+                    QSV_HIP(h, hipEventCreate(&seed->timed->back().second));
+                    QSV_HIP(h, hipEventRecord(seed->timed->back().first, h->stream));
+                }
+                QSV_HIP(h, launch_deflate(h->dtype, h->d_adj_lambda.ptr, h->d_prefix.ptr, seed->refs, uint32_t(K), h->n, int(gc), d_betas, d_ovl,
+                                          streaming, h->stream));
+                if (timing) QSV_HIP(h, hipEventRecord(seed->timed->back().second, h->stream));
+                h->adj_stats.n_state_sweeps += int64_t(gc);
+            }
+        }
         for (uint32_t r = 0; r < most_runs; ++r) {
             QSV_HIP(h, launch_adjoint_run(h->dtype, h->d_states.ptr, h->d_adj_lambda.ptr, h->n, int(gc), r, d_evals + g0, d_runs, d_gates, mats,
                                           max_gates, streaming, partials, h->stream));
             h->adj_stats.n_runs += 1;
         }
         QSV_HIP(h, launch_adjoint_combine(d_evals + g0, int(gc), d_offsets, d_entries, d_slots, partials, max_gates, blocks, e_partials,
-                                          op_blocks, call.out_width, call.out, call.out_values, h->stream));
+                                          op_blocks, call.out_width, call.out, d_energies, h->stream));
+        if (seed && (K || (seed->out_energies && call.out_values)))
+            QSV_HIP(h, launch_deflation_finish(d_evals + g0, int(gc), uint32_t(K), d_betas, d_ovl, d_energies, call.out_values,
+                                               K ? seed->out_overlaps : nullptr, h->stream));
         return QSV_OK;
     };
     return run_laid_out(h, args, run, lay, {}, sweep);
@@ -5071,12 +5124,134 @@ int qsv_adjoint_gradient_device(qsv_t* h, int n_evals, const int* circuit_ids, i
     return rc;
 }
 
+// ---- deflated costs against kept states (qsv.h: DEFLATED COSTS; deflation.hpp) -----------------------------------------------------
+
+// The kept states and weights of a deflated call, checked, as adjoint_locked's seed extension.
+static int deflation_seed(qsv_t* h, int n_states, const int* prefix_ids, const double* betas, int n_evals, AdjSeed& seed) {
+    if (n_states < 0) return fail(h, QSV_E_ARG, "n_states is negative");
+    if (n_states > int(kOvlMaxStates)) return fail(h, QSV_E_UNSUPPORTED, "n_states: deflated costs are available against up to 64 kept states per call");
+    if (n_states > 0 && !prefix_ids) return fail(h, QSV_E_ARG, "prefix_ids is null");
+    if (n_states > 0 && !betas) return fail(h, QSV_E_ARG, "betas is null");
+    for (int k = 0; k < n_states; ++k)
+        if (!std::isfinite(betas[k])) return fail(h, QSV_E_ARG, "betas[" + std::to_string(k) + "] is not finite");
+    // (the register's size is the handle's own: asked before the kept states, which such a handle need not hold)
+    if (n_evals > 0 && h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "deflated costs are available up to 28 qubits, this handle has " + std::to_string(h->n));
+    seed.n_refs = uint32_t(n_states);
+    seed.betas = betas;
+    for (int k = 0; k < n_states; ++k) {
+        const auto it = h->prefixes.find(prefix_ids[k]);
+        if (it == h->prefixes.end() || it->second.released) return fail(h, QSV_E_ARG, "unknown kept state " + std::to_string(prefix_ids[k]));
+        seed.refs.slot[k] = it->second.slot;
+    }
+    return QSV_OK;
+}
+
+int qsv_deflated_gradient_circuits(qsv_t* h, int n_states, const int* prefix_ids, const double* betas, int n_evals, const int* circuit_ids,
+                                   const int64_t* param_offsets, const double* params, const int64_t* wrt_offsets, const int32_t* wrt,
+                                   double* out, double* out_values, double* out_energies, double* out_overlaps) {
+    QSV_OPEN(h, "qsv_deflated_gradient_circuits", kDevice);
+    if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets))) return fail(h, QSV_E_ARG, "bad arguments");
+    AdjSeed seed;
+    int rc = deflation_seed(h, n_states, prefix_ids, betas, n_evals, seed);
+    if (rc) return rc;
+    if (n_evals == 0) return QSV_OK;
+    BatchArgs packed;
+    if ((rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, packed, "deflated gradients of a circuit on a kept state are not built")))
+        return rc;
+    int64_t width, out_width;
+    std::vector<double> base;
+    if ((rc = pack_rows(h, packed, wrt_offsets, out, true, width, out_width, base))) return rc;
+    if ((rc = wait_pending(h))) return rc;  // (the buffers below may still be read or written by a call that did not wait)
+    const size_t n = size_t(n_evals), K = size_t(n_states);
+    int64_t& allocations = h->adj_stats.n_allocations;
+    if ((rc = ensure_counted(h, h->d_adj_base, base.size() * sizeof(double), allocations)) ||
+        (rc = ensure_counted(h, h->d_adj_out, n * size_t(out_width) * sizeof(double), allocations)) ||
+        (rc = ensure_counted(h, h->d_adj_values, n * sizeof(double), allocations)) ||
+        (rc = ensure_counted(h, h->d_defl_out, (n + n * K * 2) * sizeof(double), allocations)))
+        return rc;
+    QSV_HIP(h, hipMemcpy(h->d_adj_base.ptr, base.data(), base.size() * sizeof(double), hipMemcpyHostToDevice));
+    BatchArgs args;
+    args.circs = packed.circs;
+    args.values.assign(1, 0.0);
+    args.n_params.assign(n, width);
+    args.device_values = static_cast<const double*>(h->d_adj_base.ptr);
+    const AdjCall call{args.device_values, int(width), static_cast<double*>(h->d_adj_out.ptr), int(out_width), static_cast<double*>(h->d_adj_values.ptr)};
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> timed;
+    struct DestroyEvents {
+        std::vector<std::pair<hipEvent_t, hipEvent_t>>& list;
+        ~DestroyEvents() {
+            for (auto& p : list) {
+                if (p.first) (void)hipEventDestroy(p.first);
+                if (p.second) (void)hipEventDestroy(p.second);
+            }
+        }
+    } destroy_events{timed};
+    double* const d_energies = static_cast<double*>(h->d_defl_out.ptr);
+    seed.out_energies = out_energies ? d_energies : nullptr;
+    seed.out_overlaps = out_overlaps && K ? d_energies + n : nullptr;
+    seed.timed = &timed;
+    rc = adjoint_locked(h, args, circuit_ids, wrt_offsets, wrt, call, &seed);
+    if (rc) {
+        (void)sync_streams(h);
+        return rc;
+    }
+    std::vector<double> rows(n * size_t(out_width)), values(n), extra(n + n * K * 2);
+    QSV_HIP(h, hipMemcpyAsync(rows.data(), h->d_adj_out.ptr, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QSV_HIP(h, hipMemcpyAsync(values.data(), h->d_adj_values.ptr, values.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (seed.out_energies || seed.out_overlaps)
+        QSV_HIP(h, hipMemcpyAsync(extra.data(), d_energies, extra.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QSV_HIP(h, sync_streams(h));
+    h->async_pending = false;
+    for (const auto& p : timed) {
+        float ms = 0.0f;
+        QSV_HIP(h, hipEventElapsedTime(&ms, p.first, p.second));
+        h->prof.expect_ms += double(ms);
+    }
+    unpack_rows(packed, wrt_offsets, rows, out_width, out);
+    if (out_values) std::memcpy(out_values, values.data(), n * sizeof(double));
+    if (out_energies) std::memcpy(out_energies, extra.data(), n * sizeof(double));
+    if (seed.out_overlaps) std::memcpy(out_overlaps, extra.data() + n, n * K * 2 * sizeof(double));
+    return QSV_OK;
+}
+
+int qsv_deflated_gradient_device(qsv_t* h, int n_states, const int* prefix_ids, const double* betas, int n_evals, const int* circuit_ids,
+                                 int width, const double* device_values, void* ready_event, const int64_t* wrt_offsets, const int32_t* wrt,
+                                 int out_width, double* device_out, double* device_out_values, double* device_out_energies,
+                                 double* device_out_overlaps) {
+    QSV_OPEN(h, "qsv_deflated_gradient_device", kDevice);
+    if (n_evals < 0 || width < 0 || out_width < 0 || (n_evals > 0 && (!circuit_ids || (out_width > 0 && !device_out) || (width > 0 && !device_values))))
+        return fail(h, QSV_E_ARG, "bad arguments");
+    AdjSeed seed;
+    int rc = deflation_seed(h, n_states, prefix_ids, betas, n_evals, seed);
+    if (rc) return rc;
+    if (n_evals == 0) return QSV_OK;
+    const void* given[5] = {width > 0 ? device_values : nullptr, out_width > 0 ? device_out : nullptr, device_out_values, device_out_energies,
+                            n_states > 0 ? device_out_overlaps : nullptr};
+    static const char* const names[5] = {"device_values", "device_out", "device_out_values", "device_out_energies", "device_out_overlaps"};
+    if ((rc = check_device_pointers(h, given, names, h->defl_checked, 5))) return rc;
+    BatchArgs args;
+    if ((rc = resolve_batch(h, size_t(n_evals), circuit_ids, nullptr, nullptr, args, "deflated gradients of a circuit on a kept state are not built")))
+        return rc;
+    args.n_params.assign(size_t(n_evals), int64_t(width));
+    args.device_values = width > 0 ? device_values : nullptr;
+    if (ready_event) QSV_HIP(h, hipStreamWaitEvent(h->stream, static_cast<hipEvent_t>(ready_event), 0));
+    const AdjCall call{device_values, width, device_out, out_width, device_out_values};
+    seed.out_energies = device_out_energies;
+    seed.out_overlaps = n_states > 0 ? device_out_overlaps : nullptr;
+    rc = adjoint_locked(h, args, circuit_ids, wrt_offsets, wrt, call, &seed);
+    if (rc)
+        (void)sync_streams(h);  // nothing of a failed call may still be running
+    else
+        h->async_pending = true;
+    return rc;
+}
+
 int qsv_adjoint_stats(const qsv_t* h, qsv_adjoint_stats_t* out) {
     if (!out) return QSV_E_ARG;
     QSV_OPEN(h, "qsv_adjoint_stats", kHostOnly);
     *out = h->adj_stats;
     out->scratch_bytes = int64_t(h->d_adj_lambda.bytes + h->d_adj_tab.bytes + h->d_adj_mats.bytes + h->d_adj_partials.bytes + h->d_adj_epart.bytes +
-                                 h->d_adj_base.bytes + h->d_adj_out.bytes + h->d_adj_values.bytes);
+                                 h->d_adj_base.bytes + h->d_adj_out.bytes + h->d_adj_values.bytes + h->d_defl.bytes + h->d_defl_out.bytes);
     return QSV_OK;
 }
 

@@ -717,6 +717,13 @@ class EVQEResult:
     # eigenvalues above 1e-10 (fp64) or 1e-5 (fp32): how many directions of parameter space move the state (None: not asked for)
     parameter_metric: Optional[np.ndarray] = None
     parameter_metric_rank: Optional[int] = None
+    # set by evqe.deflation.compute_eigenvalues (None from compute_minimum_eigenvalue itself): the deflated cost the run
+    # minimised, E + sum_k beta_k |<phi_k|psi>|^2 at the best individual -- `eigenvalue` is then E alone --, and the best
+    # individual's overlaps <phi_k|psi> with the states kept by the runs before it, complex, (number of runs before,)
+    deflated_value: Optional[float] = None
+    overlaps_with_previous: Optional[np.ndarray] = None
+    # ... and, with keep=True, the best individual's state as it stays kept on the evaluator's device (a KeptState)
+    kept_state: Optional[Any] = None
 
 
 # ---- the solver -----------------------------------------------------------------------------------------------
