@@ -3263,7 +3263,10 @@ struct HalfRows {
     int32_t at[4] = {0, 0, 0, 0};
     bool on = false;
 };
-template <typename real, int J, bool AHEAD = true>
+// USED_ONLY: of the block number's ten accumulators only those of bits the side has (q < bits - 6) are added across the lanes
+// and written to `out` -- the others are zero and no weight of theirs is ever handed off (the pass kernel's tail, whose
+// readers stop at weight 2 + bits; profiles/r27_full_form_tail.txt).
+template <typename real, int J, bool AHEAD = true, bool USED_ONLY = false>
 __device__ __forceinline__ void factor_side_body(const cx<real>* __restrict__ tab, uint32_t bits, uint32_t mask, const double* __restrict__ diag,
                                  uint32_t first_block, uint32_t block_step, cx<real>* stage, double* dstage, double* out,
                                  double (&dq)[kFactorDAhead] QSV_PSTAMP_PARAMS, HalfRows row_bytes = HalfRows{}, uint32_t end_block = 0xffffffffu) {
@@ -3351,7 +3354,8 @@ __device__ __forceinline__ void factor_side_body(const cx<real>* __restrict__ ta
 #pragma unroll
     for (int q = 0; q < 6; ++q) acc_low[q] = across(acc_low[q]);
 #pragma unroll
-    for (int q = 0; q < 10; ++q) acc_high[q] = across(acc_high[q]);
+    for (int q = 0; q < 10; ++q)
+        if (!USED_ONLY || uint32_t(q) + 6u < bits) acc_high[q] = across(acc_high[q]);  // (uniform: the side's size)
     QSV_PSTAMP(6);  // sums across lanes
     __syncthreads();  // (every wave of the workgroup is here: nobody reads a staging region any more)
     if ((lane & 15u) < NQ && out) {  // (out = null: a wave that only keeps the others company at the barrier)
@@ -3361,7 +3365,8 @@ __device__ __forceinline__ void factor_side_body(const cx<real>* __restrict__ ta
 #pragma unroll
         for (int q = 0; q < 6; ++q) out[(2 + q) * 64 + lane] = acc_low[q];
 #pragma unroll
-        for (int q = 0; q < 10; ++q) out[(8 + q) * 64 + lane] = acc_high[q];
+        for (int q = 0; q < 10; ++q)
+            if (!USED_ONLY || uint32_t(q) + 6u < bits) out[(8 + q) * 64 + lane] = acc_high[q];
     }
 }
 
@@ -4007,6 +4012,11 @@ __device__ __forceinline__ double factor_reduced_value(const double* partial, co
 // workgroup barrier, then agent-scope loads of both sets (MI355X_MICROARCH.md, hand-offs with sc1 stores and loads in place
 // of a release / acquire pair, first row: one unsharded counter, the last adder told by its add's return value).  The order in
 // which the two sides finish does not enter any sum.
+#ifdef QSV_ABL_OLD_TAIL  // (measurement: the Gram sums' every accumulator added across the lanes and written, as before r27)
+constexpr bool kTailUsedOnly = false;
+#else
+constexpr bool kTailUsedOnly = true;
+#endif
 template <typename real, bool REDUCED>
 __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ plan_arena, const EvalDesc& ev,
                                                   const cx<real>* __restrict__ slot_tables, uint64_t side_stride,
@@ -4159,14 +4169,14 @@ __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ p
         }
         if (body_keys == 0)
 #endif
-            factor_side_body<real, 1, true>(tab, bits, mask, diag, half_first, step, stage, dstage_all + w * 64, sink, dq QSV_PSTAMP_ARGS,
+            factor_side_body<real, 1, true, kTailUsedOnly>(tab, bits, mask, diag, half_first, step, stage, dstage_all + w * 64, sink, dq QSV_PSTAMP_ARGS,
                                             half_rows, half_end);
 #ifndef QSV_ABL_TAIL_GRAM
         else if (body_keys == 1)
-            factor_side_body<real, 2, true>(tab, bits, mask, diag, half_first, step, stage, dstage_all + w * 64, sink, dq QSV_PSTAMP_ARGS,
+            factor_side_body<real, 2, true, kTailUsedOnly>(tab, bits, mask, diag, half_first, step, stage, dstage_all + w * 64, sink, dq QSV_PSTAMP_ARGS,
                                             half_rows, half_end);
         else if (body_keys == 2)
-            factor_side_body<real, 4, false>(tab, bits, mask, diag, half_first, step, stage, dstage_all + w * 64, sink, dq QSV_PSTAMP_ARGS,
+            factor_side_body<real, 4, false, kTailUsedOnly>(tab, bits, mask, diag, half_first, step, stage, dstage_all + w * 64, sink, dq QSV_PSTAMP_ARGS,
                                              half_rows, half_end);
         else if (halves) {
             // rows 4 h .. 4 h + 3 are mine (pitch kFusedLdsRowPitch, every x), the others the partner's (this half of x only, so that
@@ -4251,6 +4261,7 @@ __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ p
         }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave, before the barrier the signalling lane joins
     __syncthreads();
+    QSV_PSTAMP(9);  // (diagnostic build: the sums of the partials, the stores out and drained, barrier)
     if (tid == 0) {
         // (four per evaluation: a side's one workgroup adds two, a half side's one -- whoever completes the four combines)
         const uint32_t add = halves ? 1u : 2u;
@@ -4276,6 +4287,7 @@ __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ p
         coupling = a.quad[qa * a.n_full + qb];
     }
     const double d00 = whole_diag[0];
+    QSV_PSTAMP(10);  // (diagnostic build: the combination's inputs)
     double* gram = reinterpret_cast<double*>(lds);  // [side][weight][kFactorPitch] (the partial matrices are no longer needed)
     const uint32_t side_bits[2] = {bx, by};
     // (half sides: two partial tables a side; a reduced side has key qubits for its simulated keys only and is never one.  Known
@@ -4314,6 +4326,7 @@ __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ p
             }
     }
     __syncthreads();
+    QSV_PSTAMP(11);  // (diagnostic build: the tables loaded and laid out, barrier)
     const double* g0 = gram;
     const double* g1 = gram + size_t(kFactorWeights) * kFactorPitch;
     double v = 0.0;
@@ -4358,6 +4371,7 @@ __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ p
             v = -d00 * factor_pairing(g0, g1, n_keys);          // - D(0, 0) <psi|psi>
         }
     }
+    QSV_PSTAMP(12);  // (diagnostic build: the pairing)
     // fixed-order sum over the first 256 threads (bx by + 3 <= 172 of them carry a term)
     double* red = reinterpret_cast<double*>(flag) + 1;
 #pragma unroll
@@ -4365,7 +4379,7 @@ __device__ __forceinline__ void fused_factor_tail(const uint32_t* __restrict__ p
     if ((tid & 63u) == 0 && wave < 4) red[wave] = v;
     __syncthreads();
     if (tid == 0) a.result_out[ev.out_index] = red[0] + red[1] + red[2] + red[3];
-    QSV_PSTAMP(3);  // combination
+    QSV_PSTAMP(3);  // combination (diagnostic build: its last sum and the result)
 }
 
 hipError_t launch_factor(int dtype, unsigned n_evals, double* scratch, const double* quad, int n_qubits, hipStream_t stream,

@@ -66,7 +66,11 @@ def main() -> None:
         per = t[p, :NP] / wgs
         if p == 7:  # (the tail of the one-launch route of split evaluations: its own phases)
             names = ["stores drained", "Gram matrices", "hand-off", "combination (second side only)"]
-            print(f"tail  {wgs / reps:11.0f}   " + "   ".join(f"{nm} {c:.0f}" for nm, c in zip(names, per)) + f"   total {per[:8].sum():.0f}")
+            # (the hand-off and the combination are stamped in parts: slots 9 .. 12 beside their own last part in slots 2 and 3)
+            whole = [per[0], per[1], per[2] + per[9], per[3] + per[10] + per[11] + per[12]]
+            print(f"tail  {wgs / reps:11.0f}   " + "   ".join(f"{nm} {c:.0f}" for nm, c in zip(names, whole)) + f"   total {per[:13].sum():.0f}")
+            print("      hand-off: " + "   ".join(f"{nm} {c:.0f}" for nm, c in zip(["sums of partials, stores, drain, barrier", "counter"], [per[9], per[2]])))
+            print("      combination: " + "   ".join(f"{nm} {c:.0f}" for nm, c in zip(["inputs", "tables loaded", "pairing", "last sum, result"], [per[10], per[11], per[12], per[3]])))
             # (inside the Gram phase, sides of up to four product terms: stamped separately, the phase's own column holds the rest)
             print("      Gram phase: " + "   ".join(f"{nm} {c:.0f}" for nm, c in zip(["rows staged (eight terms: all that is not the steps)", "blocks (eight terms: the tail of the last)", "sums across lanes", "eight terms: the blocks' steps"], per[4:8])))
             continue
