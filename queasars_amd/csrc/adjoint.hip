@@ -281,20 +281,19 @@ hipError_t launch_adjoint_prepare(const AdjEval* evals, int n_evals, const AdjGa
     return hipGetLastError();
 }
 
-hipError_t launch_adjoint_apply_operator(int dtype, const void* states, void* lambda, int n_qubits, int n_evals, const double* diag,
-                                         int n_groups, const PauliGroup* groups, const uint64_t* term_z, const double* term_coef,
-                                         const uint32_t* term_odd, bool streaming, double* e_partials, hipStream_t stream) {
+hipError_t launch_adjoint_apply_operator(int dtype, const void* states, void* lambda, int n_qubits, int n_evals, const OperatorView& op,
+                                         bool streaming, double* e_partials, hipStream_t stream) {
     if (n_evals <= 0) return hipSuccess;
     const dim3 grid(adjoint_op_blocks(n_qubits), unsigned(n_evals));
     const unsigned long long dim = 1ull << n_qubits;
     if (dtype == QSV_F64)
         hipLaunchKernelGGL(adjoint_apply_operator_kernel<double>, grid, dim3(kAdjointThreads), 0, stream,
-                           static_cast<const acx<double>*>(states), static_cast<acx<double>*>(lambda), dim, diag, n_groups, groups,
-                           term_z, term_coef, term_odd, streaming, e_partials);
+                           static_cast<const acx<double>*>(states), static_cast<acx<double>*>(lambda), dim, op.diag, op.n_groups, op.groups,
+                           op.term_z, op.term_coef, op.term_odd, streaming, e_partials);
     else
         hipLaunchKernelGGL(adjoint_apply_operator_kernel<float>, grid, dim3(kAdjointThreads), 0, stream,
-                           static_cast<const acx<float>*>(states), static_cast<acx<float>*>(lambda), dim, diag, n_groups, groups,
-                           term_z, term_coef, term_odd, streaming, e_partials);
+                           static_cast<const acx<float>*>(states), static_cast<acx<float>*>(lambda), dim, op.diag, op.n_groups, op.groups,
+                           op.term_z, op.term_coef, op.term_odd, streaming, e_partials);
     return hipGetLastError();
 }
 

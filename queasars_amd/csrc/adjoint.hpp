@@ -10,20 +10,7 @@
 
 namespace qsv {
 
-// One swept gate of a circuit, in sweep order (the circuit's last gate first).
-struct AdjGate {
-    uint8_t kind;     // QSV_OP_U / QSV_OP_CU3
-    uint8_t tpos;     // the target's bit inside the tile of the gate's run
-    uint8_t cpos;     // the control's (cu3), QSV_NO_CONTROL otherwise
-    uint8_t pad;
-    int32_t p[3];     // theta, phi, lambda: parameter index, or -1 for the literal
-    double lit[3];
-};
-struct AdjRunDesc {
-    uint64_t mask;        // the tile's qubits
-    uint32_t first_gate;  // its gates are [first_gate, first_gate + n_gates) of the circuit's swept gates
-    uint32_t n_gates;
-};
+// (The gate and run tables, AdjGate and AdjRunDesc, are adjoint_plan.hpp's.)
 // One evaluation of a launch group, by its position in the group.
 struct AdjEval {
     uint32_t gate_base;  // the circuit's gates in the gate table
@@ -64,9 +51,8 @@ hipError_t launch_adjoint_prepare(const AdjEval* evals, int n_evals, const AdjGa
 // lambda = H_h psi for the group's states (slot s at s * 2^n amplitudes of `states` / `lambda`): the diagonal table (may be null)
 // for the x = 0 group, the x-mask groups with pauli_groups_kernel's conventions.  e_partials[position * adjoint_op_blocks(n) + b]:
 // workgroup b's share of Re<psi|lambda>.
-hipError_t launch_adjoint_apply_operator(int dtype, const void* states, void* lambda, int n_qubits, int n_evals, const double* diag,
-                                         int n_groups, const PauliGroup* groups, const uint64_t* term_z, const double* term_coef,
-                                         const uint32_t* term_odd, bool streaming, double* e_partials, hipStream_t stream);
+hipError_t launch_adjoint_apply_operator(int dtype, const void* states, void* lambda, int n_qubits, int n_evals, const OperatorView& op,
+                                         bool streaming, double* e_partials, hipStream_t stream);
 
 // Run `run` of every evaluation of the group that has one.  partials[(position * 3 * max_gates + 3 * g + slot) *
 // adjoint_blocks(n) + b]: workgroup b's sum of Re<lambda_g| dU_g/d(slot) |psi_(g-1)> over its tiles, for the gates g of the run.

@@ -80,4 +80,33 @@ int adjoint_plan(int n_qubits, int n_ops, const qsv_op* ops, int n_params, int n
     return QSV_OK;
 }
 
+const SweepCircuit* sweep_tables_add(SweepTables& tables, const void* key, int n_qubits, int n_ops, const qsv_op* ops, int n_params) {
+    const auto found = tables.circuits.find(key);
+    if (found != tables.circuits.end()) return &found->second;
+    AdjointPlan plan;
+    if (adjoint_plan(n_qubits, n_ops, ops, n_params, -1, nullptr, &plan)) return nullptr;
+    SweepCircuit t{uint32_t(tables.gates.size()), uint32_t(tables.runs.size()), uint32_t(plan.runs.size()), uint32_t(plan.gates.size()), {}};
+    t.readers.resize(size_t(n_params));
+    for (const AdjointRun& r : plan.runs) {
+        tables.runs.push_back(AdjRunDesc{r.mask, uint32_t(r.first_gate), uint32_t(r.n_gates)});
+        for (int32_t g = r.first_gate; g < r.first_gate + r.n_gates; ++g) {
+            const qsv_op& o = ops[size_t(plan.gates[size_t(g)])];
+            auto tile_bit = [&](int q) { return uint8_t(__builtin_popcountll(r.mask & ((uint64_t(1) << q) - 1))); };
+            AdjGate ag{};
+            ag.kind = o.kind;
+            ag.tpos = tile_bit(o.target);
+            ag.cpos = o.kind == QSV_OP_CU3 ? tile_bit(o.control) : uint8_t(QSV_NO_CONTROL);
+            const int32_t p[3] = {o.p_theta, o.p_phi, o.p_lambda};
+            const double lit[3] = {o.theta, o.phi, o.lambda};
+            for (int s = 0; s < 3; ++s) {
+                ag.p[s] = p[s] >= 0 ? p[s] : -1;
+                ag.lit[s] = lit[s];
+                if (p[s] >= 0) t.readers[size_t(p[s])].push_back(uint32_t(3 * g + s));
+            }
+            tables.gates.push_back(ag);
+        }
+    }
+    return &tables.circuits.emplace(key, std::move(t)).first->second;
+}
+
 }  // namespace qsv

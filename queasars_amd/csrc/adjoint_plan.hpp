@@ -1,8 +1,12 @@
 // Host planner of the adjoint gradient sweep: which gates one reverse sweep of the state visits, cut into
-// runs of consecutive gates whose qubits fit one workgroup tile.  Plain C++, no device.
+// runs of consecutive gates whose qubits fit one workgroup tile, and the gate and run tables the sweep's kernels read of a
+// call's circuits.  Plain C++, no device.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
+#include <cstring>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/qsv.h"
@@ -39,5 +43,59 @@ struct AdjointPlan {
 // partial sum) of a gate do not depend on wrt.  Returns QSV_OK or QSV_E_ARG (an op kind, qubit, parameter or wrt index out of
 // range; n_qubits outside 1 .. 63).
 int adjoint_plan(int n_qubits, int n_ops, const qsv_op* ops, int n_params, int n_wrt, const int32_t* wrt, AdjointPlan* out);
+
+// ---- the sweep's tables, as the kernels of adjoint.hpp and metric.hpp read them ------------------------------------------------
+
+// One swept gate of a circuit, in sweep order (the circuit's last gate first).
+struct AdjGate {
+    uint8_t kind;     // QSV_OP_U / QSV_OP_CU3
+    uint8_t tpos;     // the target's bit inside the tile of the gate's run
+    uint8_t cpos;     // the control's (cu3), QSV_NO_CONTROL otherwise
+    uint8_t pad;
+    int32_t p[3];     // theta, phi, lambda: parameter index, or -1 for the literal
+    double lit[3];
+};
+struct AdjRunDesc {
+    uint64_t mask;        // the tile's qubits
+    uint32_t first_gate;  // its gates are [first_gate, first_gate + n_gates) of the circuit's swept gates
+    uint32_t n_gates;
+};
+
+// A distinct circuit of a call in the tables below: the sweep by EVERY parameter (every other sweep of the circuit is a front
+// part of it).
+struct SweepCircuit {
+    uint32_t gate_base, run_base;  // its gates and runs in SweepTables::gates / runs
+    uint32_t n_runs, n_gates;
+    std::vector<std::vector<uint32_t>> readers;  // per parameter: 3 * (swept gate) + slot, ascending -- the latest gate first
+};
+struct SweepTables {
+    std::vector<AdjGate> gates;
+    std::vector<AdjRunDesc> runs;
+    std::unordered_map<const void*, SweepCircuit> circuits;  // by the caller's key (any pointer that tells circuits apart)
+};
+// The entry of the circuit `key` names, appended to the tables when the key is seen for the first time; nullptr where adjoint_plan
+// refuses the circuit (the tables are then as they were).  The entry stays where it is while the tables live.
+const SweepCircuit* sweep_tables_add(SweepTables& tables, const void* key, int n_qubits, int n_ops, const qsv_op* ops, int n_params);
+
+// The tables of a call back to back, as one upload takes them: every part starts on 8 bytes (zeros fill the gaps).
+struct TableBlob {
+    std::vector<char> bytes;
+    // the offset of the part
+    size_t add(const void* src, size_t n) {
+        const size_t off = bytes.size();
+        bytes.resize(off + (n + 7) / 8 * 8, 0);
+        if (n) std::memcpy(bytes.data() + off, src, n);
+        return off;
+    }
+    template <class T>
+    size_t add(const std::vector<T>& part) {
+        return add(part.data(), part.size() * sizeof(T));
+    }
+    // the part at `off` of the blob's copy at `base`
+    template <class T>
+    static const T* at(const void* base, size_t off) {
+        return reinterpret_cast<const T*>(static_cast<const char*>(base) + off);
+    }
+};
 
 }  // namespace qsv

@@ -2325,22 +2325,20 @@ __global__ void __launch_bounds__(256) pauli_groups_kernel(const cx<real>* __res
     if (threadIdx.x == 0) partials[(size_t(slot) * n_groups + group) * gridDim.x + blockIdx.x] = total;
 }
 
-hipError_t launch_pauli_groups(int dtype, const void* states, uint64_t state_stride, int n_qubits, int n_slots,
-                               int n_groups, const PauliGroup* groups, const uint64_t* term_z,
-                               const double* term_coef, const uint32_t* term_odd, int nb, double* partials,
-                               hipStream_t stream, int first_group, int group_count) {
-    if (group_count < 0) group_count = n_groups - first_group;
+hipError_t launch_pauli_groups(int dtype, const void* states, uint64_t state_stride, int n_qubits, int n_slots, const OperatorView& op,
+                               int nb, double* partials, hipStream_t stream, int first_group, int group_count) {
+    if (group_count < 0) group_count = op.n_groups - first_group;
     if (n_slots <= 0 || group_count <= 0) return hipSuccess;
     const uint64_t n_pairs = uint64_t(1) << (n_qubits - 1);
     dim3 grid(nb, group_count, n_slots);
     if (dtype == 0)
         hipLaunchKernelGGL(pauli_groups_kernel<double>, grid, dim3(256), 0, stream,
-                           reinterpret_cast<const cx<double>*>(states), state_stride, n_pairs, groups, term_z,
-                           term_coef, term_odd, partials, uint32_t(first_group), uint32_t(n_groups));
+                           reinterpret_cast<const cx<double>*>(states), state_stride, n_pairs, op.groups, op.term_z,
+                           op.term_coef, op.term_odd, partials, uint32_t(first_group), uint32_t(op.n_groups));
     else
         hipLaunchKernelGGL(pauli_groups_kernel<float>, grid, dim3(256), 0, stream,
-                           reinterpret_cast<const cx<float>*>(states), state_stride, n_pairs, groups, term_z,
-                           term_coef, term_odd, partials, uint32_t(first_group), uint32_t(n_groups));
+                           reinterpret_cast<const cx<float>*>(states), state_stride, n_pairs, op.groups, op.term_z,
+                           op.term_coef, op.term_odd, partials, uint32_t(first_group), uint32_t(op.n_groups));
     return hipGetLastError();
 }
 

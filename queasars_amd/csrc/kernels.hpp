@@ -344,13 +344,22 @@ struct PauliGroup {
     uint32_t pivot;   // highest set bit of x
     uint32_t pad;
 };
+// The operator set on a handle, as the kernels that apply it read it from device memory: the diagonal table of the x = 0 part
+// (null: it has none) and the x-mask groups over the term arrays.
+struct OperatorView {
+    const double* diag;
+    int n_groups;
+    const PauliGroup* groups;
+    const uint64_t* term_z;
+    const double* term_coef;
+    const uint32_t* term_odd;
+};
 // partials[(slot * n_groups + g) * nb + b]: workgroup b's share of group g on state slot `slot`.  One launch covers the
 // groups first_group .. first_group + group_count - 1 (grid nb x group_count x n_slots; group_count < 0: all from first_group):
-// the caller keeps group_count within the device's largest gridDim.y, the layout does not depend on how it slices.
-hipError_t launch_pauli_groups(int dtype, const void* states, uint64_t state_stride, int n_qubits, int n_slots,
-                               int n_groups, const PauliGroup* groups, const uint64_t* term_z,
-                               const double* term_coef, const uint32_t* term_odd, int nb, double* partials,
-                               hipStream_t stream, int first_group = 0, int group_count = -1);
+// the caller keeps group_count within the device's largest gridDim.y, the layout does not depend on how it slices.  (The
+// diagonal part is not this kernel's.)
+hipError_t launch_pauli_groups(int dtype, const void* states, uint64_t state_stride, int n_qubits, int n_slots, const OperatorView& op,
+                               int nb, double* partials, hipStream_t stream, int first_group = 0, int group_count = -1);
 hipError_t launch_pauli_combine(const double* partials, uint32_t per_slot, const double* diag_partials,
                                 uint32_t diag_per_eval, int n_slots, const EvalDesc* evals, double* out,
                                 hipStream_t stream);

@@ -76,18 +76,17 @@ moments_combine_kernel(const double* __restrict__ partials, uint32_t blocks, dou
 
 }  // namespace
 
-hipError_t launch_operator_moments(int dtype, const void* states, int n_qubits, int n_evals, const double* diag, int n_groups,
-                                   const PauliGroup* groups, const uint64_t* term_z, const double* term_coef, const uint32_t* term_odd,
-                                   double* partials, hipStream_t stream) {
+hipError_t launch_operator_moments(int dtype, const void* states, int n_qubits, int n_evals, const OperatorView& op, double* partials,
+                                   hipStream_t stream) {
     if (n_evals <= 0) return hipSuccess;
     const dim3 grid(moments_blocks(n_qubits), unsigned(n_evals));
     const unsigned long long dim = 1ull << n_qubits;
     if (dtype == QSV_F64)
-        hipLaunchKernelGGL(operator_moments_kernel<double>, grid, dim3(kMomentsThreads), 0, stream,
-                           static_cast<const mcx<double>*>(states), dim, diag, n_groups, groups, term_z, term_coef, term_odd, partials);
+        hipLaunchKernelGGL(operator_moments_kernel<double>, grid, dim3(kMomentsThreads), 0, stream, static_cast<const mcx<double>*>(states),
+                           dim, op.diag, op.n_groups, op.groups, op.term_z, op.term_coef, op.term_odd, partials);
     else
-        hipLaunchKernelGGL(operator_moments_kernel<float>, grid, dim3(kMomentsThreads), 0, stream,
-                           static_cast<const mcx<float>*>(states), dim, diag, n_groups, groups, term_z, term_coef, term_odd, partials);
+        hipLaunchKernelGGL(operator_moments_kernel<float>, grid, dim3(kMomentsThreads), 0, stream, static_cast<const mcx<float>*>(states),
+                           dim, op.diag, op.n_groups, op.groups, op.term_z, op.term_coef, op.term_odd, partials);
     return hipGetLastError();
 }
 

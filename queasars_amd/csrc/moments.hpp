@@ -21,9 +21,8 @@ inline uint32_t moments_blocks(int n_qubits) {
 // partials[(position * moments_blocks(n) + b) * 2 + {0, 1}]: workgroup b's share of Re<psi|H_h psi> and of |H_h psi|^2 for the
 // state in slot `position` (slot s at s * 2^n amplitudes of `states`): the diagonal table (may be null) for the x = 0 group, the
 // x-mask groups with pauli_groups_kernel's conventions.  One read of the state per group; nothing state-sized is written.
-hipError_t launch_operator_moments(int dtype, const void* states, int n_qubits, int n_evals, const double* diag, int n_groups,
-                                   const PauliGroup* groups, const uint64_t* term_z, const double* term_coef, const uint32_t* term_odd,
-                                   double* partials, hipStream_t stream);
+hipError_t launch_operator_moments(int dtype, const void* states, int n_qubits, int n_evals, const OperatorView& op, double* partials,
+                                   hipStream_t stream);
 
 // out[position * 2] = m1, out[position * 2 + 1] = m2 - m1 * m1 (not clamped), m1 / m2 the sums of the position's `blocks`
 // partials in a fixed order.

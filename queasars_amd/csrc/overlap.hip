@@ -161,15 +161,14 @@ overlap_combine_kernel(const double* __restrict__ partials, uint32_t blocks, uin
 
 template <typename real>
 void launch_panels(const void* states, const void* kept, const OverlapRefs& refs, uint32_t n_refs, int n_qubits, int n_evals,
-                   const double* diag, int n_groups, const PauliGroup* groups, const uint64_t* term_z, const double* term_coef,
-                   const uint32_t* term_odd, double* partials, hipStream_t stream) {
+                   const OperatorView& op, double* partials, hipStream_t stream) {
     const dim3 grid(overlap_blocks(n_qubits), overlap_state_blocks(n_refs), overlap_state_blocks(size_t(n_evals)));
     const unsigned long long dim = 1ull << n_qubits;
     const ocx<real>* st = static_cast<const ocx<real>*>(states);
     const ocx<real>* kp = static_cast<const ocx<real>*>(kept);
-    if (n_groups >= 0)
-        hipLaunchKernelGGL((overlap_panels_kernel<real, true>), grid, dim3(64), 0, stream, st, kp, refs, n_refs, uint32_t(n_evals), dim, diag,
-                           n_groups, groups, term_z, term_coef, term_odd, partials);
+    if (op.n_groups >= 0)
+        hipLaunchKernelGGL((overlap_panels_kernel<real, true>), grid, dim3(64), 0, stream, st, kp, refs, n_refs, uint32_t(n_evals), dim, op.diag,
+                           op.n_groups, op.groups, op.term_z, op.term_coef, op.term_odd, partials);
     else
         hipLaunchKernelGGL((overlap_panels_kernel<real, false>), grid, dim3(64), 0, stream, st, kp, refs, n_refs, uint32_t(n_evals), dim,
                            nullptr, 0, nullptr, nullptr, nullptr, nullptr, partials);
@@ -178,13 +177,12 @@ void launch_panels(const void* states, const void* kept, const OverlapRefs& refs
 }  // namespace
 
 hipError_t launch_overlap_panels(int dtype, const void* states, const void* kept, const OverlapRefs& refs, uint32_t n_refs, int n_qubits,
-                                 int n_evals, const double* diag, int n_groups, const PauliGroup* groups, const uint64_t* term_z,
-                                 const double* term_coef, const uint32_t* term_odd, double* partials, hipStream_t stream) {
+                                 int n_evals, const OperatorView& op, double* partials, hipStream_t stream) {
     if (n_evals <= 0 || n_refs == 0) return hipSuccess;
     if (dtype == QSV_F64)
-        launch_panels<double>(states, kept, refs, n_refs, n_qubits, n_evals, diag, n_groups, groups, term_z, term_coef, term_odd, partials, stream);
+        launch_panels<double>(states, kept, refs, n_refs, n_qubits, n_evals, op, partials, stream);
     else
-        launch_panels<float>(states, kept, refs, n_refs, n_qubits, n_evals, diag, n_groups, groups, term_z, term_coef, term_odd, partials, stream);
+        launch_panels<float>(states, kept, refs, n_refs, n_qubits, n_evals, op, partials, stream);
     return hipGetLastError();
 }
 

@@ -47,12 +47,12 @@ inline size_t overlap_group(int n_qubits, size_t n_refs, bool with_operator, siz
 
 // partials[((eb * ref_blocks + rb) * blocks + w) * overlap_partial(..) + ..]: workgroup w's share, for the evaluations
 // 16 eb + c in the state slots of `states` and the kept states refs.slot[16 rb + r] of `kept`, of <phi_r|psi_c> at [r * 16 + c]
-// (real part) and [256 + r * 16 + c] (imaginary part) and, where n_groups >= 0, of <phi_r|H_h psi_c> at 512 + the same: the
-// diagonal table (may be null) and the x-mask groups as operator_row reads them.  n_groups < 0: no operator, nothing of it is
-// read.  Rows and columns past n_refs / n_evals are zero.  Nothing state-sized is written.
+// (real part) and [256 + r * 16 + c] (imaginary part) and, where op.n_groups >= 0, of <phi_r|H_h psi_c> at 512 + the same: the
+// diagonal table (may be null) and the x-mask groups as operator_row reads them.  op.n_groups < 0 (kNoOperator): no operator,
+// nothing of it is read.  Rows and columns past n_refs / n_evals are zero.  Nothing state-sized is written.
+constexpr OperatorView kNoOperator{nullptr, -1, nullptr, nullptr, nullptr, nullptr};
 hipError_t launch_overlap_panels(int dtype, const void* states, const void* kept, const OverlapRefs& refs, uint32_t n_refs, int n_qubits,
-                                 int n_evals, const double* diag, int n_groups, const PauliGroup* groups, const uint64_t* term_z,
-                                 const double* term_coef, const uint32_t* term_odd, double* partials, hipStream_t stream);
+                                 int n_evals, const OperatorView& op, double* partials, hipStream_t stream);
 
 // out_s[((position * n_refs) + k) * 2 + {0, 1}] = <phi_k|psi_position>, the sums of the partial tiles in ascending workgroup
 // order; out_t the same for <phi_k|H_h psi> (null: the partials hold no such tile).

@@ -10,6 +10,7 @@
 #include <condition_variable>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -627,6 +628,13 @@ int ensure_counted(qsv_t* h, DeviceBuffer& b, size_t bytes, int64_t& counter) {
     if (!(b.bytes >= bytes && b.ptr)) counter += 1;
     return ensure(h, b, bytes);
 }
+// A call's tables (adjoint_plan.hpp: TableBlob) into `b`, grown where it has to: one copy that waits.  TableBlob::at(b.ptr, offset)
+// is a part in device memory.
+int upload_blob(qsv_t* h, DeviceBuffer& b, const TableBlob& blob, int64_t& counter) {
+    if (const int rc = ensure_counted(h, b, blob.bytes.size(), counter)) return rc;
+    QSV_HIP(h, hipMemcpy(b.ptr, blob.bytes.data(), blob.bytes.size(), hipMemcpyHostToDevice));
+    return QSV_OK;
+}
 
 // ---- what the entry points have in common (the entry layer) ------------------------------------------------------
 // Between qsv_eval_begin and qsv_eval_end the calling thread holds the handle's lock (batch_lock): an entry point that took it
@@ -678,6 +686,44 @@ int check_device_pointers(qsv_t* h, const void* const* given, const char* const*
 
 int too_few_values(qsv_t* h, int need, int64_t got) {
     return fail(h, QSV_E_ARG, "circuit needs " + std::to_string(need) + " parameter values, got " + std::to_string(got));
+}
+
+// The consumers of whole final states are built up to 28 qubits: `message` is the caller's refusal as far as "... 28 qubits",
+// `name_size` adds the handle's own size behind it.
+int qubit_guard(qsv_t* h, const char* message, bool name_size = false) {
+    if (h->n <= 28) return QSV_OK;
+    return fail(h, QSV_E_UNSUPPORTED, name_size ? std::string(message) + ", this handle has " + std::to_string(h->n) : std::string(message));
+}
+
+// The kept states prefix_ids[0 .. n_states) as the overlap panels and the deflate kernel address them (n_states <= kOvlMaxStates).
+int kept_refs(qsv_t* h, int n_states, const int* prefix_ids, OverlapRefs& refs) {
+    for (int k = 0; k < n_states; ++k) {
+        const auto it = h->prefixes.find(prefix_ids[k]);
+        if (it == h->prefixes.end() || it->second.released) return fail(h, QSV_E_ARG, "unknown kept state " + std::to_string(prefix_ids[k]));
+        refs.slot[k] = it->second.slot;
+    }
+    return QSV_OK;
+}
+
+// What evaluation e of a gradient-like call asks for: the parameters wrt[first .. first + count) of its circuit c, or, without
+// wrt_offsets, all of them in their order.  Checked: the offsets do not fall, a row of out_width takes the count (`noun`: what
+// the call's message counts), and every index names a parameter of c.
+struct WrtRequest {
+    int64_t first, count;
+};
+int wrt_request(qsv_t* h, const Circuit& c, int circuit_id, size_t e, const int64_t* wrt_offsets, const int32_t* wrt, int out_width,
+                const char* noun, WrtRequest& out) {
+    const int64_t first = wrt_offsets ? wrt_offsets[e] : 0, count = wrt_offsets ? wrt_offsets[e + 1] - first : int64_t(c.n_params);
+    if (count < 0) return fail(h, QSV_E_ARG, "wrt_offsets must be non-decreasing");
+    if (count > out_width)
+        return fail(h, QSV_E_ARG, "out_width " + std::to_string(out_width) + " is too small for " + std::to_string(count) + " " + noun);
+    if (count > 0 && wrt_offsets && !wrt) return fail(h, QSV_E_ARG, "wrt is null");
+    for (int64_t j = 0; wrt_offsets && j < count; ++j)
+        if (wrt[first + j] < 0 || wrt[first + j] >= c.n_params)
+            return fail(h, QSV_E_ARG, "wrt index " + std::to_string(wrt[first + j]) + " is outside the " + std::to_string(c.n_params) +
+                                          " parameters of circuit " + std::to_string(circuit_id));
+    out = WrtRequest{first, count};
+    return QSV_OK;
 }
 
 int validate_ops(qsv_t* h, int n, int n_ops, const qsv_op* ops, int n_params) {
@@ -1354,8 +1400,42 @@ int ensure_host_out(qsv_t* h, size_t count) {
     return QSV_OK;
 }
 
-struct EventPair {
-    hipEvent_t a, b;
+// Device time of spans of a stream (option "time_moments"): begin(stream, tag) .. end(stream) bracket one between two events;
+// after the caller's synchronise, elapsed(tag, sum) adds the milliseconds of the tag's spans, in their order.  The timer owns its
+// events: they are destroyed on every exit path.
+struct SpanTimer {
+    struct Span {
+        hipEvent_t t0 = nullptr, t1 = nullptr;
+        int tag = 0;
+    };
+    std::vector<Span> spans;
+    SpanTimer() = default;
+    SpanTimer(const SpanTimer&) = delete;
+    SpanTimer& operator=(const SpanTimer&) = delete;
+    ~SpanTimer() {
+        for (Span& s : spans) {
+            if (s.t0) (void)hipEventDestroy(s.t0);
+            if (s.t1) (void)hipEventDestroy(s.t1);
+        }
+    }
+    hipError_t begin(hipStream_t stream, int tag = 0) {
+        spans.emplace_back();
+        Span& s = spans.back();
+        s.tag = tag;
+        hipError_t err = hipEventCreate(&s.t0);
+        if (err == hipSuccess) err = hipEventCreate(&s.t1);
+        return err == hipSuccess ? hipEventRecord(s.t0, stream) : err;
+    }
+    hipError_t end(hipStream_t stream) { return hipEventRecord(spans.back().t1, stream); }
+    hipError_t elapsed(int tag, double& sum_ms) const {
+        for (const Span& s : spans) {
+            if (s.tag != tag) continue;
+            float ms = 0.0f;
+            if (const hipError_t err = hipEventElapsedTime(&ms, s.t0, s.t1)) return err;
+            sum_ms += double(ms);
+        }
+        return hipSuccess;
+    }
 };
 
 // ---- batches ---------------------------------------------------------------------------------------------
@@ -2156,10 +2236,13 @@ size_t order_split_first(qsv_t* h, size_t first, size_t count, size_t* n_cont = 
 
 // The expectation kernels of the general-operator path over the gc states of a launch group: x-mask groups [g1, g1 + groups), then
 // their combination into d_out (every argument but these is the operator's or the handle's; both run on the handle's own stream)
+OperatorView operator_view(const qsv_t* h) {
+    return OperatorView{h->has_diag_part ? static_cast<const double*>(h->d_diag.ptr) : nullptr, h->n_groups,
+                        static_cast<const PauliGroup*>(h->d_groups.ptr), static_cast<const uint64_t*>(h->d_z.ptr),
+                        static_cast<const double*>(h->d_cre.ptr), static_cast<const uint32_t*>(h->d_term_odd.ptr)};
+}
 hipError_t launch_pauli_groups_of(qsv_t* h, int gc, int g1, int groups) {
-    return launch_pauli_groups(h->dtype, h->d_states.ptr, uint64_t(1) << h->n, h->n, gc, h->n_groups,
-                               static_cast<const PauliGroup*>(h->d_groups.ptr), static_cast<const uint64_t*>(h->d_z.ptr),
-                               static_cast<const double*>(h->d_cre.ptr), static_cast<const uint32_t*>(h->d_term_odd.ptr), h->pauli_nb,
+    return launch_pauli_groups(h->dtype, h->d_states.ptr, uint64_t(1) << h->n, h->n, gc, operator_view(h), h->pauli_nb,
                                static_cast<double*>(h->d_term_partials.ptr), h->stream, g1, groups);
 }
 hipError_t launch_pauli_combine_of(qsv_t* h, int gc, const EvalDesc* evals) {
@@ -2692,6 +2775,38 @@ void unpack_rows(const BatchArgs& args, const int64_t* wrt_offsets, const std::v
         cur += count;
     }
 }
+// The head of a host form that runs on rows in device memory: the points pack_rows packed (`base`, rows of `width`) go to
+// `buffer`, and `args` become the forward run's arguments that read them there.
+int rows_to_device(qsv_t* h, const BatchArgs& packed, const std::vector<double>& base, int64_t width, DeviceBuffer& buffer, int64_t& allocations,
+                   BatchArgs& args) {
+    int rc;
+    if ((rc = wait_pending(h))) return rc;  // (the buffers may still be read or written by a call that did not wait)
+    if ((rc = ensure_counted(h, buffer, base.size() * sizeof(double), allocations))) return rc;
+    QSV_HIP(h, hipMemcpy(buffer.ptr, base.data(), base.size() * sizeof(double), hipMemcpyHostToDevice));
+    args.circs = packed.circs;
+    args.values.assign(1, 0.0);
+    args.n_params.assign(packed.circs.size(), width);
+    args.device_values = static_cast<const double*>(buffer.ptr);
+    return QSV_OK;
+}
+// The tail of such a form: the output rows at d_rows (and `also`: further doubles from device memory into the caller's host
+// arrays) come back, the streams are waited for, and the rows are unpacked into `out` as the call's wrt_offsets lay them out.
+struct ReadBack {
+    const void* src;
+    double* dst;
+    size_t count;
+};
+int rows_to_host(qsv_t* h, const BatchArgs& packed, const int64_t* wrt_offsets, const void* d_rows, int64_t out_width, double* out,
+                 std::initializer_list<ReadBack> also = {}) {
+    std::vector<double> rows(packed.circs.size() * size_t(out_width));
+    QSV_HIP(h, hipMemcpyAsync(rows.data(), d_rows, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    for (const ReadBack& r : also)
+        if (r.count) QSV_HIP(h, hipMemcpyAsync(r.dst, r.src, r.count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QSV_HIP(h, sync_streams(h));
+    h->async_pending = false;
+    unpack_rows(packed, wrt_offsets, rows, out_width, out);
+    return QSV_OK;
+}
 
 // One-shot evaluation: begin + one push + end.
 int eval_all(qsv_t* h, const BatchArgs& args, double* out) {
@@ -2787,25 +2902,11 @@ int run_to_states(qsv_t* h, const BatchArgs& args, const StateRun& run, const Gr
 // `count` doubles are in h_out when it returns, and batch.eval_at says whose they are; nothing of a failed call is still
 // running.  Option "time_moments": each group's kernels are bracketed by events, and their device time goes to prof.expect_ms.
 int run_whole_states(qsv_t* h, const BatchArgs& args, size_t G, const GroupFn& launch, const double* results, size_t count) {
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> timed;
-    struct DestroyEvents {
-        std::vector<std::pair<hipEvent_t, hipEvent_t>>& list;
-        ~DestroyEvents() {
-            for (auto& p : list) {
-                if (p.first) (void)hipEventDestroy(p.first);
-                if (p.second) (void)hipEventDestroy(p.second);
-            }
-        }
-    } destroy_events{timed};
+    SpanTimer timer;
     auto group = [&](size_t g0, size_t gc) -> int {
-        if (h->time_moments) {
-            timed.emplace_back(nullptr, nullptr);
-            QSV_HIP(h, hipEventCreate(&timed.back().first));
-            QSV_HIP(h, hipEventCreate(&timed.back().second));
-            QSV_HIP(h, hipEventRecord(timed.back().first, h->stream));
-        }
+        if (h->time_moments) QSV_HIP(h, timer.begin(h->stream));
         if (const int rc = launch(g0, gc)) return rc;
-        if (h->time_moments) QSV_HIP(h, hipEventRecord(timed.back().second, h->stream));
+        if (h->time_moments) QSV_HIP(h, timer.end(h->stream));
         return QSV_OK;
     };
     const int rc = run_to_states(h, args, StateRun{SplitRule{}, 1, G, false, 0, kModeSynthFirst | kModeFinalStore}, {}, group);
@@ -2815,11 +2916,7 @@ int run_whole_states(qsv_t* h, const BatchArgs& args, size_t G, const GroupFn& l
     }
     QSV_HIP(h, hipMemcpyAsync(h->h_out, results, count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     QSV_HIP(h, sync_streams(h));
-    for (const auto& p : timed) {
-        float ms = 0.0f;
-        QSV_HIP(h, hipEventElapsedTime(&ms, p.first, p.second));
-        h->prof.expect_ms += double(ms);
-    }
+    QSV_HIP(h, timer.elapsed(0, h->prof.expect_ms));
     return QSV_OK;
 }
 
@@ -4116,7 +4213,7 @@ static int exact_cvar_locked(qsv_t* h, const BatchArgs& args, double alpha, doub
     if (n_evals == 0) return QSV_OK;
     if (!(h->has_diag_part && h->diagonal))
         return fail(h, QSV_E_STATE, "the exact CVaR needs a diagonal operator (call qsv_set_operator with I/Z terms only)");
-    if (h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "the exact CVaR is available up to 28 qubits");
+    if (const int rc = qubit_guard(h, "the exact CVaR is available up to 28 qubits")) return rc;
     // alpha = 1 (numpy.isclose(alpha, 1), the reference's test): the reference takes the plain mean of the values there
     // (expectation_calculation.py:55-69), not its accumulation loop, whose stopping rule leaves out the last 1e-5 of the mass
     // (5e-4 of an Ising value at 20 qubits): the expectation value, as qsv_eval_circuits computes it
@@ -4305,7 +4402,7 @@ int qsv_top_states(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t*
                    uint64_t* out_states, double* out_probs, double* out_values) {
     QSV_OPEN(h, "qsv_top_states", kDevice);
     if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets || !out_states || !out_probs))) return fail(h, QSV_E_ARG, "bad arguments");
-    if (h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "the top states are available up to 28 qubits");
+    if (const int rc = qubit_guard(h, "the top states are available up to 28 qubits")) return rc;
     if (k < 1 || k > int(kTopMaxStates) || uint64_t(k) > (uint64_t(1) << h->n))
         return fail(h, QSV_E_ARG, "k must be between 1 and min(" + std::to_string(kTopMaxStates) + ", 2^n)");
     BatchArgs args;
@@ -4645,16 +4742,10 @@ static int gradient_tables(qsv_t* h, const std::vector<Circuit*>& circs, const i
     for (size_t e = 0; e < n_evals; ++e) {
         const Circuit& c = *circs[e];
         if (base_width < c.n_params) return too_few_values(h, c.n_params, base_width);
-        const int64_t first = wrt_offsets ? wrt_offsets[e] : 0, count = wrt_offsets ? wrt_offsets[e + 1] - first : int64_t(c.n_params);
-        if (count < 0) return fail(h, QSV_E_ARG, "wrt_offsets must be non-decreasing");
-        if (count > out_width)
-            return fail(h, QSV_E_ARG, "out_width " + std::to_string(out_width) + " is too small for " + std::to_string(count) + " gradient entries");
-        if (count > 0 && wrt_offsets && !wrt) return fail(h, QSV_E_ARG, "wrt is null");
-        for (int64_t j = 0; j < count; ++j) {
-            const int64_t p = wrt_offsets ? int64_t(wrt[first + j]) : j;
-            if (p < 0 || p >= c.n_params)
-                return fail(h, QSV_E_ARG, "wrt index " + std::to_string(p) + " is outside the " + std::to_string(c.n_params) +
-                                              " parameters of circuit " + std::to_string(circuit_ids[e]));
+        WrtRequest asked;
+        if (const int rc = wrt_request(h, c, circuit_ids[e], e, wrt_offsets, wrt, out_width, "gradient entries", asked)) return rc;
+        for (int64_t j = 0; j < asked.count; ++j) {
+            const int64_t p = wrt_offsets ? int64_t(wrt[asked.first + j]) : j;
             const int32_t t = c.grad_terms[size_t(p)];
             if (t < 0)
                 return fail(h, QSV_E_UNSUPPORTED, "parameter " + std::to_string(p) + " of circuit " + std::to_string(circuit_ids[e]) +
@@ -4785,32 +4876,68 @@ int qsv_gradient_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const i
         (void)sync_streams(h);
         return rc;
     }
-    std::vector<double> rows(size_t(n_evals) * size_t(out_width));
-    QSV_HIP(h, hipMemcpyAsync(rows.data(), h->d_grad_out.ptr, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    QSV_HIP(h, sync_streams(h));
-    h->async_pending = false;
-    unpack_rows(args, wrt_offsets, rows, out_width, out);
+    return rows_to_host(h, args, wrt_offsets, h->d_grad_out.ptr, out_width, out);
+}
+
+// The device forms of the gradient-like calls: points in rows of `width` at device_values, gradients into rows of out_width at
+// device_out, both device memory, queued behind ready_event (may be null) on the handle's stream and not waited for.
+struct DeviceForm {
+    int n_evals;
+    const int* circuit_ids;
+    int width;
+    const double* device_values;
+    void* ready_event;
+    int out_width;
+    double* device_out;
+};
+static int device_form_guard(qsv_t* h, const DeviceForm& f) {
+    if (f.n_evals < 0 || f.width < 0 || f.out_width < 0 ||
+        (f.n_evals > 0 && (!f.circuit_ids || (f.out_width > 0 && !f.device_out) || (f.width > 0 && !f.device_values))))
+        return fail(h, QSV_E_ARG, "bad arguments");
     return QSV_OK;
+}
+// Opens one of at least one evaluation: its pointers -- the two above and the call's further outputs `more` (name, pointer; null:
+// not given), remembered in `cache` -- are memory of the handle's device, its circuits exist (kept_refusal: resolve_batch's), the
+// forward run's `args` read the points where they are, and the stream waits for ready_event.
+static int device_form_open(qsv_t* h, const DeviceForm& f, std::initializer_list<std::pair<const char*, const void*>> more, const void** cache,
+                            const char* kept_refusal, BatchArgs& args) {
+    const void* given[8] = {f.width > 0 ? f.device_values : nullptr, f.out_width > 0 ? f.device_out : nullptr};
+    const char* names[8] = {"device_values", "device_out"};
+    int count = 2;
+    for (const auto& m : more) {
+        names[count] = m.first;
+        given[count++] = m.second;
+    }
+    int rc = check_device_pointers(h, given, names, cache, count);
+    if (rc) return rc;
+    if ((rc = resolve_batch(h, size_t(f.n_evals), f.circuit_ids, nullptr, nullptr, args, kept_refusal))) return rc;
+    args.n_params.assign(size_t(f.n_evals), int64_t(f.width));
+    args.device_values = f.width > 0 ? f.device_values : nullptr;
+    if (f.ready_event) QSV_HIP(h, hipStreamWaitEvent(h->stream, static_cast<hipEvent_t>(f.ready_event), 0));
+    return QSV_OK;
+}
+// ... and ends it: nothing of a failed call may still be running; one that queued its work leaves it pending where `pending` says so.
+static int device_form_end(qsv_t* h, int rc, bool pending) {
+    if (rc)
+        (void)sync_streams(h);
+    else if (pending)
+        h->async_pending = true;
+    return rc;
 }
 
 int qsv_gradient_device(qsv_t* h, int n_evals, const int* circuit_ids, int width, const double* device_values, void* ready_event,
                         const int64_t* wrt_offsets, const int32_t* wrt, int out_width, double* device_out, int64_t* out_n_shifted) {
     QSV_OPEN(h, "qsv_gradient_device", kDevice);
-    if (n_evals < 0 || width < 0 || out_width < 0 || (n_evals > 0 && (!circuit_ids || (out_width > 0 && !device_out) || (width > 0 && !device_values))))
-        return fail(h, QSV_E_ARG, "bad arguments");
+    const DeviceForm form{n_evals, circuit_ids, width, device_values, ready_event, out_width, device_out};
+    int rc = device_form_guard(h, form);
+    if (rc) return rc;
     if (out_n_shifted) *out_n_shifted = 0;
     if (n_evals == 0) return QSV_OK;
-    const void* given[2] = {width > 0 ? device_values : nullptr, out_width > 0 ? device_out : nullptr};
-    static const char* const names[2] = {"device_values", "device_out"};
-    int rc = check_device_pointers(h, given, names, h->grad_checked, 2);
-    if (rc) return rc;
     BatchArgs args;
-    if ((rc = resolve_batch(h, size_t(n_evals), circuit_ids, nullptr, nullptr, args))) return rc;
-    if (ready_event) QSV_HIP(h, hipStreamWaitEvent(h->stream, static_cast<hipEvent_t>(ready_event), 0));
+    if ((rc = device_form_open(h, form, {}, h->grad_checked, nullptr, args))) return rc;
     const GradCall call{device_values, int64_t(width), width, device_out, out_width};
-    rc = gradient_locked(h, args.circs, circuit_ids, wrt_offsets, wrt, call, out_n_shifted);
-    if (rc) (void)sync_streams(h);  // nothing of a failed call may still be running
-    return rc;
+    // (the shifted evaluations are batches of the ordinary driver, which keeps async_pending itself)
+    return device_form_end(h, gradient_locked(h, args.circs, circuit_ids, wrt_offsets, wrt, call, out_n_shifted), false);
 }
 
 int qsv_gradient_stats(const qsv_t* h, qsv_gradient_stats_t* out) {
@@ -4851,15 +4978,15 @@ struct AdjCall {
 };
 // The deflated cost's extension of the sweep's seed: lambda_G = H_h psi + sum_k betas[k] c_k phi_k against the
 // kept states `refs`, c_k = <phi_k|psi> from the overlap panels.  With it AdjCall::out_values receives the cost
-// E + sum_k betas[k] |c_k|^2; out_energies (E) and out_overlaps ([row][k][2]) are device memory and may be null.  `timed`
-// (may be null): under option "time_moments" the deflate kernel of every group between events of its own.
+// E + sum_k betas[k] |c_k|^2; out_energies (E) and out_overlaps ([row][k][2]) are device memory and may be null.  `timer`
+// (may be null): under option "time_moments" the deflate kernel of every group is a span of it.
 struct AdjSeed {
     uint32_t n_refs = 0;
     OverlapRefs refs{};
     const double* betas = nullptr;  // host memory
     double* out_energies = nullptr;
     double* out_overlaps = nullptr;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>>* timed = nullptr;
+    SpanTimer* timer = nullptr;
 };
 
 // What both entry points run with the lock held: the call's tables, the forward run group by group, and behind each group the H
@@ -4870,15 +4997,14 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
     const size_t K = seed ? size_t(seed->n_refs) : 0;
     if (h->n_terms == 0) return fail(h, QSV_E_STATE, "no operator set (call qsv_set_operator first)");
     h->adj_stats.n_gates = h->adj_stats.n_runs = h->adj_stats.n_state_sweeps = 0;
-    // ---- the tables: per distinct circuit its swept gates, runs and the slots that read each parameter; per evaluation its entries
-    struct CircuitTables {
-        uint32_t gate_base, run_base, slot_base;
-        AdjointPlan plan;                 // differentiated by every parameter: every other sweep of the circuit is a front part of it
+    // ---- the tables: per distinct circuit its swept gates and runs (adjoint_plan.hpp: sweep_tables_add) and, flattened, the slots
+    // that read each parameter; per evaluation its entries
+    struct CircuitSlots {
+        uint32_t slot_base = 0;
         std::vector<uint32_t> slot_first;  // per parameter: its slots are slots[slot_base + slot_first[p] .. + slot_first[p + 1])
     };
-    std::unordered_map<const Circuit*, CircuitTables> tables;
-    std::vector<AdjGate> gates;
-    std::vector<AdjRunDesc> runs;
+    SweepTables tables;
+    std::unordered_map<const SweepCircuit*, CircuitSlots> slots_of;
     std::vector<uint32_t> slots;
     std::vector<AdjEntry> entries;
     std::vector<int64_t> entry_offsets(n_evals + 1, 0);
@@ -4887,64 +5013,33 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
     for (size_t e = 0; e < n_evals; ++e) {
         const Circuit& c = *args.circs[e];
         if (call.width < c.n_params) return too_few_values(h, c.n_params, call.width);
-        const int64_t first = wrt_offsets ? wrt_offsets[e] : 0, count = wrt_offsets ? wrt_offsets[e + 1] - first : int64_t(c.n_params);
-        if (count < 0) return fail(h, QSV_E_ARG, "wrt_offsets must be non-decreasing");
-        if (count > call.out_width)
-            return fail(h, QSV_E_ARG, "out_width " + std::to_string(call.out_width) + " is too small for " + std::to_string(count) + " gradient entries");
-        if (count > 0 && wrt_offsets && !wrt) return fail(h, QSV_E_ARG, "wrt is null");
-        for (int64_t j = 0; wrt_offsets && j < count; ++j)
-            if (wrt[first + j] < 0 || wrt[first + j] >= c.n_params)
-                return fail(h, QSV_E_ARG, "wrt index " + std::to_string(wrt[first + j]) + " is outside the " + std::to_string(c.n_params) +
-                                              " parameters of circuit " + std::to_string(circuit_ids[e]));
-        auto it = tables.find(&c);
-        if (it == tables.end()) {
-            CircuitTables t;
-            if (adjoint_plan(h->n, int(c.ops.size()), c.ops.data(), c.n_params, -1, nullptr, &t.plan))
-                return fail(h, QSV_E_ARG, "circuit " + std::to_string(circuit_ids[e]) + " cannot be planned for the adjoint sweep");
-            t.gate_base = uint32_t(gates.size());
-            t.run_base = uint32_t(runs.size());
-            t.slot_base = uint32_t(slots.size());
-            std::vector<std::vector<uint32_t>> readers(size_t(c.n_params));
-            for (const AdjointRun& r : t.plan.runs) {
-                runs.push_back(AdjRunDesc{r.mask, uint32_t(r.first_gate), uint32_t(r.n_gates)});
-                for (int32_t g = r.first_gate; g < r.first_gate + r.n_gates; ++g) {
-                    const qsv_op& o = c.ops[size_t(t.plan.gates[size_t(g)])];
-                    auto tile_bit = [&](int q) { return uint8_t(__builtin_popcountll(r.mask & ((uint64_t(1) << q) - 1))); };
-                    AdjGate ag{};
-                    ag.kind = o.kind;
-                    ag.tpos = tile_bit(o.target);
-                    ag.cpos = o.kind == QSV_OP_CU3 ? tile_bit(o.control) : uint8_t(QSV_NO_CONTROL);
-                    const int32_t p[3] = {o.p_theta, o.p_phi, o.p_lambda};
-                    const double lit[3] = {o.theta, o.phi, o.lambda};
-                    for (int s = 0; s < 3; ++s) {
-                        ag.p[s] = p[s] >= 0 ? p[s] : -1;
-                        ag.lit[s] = lit[s];
-                        if (p[s] >= 0) readers[size_t(p[s])].push_back(uint32_t(3 * g + s));
-                    }
-                    gates.push_back(ag);
-                }
-            }
-            t.slot_first.assign(size_t(c.n_params) + 1, 0);
+        WrtRequest asked;
+        if (const int rc = wrt_request(h, c, circuit_ids[e], e, wrt_offsets, wrt, call.out_width, "gradient entries", asked)) return rc;
+        const int64_t first = asked.first, count = asked.count;
+        const SweepCircuit* const t = sweep_tables_add(tables, &c, h->n, int(c.ops.size()), c.ops.data(), c.n_params);
+        if (!t) return fail(h, QSV_E_ARG, "circuit " + std::to_string(circuit_ids[e]) + " cannot be planned for the adjoint sweep");
+        CircuitSlots& s = slots_of[t];
+        if (s.slot_first.empty()) {  // (the circuit's first evaluation)
+            s.slot_base = uint32_t(slots.size());
+            s.slot_first.assign(size_t(c.n_params) + 1, 0);
             for (int p = 0; p < c.n_params; ++p) {
-                slots.insert(slots.end(), readers[size_t(p)].begin(), readers[size_t(p)].end());
-                t.slot_first[size_t(p) + 1] = t.slot_first[size_t(p)] + uint32_t(readers[size_t(p)].size());
+                slots.insert(slots.end(), t->readers[size_t(p)].begin(), t->readers[size_t(p)].end());
+                s.slot_first[size_t(p) + 1] = s.slot_first[size_t(p)] + uint32_t(t->readers[size_t(p)].size());
             }
-            it = tables.emplace(&c, std::move(t)).first;
         }
-        const CircuitTables& t = it->second;
         if (wrt_offsets) {  // (its own sweep: the front part of the circuit's that reaches the earliest gate reading one of ITS parameters)
             AdjointPlan own;
             (void)adjoint_plan(h->n, int(c.ops.size()), c.ops.data(), c.n_params, int(count), wrt + first, &own);
             eval_runs[e] = uint32_t(own.runs.size());
             eval_gates[e] = uint32_t(own.gates.size());
         } else {
-            eval_runs[e] = uint32_t(t.plan.runs.size());
-            eval_gates[e] = uint32_t(t.plan.gates.size());
+            eval_runs[e] = t->n_runs;
+            eval_gates[e] = t->n_gates;
         }
         max_gates = std::max(max_gates, eval_gates[e]);
         for (int64_t j = 0; j < count; ++j) {
             const size_t p = size_t(wrt_offsets ? int64_t(wrt[first + j]) : j);
-            entries.push_back(AdjEntry{t.slot_base + t.slot_first[p], t.slot_first[p + 1] - t.slot_first[p]});
+            entries.push_back(AdjEntry{s.slot_base + s.slot_first[p], s.slot_first[p + 1] - s.slot_first[p]});
         }
         entry_offsets[e + 1] = int64_t(entries.size());
         h->adj_stats.n_gates += int64_t(eval_gates[e]);
@@ -4965,31 +5060,20 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
     std::vector<AdjEval> evals(n_evals);
     for (size_t j = 0; j < n_evals; ++j) {
         const size_t e = h->batch.eval_at[j];
-        const CircuitTables& t = tables.at(args.circs[e]);
+        const SweepCircuit& t = tables.circuits.at(args.circs[e]);
         evals[j] = AdjEval{t.gate_base, t.run_base, eval_runs[e], eval_gates[e], uint32_t(e), 0};
     }
-    // one blob: [gates][runs][entries][entry offsets][slots, padded to 8 bytes][evaluations by position][the seed's betas]
-    auto padded = [](size_t bytes) { return (bytes + 7) / 8 * 8; };
-    const size_t off_gates = 0, off_runs = off_gates + gates.size() * sizeof(AdjGate), off_entries = off_runs + runs.size() * sizeof(AdjRunDesc),
-                 off_offsets = off_entries + entries.size() * sizeof(AdjEntry), off_slots = off_offsets + entry_offsets.size() * sizeof(int64_t),
-                 off_evals = off_slots + padded(slots.size() * sizeof(uint32_t)), off_betas = off_evals + evals.size() * sizeof(AdjEval),
-                 tab_bytes = off_betas + K * sizeof(double);
-    std::vector<char> blob(tab_bytes, 0);
-    auto put = [&](size_t off, const void* src, size_t bytes) {
-        if (bytes) std::memcpy(blob.data() + off, src, bytes);
-    };
-    put(off_gates, gates.data(), gates.size() * sizeof(AdjGate));
-    put(off_runs, runs.data(), runs.size() * sizeof(AdjRunDesc));
-    put(off_entries, entries.data(), entries.size() * sizeof(AdjEntry));
-    put(off_offsets, entry_offsets.data(), entry_offsets.size() * sizeof(int64_t));
-    put(off_slots, slots.data(), slots.size() * sizeof(uint32_t));
-    put(off_evals, evals.data(), evals.size() * sizeof(AdjEval));
-    if (K) put(off_betas, seed->betas, K * sizeof(double));
+    // one blob: [gates][runs][entries][entry offsets][slots][evaluations by position][the seed's betas]
+    TableBlob blob;
+    const size_t off_gates = blob.add(tables.gates), off_runs = blob.add(tables.runs), off_entries = blob.add(entries),
+                 off_offsets = blob.add(entry_offsets), off_slots = blob.add(slots), off_evals = blob.add(evals),
+                 off_betas = blob.add(K ? seed->betas : nullptr, K * sizeof(double));
     const size_t gc_max = std::min(G, n_evals);
     const uint64_t dim = uint64_t(1) << h->n;
     const uint32_t blocks = adjoint_blocks(h->n), op_blocks = adjoint_op_blocks(h->n);
     int64_t& allocations = h->adj_stats.n_allocations;
-    if ((rc = ensure_counted(h, h->d_adj_tab, tab_bytes, allocations)) || (rc = ensure_counted(h, h->d_adj_lambda, gc_max * dim * h->amp_bytes, allocations)) ||
+    // (lay_out_states has waited for whatever an earlier call without a wait left running: nothing reads the old tables)
+    if ((rc = upload_blob(h, h->d_adj_tab, blob, allocations)) || (rc = ensure_counted(h, h->d_adj_lambda, gc_max * dim * h->amp_bytes, allocations)) ||
         (rc = ensure_counted(h, h->d_adj_mats, gc_max * std::max<size_t>(1, max_gates) * kAdjointMatDoubles * sizeof(double), allocations)) ||
         (rc = ensure_counted(h, h->d_adj_partials, gc_max * 3 * std::max<size_t>(1, max_gates) * blocks * sizeof(double), allocations)) ||
         (rc = ensure_counted(h, h->d_adj_epart, gc_max * op_blocks * sizeof(double), allocations)))
@@ -4997,16 +5081,14 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
     // the seed's scratch: the group's overlaps by position | the panels' partial tiles
     const size_t ovl_bytes = (gc_max * K * 2 * sizeof(double) + 63) / 64 * 64;
     if (K && (rc = ensure_counted(h, h->d_defl, ovl_bytes + overlap_partial_bytes(h->n, K, false, gc_max), allocations))) return rc;
-    // (lay_out_states has waited for whatever an earlier call without a wait left running: nothing reads the old tables)
-    QSV_HIP(h, hipMemcpy(h->d_adj_tab.ptr, blob.data(), tab_bytes, hipMemcpyHostToDevice));
-    const char* dt = static_cast<const char*>(h->d_adj_tab.ptr);
-    const AdjGate* d_gates = reinterpret_cast<const AdjGate*>(dt + off_gates);
-    const AdjRunDesc* d_runs = reinterpret_cast<const AdjRunDesc*>(dt + off_runs);
-    const AdjEntry* d_entries = reinterpret_cast<const AdjEntry*>(dt + off_entries);
-    const int64_t* d_offsets = reinterpret_cast<const int64_t*>(dt + off_offsets);
-    const uint32_t* d_slots = reinterpret_cast<const uint32_t*>(dt + off_slots);
-    const AdjEval* d_evals = reinterpret_cast<const AdjEval*>(dt + off_evals);
-    const double* d_betas = reinterpret_cast<const double*>(dt + off_betas);
+    const void* dt = h->d_adj_tab.ptr;
+    const AdjGate* d_gates = TableBlob::at<AdjGate>(dt, off_gates);
+    const AdjRunDesc* d_runs = TableBlob::at<AdjRunDesc>(dt, off_runs);
+    const AdjEntry* d_entries = TableBlob::at<AdjEntry>(dt, off_entries);
+    const int64_t* d_offsets = TableBlob::at<int64_t>(dt, off_offsets);
+    const uint32_t* d_slots = TableBlob::at<uint32_t>(dt, off_slots);
+    const AdjEval* d_evals = TableBlob::at<AdjEval>(dt, off_evals);
+    const double* d_betas = TableBlob::at<double>(dt, off_betas);
     double* d_ovl = static_cast<double*>(h->d_defl.ptr);
     double* ovl_partials = K ? reinterpret_cast<double*>(static_cast<char*>(h->d_defl.ptr) + ovl_bytes) : nullptr;
     // E goes where the caller wants it apart from the cost; the cost is written behind it by the seed's finishing kernel
@@ -5017,30 +5099,22 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
     const bool streaming = h->stream_mode != 0;
     auto sweep = [&](size_t g0, size_t gc) -> int {
         QSV_HIP(h, launch_adjoint_prepare(d_evals + g0, int(gc), d_gates, max_gates, call.base, call.width, mats, h->stream));
-        QSV_HIP(h, launch_adjoint_apply_operator(h->dtype, h->d_states.ptr, h->d_adj_lambda.ptr, h->n, int(gc),
-                                                 h->has_diag_part ? static_cast<const double*>(h->d_diag.ptr) : nullptr, h->n_groups,
-                                                 static_cast<const PauliGroup*>(h->d_groups.ptr), static_cast<const uint64_t*>(h->d_z.ptr),
-                                                 static_cast<const double*>(h->d_cre.ptr), static_cast<const uint32_t*>(h->d_term_odd.ptr),
-                                                 streaming, e_partials, h->stream));
+        QSV_HIP(h, launch_adjoint_apply_operator(h->dtype, h->d_states.ptr, h->d_adj_lambda.ptr, h->n, int(gc), operator_view(h), streaming,
+                                                 e_partials, h->stream));
         uint32_t most_runs = 0;
         for (size_t j = g0; j < g0 + gc; ++j) most_runs = std::max(most_runs, evals[j].n_runs);
         if (K) {
             // c = Phi^H Psi while the states are still the final ones (the runs rewrite them), then -- where a gate is swept at all --
             // lambda += sum_k beta_k c_k phi_k
-            QSV_HIP(h, launch_overlap_panels(h->dtype, h->d_states.ptr, h->d_prefix.ptr, seed->refs, uint32_t(K), h->n, int(gc), nullptr, -1,
-                                             nullptr, nullptr, nullptr, nullptr, ovl_partials, h->stream));
+            QSV_HIP(h, launch_overlap_panels(h->dtype, h->d_states.ptr, h->d_prefix.ptr, seed->refs, uint32_t(K), h->n, int(gc), kNoOperator,
+                                             ovl_partials, h->stream));
             QSV_HIP(h, launch_overlap_combine(ovl_partials, h->n, int(gc), uint32_t(K), d_ovl, nullptr, h->stream));
             if (most_runs > 0) {
-                const bool timing = h->time_moments && seed->timed;
-                if (timing) {
-                    seed->timed->emplace_back(nullptr, nullptr);
-                    QSV_HIP(h, hipEventCreate(&seed->timed->back().first));
-                    QSV_HIP(h, hipEventCreate(&seed->timed->back().second));
-                    QSV_HIP(h, hipEventRecord(seed->timed->back().first, h->stream));
-                }
+                const bool timing = h->time_moments && seed->timer;
+                if (timing) QSV_HIP(h, seed->timer->begin(h->stream));
                 QSV_HIP(h, launch_deflate(h->dtype, h->d_adj_lambda.ptr, h->d_prefix.ptr, seed->refs, uint32_t(K), h->n, int(gc), d_betas, d_ovl,
                                           streaming, h->stream));
-                if (timing) QSV_HIP(h, hipEventRecord(seed->timed->back().second, h->stream));
+                if (timing) QSV_HIP(h, seed->timer->end(h->stream));
                 h->adj_stats.n_state_sweeps += int64_t(gc);
             }
         }
@@ -5059,69 +5133,70 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
     return run_laid_out(h, args, run, lay, {}, sweep);
 }
 
+// The host form of the adjoint call and, with `seed` (deflation_seed's), of the deflated one, whose energies and overlaps then go
+// to out_energies / out_overlaps (may be null): the points as one matrix in device memory, a row per evaluation (rows of an even
+// number of doubles), the gradient rows as wide as the longest request, everything back after one wait.
+static int adjoint_host_form(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
+                             const int64_t* wrt_offsets, const int32_t* wrt, double* out, double* out_values, const char* kept_refusal,
+                             AdjSeed* seed = nullptr, double* out_energies = nullptr, double* out_overlaps = nullptr) {
+    BatchArgs packed, args;
+    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, packed, kept_refusal);
+    if (rc) return rc;
+    int64_t width, out_width;
+    std::vector<double> base;
+    if ((rc = pack_rows(h, packed, wrt_offsets, out, true, width, out_width, base))) return rc;
+    const size_t n = size_t(n_evals), K = seed ? size_t(seed->n_refs) : 0, n_extra = seed ? n + n * K * 2 : 0;
+    int64_t& allocations = h->adj_stats.n_allocations;
+    if ((rc = rows_to_device(h, packed, base, width, h->d_adj_base, allocations, args)) ||
+        (rc = ensure_counted(h, h->d_adj_out, n * size_t(out_width) * sizeof(double), allocations)) ||
+        (rc = ensure_counted(h, h->d_adj_values, n * sizeof(double), allocations)) ||
+        (seed && (rc = ensure_counted(h, h->d_defl_out, n_extra * sizeof(double), allocations))))
+        return rc;
+    const AdjCall call{args.device_values, int(width), static_cast<double*>(h->d_adj_out.ptr), int(out_width), static_cast<double*>(h->d_adj_values.ptr)};
+    SpanTimer timer;
+    double* const d_energies = static_cast<double*>(h->d_defl_out.ptr);
+    if (seed) {
+        seed->out_energies = out_energies ? d_energies : nullptr;
+        seed->out_overlaps = out_overlaps && K ? d_energies + n : nullptr;
+        seed->timer = &timer;
+    }
+    if ((rc = adjoint_locked(h, args, circuit_ids, wrt_offsets, wrt, call, seed))) {
+        (void)sync_streams(h);
+        return rc;
+    }
+    std::vector<double> values(n), extra(n_extra);
+    const bool any_extra = seed && (seed->out_energies || seed->out_overlaps);
+    if ((rc = rows_to_host(h, packed, wrt_offsets, h->d_adj_out.ptr, out_width, out,
+                           {{h->d_adj_values.ptr, values.data(), n}, {d_energies, extra.data(), any_extra ? n_extra : 0}})))
+        return rc;
+    QSV_HIP(h, timer.elapsed(0, h->prof.expect_ms));
+    if (out_values) std::memcpy(out_values, values.data(), n * sizeof(double));
+    if (seed && out_energies) std::memcpy(out_energies, extra.data(), n * sizeof(double));
+    if (seed && seed->out_overlaps) std::memcpy(out_overlaps, extra.data() + n, n * K * 2 * sizeof(double));
+    return QSV_OK;
+}
+
 int qsv_adjoint_gradient_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
                                   const int64_t* wrt_offsets, const int32_t* wrt, double* out, double* out_values) {
     QSV_OPEN(h, "qsv_adjoint_gradient_circuits", kDevice);
     if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets))) return fail(h, QSV_E_ARG, "bad arguments");
     if (n_evals == 0) return QSV_OK;
-    BatchArgs packed;
-    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, packed, "adjoint gradients of a circuit on a kept state are not built");
-    if (rc) return rc;
-    // the points as one matrix, a row per evaluation (rows of an even number of doubles); the gradient rows as wide as the longest request
-    int64_t width, out_width;
-    std::vector<double> base;
-    if ((rc = pack_rows(h, packed, wrt_offsets, out, true, width, out_width, base))) return rc;
-    if ((rc = wait_pending(h))) return rc;  // (the buffers below may still be read or written by a call that did not wait)
-    int64_t& allocations = h->adj_stats.n_allocations;
-    if ((rc = ensure_counted(h, h->d_adj_base, base.size() * sizeof(double), allocations)) ||
-        (rc = ensure_counted(h, h->d_adj_out, size_t(n_evals) * size_t(out_width) * sizeof(double), allocations)) ||
-        (rc = ensure_counted(h, h->d_adj_values, size_t(n_evals) * sizeof(double), allocations)))
-        return rc;
-    QSV_HIP(h, hipMemcpy(h->d_adj_base.ptr, base.data(), base.size() * sizeof(double), hipMemcpyHostToDevice));
-    BatchArgs args;
-    args.circs = packed.circs;
-    args.values.assign(1, 0.0);
-    args.n_params.assign(size_t(n_evals), width);
-    args.device_values = static_cast<const double*>(h->d_adj_base.ptr);
-    const AdjCall call{args.device_values, int(width), static_cast<double*>(h->d_adj_out.ptr), int(out_width), static_cast<double*>(h->d_adj_values.ptr)};
-    rc = adjoint_locked(h, args, circuit_ids, wrt_offsets, wrt, call);
-    if (rc) {
-        (void)sync_streams(h);
-        return rc;
-    }
-    std::vector<double> rows(size_t(n_evals) * size_t(out_width));
-    std::vector<double> values(static_cast<size_t>(n_evals));
-    QSV_HIP(h, hipMemcpyAsync(rows.data(), h->d_adj_out.ptr, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    QSV_HIP(h, hipMemcpyAsync(values.data(), h->d_adj_values.ptr, values.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    QSV_HIP(h, sync_streams(h));
-    h->async_pending = false;
-    unpack_rows(packed, wrt_offsets, rows, out_width, out);
-    if (out_values) std::memcpy(out_values, values.data(), values.size() * sizeof(double));
-    return QSV_OK;
+    return adjoint_host_form(h, n_evals, circuit_ids, param_offsets, params, wrt_offsets, wrt, out, out_values,
+                             "adjoint gradients of a circuit on a kept state are not built");
 }
 
 int qsv_adjoint_gradient_device(qsv_t* h, int n_evals, const int* circuit_ids, int width, const double* device_values, void* ready_event,
                                 const int64_t* wrt_offsets, const int32_t* wrt, int out_width, double* device_out, double* device_out_values) {
     QSV_OPEN(h, "qsv_adjoint_gradient_device", kDevice);
-    if (n_evals < 0 || width < 0 || out_width < 0 || (n_evals > 0 && (!circuit_ids || (out_width > 0 && !device_out) || (width > 0 && !device_values))))
-        return fail(h, QSV_E_ARG, "bad arguments");
-    if (n_evals == 0) return QSV_OK;
-    const void* given[3] = {width > 0 ? device_values : nullptr, out_width > 0 ? device_out : nullptr, device_out_values};
-    static const char* const names[3] = {"device_values", "device_out", "device_out_values"};
-    int rc = check_device_pointers(h, given, names, h->adj_checked, 3);
-    if (rc) return rc;
+    const DeviceForm form{n_evals, circuit_ids, width, device_values, ready_event, out_width, device_out};
+    int rc = device_form_guard(h, form);
+    if (rc || n_evals == 0) return rc;
     BatchArgs args;
-    if ((rc = resolve_batch(h, size_t(n_evals), circuit_ids, nullptr, nullptr, args, "adjoint gradients of a circuit on a kept state are not built"))) return rc;
-    args.n_params.assign(size_t(n_evals), int64_t(width));
-    args.device_values = width > 0 ? device_values : nullptr;
-    if (ready_event) QSV_HIP(h, hipStreamWaitEvent(h->stream, static_cast<hipEvent_t>(ready_event), 0));
+    if ((rc = device_form_open(h, form, {{"device_out_values", device_out_values}}, h->adj_checked,
+                               "adjoint gradients of a circuit on a kept state are not built", args)))
+        return rc;
     const AdjCall call{device_values, width, device_out, out_width, device_out_values};
-    rc = adjoint_locked(h, args, circuit_ids, wrt_offsets, wrt, call);
-    if (rc)
-        (void)sync_streams(h);  // nothing of a failed call may still be running
-    else
-        h->async_pending = true;
-    return rc;
+    return device_form_end(h, adjoint_locked(h, args, circuit_ids, wrt_offsets, wrt, call), true);
 }
 
 // ---- deflated costs against kept states (qsv.h: DEFLATED COSTS; deflation.hpp) -----------------------------------------------------
@@ -5135,15 +5210,11 @@ static int deflation_seed(qsv_t* h, int n_states, const int* prefix_ids, const d
     for (int k = 0; k < n_states; ++k)
         if (!std::isfinite(betas[k])) return fail(h, QSV_E_ARG, "betas[" + std::to_string(k) + "] is not finite");
     // (the register's size is the handle's own: asked before the kept states, which such a handle need not hold)
-    if (n_evals > 0 && h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "deflated costs are available up to 28 qubits, this handle has " + std::to_string(h->n));
+    if (n_evals > 0)
+        if (const int rc = qubit_guard(h, "deflated costs are available up to 28 qubits", true)) return rc;
     seed.n_refs = uint32_t(n_states);
     seed.betas = betas;
-    for (int k = 0; k < n_states; ++k) {
-        const auto it = h->prefixes.find(prefix_ids[k]);
-        if (it == h->prefixes.end() || it->second.released) return fail(h, QSV_E_ARG, "unknown kept state " + std::to_string(prefix_ids[k]));
-        seed.refs.slot[k] = it->second.slot;
-    }
-    return QSV_OK;
+    return kept_refs(h, n_states, prefix_ids, seed.refs);
 }
 
 int qsv_deflated_gradient_circuits(qsv_t* h, int n_states, const int* prefix_ids, const double* betas, int n_evals, const int* circuit_ids,
@@ -5155,63 +5226,8 @@ int qsv_deflated_gradient_circuits(qsv_t* h, int n_states, const int* prefix_ids
     int rc = deflation_seed(h, n_states, prefix_ids, betas, n_evals, seed);
     if (rc) return rc;
     if (n_evals == 0) return QSV_OK;
-    BatchArgs packed;
-    if ((rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, packed, "deflated gradients of a circuit on a kept state are not built")))
-        return rc;
-    int64_t width, out_width;
-    std::vector<double> base;
-    if ((rc = pack_rows(h, packed, wrt_offsets, out, true, width, out_width, base))) return rc;
-    if ((rc = wait_pending(h))) return rc;  // (the buffers below may still be read or written by a call that did not wait)
-    const size_t n = size_t(n_evals), K = size_t(n_states);
-    int64_t& allocations = h->adj_stats.n_allocations;
-    if ((rc = ensure_counted(h, h->d_adj_base, base.size() * sizeof(double), allocations)) ||
-        (rc = ensure_counted(h, h->d_adj_out, n * size_t(out_width) * sizeof(double), allocations)) ||
-        (rc = ensure_counted(h, h->d_adj_values, n * sizeof(double), allocations)) ||
-        (rc = ensure_counted(h, h->d_defl_out, (n + n * K * 2) * sizeof(double), allocations)))
-        return rc;
-    QSV_HIP(h, hipMemcpy(h->d_adj_base.ptr, base.data(), base.size() * sizeof(double), hipMemcpyHostToDevice));
-    BatchArgs args;
-    args.circs = packed.circs;
-    args.values.assign(1, 0.0);
-    args.n_params.assign(n, width);
-    args.device_values = static_cast<const double*>(h->d_adj_base.ptr);
-    const AdjCall call{args.device_values, int(width), static_cast<double*>(h->d_adj_out.ptr), int(out_width), static_cast<double*>(h->d_adj_values.ptr)};
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> timed;
-    struct DestroyEvents {
-        std::vector<std::pair<hipEvent_t, hipEvent_t>>& list;
-        ~DestroyEvents() {
-            for (auto& p : list) {
-                if (p.first) (void)hipEventDestroy(p.first);
-                if (p.second) (void)hipEventDestroy(p.second);
-            }
-        }
-    } destroy_events{timed};
-    double* const d_energies = static_cast<double*>(h->d_defl_out.ptr);
-    seed.out_energies = out_energies ? d_energies : nullptr;
-    seed.out_overlaps = out_overlaps && K ? d_energies + n : nullptr;
-    seed.timed = &timed;
-    rc = adjoint_locked(h, args, circuit_ids, wrt_offsets, wrt, call, &seed);
-    if (rc) {
-        (void)sync_streams(h);
-        return rc;
-    }
-    std::vector<double> rows(n * size_t(out_width)), values(n), extra(n + n * K * 2);
-    QSV_HIP(h, hipMemcpyAsync(rows.data(), h->d_adj_out.ptr, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    QSV_HIP(h, hipMemcpyAsync(values.data(), h->d_adj_values.ptr, values.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (seed.out_energies || seed.out_overlaps)
-        QSV_HIP(h, hipMemcpyAsync(extra.data(), d_energies, extra.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    QSV_HIP(h, sync_streams(h));
-    h->async_pending = false;
-    for (const auto& p : timed) {
-        float ms = 0.0f;
-        QSV_HIP(h, hipEventElapsedTime(&ms, p.first, p.second));
-        h->prof.expect_ms += double(ms);
-    }
-    unpack_rows(packed, wrt_offsets, rows, out_width, out);
-    if (out_values) std::memcpy(out_values, values.data(), n * sizeof(double));
-    if (out_energies) std::memcpy(out_energies, extra.data(), n * sizeof(double));
-    if (seed.out_overlaps) std::memcpy(out_overlaps, extra.data() + n, n * K * 2 * sizeof(double));
-    return QSV_OK;
+    return adjoint_host_form(h, n_evals, circuit_ids, param_offsets, params, wrt_offsets, wrt, out, out_values,
+                             "deflated gradients of a circuit on a kept state are not built", &seed, out_energies, out_overlaps);
 }
 
 int qsv_deflated_gradient_device(qsv_t* h, int n_states, const int* prefix_ids, const double* betas, int n_evals, const int* circuit_ids,
@@ -5219,31 +5235,19 @@ int qsv_deflated_gradient_device(qsv_t* h, int n_states, const int* prefix_ids, 
                                  int out_width, double* device_out, double* device_out_values, double* device_out_energies,
                                  double* device_out_overlaps) {
     QSV_OPEN(h, "qsv_deflated_gradient_device", kDevice);
-    if (n_evals < 0 || width < 0 || out_width < 0 || (n_evals > 0 && (!circuit_ids || (out_width > 0 && !device_out) || (width > 0 && !device_values))))
-        return fail(h, QSV_E_ARG, "bad arguments");
-    AdjSeed seed;
-    int rc = deflation_seed(h, n_states, prefix_ids, betas, n_evals, seed);
+    const DeviceForm form{n_evals, circuit_ids, width, device_values, ready_event, out_width, device_out};
+    int rc = device_form_guard(h, form);
     if (rc) return rc;
-    if (n_evals == 0) return QSV_OK;
-    const void* given[5] = {width > 0 ? device_values : nullptr, out_width > 0 ? device_out : nullptr, device_out_values, device_out_energies,
-                            n_states > 0 ? device_out_overlaps : nullptr};
-    static const char* const names[5] = {"device_values", "device_out", "device_out_values", "device_out_energies", "device_out_overlaps"};
-    if ((rc = check_device_pointers(h, given, names, h->defl_checked, 5))) return rc;
-    BatchArgs args;
-    if ((rc = resolve_batch(h, size_t(n_evals), circuit_ids, nullptr, nullptr, args, "deflated gradients of a circuit on a kept state are not built")))
-        return rc;
-    args.n_params.assign(size_t(n_evals), int64_t(width));
-    args.device_values = width > 0 ? device_values : nullptr;
-    if (ready_event) QSV_HIP(h, hipStreamWaitEvent(h->stream, static_cast<hipEvent_t>(ready_event), 0));
-    const AdjCall call{device_values, width, device_out, out_width, device_out_values};
+    AdjSeed seed;
+    if ((rc = deflation_seed(h, n_states, prefix_ids, betas, n_evals, seed)) || n_evals == 0) return rc;
     seed.out_energies = device_out_energies;
     seed.out_overlaps = n_states > 0 ? device_out_overlaps : nullptr;
-    rc = adjoint_locked(h, args, circuit_ids, wrt_offsets, wrt, call, &seed);
-    if (rc)
-        (void)sync_streams(h);  // nothing of a failed call may still be running
-    else
-        h->async_pending = true;
-    return rc;
+    BatchArgs args;
+    if ((rc = device_form_open(h, form, {{"device_out_values", device_out_values}, {"device_out_energies", seed.out_energies}, {"device_out_overlaps", seed.out_overlaps}},
+                               h->defl_checked, "deflated gradients of a circuit on a kept state are not built", args)))
+        return rc;
+    const AdjCall call{device_values, width, device_out, out_width, device_out_values};
+    return device_form_end(h, adjoint_locked(h, args, circuit_ids, wrt_offsets, wrt, call, &seed), true);
 }
 
 int qsv_adjoint_stats(const qsv_t* h, qsv_adjoint_stats_t* out) {
@@ -5263,7 +5267,7 @@ int qsv_variance_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const i
     if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets || !out_variances))) return fail(h, QSV_E_ARG, "bad arguments");
     if (n_evals == 0) return QSV_OK;
     if (h->n_terms == 0) return fail(h, QSV_E_STATE, "no operator set (call qsv_set_operator first)");
-    if (h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "the variance is available up to 28 qubits");
+    if (const int rc = qubit_guard(h, "the variance is available up to 28 qubits")) return rc;
     BatchArgs args;
     int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args,
                            "the variance of a circuit on a kept state is not built");
@@ -5278,11 +5282,7 @@ int qsv_variance_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const i
     double* const pairs = static_cast<double*>(h->d_moments.ptr);
     double* const partials = reinterpret_cast<double*>(static_cast<char*>(h->d_moments.ptr) + out_bytes);
     auto moments = [&](size_t g0, size_t gc) -> int {
-        QSV_HIP(h, launch_operator_moments(h->dtype, h->d_states.ptr, h->n, int(gc),
-                                           h->has_diag_part ? static_cast<const double*>(h->d_diag.ptr) : nullptr, h->n_groups,
-                                           static_cast<const PauliGroup*>(h->d_groups.ptr), static_cast<const uint64_t*>(h->d_z.ptr),
-                                           static_cast<const double*>(h->d_cre.ptr), static_cast<const uint32_t*>(h->d_term_odd.ptr),
-                                           partials, h->stream));
+        QSV_HIP(h, launch_operator_moments(h->dtype, h->d_states.ptr, h->n, int(gc), operator_view(h), partials, h->stream));
         QSV_HIP(h, launch_moments_combine(partials, blocks, int(gc), pairs + 2 * g0, h->stream));
         return QSV_OK;
     };
@@ -5534,7 +5534,7 @@ int qsv_observables_covariance(qsv_t* h, int set_id, int n_evals, const int* cir
     const ObservableSet& set = found->second;
     if (set.n_obs > kCovMaxObservables) return fail(h, QSV_E_UNSUPPORTED, "covariances are available for sets of up to 64 observables");
     if (n_evals == 0) return QSV_OK;
-    if (h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "covariances are available up to 28 qubits");
+    if (const int rc = qubit_guard(h, "covariances are available up to 28 qubits")) return rc;
     BatchArgs args;
     int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args,
                            "the covariances of a circuit on a kept state are not built");
@@ -5580,20 +5580,16 @@ int qsv_overlap_circuits(qsv_t* h, int n_states, const int* prefix_ids, int with
     if (n_evals > 0 && !out_overlaps) return fail(h, QSV_E_ARG, "out_overlaps is null");
     if (n_evals > 0 && with_operator && !out_elements) return fail(h, QSV_E_ARG, "out_elements is null (required with with_operator)");
     // (the register's size is the handle's own: asked before the kept states, which such a handle need not hold)
-    if (n_evals > 0 && h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "overlaps are available up to 28 qubits, this handle has " + std::to_string(h->n));
+    if (n_evals > 0)
+        if (const int rc = qubit_guard(h, "overlaps are available up to 28 qubits", true)) return rc;
     const size_t K = size_t(n_states);
     OverlapRefs refs{};
-    for (size_t k = 0; k < K; ++k) {
-        const auto it = h->prefixes.find(prefix_ids[k]);
-        if (it == h->prefixes.end() || it->second.released) return fail(h, QSV_E_ARG, "unknown kept state " + std::to_string(prefix_ids[k]));
-        refs.slot[k] = it->second.slot;
-    }
-    if (n_evals == 0) return QSV_OK;
+    int rc = kept_refs(h, n_states, prefix_ids, refs);
+    if (rc || n_evals == 0) return rc;
     if (with_operator && h->n_terms == 0) return fail(h, QSV_E_STATE, "with_operator: no operator set (call qsv_set_operator first)");
     BatchArgs args;
-    int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args,
-                           "circuit_ids: the overlaps of a circuit on a kept state are not built");
-    if (rc) return rc;
+    if ((rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args, "circuit_ids: the overlaps of a circuit on a kept state are not built")))
+        return rc;
     if ((rc = wait_pending(h))) return rc;  // (the buffers below may still be read or written by a call that did not wait)
     const size_t n = size_t(n_evals);
     const bool op = with_operator != 0;
@@ -5607,10 +5603,7 @@ int qsv_overlap_circuits(qsv_t* h, int n_states, const int* prefix_ids, int with
     double* const partials = reinterpret_cast<double*>(static_cast<char*>(h->d_overlap.ptr) + out_bytes);
     auto tiles = [&](size_t g0, size_t gc) -> int {
         QSV_HIP(h, launch_overlap_panels(h->dtype, h->d_states.ptr, h->d_prefix.ptr, refs, uint32_t(K), h->n, int(gc),
-                                         op && h->has_diag_part ? static_cast<const double*>(h->d_diag.ptr) : nullptr, op ? h->n_groups : -1,
-                                         static_cast<const PauliGroup*>(h->d_groups.ptr), static_cast<const uint64_t*>(h->d_z.ptr),
-                                         static_cast<const double*>(h->d_cre.ptr), static_cast<const uint32_t*>(h->d_term_odd.ptr),
-                                         partials, h->stream));
+                                         op ? operator_view(h) : kNoOperator, partials, h->stream));
         QSV_HIP(h, launch_overlap_combine(partials, h->n, int(gc), uint32_t(K), d_s + g0 * K * 2, op ? d_t + g0 * K * 2 : nullptr, h->stream));
         return QSV_OK;
     };
@@ -5636,7 +5629,7 @@ int qsv_reduced_density_circuits(qsv_t* h, int n_subsets, const int32_t* subset_
     if (n_evals > 0 && (!circuit_ids || !param_offsets)) return fail(h, QSV_E_ARG, "circuit_ids or param_offsets is null");
     if (n_evals > 0 && !out) return fail(h, QSV_E_ARG, "out is null");
     // (the register's size is asked before anything is built or uploaded)
-    if (h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "reduced density matrices are available up to 28 qubits, this handle has " + std::to_string(h->n));
+    if (const int rc = qubit_guard(h, "reduced density matrices are available up to 28 qubits", true)) return rc;
     const size_t S = size_t(n_subsets);
     std::vector<RdmSubset> table(S);
     size_t R = 0;  // doubles of an evaluation's row of the output
@@ -5696,7 +5689,7 @@ int qsv_metric_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int
     if (!out) return fail(h, QSV_E_ARG, "out is null");
     if (out_width < 1) return fail(h, QSV_E_ARG, "out_width must be at least 1");
     // (the register's size is asked before anything is built or uploaded)
-    if (h->n > 28) return fail(h, QSV_E_UNSUPPORTED, "the metric is available up to 28 qubits, this handle has " + std::to_string(h->n));
+    if (const int rc = qubit_guard(h, "the metric is available up to 28 qubits", true)) return rc;
     BatchArgs packed;
     int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, packed, "circuit_ids: the metric of a circuit on a kept state is not built");
     if (rc) return rc;
@@ -5708,14 +5701,9 @@ int qsv_metric_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int
     h->met_stats.run_ms = h->met_stats.gram_ms = 0.0;
 
     // ---- the tables: per distinct circuit the adjoint sweep's gates and runs of the WHOLE circuit and the slots that read each
-    // parameter; per evaluation its columns (the requested slots in the sweep's order) and its entries
-    struct CircuitTables {
-        uint32_t gate_base, run_base, n_runs, n_gates;
-        std::vector<std::vector<uint32_t>> readers;  // per parameter: 3 * (swept gate) + slot, ascending -- the latest gate first
-    };
-    std::unordered_map<const Circuit*, CircuitTables> tables;
-    std::vector<AdjGate> gates;
-    std::vector<AdjRunDesc> runs;
+    // parameter (adjoint_plan.hpp: sweep_tables_add); per evaluation its columns (the requested slots in the sweep's order) and
+    // its entries
+    SweepTables tables;
     std::vector<MetCol> cols;
     std::vector<MetEntry> entries;
     std::vector<uint32_t> entry_cols;
@@ -5723,47 +5711,12 @@ int qsv_metric_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int
     uint32_t max_gates = 0, max_cols = 0;
     for (size_t e = 0; e < n; ++e) {
         const Circuit& c = *packed.circs[e];
-        const int64_t first = wrt_offsets ? wrt_offsets[e] : 0, count = wrt_offsets ? wrt_offsets[e + 1] - first : int64_t(c.n_params);
-        if (count > int64_t(W))
-            return fail(h, QSV_E_ARG, "out_width " + std::to_string(out_width) + " is too small for " + std::to_string(count) + " parameters");
-        if (count > 0 && wrt_offsets && !wrt) return fail(h, QSV_E_ARG, "wrt is null");
-        for (int64_t j = 0; wrt_offsets && j < count; ++j)
-            if (wrt[first + j] < 0 || wrt[first + j] >= c.n_params)
-                return fail(h, QSV_E_ARG, "wrt index " + std::to_string(wrt[first + j]) + " is outside the " + std::to_string(c.n_params) +
-                                              " parameters of circuit " + std::to_string(circuit_ids[e]));
-        auto it = tables.find(&c);
-        if (it == tables.end()) {
-            CircuitTables t;
-            AdjointPlan plan;
-            if (adjoint_plan(h->n, int(c.ops.size()), c.ops.data(), c.n_params, -1, nullptr, &plan))
-                return fail(h, QSV_E_ARG, "circuit " + std::to_string(circuit_ids[e]) + " cannot be planned for the adjoint sweep");
-            t.gate_base = uint32_t(gates.size());
-            t.run_base = uint32_t(runs.size());
-            t.n_runs = uint32_t(plan.runs.size());
-            t.n_gates = uint32_t(plan.gates.size());
-            t.readers.resize(size_t(c.n_params));
-            for (const AdjointRun& r : plan.runs) {
-                runs.push_back(AdjRunDesc{r.mask, uint32_t(r.first_gate), uint32_t(r.n_gates)});
-                for (int32_t g = r.first_gate; g < r.first_gate + r.n_gates; ++g) {
-                    const qsv_op& o = c.ops[size_t(plan.gates[size_t(g)])];
-                    auto tile_bit = [&](int q) { return uint8_t(__builtin_popcountll(r.mask & ((uint64_t(1) << q) - 1))); };
-                    AdjGate ag{};
-                    ag.kind = o.kind;
-                    ag.tpos = tile_bit(o.target);
-                    ag.cpos = o.kind == QSV_OP_CU3 ? tile_bit(o.control) : uint8_t(QSV_NO_CONTROL);
-                    const int32_t p[3] = {o.p_theta, o.p_phi, o.p_lambda};
-                    const double lit[3] = {o.theta, o.phi, o.lambda};
-                    for (int s = 0; s < 3; ++s) {
-                        ag.p[s] = p[s] >= 0 ? p[s] : -1;
-                        ag.lit[s] = lit[s];
-                        if (p[s] >= 0) t.readers[size_t(p[s])].push_back(uint32_t(3 * g + s));
-                    }
-                    gates.push_back(ag);
-                }
-            }
-            it = tables.emplace(&c, std::move(t)).first;
-        }
-        const CircuitTables& t = it->second;
+        WrtRequest asked;
+        if ((rc = wrt_request(h, c, circuit_ids[e], e, wrt_offsets, wrt, out_width, "parameters", asked))) return rc;
+        const int64_t first = asked.first, count = asked.count;
+        const SweepCircuit* const found = sweep_tables_add(tables, &c, h->n, int(c.ops.size()), c.ops.data(), c.n_params);
+        if (!found) return fail(h, QSV_E_ARG, "circuit " + std::to_string(circuit_ids[e]) + " cannot be planned for the adjoint sweep");
+        const SweepCircuit& t = *found;
         // the columns: every slot that reads a requested parameter, once, in birth order (the sweep's: ascending 3 * gate + slot)
         std::vector<uint32_t> born;
         for (int64_t j = 0; j < count; ++j) {
@@ -5805,17 +5758,11 @@ int qsv_metric_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int
     const size_t eval_partials = size_t(max_pairs) * gram_blocks * kMetTile * sizeof(double);
     const size_t gram_group = std::max<size_t>(1, std::min(G, (size_t(64) << 20) / eval_partials));
 
-    if ((rc = wait_pending(h))) return rc;  // (the buffers below may still be read or written by a call that did not wait)
     int64_t& allocations = h->met_stats.n_allocations;
-    if ((rc = ensure_counted(h, h->d_met_base, base.size() * sizeof(double), allocations)) ||
+    BatchArgs args;
+    if ((rc = rows_to_device(h, packed, base, width, h->d_met_base, allocations, args)) ||
         (rc = ensure_counted(h, h->d_met_out, n * W * W * sizeof(double), allocations)))
         return rc;
-    QSV_HIP(h, hipMemcpy(h->d_met_base.ptr, base.data(), base.size() * sizeof(double), hipMemcpyHostToDevice));
-    BatchArgs args;
-    args.circs = packed.circs;
-    args.values.assign(1, 0.0);
-    args.n_params.assign(n, width);
-    args.device_values = static_cast<const double*>(h->d_met_base.ptr);
 
     // ---- the forward run's layout (ordinary plans into state slots, never split: as qsv_adjoint_gradient_circuits runs them)
     const StateRun run{SplitRule{}, 1, G, false, 0, kModeSynthFirst | kModeFinalStore};
@@ -5829,87 +5776,51 @@ int qsv_metric_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int
         evals[j] = by_eval[h->batch.eval_at[j]];
         adj_evals[j] = AdjEval{evals[j].gate_base, evals[j].run_base, evals[j].n_runs, evals[j].n_runs ? evals[j].n_gates : 0u, evals[j].row, 0};
     }
-    // one blob, every part a multiple of 8 bytes: [gates][runs][evaluations][... as the adjoint sweep's][columns][entries][entry columns]
-    auto padded = [](size_t bytes) { return (bytes + 7) / 8 * 8; };
-    const size_t off_gates = 0, off_runs = off_gates + gates.size() * sizeof(AdjGate), off_evals = off_runs + runs.size() * sizeof(AdjRunDesc),
-                 off_adj = off_evals + evals.size() * sizeof(MetEval), off_cols = off_adj + adj_evals.size() * sizeof(AdjEval),
-                 off_entries = off_cols + padded(cols.size() * sizeof(MetCol)), off_ecols = off_entries + entries.size() * sizeof(MetEntry),
-                 tab_bytes = off_ecols + padded(entry_cols.size() * sizeof(uint32_t));
-    std::vector<char> blob(tab_bytes, 0);
-    auto put = [&](size_t off, const void* src, size_t bytes) {
-        if (bytes) std::memcpy(blob.data() + off, src, bytes);
-    };
-    put(off_gates, gates.data(), gates.size() * sizeof(AdjGate));
-    put(off_runs, runs.data(), runs.size() * sizeof(AdjRunDesc));
-    put(off_evals, evals.data(), evals.size() * sizeof(MetEval));
-    put(off_adj, adj_evals.data(), adj_evals.size() * sizeof(AdjEval));
-    put(off_cols, cols.data(), cols.size() * sizeof(MetCol));
-    put(off_entries, entries.data(), entries.size() * sizeof(MetEntry));
-    put(off_ecols, entry_cols.data(), entry_cols.size() * sizeof(uint32_t));
+    // one blob: [gates][runs][evaluations][... as the adjoint sweep's][columns][entries][entry columns]
+    TableBlob blob;
+    const size_t off_gates = blob.add(tables.gates), off_runs = blob.add(tables.runs), off_evals = blob.add(evals), off_adj = blob.add(adj_evals),
+                 off_cols = blob.add(cols), off_entries = blob.add(entries), off_ecols = blob.add(entry_cols);
     const size_t gc_max = std::min(G, n);
-    if ((rc = ensure_counted(h, h->d_met_tab, tab_bytes, allocations)) || (rc = ensure_counted(h, h->d_met_scratch, gc_max * eval_bytes, allocations)) ||
+    // (lay_out_states has waited for whatever an earlier call without a wait left running: nothing reads the old tables)
+    if ((rc = upload_blob(h, h->d_met_tab, blob, allocations)) || (rc = ensure_counted(h, h->d_met_scratch, gc_max * eval_bytes, allocations)) ||
         (rc = ensure_counted(h, h->d_met_mats, gc_max * std::max<size_t>(1, max_gates) * kAdjointMatDoubles * sizeof(double), allocations)) ||
         (rc = ensure_counted(h, h->d_met_partials, std::min(gram_group, gc_max) * eval_partials, allocations)))
         return rc;
-    // (lay_out_states has waited for whatever an earlier call without a wait left running: nothing reads the old tables)
-    QSV_HIP(h, hipMemcpy(h->d_met_tab.ptr, blob.data(), tab_bytes, hipMemcpyHostToDevice));
-    const char* dt = static_cast<const char*>(h->d_met_tab.ptr);
-    const AdjGate* d_gates = reinterpret_cast<const AdjGate*>(dt + off_gates);
-    const AdjRunDesc* d_runs = reinterpret_cast<const AdjRunDesc*>(dt + off_runs);
-    const MetEval* d_evals = reinterpret_cast<const MetEval*>(dt + off_evals);
-    const AdjEval* d_adj = reinterpret_cast<const AdjEval*>(dt + off_adj);
-    const MetCol* d_cols = reinterpret_cast<const MetCol*>(dt + off_cols);
-    const MetEntry* d_entries = reinterpret_cast<const MetEntry*>(dt + off_entries);
-    const uint32_t* d_ecols = reinterpret_cast<const uint32_t*>(dt + off_ecols);
+    const void* dt = h->d_met_tab.ptr;
+    const AdjGate* d_gates = TableBlob::at<AdjGate>(dt, off_gates);
+    const AdjRunDesc* d_runs = TableBlob::at<AdjRunDesc>(dt, off_runs);
+    const MetEval* d_evals = TableBlob::at<MetEval>(dt, off_evals);
+    const AdjEval* d_adj = TableBlob::at<AdjEval>(dt, off_adj);
+    const MetCol* d_cols = TableBlob::at<MetCol>(dt, off_cols);
+    const MetEntry* d_entries = TableBlob::at<MetEntry>(dt, off_entries);
+    const uint32_t* d_ecols = TableBlob::at<uint32_t>(dt, off_ecols);
     double* mats = static_cast<double*>(h->d_met_mats.ptr);
     double* partials = static_cast<double*>(h->d_met_partials.ptr);
     double* d_out = static_cast<double*>(h->d_met_out.ptr);
     char* scratch = static_cast<char*>(h->d_met_scratch.ptr);
     const bool streaming = h->stream_mode != 0;
-    // option "time_moments": the run launches and the Gram kernels of every group between events of their own
-    struct Timed {
-        hipEvent_t t0 = nullptr, t1 = nullptr;
-        bool gram = false;
-    };
-    std::vector<Timed> timed;
-    struct DestroyEvents {
-        std::vector<Timed>& list;
-        ~DestroyEvents() {
-            for (Timed& t : list) {
-                if (t.t0) (void)hipEventDestroy(t.t0);
-                if (t.t1) (void)hipEventDestroy(t.t1);
-            }
-        }
-    } destroy_events{timed};
-    auto mark = [&](bool begin, bool gram) -> int {
-        if (!h->time_moments) return QSV_OK;
-        if (begin) {
-            timed.emplace_back();
-            timed.back().gram = gram;
-            QSV_HIP(h, hipEventCreate(&timed.back().t0));
-            QSV_HIP(h, hipEventCreate(&timed.back().t1));
-            QSV_HIP(h, hipEventRecord(timed.back().t0, h->stream));
-        } else {
-            QSV_HIP(h, hipEventRecord(timed.back().t1, h->stream));
-        }
-        return QSV_OK;
-    };
+    // option "time_moments": the run launches and the Gram kernels of every group are spans of their own
+    enum { kRunSpan, kGramSpan };
+    SpanTimer timer;
+    const bool timing = h->time_moments;
     auto sweep = [&](size_t g0, size_t gc) -> int {
         uint32_t most_runs = 0, group_cols = 0;
         for (size_t j = g0; j < g0 + gc; ++j) {
             most_runs = std::max(most_runs, evals[j].n_runs);
             group_cols = std::max(group_cols, evals[j].n_cols);
         }
-        int rc2;
         if (most_runs > 0) {
             QSV_HIP(h, launch_adjoint_prepare(d_adj + g0, int(gc), d_gates, max_gates, args.device_values, width, mats, h->stream));
-            if ((rc2 = mark(true, false))) return rc2;
+            if (timing) QSV_HIP(h, timer.begin(h->stream, kRunSpan));
             for (uint32_t r = 0; r < most_runs; ++r) {
                 QSV_HIP(h, launch_metric_run(h->dtype, h->d_states.ptr, scratch, stride, h->n, int(gc), group_cols, r, d_evals + g0, d_runs, d_gates,
                                              d_cols, mats, max_gates, streaming, h->stream));
                 h->met_stats.n_run_launches += 1;
             }
-            if ((rc2 = mark(false, false)) || (rc2 = mark(true, true))) return rc2;
+            if (timing) {
+                QSV_HIP(h, timer.end(h->stream));
+                QSV_HIP(h, timer.begin(h->stream, kGramSpan));
+            }
         }
         for (size_t c0 = 0; c0 < gc; c0 += gram_group) {
             const size_t cc = std::min(gram_group, gc - c0);
@@ -5920,7 +5831,7 @@ int qsv_metric_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int
             }
             QSV_HIP(h, launch_metric_combine(d_evals + g0 + c0, int(cc), d_entries, d_ecols, partials, max_pairs, gram_blocks, out_width, d_out, h->stream));
         }
-        if (most_runs > 0 && (rc2 = mark(false, true))) return rc2;
+        if (most_runs > 0 && timing) QSV_HIP(h, timer.end(h->stream));
         return QSV_OK;
     };
     rc = run_laid_out(h, args, run, lay, {}, sweep);
@@ -5931,11 +5842,8 @@ int qsv_metric_circuits(qsv_t* h, int n_evals, const int* circuit_ids, const int
     QSV_HIP(h, hipMemcpyAsync(out, d_out, n * W * W * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     QSV_HIP(h, sync_streams(h));
     h->async_pending = false;
-    for (const Timed& t : timed) {
-        float ms = 0.0f;
-        QSV_HIP(h, hipEventElapsedTime(&ms, t.t0, t.t1));
-        (t.gram ? h->met_stats.gram_ms : h->met_stats.run_ms) += double(ms);
-    }
+    QSV_HIP(h, timer.elapsed(kRunSpan, h->met_stats.run_ms));
+    QSV_HIP(h, timer.elapsed(kGramSpan, h->met_stats.gram_ms));
     return QSV_OK;
 }
 
