@@ -868,6 +868,32 @@ int qsv_reduced_density_circuits(qsv_t* h, int n_subsets, const int32_t* subset_
                                  const int32_t* subset_qubits, int n_evals, const int* circuit_ids,
                                  const int64_t* param_offsets, const double* params, double* out);
 
+/*
+ * OPERATOR DENSITY MATRICES: the operator-weighted reduced density matrices W_A = Tr_rest(H_h |psi_e><psi_e|)
+ * of the final states psi_e of n_evals (circuit, parameter vector) pairs, laid out as in qsv_eval_circuits, for H_h the Hermitian
+ * part of the operator set with qsv_set_operator and n_subsets qubit subsets given as in qsv_reduced_density_circuits (the same
+ * limits, the same row convention):
+ *     out[e * R + off_s + 2 * (a * 2^k_s + a') + {0, 1}] = W_s[a][a'] = sum_b (H_h psi_e)(a, b) conj psi_e(a', b)   (re, im)
+ * in qsv_reduced_density_circuits' layout; out_values[e] (may be NULL) = <psi_e|H_h|psi_e>, which is also Tr W_s of every subset.
+ * For a gate V(s) on A with V(0) = 1 and D = dV/ds at 0 appended to the circuit, dE/ds at 0 is 2 Re sum_{a,a'} D[a][a'] conj
+ * W_A[a][a'].  W is not Hermitian in general and is raw: not divided by |psi|^2.  The call runs as qsv_reduced_density_circuits
+ * runs: ordinary plans into state slots (no split route), then on the handle's stream, per launch group, the adjoint sweep's
+ * operator kernel, which writes lambda = H_h psi of the group into its scratch (allocated on first need, grown by need; the only
+ * state-sized write) and leaves its shares of <H>, and per run of subsets one kernel that walks psi and lambda in blocks of the
+ * subset's qubits and the six lowest others and accumulates four 16 x 16 tiles on the fp64 matrix pipe, and a second that adds the
+ * workgroups' tiles in ascending order.  The matrix of an (evaluation, subset) is the same bits in any batch, at any position of
+ * a launch group and of the subset list, whatever other subsets the call names, and on every call (fixed-order sums, no
+ * floating-point atomics); so is a value.  Every sum is fp64, also on an fp32 handle, whose lambda is fp32.  The call lays a
+ * batch out as every batch call does, so a recorded batch is dropped and laid out again by the next qsv_eval_* call, which returns
+ * the bits it returned before.  Goes between batches.
+ * Errors: everything qsv_reduced_density_circuits refuses, with the same codes; no operator set QSV_E_STATE; n_evals == 0 QSV_OK
+ * once the subsets were checked.
+ */
+int qsv_operator_density_circuits(qsv_t* h, int n_subsets, const int32_t* subset_offsets /* n_subsets + 1 */,
+                                  const int32_t* subset_qubits, int n_evals, const int* circuit_ids,
+                                  const int64_t* param_offsets, const double* params, double* out,
+                                  double* out_values /* may be NULL: <H> per evaluation */);
+
 /* ---- the geometry of a circuit's parameters ---------------------------------------------------------- */
 
 /*

@@ -305,6 +305,7 @@ SIGNATURES = {
     "qsv_observables_covariance": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "qsv_overlap_circuits": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "qsv_reduced_density_circuits": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P]),
+    "qsv_operator_density_circuits": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "qsv_metric_circuits": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P]),
     "qsv_metric_stats": (C.c_int, [_P, C.POINTER(QsvMetricStats)]),
     "qsv_observables_create": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.POINTER(C.c_int)]),

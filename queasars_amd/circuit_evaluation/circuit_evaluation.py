@@ -1405,6 +1405,40 @@ class StatevectorDevice:
     MAX_RDM_QUBITS = 4      # (QSV_RDM_MAX_QUBITS)
     MAX_RDM_SUBSETS = 1024  # (QSV_RDM_MAX_SUBSETS)
 
+    def _checked_subsets(self, circuits: Sequence[CircuitIR], subsets: Sequence[Sequence[int]], what: str) -> list[list[int]]:
+        """The qubit subsets of a reduced density call (`what`: whose matrices, for the message) as lists of ints, checked."""
+        subsets = [[int(q) for q in subset] for subset in subsets]
+        if not subsets:
+            raise ValueError("at least one subset of qubits is needed")
+        for subset in subsets:
+            if not 1 <= len(subset) <= self.MAX_RDM_QUBITS:
+                raise ValueError(f"a subset names 1 to {self.MAX_RDM_QUBITS} qubits, not {len(subset)}")
+            if len(set(subset)) != len(subset) or not all(0 <= q < self._n_qubits for q in subset):
+                raise ValueError(f"a subset names distinct qubits below {self._n_qubits}, not {subset}")
+        if any(c._kept_state is not None for c in circuits):
+            raise ValueError(f"the {what} of a circuit that continues a kept state are not supported")
+        return subsets
+
+    def _subset_matrices(self, n: int, subsets: list[list[int]], call) -> list[np.ndarray]:
+        """One complex128 ``(n, 2**k, 2**k)`` array per subset, filled in runs of :attr:`MAX_RDM_SUBSETS` subsets:
+        ``call(first, count, offsets, qubits, out)`` is one library call for the run that starts at subset ``first``, with the
+        run's subset offsets and qubits and its ``(n, sum 4**k)`` output."""
+        result = [np.zeros((n, 1 << len(subset), 1 << len(subset)), dtype=np.complex128) for subset in subsets]
+        if n == 0:
+            return result
+        for s0 in range(0, len(subsets), self.MAX_RDM_SUBSETS):
+            run = subsets[s0:s0 + self.MAX_RDM_SUBSETS]
+            offsets = np.zeros(len(run) + 1, dtype=np.int32)
+            np.cumsum([len(subset) for subset in run], out=offsets[1:])
+            qubits = np.asarray([q for subset in run for q in subset], dtype=np.int32)
+            starts = np.zeros(len(run) + 1, dtype=np.int64)  # (in complex entries of an evaluation's row)
+            np.cumsum([4 ** len(subset) for subset in run], out=starts[1:])
+            out = np.zeros((n, int(starts[-1])), dtype=np.complex128)
+            call(s0, len(run), offsets, qubits, out)
+            for j, subset in enumerate(run):
+                result[s0 + j][...] = out[:, starts[j]:starts[j + 1]].reshape(n, 1 << len(subset), 1 << len(subset))
+        return result
+
     def reduced_density_matrices(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]],
                                  subsets: Sequence[Sequence[int]]) -> list[np.ndarray]:
         """The reduced density matrices ``rho_A = Tr_rest |psi_i><psi_i|`` of every (circuit, parameter vector) pair's final
@@ -1415,34 +1449,42 @@ class StatevectorDevice:
         point and subset alone.  Reads no operator.  More than :attr:`MAX_RDM_SUBSETS` subsets are served in runs of that
         many, one library call each.  A circuit that continues a kept state raises ``ValueError``."""
         batch = _HostBatch(self, circuits, parameter_values)
-        n = batch.n
-        subsets = [[int(q) for q in subset] for subset in subsets]
-        if not subsets:
-            raise ValueError("at least one subset of qubits is needed")
-        for subset in subsets:
-            if not 1 <= len(subset) <= self.MAX_RDM_QUBITS:
-                raise ValueError(f"a subset names 1 to {self.MAX_RDM_QUBITS} qubits, not {len(subset)}")
-            if len(set(subset)) != len(subset) or not all(0 <= q < self._n_qubits for q in subset):
-                raise ValueError(f"a subset names distinct qubits below {self._n_qubits}, not {subset}")
-        if any(c._kept_state is not None for c in circuits):
-            raise ValueError("the reduced density matrices of a circuit that continues a kept state are not supported")
-        result = [np.zeros((n, 1 << len(subset), 1 << len(subset)), dtype=np.complex128) for subset in subsets]
-        if n > 0:
-            arguments = batch.arguments()
-            for s0 in range(0, len(subsets), self.MAX_RDM_SUBSETS):
-                run = subsets[s0:s0 + self.MAX_RDM_SUBSETS]
-                offsets = np.zeros(len(run) + 1, dtype=np.int32)
-                np.cumsum([len(subset) for subset in run], out=offsets[1:])
-                qubits = np.asarray([q for subset in run for q in subset], dtype=np.int32)
-                starts = np.zeros(len(run) + 1, dtype=np.int64)  # (in complex entries of an evaluation's row)
-                np.cumsum([4 ** len(subset) for subset in run], out=starts[1:])
-                out = np.zeros((n, int(starts[-1])), dtype=np.complex128)
-                # (a refusal with QSV_E_UNSUPPORTED as a ValueError with the library's message)
-                self._check_gradient(self._lib.qsv_reduced_density_circuits(
-                    self._handle, len(run), _lib.as_ptr(offsets), _lib.as_ptr(qubits), *arguments, _lib.as_ptr(out)))
-                for j, subset in enumerate(run):
-                    result[s0 + j][...] = out[:, starts[j]:starts[j + 1]].reshape(n, 1 << len(subset), 1 << len(subset))
-        return result
+        subsets = self._checked_subsets(circuits, subsets, "reduced density matrices")
+        arguments = batch.arguments() if batch.n else ()
+
+        def call(first, count, offsets, qubits, out):
+            # (a refusal with QSV_E_UNSUPPORTED as a ValueError with the library's message)
+            self._check_gradient(self._lib.qsv_reduced_density_circuits(
+                self._handle, count, _lib.as_ptr(offsets), _lib.as_ptr(qubits), *arguments, _lib.as_ptr(out)))
+
+        return self._subset_matrices(batch.n, subsets, call)
+
+    def operator_density_matrices(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]],
+                                  subsets: Sequence[Sequence[int]], with_values: bool = False):
+        """The operator-weighted reduced density matrices ``W_A = Tr_rest(H |psi_i><psi_i|)`` of every (circuit, parameter
+        vector) pair's final state on every qubit subset A of ``subsets``, for the Hermitian part H of the operator set on the
+        device: a list with one complex128 ``(n, 2**k, 2**k)`` array per subset, ``W[a][a'] = sum_b (H psi)(a, b) conj psi(a',
+        b)``, reduced on the device from the states where they are (``qsv_operator_density_circuits``).  Subsets
+        and row indices as in :meth:`reduced_density_matrices`.  A gate ``V(s)`` on A with ``V(0) = 1`` and ``D = dV/ds`` at 0,
+        appended to the circuit, changes the energy at the rate ``2 Re sum D[a][a'] conj W[a][a']``
+        (``queasars_amd.evqe.growth``).  Raw numbers; W is not Hermitian in general; ``Tr W = <H>`` on every subset.  Each matrix
+        depends on its circuit, point and subset alone.  With ``with_values`` the pair ``(matrices, values)``, ``values`` the
+        float64 ``(n,)`` array of ``<H>`` from the same pass.  More than :attr:`MAX_RDM_SUBSETS` subsets are served in runs of
+        that many, one library call each.  A circuit that continues a kept state raises ``ValueError``; no operator on the
+        device raises ``CircuitEvaluatorException``."""
+        batch = _HostBatch(self, circuits, parameter_values)
+        subsets = self._checked_subsets(circuits, subsets, "operator density matrices")
+        values = np.zeros(batch.n, dtype=np.float64)
+        arguments = batch.arguments() if batch.n else ()
+
+        def call(first, count, offsets, qubits, out):
+            # (a refusal with QSV_E_UNSUPPORTED as a ValueError with the library's message; the values come with the first run)
+            self._check_gradient(self._lib.qsv_operator_density_circuits(
+                self._handle, count, _lib.as_ptr(offsets), _lib.as_ptr(qubits), *arguments, _lib.as_ptr(out),
+                _lib.as_ptr(values) if with_values and first == 0 else None))
+
+        result = self._subset_matrices(batch.n, subsets, call)
+        return (result, values) if with_values else result
 
     # -- the geometry of a circuit's parameters -------------------------------------------------------
     def metric_tensors(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]], wrt=None) -> list[np.ndarray]:
@@ -1892,6 +1934,20 @@ class OperatorCircuitEvaluator(_OperatorEvaluator):
         _same_length(len(circuits), len(parameter_values))
         circuits, parameter_values = _present_pairs(circuits, parameter_values)
         return self._device.reduced_density_matrices(self._behind_initial_state(circuits), parameter_values, subsets)
+
+    def operator_density_matrices(self, circuits: list[CircuitIR], parameter_values: list[list[float]],
+                                  subsets: Sequence[Sequence[int]], with_values: bool = False):
+        """The operator-weighted reduced density matrices ``W_A = Tr_rest(H |psi><psi|)`` of every circuit's final state (behind
+        this evaluator's initial state) on the qubit subsets ``subsets``, for the evaluator's operator: one complex128 ``(n,
+        2**k, 2**k)`` array per subset (:meth:`StatevectorDevice.operator_density_matrices`, DESIGN.md 4.19;
+        ``queasars_amd.evqe.growth`` turns them into the gradients of gates appended at identity); with ``with_values`` the pair
+        ``(matrices, values)``, the float64 ``(n,)`` expectation values from the same pass.  Pairs of which either half is None
+        are dropped.  Exact numbers: no noise is added and no random number is drawn."""
+        _same_length(len(circuits), len(parameter_values))
+        circuits, parameter_values = _present_pairs(circuits, parameter_values)
+        circuits = self._behind_initial_state(circuits)
+        with self._own_operator():
+            return self._device.operator_density_matrices(circuits, parameter_values, subsets, with_values=with_values)
 
     def evaluate_subspace_matrices(self, circuits: list[CircuitIR], parameter_values: list[list[float]]):
         """``(S, H)`` of the circuits' final states among themselves: ``S[i, j] = <psi_i|psi_j>`` and ``H[i, j] =

@@ -23,6 +23,7 @@
 #include "moments.hpp"
 #include "covariance.hpp"
 #include "overlap.hpp"
+#include "operator_density.hpp"
 #include "reduced_density.hpp"
 #include "metric.hpp"
 #include "deflation.hpp"
@@ -511,6 +512,10 @@ struct qsv_handle {
     // reduced density matrices (qsv_reduced_density_circuits; reduced_density.hpp): the call's subset table | its matrices by
     // position | one launch's partial tiles
     DeviceBuffer d_rdm;
+    // operator-weighted reduced density matrices (qsv_operator_density_circuits; operator_density.hpp): the call's subset table | its
+    // matrices by position | its values by position | one launch's partial tiles.  lambda = H_h psi of a launch group and the
+    // operator kernel's shares of <H> are the adjoint sweep's d_adj_lambda and d_adj_epart.
+    DeviceBuffer d_opdm;
     // the Fubini-Study metric (qsv_metric_circuits; metric.hpp): one launch group's psi buffers and derivative states | the call's
     // tables | the group's gate matrices | one Gram launch's partial tiles | the points | the call's matrices
     DeviceBuffer d_met_scratch, d_met_tab, d_met_mats, d_met_partials, d_met_base, d_met_out;
@@ -3233,7 +3238,7 @@ void qsv_destroy(qsv_t* h) {
                             &h->d_states, &h->d_wtab, &h->d_side, &h->d_factor, &h->d_factor_count, &h->d_factor_big, &h->d_factor_big_count, &h->d_quad, &h->d_fterms, &h->d_fpart, &h->d_batch, &h->d_mats, &h->d_partials, &h->d_out, &h->d_scratch, &h->d_prefix, &h->d_sdiag,
                             &h->d_obs_partials, &h->d_obs_values, &h->d_grad_tab, &h->d_grad_rows, &h->d_grad_values, &h->d_grad_base,
                             &h->d_grad_out, &h->d_adj_lambda, &h->d_adj_tab, &h->d_adj_mats, &h->d_adj_partials, &h->d_adj_epart, &h->d_adj_base,
-                            &h->d_adj_out, &h->d_adj_values, &h->d_defl, &h->d_defl_out, &h->d_moments, &h->d_cov, &h->d_overlap, &h->d_rdm,
+                            &h->d_adj_out, &h->d_adj_values, &h->d_defl, &h->d_defl_out, &h->d_moments, &h->d_cov, &h->d_overlap, &h->d_rdm, &h->d_opdm,
                             &h->d_met_scratch, &h->d_met_tab, &h->d_met_mats, &h->d_met_partials, &h->d_met_base, &h->d_met_out})
         if (b->ptr) (void)hipFree(b->ptr);
     for (auto& kv : h->obs_sets) free_observable_set(kv.second);
@@ -5619,26 +5624,29 @@ int qsv_overlap_circuits(qsv_t* h, int n_states, const int* prefix_ids, int with
 
 // ---- reduced density matrices of qubit subsets (qsv.h: REDUCED DENSITY MATRICES; reduced_density.hpp) ----------------------------
 
-int qsv_reduced_density_circuits(qsv_t* h, int n_subsets, const int32_t* subset_offsets, const int32_t* subset_qubits, int n_evals,
-                                 const int* circuit_ids, const int64_t* param_offsets, const double* params, double* out) {
-    QSV_OPEN(h, "qsv_reduced_density_circuits", kDevice);
+// What qsv_reduced_density_circuits and qsv_operator_density_circuits check alike before anything is built: the pointers, the
+// register's size and the subsets (`what`: whose matrices, for the messages).  Fills the subset table and R, the doubles of an
+// evaluation's row of the output.
+static int rdm_open_subsets(qsv_t* h, const std::string& what, int n_subsets, const int32_t* subset_offsets, const int32_t* subset_qubits,
+                            int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* out,
+                            std::vector<RdmSubset>& table, size_t& R) {
     if (n_subsets < 1) return fail(h, QSV_E_ARG, "n_subsets must be at least 1");
-    if (n_subsets > int(kRdmMaxSubsets)) return fail(h, QSV_E_UNSUPPORTED, "n_subsets: reduced density matrices are available for up to 1024 subsets per call");
+    if (n_subsets > int(kRdmMaxSubsets)) return fail(h, QSV_E_UNSUPPORTED, "n_subsets: " + what + " are available for up to 1024 subsets per call");
     if (!subset_offsets || !subset_qubits) return fail(h, QSV_E_ARG, "subset_offsets or subset_qubits is null");
     if (n_evals < 0) return fail(h, QSV_E_ARG, "n_evals is negative");
     if (n_evals > 0 && (!circuit_ids || !param_offsets)) return fail(h, QSV_E_ARG, "circuit_ids or param_offsets is null");
     if (n_evals > 0 && !out) return fail(h, QSV_E_ARG, "out is null");
     // (the register's size is asked before anything is built or uploaded)
-    if (const int rc = qubit_guard(h, "reduced density matrices are available up to 28 qubits", true)) return rc;
+    if (const int rc = qubit_guard(h, (what + " are available up to 28 qubits").c_str(), true)) return rc;
     const size_t S = size_t(n_subsets);
-    std::vector<RdmSubset> table(S);
-    size_t R = 0;  // doubles of an evaluation's row of the output
+    table.assign(S, RdmSubset{});
+    R = 0;
     for (size_t s = 0; s < S; ++s) {
         const int64_t k = int64_t(subset_offsets[s + 1]) - int64_t(subset_offsets[s]);
         const std::string name = "subset " + std::to_string(s);
         if (subset_offsets[s] < 0 || k < 0) return fail(h, QSV_E_ARG, "subset_offsets must start at or above 0 and not fall (" + name + ")");
         if (k == 0) return fail(h, QSV_E_ARG, name + " is empty");
-        if (k > int64_t(kRdmMaxQubits)) return fail(h, QSV_E_UNSUPPORTED, name + " has " + std::to_string(k) + " qubits: reduced density matrices are available for up to 4");
+        if (k > int64_t(kRdmMaxQubits)) return fail(h, QSV_E_UNSUPPORTED, name + " has " + std::to_string(k) + " qubits: " + what + " are available for up to 4");
         const int32_t* q = subset_qubits + subset_offsets[s];
         for (int64_t j = 0; j < k; ++j) {
             if (q[j] < 0 || q[j] >= h->n) return fail(h, QSV_E_ARG, name + ": qubit " + std::to_string(q[j]) + " is out of range");
@@ -5648,6 +5656,17 @@ int qsv_reduced_density_circuits(qsv_t* h, int n_subsets, const int32_t* subset_
         rdm_subset(h->n, q, uint32_t(k), uint32_t(R), table[s]);
         R += size_t(2) << (2 * k);
     }
+    return QSV_OK;
+}
+
+int qsv_reduced_density_circuits(qsv_t* h, int n_subsets, const int32_t* subset_offsets, const int32_t* subset_qubits, int n_evals,
+                                 const int* circuit_ids, const int64_t* param_offsets, const double* params, double* out) {
+    QSV_OPEN(h, "qsv_reduced_density_circuits", kDevice);
+    std::vector<RdmSubset> table;
+    size_t R = 0;  // doubles of an evaluation's row of the output
+    if (const int rc = rdm_open_subsets(h, "reduced density matrices", n_subsets, subset_offsets, subset_qubits, n_evals, circuit_ids, param_offsets, out, table, R))
+        return rc;
+    const size_t S = size_t(n_subsets);
     if (n_evals == 0) return QSV_OK;
     BatchArgs args;
     int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args,
@@ -5675,6 +5694,61 @@ int qsv_reduced_density_circuits(qsv_t* h, int n_subsets, const int32_t* subset_
     };
     if ((rc = run_whole_states(h, args, G, tiles, d_out, out_count))) return rc;
     for (size_t j = 0; j < n; ++j) std::copy(h->h_out + j * R, h->h_out + (j + 1) * R, out + size_t(h->batch.eval_at[j]) * R);
+    return QSV_OK;
+}
+
+// ---- operator-weighted reduced density matrices (qsv.h: OPERATOR DENSITY MATRICES; operator_density.hpp) --------------------------
+
+int qsv_operator_density_circuits(qsv_t* h, int n_subsets, const int32_t* subset_offsets, const int32_t* subset_qubits, int n_evals,
+                                  const int* circuit_ids, const int64_t* param_offsets, const double* params, double* out,
+                                  double* out_values) {
+    QSV_OPEN(h, "qsv_operator_density_circuits", kDevice);
+    std::vector<RdmSubset> table;
+    size_t R = 0;  // doubles of an evaluation's row of the output
+    int rc = rdm_open_subsets(h, "operator density matrices", n_subsets, subset_offsets, subset_qubits, n_evals, circuit_ids, param_offsets, out, table, R);
+    if (rc || n_evals == 0) return rc;
+    if (h->n_terms == 0) return fail(h, QSV_E_STATE, "no operator set (call qsv_set_operator first)");
+    BatchArgs args;
+    if ((rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, args,
+                            "circuit_ids: the operator density matrices of a circuit on a kept state are not built")))
+        return rc;
+    if ((rc = wait_pending(h))) return rc;  // (the buffers below may still be read or written by a call that did not wait)
+    const size_t S = size_t(n_subsets), n = size_t(n_evals);
+    const size_t G = rdm_group(h->n, std::max<size_t>(1, std::min(size_t(h->group), size_t(h->max_grid_y))));
+    // device scratch: the subset table | the call's matrices by position | its values by position | the partial tiles of one launch
+    const size_t table_bytes = S * sizeof(RdmSubset), out_count = n * R + n, out_bytes = (out_count * sizeof(double) + 63) / 64 * 64;
+    const size_t most = std::min(G, n), run = std::min(S, rdm_subset_run(h->n, most));
+    const size_t partial_bytes = most * run * rdm_blocks(h->n) * kOpdmPartial * sizeof(double);
+    const uint32_t op_blocks = adjoint_op_blocks(h->n);
+    // (lambda and the operator's shares are the adjoint sweep's buffers, grown by need; qsv_adjoint_stats counts the sweep's own
+    // allocations only)
+    if ((rc = ensure(h, h->d_opdm, table_bytes + out_bytes + partial_bytes)) || (rc = ensure_host_out(h, out_count)) ||
+        (rc = ensure(h, h->d_adj_lambda, (most << h->n) * h->amp_bytes)) || (rc = ensure(h, h->d_adj_epart, most * op_blocks * sizeof(double))))
+        return rc;
+    const RdmSubset* const d_table = static_cast<const RdmSubset*>(h->d_opdm.ptr);
+    double* const d_out = reinterpret_cast<double*>(static_cast<char*>(h->d_opdm.ptr) + table_bytes);
+    double* const d_values = d_out + n * R;
+    double* const partials = reinterpret_cast<double*>(static_cast<char*>(h->d_opdm.ptr) + table_bytes + out_bytes);
+    double* const e_partials = static_cast<double*>(h->d_adj_epart.ptr);
+    QSV_HIP(h, hipMemcpy(h->d_opdm.ptr, table.data(), table_bytes, hipMemcpyHostToDevice));
+    const bool streaming = h->stream_mode != 0;
+    auto tiles = [&](size_t g0, size_t gc) -> int {
+        QSV_HIP(h, launch_adjoint_apply_operator(h->dtype, h->d_states.ptr, h->d_adj_lambda.ptr, h->n, int(gc), operator_view(h), streaming,
+                                                 e_partials, h->stream));
+        QSV_HIP(h, launch_opdm_values(e_partials, op_blocks, int(gc), d_values + g0, h->stream));
+        for (size_t s0 = 0; s0 < S; s0 += run) {
+            const uint32_t sc = uint32_t(std::min(run, S - s0));
+            QSV_HIP(h, launch_opdm_panels(h->dtype, h->d_states.ptr, h->d_adj_lambda.ptr, h->n, int(gc), d_table + s0, sc, partials, h->stream));
+            QSV_HIP(h, launch_opdm_combine(partials, h->n, int(gc), d_table + s0, sc, R, d_out + g0 * R, h->stream));
+        }
+        return QSV_OK;
+    };
+    if ((rc = run_whole_states(h, args, G, tiles, d_out, out_count))) return rc;
+    for (size_t j = 0; j < n; ++j) {
+        const size_t e = h->batch.eval_at[j];
+        std::copy(h->h_out + j * R, h->h_out + (j + 1) * R, out + e * R);
+        if (out_values) out_values[e] = h->h_out[n * R + j];
+    }
     return QSV_OK;
 }
 

@@ -35,7 +35,7 @@ import numpy as np
 
 from queasars_amd.evqe import device_search
 from queasars_amd.evqe.device_search import _full_point, _PackedRuns, _positions  # (the run layout is stated there)
-from queasars_amd.evqe.genome import EVQEIndividual, EVQEPopulation, new_random_seed
+from queasars_amd.evqe.genome import EVQECircuitLayer, EVQEIndividual, EVQEPopulation, new_random_seed
 
 
 # ---- optimiser ------------------------------------------------------------------------------------------------
@@ -667,10 +667,18 @@ class EVQEMinimumEigensolverConfiguration:
     # (mutation.py:57-59: only that layer's angles change) -- where the evaluator can (``keep_states``) and the circuit costs
     # say it pays.  None: yes; False: never (QSV_KEPT_STATES=0 / 1 overrides).
     kept_state_search: Optional[bool] = None
+    # Layers drawn per individual that the topological search grows (evqe/growth.py): with k > 1 the layer whose
+    # parameters have the largest gradient norm at zero angles is kept -- exact first-order numbers from ONE
+    # ``evaluator.operator_density_matrices`` call per generation over all chosen parents; no candidate circuit is run and no
+    # circuit evaluation is counted.  Candidate 0 is the layer that is drawn with 1, and the solver's random streams are consumed
+    # as with 1.  1: every draw, circuit and result as without the option.
+    growth_candidates: int = 1
 
     def __post_init__(self):
         if self.population_size < 1:
             raise ValueError("population_size must be at least 1!")
+        if self.growth_candidates < 1:
+            raise ValueError("growth_candidates must be at least 1!")
         if self.max_generations is None and self.max_circuit_evaluations is None and self.termination_criterion is None:
             raise ValueError("At least one of max_generations, max_circuit_evaluations or termination_criterion is needed!")
         if self.use_tournament_selection and (self.tournament_size is None or self.tournament_size < 1):
@@ -753,6 +761,8 @@ class EVQEMinimumEigensolver:
         self._rng_parameter_search = Random(new_random_seed(rng))
         self._rng_topological = Random(new_random_seed(rng))
         self._rng_layer_removal = Random(new_random_seed(rng))
+        # per grown individual of the last topological search with growth_candidates > 1: (kept candidate, every candidate's norm)
+        self.last_growth_scores: list = []
 
     # -- mutation helpers -----------------------------------------------------------------------------------
     @staticmethod
@@ -903,12 +913,40 @@ class EVQEMinimumEigensolver:
             individuals[i] = ind
         return EVQEPopulation(tuple(individuals), population.species_representatives, None, None), total
 
-    def _topological_search(self, population: EVQEPopulation) -> EVQEPopulation:
+    def _topological_search(self, population: EVQEPopulation, evaluator=None) -> EVQEPopulation:
         chosen = self._chosen(population, self._rng_topological, self.configuration.topological_search_probability)
         individuals = list(population.individuals)
-        for i, seed in chosen.items():
-            individuals[i] = EVQEIndividual.add_random_layers(individuals[i], 1, False, random_seed=seed)
+        candidates = self.configuration.growth_candidates
+        if candidates > 1 and not callable(getattr(evaluator, "operator_density_matrices", None)):
+            raise ValueError("growth_candidates > 1 needs an evaluator with operator_density_matrices (an operator evaluator)")
+        if candidates > 1 and chosen:
+            grown = self._grow_by_gradient(evaluator, [individuals[i] for i in chosen], list(chosen.values()), candidates)
+            for i, individual in zip(chosen, grown):
+                individuals[i] = individual
+        else:
+            for i, seed in chosen.items():
+                individuals[i] = EVQEIndividual.add_random_layers(individuals[i], 1, False, random_seed=seed)
         return EVQEPopulation(tuple(individuals), population.species_representatives, None, None)
+
+    def _grow_by_gradient(self, evaluator, parents: list[EVQEIndividual], seeds: list[int], candidates: int) -> list[EVQEIndividual]:
+        """One new layer per parent, at zero angles: of `candidates` layers drawn against the parent's last layer, the one whose
+        parameters have the largest gradient norm at identity (evqe/growth.py); the lowest index wins a tie, candidate 0 --
+        the layer ``add_random_layers`` draws from the same seed -- when all norms are zero.  One device call for all parents."""
+        from queasars_amd.evqe.growth import appended_gate_gradients, layer_gradient
+
+        circuits = [parent.get_parameterized_quantum_circuit(shared=self.share_circuits) for parent in parents]
+        u, cu3 = appended_gate_gradients(evaluator, circuits, [list(parent.parameter_values) for parent in parents])
+        grown, self.last_growth_scores = [], []
+        for e, (parent, seed) in enumerate(zip(parents, seeds)):
+            local = Random(seed)  # (its first draw is add_random_layers' own)
+            layers = [EVQECircuitLayer.random_layer(n_qubits=parent.n_qubits, random_seed=new_random_seed(local), previous_layer=parent.layers[-1])
+                      for _ in range(candidates)]
+            norms = [float(np.linalg.norm(layer_gradient(layer, u[e], cu3[e]))) for layer in layers]
+            best = max(range(candidates), key=lambda c: (norms[c], -c))
+            self.last_growth_scores.append((best, norms))
+            layer = layers[best]
+            grown.append(EVQEIndividual(parent.n_qubits, (*parent.layers, layer), (*parent.parameter_values, *((0,) * layer.n_parameters))))
+        return grown
 
     def _layer_removal(self, population: EVQEPopulation) -> EVQEPopulation:
         chosen = self._chosen(population, self._rng_layer_removal, self.configuration.layer_removal_probability)
@@ -1047,6 +1085,8 @@ class EVQEMinimumEigensolver:
         directions of the individual's parameter space change the state at all.  The same rules as ``eigenvalue_variance``.
         ``False``: no call, both fields stay ``None``."""
         cfg = self.configuration
+        if cfg is not None and cfg.growth_candidates > 1 and not callable(getattr(evaluator, "operator_density_matrices", None)):
+            raise ValueError("growth_candidates > 1 needs an evaluator with operator_density_matrices (an operator evaluator)")
         searcher = evaluator if search_evaluator is None else search_evaluator
         if searcher.n_qubits != evaluator.n_qubits:
             raise ValueError("the search evaluator must be over the same register")
@@ -1143,7 +1183,7 @@ class EVQEMinimumEigensolver:
                 break
             population, nfev = self._parameter_search(searcher, population)
             evaluations[-1] += nfev
-            population = self._topological_search(population)
+            population = self._topological_search(population, evaluator)
             population = self._layer_removal(population)
         if evaluations and evaluations[-1] == 0 and len(evaluations) > 1:
             evaluations.pop()
