@@ -739,6 +739,50 @@ int qsv_deflated_gradient_device(qsv_t* h, int n_states, const int* prefix_ids, 
                                  double* device_out_energies /* may be NULL */, double* device_out_overlaps /* may be NULL */);
 
 /*
+ * EXACT CVAR GRADIENTS: gradients of CVaR_alpha of the diagonal operator under the EXACT output distribution,
+ * the quantity qsv_exact_cvar_batch returns.  With the basis states sorted ascending by (value v_i, index), p_i(theta) = |psi_i|^2,
+ * target = alpha - (1e-8 + 1e-5 |alpha|), b the first rank whose cumulative mass cum_b reaches target (the last rank where none
+ * does) and t = v_b, the rows are the derivative of
+ *     t - (1 / alpha) sum_i max(t - v_i, 0) p_i(theta)
+ * by theta AT t = v_b(theta) HELD FIXED (Rockafellar-Uryasev): the gradient of the expectation value of the clipped operator
+ * diag(w), w_i = -max(t - v_i, 0) / alpha.  That is dCVaR_alpha / dtheta wherever the mass in front of the boundary state and the
+ * mass up to and including it straddle alpha.  At a kink -- where the boundary state changes, or where the stopping rule
+ * (cum_b within numpy.isclose of alpha, below it) fires -- it is one of the one-sided derivatives.  States tied with t carry
+ * weight 0, so the order inside a tie does not matter.  With alpha within numpy.isclose of 1 it is the expectation value's
+ * gradient: the call IS the plain adjoint call, rows and values bit for bit qsv_adjoint_gradient_circuits', and the thresholds are
+ * the operator's largest value.
+ * It is the adjoint sweep's with another seed: per launch group, on the handle's stream behind the forward run into state slots
+ * (no split route), the exact CVaR's two-step search with p_i read from the state slot through the sorted order (no table of
+ * 2^n probabilities is written; fixed-order sums, no floating-point atomics), one streaming pass that writes
+ * lambda_G = diag(w) psi (fp64 arithmetic, rounded to the handle's type) and the workgroups' shares of Re<psi|lambda_G> in H psi's
+ * place, the runs, the combination, and one kernel for
+ *     out_values[e]     (may be NULL) CVaR_alpha = t (1 - s / alpha) + Re<psi|lambda_G>, s = max(alpha - cum_b, 0) the mass the
+ *                       stopping rule leaves out: the reference's accumulation, to rounding what qsv_exact_cvar_batch returns
+ *     out_thresholds[e] (may be NULL) t, the value at risk
+ * Arguments, wrt_offsets / wrt and `out` as qsv_adjoint_gradient_circuits.  A call whose wrt counts are all 0 is the value-only
+ * call: no run is launched.  The first call after qsv_set_operator sorts the operator's values, as the exact CVaR does.
+ * Contract: an evaluation's row, value and threshold are the same bits in any batch, at any position of a launch group, from
+ * either entry point and on every call; the entries of a wrt subset are the bits of the full gradient.  Scratch growth is counted
+ * in qsv_adjoint_stats, where the seed pass is the one state sweep the H application is.
+ * Errors: no operator or a non-diagonal one, a batch open on this thread QSV_E_STATE; alpha outside (0, 1], the adjoint call's
+ * wrt and out_width errors, a pointer of the device form that is not this device's memory QSV_E_ARG; more than 28 qubits, a
+ * circuit on a kept state QSV_E_UNSUPPORTED; n_evals == 0 QSV_OK.
+ * Not built: gradients of SAMPLED values, the split route, circuits on kept states, a device_active mask.
+ */
+int qsv_cvar_gradient_circuits(qsv_t* h, double alpha, int n_evals, const int* circuit_ids, const int64_t* param_offsets,
+                               const double* params, const int64_t* wrt_offsets /* NULL: every parameter of each circuit */,
+                               const int32_t* wrt, double* out, double* out_values /* may be NULL */,
+                               double* out_thresholds /* may be NULL */);
+/*
+ * The same with the points READ FROM and the rows LEFT IN device memory: qsv_adjoint_gradient_device's layout, ready_event and
+ * stream contract (queued on the handle's stream, not waited for).  device_out_values / device_out_thresholds: n_evals doubles
+ * each; each may be NULL.
+ */
+int qsv_cvar_gradient_device(qsv_t* h, double alpha, int n_evals, const int* circuit_ids, int width, const double* device_values,
+                             void* ready_event, const int64_t* wrt_offsets, const int32_t* wrt, int out_width, double* device_out,
+                             double* device_out_values /* may be NULL */, double* device_out_thresholds /* may be NULL */);
+
+/*
  * ENERGY VARIANCE: out_variances[e] = <psi_e| H_h^2 |psi_e> - <psi_e| H_h |psi_e>^2 and, where out_values is
  * not NULL, out_values[e] = <psi_e| H_h |psi_e>, for n_evals (circuit, parameter vector) pairs laid out as in qsv_eval_circuits;
  * H_h is the Hermitian part of the operator (what qsv_set_operator keeps).  Zero exactly on eigenstates of H_h; the spread of a

@@ -301,7 +301,9 @@ SIGNATURES = {
     "qsv_adjoint_stats": (C.c_int, [_P, C.POINTER(QsvAdjointStats)]),
     "qsv_deflated_gradient_circuits": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "qsv_deflated_gradient_device": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
-    "qsv_variance_circuits": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
+    "qsv_cvar_gradient_circuits": (C.c_int, [_P, C.c_double, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "qsv_cvar_gradient_device": (C.c_int, [_P, C.c_double, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
+    "qsv_variance_circuits":(C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
     "qsv_observables_covariance": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "qsv_overlap_circuits": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "qsv_reduced_density_circuits": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P]),

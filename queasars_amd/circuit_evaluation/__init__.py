@@ -7,6 +7,7 @@ from queasars_amd.circuit_evaluation.circuit_evaluation import (  # noqa: F401
     CircuitEvaluatorException,
     DeflatedOperatorCircuitEvaluator,
     DeviceValueCache,
+    ExactCVaRCircuitEvaluator,
     KeptState,
     OperatorCircuitEvaluator,
     OperatorSamplerCircuitEvaluator,

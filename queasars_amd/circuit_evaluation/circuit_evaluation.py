@@ -1265,6 +1265,52 @@ class StatevectorDevice:
         self.last_gradient_evaluations = len(circuits)
         return self.last_gradient_evaluations
 
+    # -- exact CVaR gradients ---------------------------------------------------------------------
+    def cvar_gradients(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]], alpha: float, wrt=None,
+                       with_values: bool = False, with_thresholds: bool = False):
+        """Gradients of :meth:`exact_cvar_batch`, the CVaR_alpha of the (diagonal) operator under the exact output
+        distribution, from the adjoint sweep with the clipped seed (``qsv_cvar_gradient_circuits``): one 1-D
+        array per circuit, ``wrt`` as in :meth:`gradients` -- an empty ``wrt`` is the value-only call, which sweeps nothing.
+        The gradient is the derivative of ``t - sum_i max(t - v_i, 0) p_i / alpha`` with the threshold ``t`` (the value at
+        risk) held fixed: the CVaR's own derivative away from its kinks, one of the one-sided derivatives at a kink.
+        ``with_values``: also the CVaR values (to rounding :meth:`exact_cvar_batch`'s); ``with_thresholds``: also the
+        thresholds; both float64 arrays.  The result is the gradients alone, or a tuple ``(gradients[, values][,
+        thresholds])``.  With ``alpha`` within ``numpy.isclose`` of 1 it is :meth:`adjoint_gradients`, bit for bit."""
+        if not 0 < alpha <= 1:
+            raise ValueError("alpha must be in the range (0, 1]!")
+        n = len(circuits)
+        values = np.zeros(n, dtype=np.float64)
+        thresholds = np.zeros(n, dtype=np.float64)
+        entry = self._lib.qsv_cvar_gradient_circuits
+
+        def function(handle, *rest):
+            return entry(handle, float(alpha), *rest[:-1], *rest[-1])
+
+        trailing = (_lib.as_ptr(values), _lib.as_ptr(thresholds) if with_thresholds else None)
+        gradients = self._host_gradients(function, circuits, parameter_values, wrt, trailing)
+        self.last_gradient_evaluations = len(gradients)
+        out = (gradients,) + ((values,) if with_values else ()) + ((thresholds,) if with_thresholds else ())
+        return out if len(out) > 1 else gradients
+
+    def cvar_gradients_of_device_parameters(self, circuits: Sequence[CircuitIR], matrix_ptr: int, width: int, event: int, out_ptr: int,
+                                            out_width: int, alpha: float, wrt=None, values_ptr: int = 0,
+                                            thresholds_ptr: int = 0) -> int:
+        """:meth:`cvar_gradients` with the layout and the contract of :meth:`gradients_of_device_parameters`
+        (``qsv_cvar_gradient_device``): points read from and gradients left in device memory, queued on the handle's stream,
+        not waited for.  ``values_ptr`` / ``thresholds_ptr``: device memory for ``len(circuits)`` doubles each, or 0.  Returns
+        ``len(circuits)``, the evaluations counted."""
+        if not 0 < alpha <= 1:
+            raise ValueError("alpha must be in the range (0, 1]!")
+        entry = self._lib.qsv_cvar_gradient_device
+
+        def function(handle, *rest):
+            return entry(handle, float(alpha), *rest[:-1], *rest[-1])
+
+        self._device_gradients(function, circuits, matrix_ptr, width, event, out_ptr, out_width, wrt,
+                               (_pointer(values_ptr), _pointer(thresholds_ptr)))
+        self.last_gradient_evaluations = len(circuits)
+        return self.last_gradient_evaluations
+
     # -- the operator's variance ------------------------------------------------------------------
     def variances(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]]) -> tuple[np.ndarray, np.ndarray]:
         """``(values, variances)`` of the operator set on the device, two float64 arrays with one entry per (circuit, parameter
@@ -2501,6 +2547,71 @@ class OperatorSamplerCircuitEvaluator(_OperatorEvaluator):
         states, _ = self._device.sample_batch(circs, values, self._shots, seed)
         columns = [_cvar_of_sample_matrix(_diagonal_values(op, states), self._alpha) for op in operators]
         return np.asarray(columns, dtype=np.float64).reshape(len(operators), len(circs)).T.tolist()
+
+
+class ExactCVaRCircuitEvaluator(OperatorSamplerCircuitEvaluator):
+    """CVaR_alpha of a diagonal operator under the EXACT output distribution, with its exact gradient: the
+    objective of :class:`OperatorSamplerCircuitEvaluator` with ``sampler_shots=None`` -- ``evaluate_circuits``,
+    ``evaluate_device_to_device`` and ``evaluate_observables`` are the parent's, bit for bit -- that gradient-based optimisers
+    (``Adam``, ``NaturalGradient``) can minimise as well.
+
+    ``evaluate_gradients`` is the derivative of ``t - sum_i max(t - v_i, 0) p_i / alpha`` by the parameters with the threshold
+    ``t`` (the value at risk) held fixed, from one adjoint sweep per circuit with the clipped seed: the CVaR's derivative
+    wherever the CVaR is differentiable, one of its one-sided derivatives at a kink (where the boundary state changes).  With
+    ``alpha`` within ``numpy.isclose`` of 1 it is the expectation value's gradient.  Gradients of SAMPLED values, circuits that
+    continue a kept state, gradient plans and a device-resident Adam on the CVaR are not built."""
+
+    #: what the solver's host drivers read: every circuit is differentiated by one sweep
+    gradient_method = "adjoint"
+    last_gradient_evaluations = 0
+    last_gradient_evaluation_counts: list = []
+
+    def __init__(
+        self,
+        operator: PauliOperator,
+        alpha: float,
+        initial_state_circuit: Optional[CircuitIR] = None,
+        dtype: str = "fp64",
+        device: int = 0,
+        statevector_device: Optional[StatevectorDevice] = None,
+    ):
+        super().__init__(None, operator, alpha=alpha, initial_state_circuit=initial_state_circuit, dtype=dtype, device=device,
+                         statevector_device=statevector_device)
+
+    @property
+    def alpha(self) -> float:
+        return self._alpha
+
+    def _cvar_gradients(self, circuits, parameter_values, wrt, **options):
+        """One :meth:`StatevectorDevice.cvar_gradients` call: behind the initial state, the operator under the guard."""
+        if _has_none(circuits) or _has_none(parameter_values):
+            circuits, parameter_values = _present_pairs(circuits, parameter_values)
+        _same_length(len(circuits), len(parameter_values))
+        circuits = self._behind_initial_state(circuits)
+        with self._own_operator():
+            return self._device.cvar_gradients(circuits, parameter_values, self._alpha, wrt, **options)
+
+    def _counted(self, gradients: list) -> list:
+        self.last_gradient_evaluations = len(gradients)
+        self.last_gradient_evaluation_counts = [1] * len(gradients)
+        return gradients
+
+    def evaluate_gradients(self, circuits: list[CircuitIR], parameter_values: list[list[float]], wrt=None) -> list[np.ndarray]:
+        """Exact gradients of :meth:`evaluate_circuits`: one 1-D array per circuit, ``wrt`` as in
+        :meth:`OperatorCircuitEvaluator.evaluate_gradients`.  :attr:`last_gradient_evaluations` counts one per circuit."""
+        return self._counted(self._cvar_gradients(circuits, parameter_values, wrt))
+
+    def evaluate_values_and_gradients(self, circuits: list[CircuitIR], parameter_values: list[list[float]], wrt=None):
+        """``(values, gradients)`` from ONE call: the CVaR values as a float64 array -- a by-product of the sweep, to rounding
+        what :meth:`evaluate_circuits` returns -- and the gradients of :meth:`evaluate_gradients`."""
+        gradients, values = self._cvar_gradients(circuits, parameter_values, wrt, with_values=True)
+        return values, self._counted(gradients)
+
+    def evaluate_thresholds(self, circuits: list[CircuitIR], parameter_values: list[list[float]]) -> np.ndarray:
+        """The value at risk of every circuit, the threshold ``t`` the CVaR's accumulation stops at, as a float64 array: a
+        value-only call, no gate is swept."""
+        _gradients, thresholds = self._cvar_gradients(circuits, parameter_values, [], with_thresholds=True)
+        return thresholds
 
 
 def _ascending(missing: np.ndarray) -> tuple[np.ndarray, np.ndarray]:

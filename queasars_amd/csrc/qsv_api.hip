@@ -27,6 +27,7 @@
 #include "reduced_density.hpp"
 #include "metric.hpp"
 #include "deflation.hpp"
+#include "cvar_gradient.hpp"
 #include "gradient.hpp"
 #include "value_cache.hpp"
 #include "kernels.hpp"
@@ -501,6 +502,10 @@ struct qsv_handle {
     // position | its partial tiles; the host form's energies | overlaps.  Counted with the adjoint scratch (adj_stats).
     DeviceBuffer d_defl, d_defl_out;
     const void* defl_checked[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // qsv_deflated_gradient_device's pointers
+    // exact CVaR gradients (qsv_cvar_gradient_circuits / qsv_cvar_gradient_device; cvar_gradient.hpp): one launch group's (t, s) pairs by
+    // position | its chunk masses.  The host form's thresholds are d_defl_out.  Counted with the adjoint scratch (adj_stats).
+    DeviceBuffer d_cvar_grad;
+    const void* cvar_grad_checked[4] = {nullptr, nullptr, nullptr, nullptr};  // qsv_cvar_gradient_device's pointers
     // the operator's moments (qsv_variance_circuits; moments.hpp): the call's (E, Var) pairs by position | one launch group's partials
     DeviceBuffer d_moments;
     // an observable set's second moments (qsv_observables_covariance; covariance.hpp): the call's values | covariances by position |
@@ -3238,7 +3243,7 @@ void qsv_destroy(qsv_t* h) {
                             &h->d_states, &h->d_wtab, &h->d_side, &h->d_factor, &h->d_factor_count, &h->d_factor_big, &h->d_factor_big_count, &h->d_quad, &h->d_fterms, &h->d_fpart, &h->d_batch, &h->d_mats, &h->d_partials, &h->d_out, &h->d_scratch, &h->d_prefix, &h->d_sdiag,
                             &h->d_obs_partials, &h->d_obs_values, &h->d_grad_tab, &h->d_grad_rows, &h->d_grad_values, &h->d_grad_base,
                             &h->d_grad_out, &h->d_adj_lambda, &h->d_adj_tab, &h->d_adj_mats, &h->d_adj_partials, &h->d_adj_epart, &h->d_adj_base,
-                            &h->d_adj_out, &h->d_adj_values, &h->d_defl, &h->d_defl_out, &h->d_moments, &h->d_cov, &h->d_overlap, &h->d_rdm, &h->d_opdm,
+                            &h->d_adj_out, &h->d_adj_values, &h->d_defl, &h->d_defl_out, &h->d_cvar_grad, &h->d_moments, &h->d_cov, &h->d_overlap, &h->d_rdm, &h->d_opdm,
                             &h->d_met_scratch, &h->d_met_tab, &h->d_met_mats, &h->d_met_partials, &h->d_met_base, &h->d_met_out})
         if (b->ptr) (void)hipFree(b->ptr);
     for (auto& kv : h->obs_sets) free_observable_set(kv.second);
@@ -4213,25 +4218,35 @@ static int sample_batch_locked(qsv_t* h, const BatchArgs& args, int shots, uint6
 // allocate where sample_batch_locked can, and the first call after qsv_set_operator sorts the operator's values, which
 // allocates and waits (sort_states_by_value).
 static int expectation_to_device(qsv_t* h, const BatchArgs& args, double* device_out, const int* plan_id = nullptr);
+// What the exact CVaR and its gradient ask of the operator, of alpha, and of the sorted values (sort.hip).
+static int cvar_operator_guard(qsv_t* h) {
+    if (h->has_diag_part && h->diagonal) return QSV_OK;
+    return fail(h, QSV_E_STATE, "the exact CVaR needs a diagonal operator (call qsv_set_operator with I/Z terms only)");
+}
+static bool cvar_alpha_is_one(double alpha) { return std::fabs(alpha - 1.0) <= 1e-8 + 1e-5; }  // numpy.isclose(alpha, 1)
+static int sorted_values_ready(qsv_t* h) {
+    if (h->order_valid) return QSV_OK;
+    const uint64_t dim = uint64_t(1) << h->n;
+    int rc;
+    if ((rc = wait_pending(h))) return rc;  // (it allocates: not beside a batch that ended without waiting)
+    if ((rc = ensure(h, h->d_order, dim * sizeof(uint32_t))) || (rc = ensure(h, h->d_sorted, dim * sizeof(double)))) return rc;
+    QSV_HIP(h, sort_states_by_value(static_cast<const double*>(h->d_diag.ptr), dim, static_cast<uint32_t*>(h->d_order.ptr),
+                                    static_cast<double*>(h->d_sorted.ptr), h->stream));
+    h->order_valid = true;
+    return QSV_OK;
+}
 static int exact_cvar_locked(qsv_t* h, const BatchArgs& args, double alpha, double* out_cvar, const DeviceCall* dev = nullptr) {
     const size_t n_evals = args.circs.size();
     if (n_evals == 0) return QSV_OK;
-    if (!(h->has_diag_part && h->diagonal))
-        return fail(h, QSV_E_STATE, "the exact CVaR needs a diagonal operator (call qsv_set_operator with I/Z terms only)");
+    if (const int rc = cvar_operator_guard(h)) return rc;
     if (const int rc = qubit_guard(h, "the exact CVaR is available up to 28 qubits")) return rc;
     // alpha = 1 (numpy.isclose(alpha, 1), the reference's test): the reference takes the plain mean of the values there
     // (expectation_calculation.py:55-69), not its accumulation loop, whose stopping rule leaves out the last 1e-5 of the mass
     // (5e-4 of an Ising value at 20 qubits): the expectation value, as qsv_eval_circuits computes it
-    if (std::fabs(alpha - 1.0) <= 1e-8 + 1e-5) return dev ? expectation_to_device(h, args, dev->out) : eval_all(h, args, out_cvar);
+    if (cvar_alpha_is_one(alpha)) return dev ? expectation_to_device(h, args, dev->out) : eval_all(h, args, out_cvar);
     const uint64_t dim = uint64_t(1) << h->n;
     int rc;
-    if (!h->order_valid) {
-        if ((rc = wait_pending(h))) return rc;  // (it allocates: not beside a batch that ended without waiting)
-        if ((rc = ensure(h, h->d_order, dim * sizeof(uint32_t))) || (rc = ensure(h, h->d_sorted, dim * sizeof(double)))) return rc;
-        QSV_HIP(h, sort_states_by_value(static_cast<const double*>(h->d_diag.ptr), dim, static_cast<uint32_t*>(h->d_order.ptr),
-                                        static_cast<double*>(h->d_sorted.ptr), h->stream));
-        h->order_valid = true;
-    }
+    if ((rc = sorted_values_ready(h))) return rc;
     const SplitRule rule = split_rule(h, SplitUse::Sampling);
     const size_t n_split = rule.count(args.circs), n_plain = n_evals - n_split;
     const size_t G = size_t(h->group), SG = size_t(std::max(1, h->side_slots));
@@ -4992,10 +5007,17 @@ struct AdjSeed {
     double* out_energies = nullptr;
     double* out_overlaps = nullptr;
     SpanTimer* timer = nullptr;
+    // The exact CVaR's seed instead (cvar_seed's): lambda_G = diag(w) psi, w_i = -max(t - v_i, 0) / alpha at the
+    // threshold t the search finds in the group's states (`clipped`; not clipped, alpha within numpy.isclose of 1: H_h psi, the plain
+    // call).  AdjCall::out_values then receives the CVaR, out_thresholds (device memory, may be null) t.
+    bool cvar = false, clipped = false;
+    double alpha = 1.0;
+    double* out_thresholds = nullptr;
 };
 
 // What both entry points run with the lock held: the call's tables, the forward run group by group, and behind each group the H
-// application, the runs and the combination on the handle's stream.  Returns without waiting.
+// application (a clipped CVaR seed: the threshold search and the seed pass in its place), the runs and the combination on the
+// handle's stream.  Returns without waiting.
 static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, const int64_t* wrt_offsets, const int32_t* wrt,
                           const AdjCall& call, const AdjSeed* seed = nullptr) {
     const size_t n_evals = args.circs.size();
@@ -5086,6 +5108,10 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
     // the seed's scratch: the group's overlaps by position | the panels' partial tiles
     const size_t ovl_bytes = (gc_max * K * 2 * sizeof(double) + 63) / 64 * 64;
     if (K && (rc = ensure_counted(h, h->d_defl, ovl_bytes + overlap_partial_bytes(h->n, K, false, gc_max), allocations))) return rc;
+    const bool clipped = seed && seed->clipped;
+    if (clipped && (rc = ensure_counted(h, h->d_cvar_grad, cvar_gradient_scratch_doubles(h->n, gc_max) * sizeof(double), allocations))) return rc;
+    double* const cvar_scratch = static_cast<double*>(h->d_cvar_grad.ptr);
+    const double* const sorted = static_cast<const double*>(h->d_sorted.ptr);  // (a CVaR seed's: sorted_values_ready)
     const void* dt = h->d_adj_tab.ptr;
     const AdjGate* d_gates = TableBlob::at<AdjGate>(dt, off_gates);
     const AdjRunDesc* d_runs = TableBlob::at<AdjRunDesc>(dt, off_runs);
@@ -5104,10 +5130,20 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
     const bool streaming = h->stream_mode != 0;
     auto sweep = [&](size_t g0, size_t gc) -> int {
         QSV_HIP(h, launch_adjoint_prepare(d_evals + g0, int(gc), d_gates, max_gates, call.base, call.width, mats, h->stream));
-        QSV_HIP(h, launch_adjoint_apply_operator(h->dtype, h->d_states.ptr, h->d_adj_lambda.ptr, h->n, int(gc), operator_view(h), streaming,
-                                                 e_partials, h->stream));
         uint32_t most_runs = 0;
         for (size_t j = g0; j < g0 + gc; ++j) most_runs = std::max(most_runs, evals[j].n_runs);
+        if (clipped) {
+            // t and s from the amplitudes while the states are still the final ones, then the clipped seed in H psi's place (its
+            // lambda is stored where a gate is swept at all)
+            QSV_HIP(h, launch_cvar_gradient_threshold(h->dtype, h->d_states.ptr, h->n, int(gc), static_cast<const uint32_t*>(h->d_order.ptr),
+                                                      sorted, seed->alpha, cvar_scratch, h->stream));
+            QSV_HIP(h, launch_cvar_gradient_seed(h->dtype, h->d_states.ptr, most_runs > 0 ? h->d_adj_lambda.ptr : nullptr, h->n, int(gc),
+                                                 static_cast<const double*>(h->d_diag.ptr), cvar_scratch, seed->alpha, streaming, e_partials,
+                                                 h->stream));
+        } else {
+            QSV_HIP(h, launch_adjoint_apply_operator(h->dtype, h->d_states.ptr, h->d_adj_lambda.ptr, h->n, int(gc), operator_view(h), streaming,
+                                                     e_partials, h->stream));
+        }
         if (K) {
             // c = Phi^H Psi while the states are still the final ones (the runs rewrite them), then -- where a gate is swept at all --
             // lambda += sum_k beta_k c_k phi_k
@@ -5133,23 +5169,29 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
         if (seed && (K || (seed->out_energies && call.out_values)))
             QSV_HIP(h, launch_deflation_finish(d_evals + g0, int(gc), uint32_t(K), d_betas, d_ovl, d_energies, call.out_values,
                                                K ? seed->out_overlaps : nullptr, h->stream));
+        if (seed && seed->cvar)
+            QSV_HIP(h, launch_cvar_gradient_finish(d_evals + g0, int(gc), clipped ? cvar_scratch : nullptr, seed->alpha, sorted + (dim - 1),
+                                                   call.out_values, seed->out_thresholds, h->stream));
         return QSV_OK;
     };
     return run_laid_out(h, args, run, lay, {}, sweep);
 }
 
 // The host form of the adjoint call and, with `seed` (deflation_seed's), of the deflated one, whose energies and overlaps then go
-// to out_energies / out_overlaps (may be null): the points as one matrix in device memory, a row per evaluation (rows of an even
-// number of doubles), the gradient rows as wide as the longest request, everything back after one wait.
+// to out_energies / out_overlaps (may be null), or (cvar_seed's) of the CVaR one, whose thresholds go to out_thresholds (may be
+// null): the points as one matrix in device memory, a row per evaluation (rows of an even number of doubles), the gradient rows
+// as wide as the longest request, everything back after one wait.
 static int adjoint_host_form(qsv_t* h, int n_evals, const int* circuit_ids, const int64_t* param_offsets, const double* params,
                              const int64_t* wrt_offsets, const int32_t* wrt, double* out, double* out_values, const char* kept_refusal,
-                             AdjSeed* seed = nullptr, double* out_energies = nullptr, double* out_overlaps = nullptr) {
+                             AdjSeed* seed = nullptr, double* out_energies = nullptr, double* out_overlaps = nullptr,
+                             double* out_thresholds = nullptr) {
     BatchArgs packed, args;
     int rc = resolve_batch(h, size_t(n_evals), circuit_ids, param_offsets, params, packed, kept_refusal);
     if (rc) return rc;
     int64_t width, out_width;
     std::vector<double> base;
     if ((rc = pack_rows(h, packed, wrt_offsets, out, true, width, out_width, base))) return rc;
+    // (behind the values: the deflated call's energies | overlaps, or the CVaR call's thresholds)
     const size_t n = size_t(n_evals), K = seed ? size_t(seed->n_refs) : 0, n_extra = seed ? n + n * K * 2 : 0;
     int64_t& allocations = h->adj_stats.n_allocations;
     if ((rc = rows_to_device(h, packed, base, width, h->d_adj_base, allocations, args)) ||
@@ -5163,6 +5205,7 @@ static int adjoint_host_form(qsv_t* h, int n_evals, const int* circuit_ids, cons
     if (seed) {
         seed->out_energies = out_energies ? d_energies : nullptr;
         seed->out_overlaps = out_overlaps && K ? d_energies + n : nullptr;
+        seed->out_thresholds = out_thresholds ? d_energies : nullptr;
         seed->timer = &timer;
     }
     if ((rc = adjoint_locked(h, args, circuit_ids, wrt_offsets, wrt, call, seed))) {
@@ -5170,7 +5213,7 @@ static int adjoint_host_form(qsv_t* h, int n_evals, const int* circuit_ids, cons
         return rc;
     }
     std::vector<double> values(n), extra(n_extra);
-    const bool any_extra = seed && (seed->out_energies || seed->out_overlaps);
+    const bool any_extra = seed && (seed->out_energies || seed->out_overlaps || seed->out_thresholds);
     if ((rc = rows_to_host(h, packed, wrt_offsets, h->d_adj_out.ptr, out_width, out,
                            {{h->d_adj_values.ptr, values.data(), n}, {d_energies, extra.data(), any_extra ? n_extra : 0}})))
         return rc;
@@ -5178,6 +5221,7 @@ static int adjoint_host_form(qsv_t* h, int n_evals, const int* circuit_ids, cons
     if (out_values) std::memcpy(out_values, values.data(), n * sizeof(double));
     if (seed && out_energies) std::memcpy(out_energies, extra.data(), n * sizeof(double));
     if (seed && seed->out_overlaps) std::memcpy(out_overlaps, extra.data() + n, n * K * 2 * sizeof(double));
+    if (seed && out_thresholds) std::memcpy(out_thresholds, extra.data(), n * sizeof(double));
     return QSV_OK;
 }
 
@@ -5255,12 +5299,57 @@ int qsv_deflated_gradient_device(qsv_t* h, int n_states, const int* prefix_ids, 
     return device_form_end(h, adjoint_locked(h, args, circuit_ids, wrt_offsets, wrt, call, &seed), true);
 }
 
+// ---- exact CVaR gradients (qsv.h: EXACT CVAR GRADIENTS; cvar_gradient.hpp) ---------------------------------------------------------
+
+// alpha and the operator of a CVaR call, checked, as adjoint_locked's seed; with an evaluation to run, the operator's values sorted.
+static int cvar_seed(qsv_t* h, double alpha, int n_evals, AdjSeed& seed) {
+    if (!(alpha > 0.0) || alpha > 1.0) return fail(h, QSV_E_ARG, "alpha must be in (0, 1]");
+    seed.cvar = true;
+    seed.alpha = alpha;
+    seed.clipped = !cvar_alpha_is_one(alpha);
+    if (n_evals == 0) return QSV_OK;
+    int rc;
+    if ((rc = cvar_operator_guard(h)) || (rc = qubit_guard(h, "the exact CVaR's gradient is available up to 28 qubits"))) return rc;
+    return sorted_values_ready(h);
+}
+
+int qsv_cvar_gradient_circuits(qsv_t* h, double alpha, int n_evals, const int* circuit_ids, const int64_t* param_offsets,
+                               const double* params, const int64_t* wrt_offsets, const int32_t* wrt, double* out, double* out_values,
+                               double* out_thresholds) {
+    QSV_OPEN(h, "qsv_cvar_gradient_circuits", kDevice);
+    if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets))) return fail(h, QSV_E_ARG, "bad arguments");
+    AdjSeed seed;
+    int rc = cvar_seed(h, alpha, n_evals, seed);
+    if (rc || n_evals == 0) return rc;
+    return adjoint_host_form(h, n_evals, circuit_ids, param_offsets, params, wrt_offsets, wrt, out, out_values,
+                             "CVaR gradients of a circuit on a kept state are not built", &seed, nullptr, nullptr, out_thresholds);
+}
+
+int qsv_cvar_gradient_device(qsv_t* h, double alpha, int n_evals, const int* circuit_ids, int width, const double* device_values,
+                             void* ready_event, const int64_t* wrt_offsets, const int32_t* wrt, int out_width, double* device_out,
+                             double* device_out_values, double* device_out_thresholds) {
+    QSV_OPEN(h, "qsv_cvar_gradient_device", kDevice);
+    const DeviceForm form{n_evals, circuit_ids, width, device_values, ready_event, out_width, device_out};
+    int rc = device_form_guard(h, form);
+    if (rc) return rc;
+    AdjSeed seed;
+    if ((rc = cvar_seed(h, alpha, n_evals, seed)) || n_evals == 0) return rc;
+    seed.out_thresholds = device_out_thresholds;
+    BatchArgs args;
+    if ((rc = device_form_open(h, form, {{"device_out_values", device_out_values}, {"device_out_thresholds", device_out_thresholds}},
+                               h->cvar_grad_checked, "CVaR gradients of a circuit on a kept state are not built", args)))
+        return rc;
+    const AdjCall call{device_values, width, device_out, out_width, device_out_values};
+    return device_form_end(h, adjoint_locked(h, args, circuit_ids, wrt_offsets, wrt, call, &seed), true);
+}
+
 int qsv_adjoint_stats(const qsv_t* h, qsv_adjoint_stats_t* out) {
     if (!out) return QSV_E_ARG;
     QSV_OPEN(h, "qsv_adjoint_stats", kHostOnly);
     *out = h->adj_stats;
     out->scratch_bytes = int64_t(h->d_adj_lambda.bytes + h->d_adj_tab.bytes + h->d_adj_mats.bytes + h->d_adj_partials.bytes + h->d_adj_epart.bytes +
-                                 h->d_adj_base.bytes + h->d_adj_out.bytes + h->d_adj_values.bytes + h->d_defl.bytes + h->d_defl_out.bytes);
+                                 h->d_adj_base.bytes + h->d_adj_out.bytes + h->d_adj_values.bytes + h->d_defl.bytes + h->d_defl_out.bytes +
+                                 h->d_cvar_grad.bytes);
     return QSV_OK;
 }
 
