@@ -210,6 +210,16 @@ def _struct_dict(raw: C.Structure) -> dict:
     return out
 
 
+def _observable_key(operators: Sequence[PauliOperator], n_qubits: int) -> tuple:
+    """The content of a list of observables on ``n_qubits`` qubits, checked: what their device-side set is cached by."""
+    for op in operators:
+        if not isinstance(op, PauliOperator):
+            raise ValueError("every observable must be a PauliOperator")
+        if op.num_qubits != n_qubits:
+            raise ValueError(f"an observable acts on {op.num_qubits} qubits, the device was created for {n_qubits}")
+    return tuple((op.num_qubits, op.x_mask.tobytes(), op.z_mask.tobytes(), op.coeffs.tobytes()) for op in operators)
+
+
 class _HostBatch:
     """The opening of a host batch method of :class:`StatevectorDevice`: the length check when it is made, ``n`` for the
     method's own checks and its empty result, and :meth:`arguments` -- what the library's batch entry points take -- once the
@@ -491,6 +501,13 @@ class StatevectorDevice:
         # held across "set the operator, then evaluate" by evaluators that share this device
         self.operator_lock = threading.RLock()
         self._observable_sets: "OrderedDict[tuple, int]" = OrderedDict()  # (observable_values; gone with the handle)
+        # held from the lookup of an observable set to the end of the library call that uses its id: a caller that misses
+        # destroys the least recently used set.  The innermost lock: nothing else is taken while it is held.
+        self._observable_lock = threading.Lock()
+        # callers inside expectation_value_coalesced_under: they wait in the library WITHOUT operator_lock (that is how the
+        # library gets to merge them), so set_operator waits for their number to fall to zero instead
+        self._coalesced = threading.Condition(threading.Lock())
+        self._coalesced_callers = 0
 
     # -- plumbing -------------------------------------------------------------------------------
     def __reduce__(self):
@@ -544,6 +561,9 @@ class StatevectorDevice:
         z = np.ascontiguousarray(operator.z_mask, dtype=np.uint64)
         cre = np.ascontiguousarray(operator.coeffs.real, dtype=np.float64)
         cim = np.ascontiguousarray(operator.coeffs.imag, dtype=np.float64)
+        with self._coalesced:  # (no new caller gets in meanwhile: that takes operator_lock, which whoever is here holds)
+            while self._coalesced_callers:
+                self._coalesced.wait()
         self._check(
             self._lib.qsv_set_operator(
                 self._handle, len(operator), _lib.as_ptr(x), _lib.as_ptr(z), _lib.as_ptr(cre), _lib.as_ptr(cim)
@@ -951,6 +971,24 @@ class StatevectorDevice:
             self._check(rc)
         return out.value
 
+    def expectation_value_coalesced_under(self, operator: PauliOperator, circuit: CircuitIR, parameter_values: Sequence[float],
+                                          window_us: float = 0.0) -> Optional[float]:
+        """:meth:`expectation_value_coalesced` where ``operator`` is the one installed, and stays so until the call has returned
+        (:meth:`set_operator` waits for such callers); ``None``, and nothing evaluated, where another operator is installed.
+        ``operator_lock`` is held for the look alone, not over the call: the callers are merged because they wait together."""
+        with self.operator_lock:
+            if self._operator is not operator:
+                return None
+            with self._coalesced:
+                self._coalesced_callers += 1
+        try:
+            return self.expectation_value_coalesced(circuit, parameter_values, window_us)
+        finally:
+            with self._coalesced:
+                self._coalesced_callers -= 1
+                if not self._coalesced_callers:
+                    self._coalesced.notify_all()
+
     def statevector(self, circuit: CircuitIR, parameter_values: Sequence[float]) -> np.ndarray:
         cid = self.circuit_id(circuit)
         p = np.ascontiguousarray(parameter_values, dtype=np.float64)
@@ -1331,15 +1369,13 @@ class StatevectorDevice:
     # -- several observables ---------------------------------------------------------------------
     MAX_OBSERVABLE_SETS = 16
 
-    def _observable_set(self, operators: Sequence[PauliOperator]) -> int:
-        """Device-side set of ``operators`` (``qsv_observables_create``), cached by content; the least recently used sets
-        beyond :attr:`MAX_OBSERVABLE_SETS` are destroyed."""
-        for op in operators:
-            if not isinstance(op, PauliOperator):
-                raise ValueError("every observable must be a PauliOperator")
-            if op.num_qubits != self._n_qubits:
-                raise ValueError(f"an observable acts on {op.num_qubits} qubits, the device was created for {self._n_qubits}")
-        key = tuple((op.num_qubits, op.x_mask.tobytes(), op.z_mask.tobytes(), op.coeffs.tobytes()) for op in operators)
+    def _observable_set(self, operators: Sequence[PauliOperator], key: Optional[tuple] = None) -> int:
+        """Device-side set of ``operators`` (``qsv_observables_create``), cached by content (``key``:
+        :func:`_observable_key`, where the caller has it); the least recently used sets beyond :attr:`MAX_OBSERVABLE_SETS`
+        are destroyed.  The id is good while the caller holds ``_observable_lock``: whoever uses it takes the lock before
+        this call and lets go after the library call the id goes to."""
+        if key is None:
+            key = _observable_key(operators, self._n_qubits)
         sets = self._observable_sets
         hit = sets.get(key)
         if hit is not None:
@@ -1371,11 +1407,13 @@ class StatevectorDevice:
         operators = list(operators)
         if not operators:
             raise ValueError("at least one observable is needed")
-        set_id = self._observable_set(operators)
-        if batch.n == 0:
-            return np.zeros((0, len(operators)), dtype=np.float64)
+        key = _observable_key(operators, self._n_qubits)
         out = np.empty((batch.n, len(operators)), dtype=np.float64)
-        self._check(self._lib.qsv_eval_observables(self._handle, set_id, *batch.arguments(), _lib.as_ptr(out)))
+        arguments = batch.arguments()
+        with self._observable_lock:  # (the set stays alive until the call that uses it has returned)
+            set_id = self._observable_set(operators, key)
+            if batch.n:
+                self._check(self._lib.qsv_eval_observables(self._handle, set_id, *arguments, _lib.as_ptr(out)))
         return out
 
     MAX_COVARIANCE_OBSERVABLES = 64  # (QSV_COVARIANCE_MAX_OBSERVABLES)
@@ -1396,14 +1434,16 @@ class StatevectorDevice:
         m = len(operators)
         if m > self.MAX_COVARIANCE_OBSERVABLES:
             raise ValueError(f"covariances are available for at most {self.MAX_COVARIANCE_OBSERVABLES} observables, not {m}")
-        set_id = self._observable_set(operators)
+        key = _observable_key(operators, self._n_qubits)
         values = np.zeros((batch.n, m), dtype=np.float64)
         covariances = np.zeros((batch.n, m, m), dtype=np.float64)
-        if batch.n == 0:
-            return values, covariances
-        # (a refused circuit -- QSV_E_UNSUPPORTED: one on a kept state -- as a ValueError with the library's message)
-        self._check_gradient(self._lib.qsv_observables_covariance(
-            self._handle, set_id, *batch.arguments(), _lib.as_ptr(values), _lib.as_ptr(covariances)))
+        arguments = batch.arguments()
+        with self._observable_lock:  # (as in observable_values)
+            set_id = self._observable_set(operators, key)
+            if batch.n:
+                # (a refused circuit -- QSV_E_UNSUPPORTED: one on a kept state -- as a ValueError with the library's message)
+                self._check_gradient(self._lib.qsv_observables_covariance(
+                    self._handle, set_id, *arguments, _lib.as_ptr(values), _lib.as_ptr(covariances)))
         return values, covariances
 
     # -- two states at a time -----------------------------------------------------------------------
@@ -2665,6 +2705,9 @@ class BitstringCircuitEvaluator(BaseCircuitEvaluator):
         self._rng = np.random.default_rng(seed)
         self._use_value_cache = bool(device_value_cache)
         self._value_cache: Optional[DeviceValueCache] = None  # (created by the first call that needs it)
+        # held from a lookup to its finish (or clear), the scoring in between included: the library takes one lookup at a
+        # time on a cache, and the evaluator is shared by threads
+        self._cache_lock = threading.Lock()
         self._last_scored = 0
         self._device = statevector_device or StatevectorDevice(bitstring_evaluator.input_length, dtype=dtype, device=device)
         self._composed = _ComposedCircuits(initial_state_circuit)
@@ -2672,7 +2715,12 @@ class BitstringCircuitEvaluator(BaseCircuitEvaluator):
     def __getstate__(self):
         state = self.__dict__.copy()
         state["_value_cache"] = None  # (a cache travels empty, like _ComposedCircuits: it is refilled where it arrives)
+        state.pop("_cache_lock", None)  # (a lock does not travel at all)
         return state
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self._cache_lock = threading.Lock()
 
     @property
     def last_scored_bitstrings(self) -> int:
@@ -2698,25 +2746,27 @@ class BitstringCircuitEvaluator(BaseCircuitEvaluator):
     def _evaluate_through_cache(self, circuits, parameter_values, seed: int) -> list[float]:
         # (measure_quasi_distributions seeds a generator with the evaluator's draw and samples with ITS first draw)
         seed = int(np.random.default_rng(seed).integers(0, 2**63 - 1))
-        if self._value_cache is None:
-            self._value_cache = self._device.value_cache()
-        cache = self._value_cache
-        missing = cache.lookup(circuits, parameter_values, self._shots, seed)
-        ordered, order = _ascending(missing)
-        self._last_scored = 0
-        n = self.n_qubits
-        try:
-            scores = []
-            for state in ordered.tolist():
-                self._last_scored += 1
-                scores.append(self._bitstring_evaluator.evaluate_bitstring(format(state, f"0{n}b")))
-            values = _unpermuted(scores, order)
-        except BaseException:
-            cache.clear()  # (the states the lookup inserted have no values: the next call starts from an empty table)
-            raise
-        if self._shots <= StatevectorDevice.MAX_CVAR_SHOTS:
-            return cache.finish(values, self._alpha)
-        return _cvar_of_sample_matrix(cache.finish(values, self._alpha, want_values=True), self._alpha)
+        with self._cache_lock:  # (one lookup at a time, its scoring and its finish with it: the callable runs under the lock)
+            if self._value_cache is None:
+                self._value_cache = self._device.value_cache()
+            cache = self._value_cache
+            missing = cache.lookup(circuits, parameter_values, self._shots, seed)
+            ordered, order = _ascending(missing)
+            self._last_scored = 0
+            n = self.n_qubits
+            try:
+                scores = []
+                for state in ordered.tolist():
+                    self._last_scored += 1
+                    scores.append(self._bitstring_evaluator.evaluate_bitstring(format(state, f"0{n}b")))
+                values = _unpermuted(scores, order)
+            except BaseException:
+                cache.clear()  # (the states the lookup inserted have no values: the next call starts from an empty table)
+                raise
+            if self._shots <= StatevectorDevice.MAX_CVAR_SHOTS:
+                return cache.finish(values, self._alpha)
+            sample_values = cache.finish(values, self._alpha, want_values=True)
+        return _cvar_of_sample_matrix(sample_values, self._alpha)
 
     @property
     def n_qubits(self) -> int:

@@ -38,8 +38,9 @@ class CoalescingCircuitEvaluator(BaseCircuitEvaluator):
 
     One-circuit calls on an exact :class:`OperatorCircuitEvaluator` (no initial state, no noise) take the native path:
     ``qsv_eval_coalesced`` merges the callers inside the library while their threads wait in C with the GIL released
-    (the Python scheme below costs several thread hand-overs under the GIL per call).  The wrapped evaluator's device
-    must then not be shared with evaluators of other operators."""
+    (the Python scheme below costs several thread hand-overs under the GIL per call).  On a device shared with evaluators
+    of other operators that path is taken while this evaluator's operator is the one installed, which it then stays until
+    the callers have their values (``StatevectorDevice.expectation_value_coalesced_under``)."""
 
     def __init__(self, evaluator: BaseCircuitEvaluator, window_s: float = 2e-4, max_batch: int = 4096, native: bool = True):
         if window_s < 0 or max_batch < 1:
@@ -70,9 +71,11 @@ class CoalescingCircuitEvaluator(BaseCircuitEvaluator):
         if not circuits:
             return []
         if self._native and len(circuits) == 1 and circuits[0] is not None and parameter_values[0] is not None:
-            device = self._evaluator._device
-            if device._operator is self._evaluator._operator:
-                return [device.expectation_value_coalesced(circuits[0], parameter_values[0], self._window_s * 1e6)]
+            # (None: another evaluator's operator is on the shared device -- the merged batch below installs this one's)
+            value = self._evaluator._device.expectation_value_coalesced_under(
+                self._evaluator._operator, circuits[0], parameter_values[0], self._window_s * 1e6)
+            if value is not None:
+                return [value]
         ticket = _Ticket(circuits, parameter_values)
         with self._lock:
             self._queue.append(ticket)
