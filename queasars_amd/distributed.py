@@ -723,10 +723,21 @@ def _mapped_receive(world: int, width: int, device, group=None, owner=None):
 # ---- layer searches sharded by individual ---------------------------------------------------------------------------------
 
 
-def shard_searches(evaluator, jobs: Sequence, group=None) -> Optional[list[int]]:
+class SearchShare(list):
+    """The jobs of a search that one rank runs (indices into the search's jobs, ascending), and ``rows``: the length of the
+    longest share of that search, the same number on every rank -- what :func:`gather_search_results` sizes every rank's
+    block by."""
+
+    def __init__(self, indices: Sequence[int], rows: int):
+        super().__init__(indices)
+        self.rows = int(rows)
+
+
+def shard_searches(evaluator, jobs: Sequence, group=None) -> Optional[SearchShare]:
     """Which of a layer search's (circuit, run) jobs THIS rank runs (reference: every individual's whole optimiser run is one task
     on the pool, mutation.py:194-235): the jobs dealt by what their circuits cost (:func:`partition_by_cost`), or None without
-    a process group of several ranks."""
+    a process group of several ranks.  The shares differ in length by design (one deep individual against many shallow ones);
+    the share carries the longest one's length to the gather, so that the costs are asked once per search."""
     import torch.distributed as dist
 
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
@@ -734,21 +745,31 @@ def shard_searches(evaluator, jobs: Sequence, group=None) -> Optional[list[int]]
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     costs = evaluation_costs(evaluator, [circuit for circuit, _ in jobs])
     shares = contiguous_shares(len(jobs), world) if costs is None else partition_by_cost(costs, world)
-    return shares[rank]
+    return SearchShare(shares[rank], max(len(share) for share in shares))
 
 
 def gather_search_results(jobs: Sequence, mine: Sequence[int], group=None) -> None:
     """After every rank has advanced ITS runs to completion: ONE all-gather per search hands every rank every run's final
     iterate, iteration count and evaluation count (mutation.py:206-218: the futures' results), so that the evolution goes on
-    identically everywhere.  Rows of max(len(x)) + 3 doubles: job index, iterations, evaluations, the iterate."""
+    identically everywhere.  Rows of max(len(x)) + 3 doubles: job index, iterations, evaluations, the iterate; every rank
+    sends as many rows as the LONGEST share has (``mine.rows`` of :func:`shard_searches`' share: the deal is a pure function
+    of the costs, every rank has the same number), the unused ones NaN.  For a share that does not say how long the longest
+    is (a plain list) the ranks agree on it first, at the price of a second small collective.  A search without jobs needs
+    none."""
     import torch
     import torch.distributed as dist
 
     world = dist.get_world_size(group)
     n = len(jobs)
-    width = max((run.x.size for _, run in jobs), default=0) + 3
-    rows = -(-n // world)
+    if n == 0:
+        return
+    width = max(run.x.size for _, run in jobs) + 3
     device = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend(group) == "nccl" else torch.device("cpu")
+    rows = getattr(mine, "rows", None)
+    if rows is None:
+        longest = torch.tensor([len(mine)], dtype=torch.int64, device=device)
+        dist.all_reduce(longest, op=dist.ReduceOp.MAX, group=group)
+        rows = int(longest.item())
     send = np.full((rows, width), np.nan)
     for slot, j in enumerate(mine):
         run = jobs[j][1]

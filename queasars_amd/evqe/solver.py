@@ -817,7 +817,7 @@ class EVQEMinimumEigensolver:
         if kept:  # (nothing may hold the search's circuits any longer: their kept states are a 2^n-amplitude buffer each)
             evaluator.forget_circuits()
         if mine is not None:
-            distributed.gather_search_results(jobs, own, self.process_group)
+            distributed.gather_search_results(jobs, mine, self.process_group)  # (the share itself: it knows the longest one's length)
         out, nfev = [], 0
         for individual, layer_id, (_, run) in zip(individuals, layer_ids, jobs):
             out.append(EVQEIndividual.change_layer_parameter_values(individual, layer_id, tuple(run.x.tolist())))

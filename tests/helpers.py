@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import ctypes as C
 import subprocess
+from contextlib import contextmanager
 from pathlib import Path
 
 import numpy as np
@@ -94,6 +95,31 @@ class COracle:
             circuit.n_qubits, len(kinds), kinds.ctypes, targets.ctypes, controls.ctypes, angles.ctypes, len(operator),
             x.ctypes, z.ctypes, cre.ctypes, cim.ctypes, table.ctypes if table is not None else None, scratch.ctypes,
         )
+
+
+@contextmanager
+def deep_seed_individuals(deep: dict):
+    """While open, every initial population a solver draws (``EVQEPopulation.random_population``) has the individuals at the
+    indices of ``deep`` replaced: ``index -> (layers, seed, which)`` puts individual ``which`` of
+    ``random_population(n_qubits, layers, which + 1, ..., seed)`` there -- deep individuals among shallow ones from the first
+    generation on, the population whose searches and evaluations are dealt unevenly.  The same population wherever it is
+    opened with the same argument: the ranks of a sharded run and the single-process run it is compared with."""
+    from queasars_amd.evqe import EVQEPopulation
+
+    draw = EVQEPopulation.random_population
+
+    def seeded(n_qubits, n_initial_layers, n_individuals, randomize_parameter_values, random_seed=None):
+        population = draw(n_qubits, n_initial_layers, n_individuals, randomize_parameter_values, random_seed=random_seed)
+        individuals = list(population.individuals)
+        for index, (layers, seed, which) in deep.items():
+            individuals[index] = draw(n_qubits, layers, which + 1, randomize_parameter_values, random_seed=seed).individuals[which]
+        return EVQEPopulation(tuple(individuals))
+
+    EVQEPopulation.random_population = staticmethod(seeded)
+    try:
+        yield
+    finally:
+        EVQEPopulation.random_population = staticmethod(draw)
 
 
 def host_cpu_share(limit: int = 16) -> int:

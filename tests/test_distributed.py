@@ -216,7 +216,29 @@ def _search_worker(rank: int, world: int, port: int, out_dir: str):
         dist.destroy_process_group()
 
 
-def _run_small_evolution(shard: bool):
+def _run_small_evolution(shard: bool, deep_layers=None, dealt=None):
+    """``deep_layers``: the initial population's second individual has that many layers.  ``dealt``: a list that receives (jobs,
+    this rank's share of them) of every sharded search."""
+    import contextlib
+
+    import helpers
+    from queasars_amd import distributed
+
+    if dealt is not None:
+        deal = distributed.shard_searches
+
+        def recorded(evaluator, jobs, group=None):
+            mine = deal(evaluator, jobs, group)
+            dealt.append((len(jobs), len(mine)))
+            return mine
+
+        distributed.shard_searches = recorded  # (a worker process of its own: nothing to put back)
+    seeded = helpers.deep_seed_individuals({1: (deep_layers, 4, 0)}) if deep_layers else contextlib.nullcontext()
+    with seeded:
+        return _small_evolution(shard)
+
+
+def _small_evolution(shard: bool):
     import helpers
     from queasars_amd.evqe.solver import SPSA, EVQEMinimumEigensolver, EVQEMinimumEigensolverConfiguration
 
@@ -248,6 +270,132 @@ def test_two_rank_sharded_searches_are_the_single_rank_evolution(tmp_path):
         seen.append(int(counts[-1]))
     assert sum(seen) == seen_single == sum(single.circuit_evaluations)
     assert max(seen) < 0.75 * seen_single
+
+
+# ---- searches whose shares differ in length: the gather's rows are the longest share's -------------------------------------
+
+
+class _PricedJob:
+    """Stands in for a search's circuit: all the deal looks at is what it costs."""
+
+    def __init__(self, price: float):
+        self.price = price
+
+
+class _PricedEvaluator:
+    def __init__(self):
+        self.asked = 0
+
+    def circuit_costs(self, circuits):
+        self.asked += 1
+        return [{"microseconds": c.price} for c in circuits]
+
+
+def _finished_run(j: int):
+    """What the rank that owns job ``j`` leaves in its run: an iterate whose LENGTH depends on the job as well."""
+    x = np.sin(np.arange(1 + 2 * (j % 3), dtype=np.float64) + 0.37 * j) * (j + 1)
+    return x, 3 + j, 7 + 2 * j
+
+
+def _gather_worker(rank: int, world: int, port: int, cases: list, out_dir: str):
+    sys.path.insert(0, str(ROOT))
+    sys.path.insert(0, str(ROOT / "tests"))
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    from datetime import timedelta
+    from types import SimpleNamespace
+
+    import torch.distributed as dist
+
+    from queasars_amd.distributed import gather_search_results, partition_by_cost, shard_searches
+
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=timedelta(seconds=60))
+    try:
+        lengths = []
+        for prices, plain in cases:
+            n = len(prices)
+            jobs = [(_PricedJob(p), SimpleNamespace(x=np.zeros(_finished_run(j)[0].size), iteration=0, nfev=0, done=False))
+                    for j, p in enumerate(prices)]
+            evaluator = _PricedEvaluator()
+            mine = shard_searches(evaluator, jobs)
+            assert list(mine) == partition_by_cost(prices, world)[rank]
+            for j in mine:
+                run = jobs[j][1]
+                run.x, run.iteration, run.nfev = _finished_run(j)
+            # (``plain``: a caller's own list of indices, which does not say how long the longest share is)
+            gather_search_results(jobs, list(mine) if plain else mine)
+            assert evaluator.asked == 1, "the costs are asked once per search"
+            for j, (_, run) in enumerate(jobs):
+                x, iteration, nfev = _finished_run(j)
+                assert run.done is True and run.iteration == iteration and run.nfev == nfev, (rank, j)
+                assert run.x.shape == x.shape and np.array_equal(run.x, x), (rank, j)
+                assert type(run.iteration) is int and type(run.nfev) is int
+            lengths.append(len(mine))
+        np.save(os.path.join(out_dir, f"lengths{rank}.npy"), np.asarray(lengths))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("world, cases, want_lengths", [
+    # one deep job among shallow ones (shares of 1 and 3 where ceil(4 / 2) = 2), the same from a plain list, one job (a rank
+    # with nothing to run) and no jobs at all
+    (2, [([100.0, 1.0, 1.0, 1.0], False), ([100.0, 1.0, 1.0, 1.0], True), ([5.0], False), ([], False)],
+     [[1, 3], [1, 3], [1, 0], [0, 0]]),
+    # eighteen against fifteen ones on four ranks: a share of 5 where ceil(16 / 4) = 4
+    (4, [([18.0] + [1.0] * 15, False)], [[1, 5, 5, 5]]),
+])
+def test_gather_search_results_with_uneven_shares(tmp_path, world, cases, want_lengths):
+    """``partition_by_cost`` deals shares of different lengths by design; the gather's block per rank is as long as the LONGEST
+    of them (before: ``ceil(n / world)`` rows, and the rank with the long share raised ``IndexError: index 2 is out of bounds
+    for axis 0 with size 2`` while its partners sat in the collective).  Every rank ends with every run's iterate (of its own
+    length: the rows are padded), iteration and evaluation counts and ``done``, as the owning rank set them."""
+    mp.spawn(_gather_worker, args=(world, _free_port(), cases, str(tmp_path)), nprocs=world, join=True)
+    lengths = np.stack([np.load(tmp_path / f"lengths{rank}.npy") for rank in range(world)], axis=1)
+    assert lengths.tolist() == want_lengths
+
+
+def _uneven_search_worker(rank: int, world: int, port: int, out_dir: str):
+    sys.path.insert(0, str(ROOT))
+    sys.path.insert(0, str(ROOT / "tests"))
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    from datetime import timedelta
+
+    import torch.distributed as dist
+
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=timedelta(seconds=60))
+    try:
+        dealt = []
+        result, seen = _run_small_evolution(shard=True, deep_layers=8, dealt=dealt)
+        np.save(os.path.join(out_dir, f"values{rank}.npy"), np.asarray(result.best_expectation_values + [result.eigenvalue]))
+        np.save(os.path.join(out_dir, f"best{rank}.npy"), np.asarray(result.best_individual.parameter_values))
+        np.save(os.path.join(out_dir, f"counts{rank}.npy"), np.asarray(result.circuit_evaluations + [seen]))
+        np.save(os.path.join(out_dir, f"dealt{rank}.npy"), np.asarray(dealt).reshape(-1, 2))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_two_rank_sharded_searches_with_a_deep_individual_are_the_single_rank_evolution(tmp_path):
+    """The evolution of a population of mixed depths (one eight-layer individual among two-layer ones, priced 17 : 1): its
+    searches are dealt in shares of different lengths -- asserted --, and every rank still reproduces the single-process run bit
+    for bit: best values per generation, the eigenvalue, the best individual's parameter values, the evaluation counts."""
+    world = 2
+    mp.spawn(_uneven_search_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    single, seen_single = _run_small_evolution(shard=False, deep_layers=8)
+    want_values = np.asarray(single.best_expectation_values + [single.eigenvalue])
+    seen = []
+    for rank in range(world):
+        assert np.array_equal(np.load(tmp_path / f"values{rank}.npy"), want_values)
+        assert np.array_equal(np.load(tmp_path / f"best{rank}.npy"), np.asarray(single.best_individual.parameter_values))
+        counts = np.load(tmp_path / f"counts{rank}.npy")
+        assert counts[:-1].tolist() == single.circuit_evaluations
+        seen.append(int(counts[-1]))
+    assert sum(seen) == seen_single == sum(single.circuit_evaluations)
+    # (jobs of the search, this rank's share of them) per search, in the order of the run
+    dealt = [np.load(tmp_path / f"dealt{rank}.npy") for rank in range(world)]
+    assert np.array_equal(dealt[0][:, 0], dealt[1][:, 0]) and np.array_equal(dealt[0][:, 1] + dealt[1][:, 1], dealt[0][:, 0])
+    uneven = [(int(n), int(a), int(b)) for (n, a), (_, b) in zip(*dealt) if max(a, b) > -(-n // world)]
+    assert uneven, "no search of this run had a share longer than ceil(jobs / ranks): the population is not of mixed depths"
 
 
 # ---- the same path on RCCL, when the box has two GPUs ----------------------------------------------------------------
