@@ -783,6 +783,52 @@ int qsv_cvar_gradient_device(qsv_t* h, double alpha, int n_evals, const int* cir
                              double* device_out_values /* may be NULL */, double* device_out_thresholds /* may be NULL */);
 
 /*
+ * FOLDED-SPECTRUM AND VARIANCE COSTS: values and gradients of
+ *     F_e = <psi_e| (H_h - c_e)^2 |psi_e>
+ * with H_h the Hermitian part of the operator (what qsv_set_operator keeps) and c_e the evaluation's centre:
+ *     centre == 0   c_e = target, one double for the call: the folded-spectrum cost, least at the eigenstate whose eigenvalue lies
+ *                   nearest the target
+ *     centre == 1   c_e = E_e = Re<psi_e|H_h psi_e>, formed on the device (target is not read beyond being finite): the variance
+ * With r = H_h psi - c psi the residual, the value is the CENTRED form |r|^2, never negative and free of the eps * E^2
+ * cancellation of qsv_variance_circuits' one pass.  The rows are the adjoint sweep's from lambda_G = (H_h - c) r with c HELD
+ * FIXED, which under centre == 1 is still the derivative of the variance: d/dc <(H_h - c)^2> = -2 (E - c) vanishes at c = E.
+ * The sweep is started from lambda_G - (E - c)^2 psi: a real multiple alpha psi of the state adds alpha d<psi|psi> = 0 to every
+ * entry, and this one is most of lambda_G's norm where the target lies far from E -- sweeping it would add only its rounding
+ * (single precision: several times the allowance of DESIGN.md 4.21).  Under centre == 1 nothing is subtracted.
+ * Per launch group, on the handle's stream behind the forward run into state slots (no split route): the adjoint call's H
+ * application (lambda_1 = H_h psi and the shares of E), one wave per evaluation for E and c, one streaming pass for r (fp64
+ * arithmetic, rounded to the handle's type into a second buffer of the group's size) with the workgroups' shares of |r|^2 taken
+ * before the rounding, one pass that writes the seed row by row from r (and psi) over lambda_1, the runs, the combination, and one kernel for
+ *     out_values[e]   (may be NULL) |r|^2       out_energies[e] (may be NULL) E_e
+ * An operator without x-mask groups (every diagonal operator) takes both passes in one, r_i = (D_i - c) psi_i and
+ * lambda_G,i = (D_i - c) r_i (less (E - c)^2 psi_i), and allocates no second buffer.  A launch group in which no evaluation has a gate to sweep -- a call
+ * whose wrt counts are all 0: the value-only call -- stops behind the shares of |r|^2: it stores neither r nor lambda_G and
+ * launches no run.  Every sum is fp64 in a fixed order, without floating-point atomics.
+ * Arguments, wrt_offsets / wrt and `out` as qsv_adjoint_gradient_circuits.
+ * Contract: an evaluation's row, value and energy are the same bits in any batch, at any position of a launch group, from either
+ * entry point and on every call; the entries of a wrt subset are the bits of the full gradient.  E agrees with qsv_eval_circuits
+ * to rounding.  Scratch growth is counted in qsv_adjoint_stats, where the residual and the seed pass are one state sweep each.
+ * Errors: no operator, a batch open on this thread QSV_E_STATE; centre outside {0, 1}, a non-finite target, the adjoint call's
+ * wrt and out_width errors, a pointer of the device form that is not this device's memory QSV_E_ARG; more than 28 qubits, a
+ * circuit on a kept state QSV_E_UNSUPPORTED; n_evals == 0 QSV_OK.
+ * Not built: penalised costs a E + b Var, a target per evaluation, the split route, circuits on kept states, gradient plans and
+ * device-resident searches on these costs, Hessians.
+ */
+int qsv_folded_gradient_circuits(qsv_t* h, int centre /* 0: target, 1: each evaluation's own mean */, double target, int n_evals,
+                                 const int* circuit_ids, const int64_t* param_offsets, const double* params,
+                                 const int64_t* wrt_offsets /* NULL: every parameter of each circuit */, const int32_t* wrt,
+                                 double* out, double* out_values /* may be NULL */, double* out_energies /* may be NULL */);
+/*
+ * The same with the points READ FROM and the rows LEFT IN device memory: qsv_adjoint_gradient_device's layout, ready_event and
+ * stream contract (queued on the handle's stream, not waited for).  device_out_values / device_out_energies: n_evals doubles
+ * each; each may be NULL.
+ */
+int qsv_folded_gradient_device(qsv_t* h, int centre, double target, int n_evals, const int* circuit_ids, int width,
+                               const double* device_values, void* ready_event, const int64_t* wrt_offsets, const int32_t* wrt,
+                               int out_width, double* device_out, double* device_out_values /* may be NULL */,
+                               double* device_out_energies /* may be NULL */);
+
+/*
  * ENERGY VARIANCE: out_variances[e] = <psi_e| H_h^2 |psi_e> - <psi_e| H_h |psi_e>^2 and, where out_values is
  * not NULL, out_values[e] = <psi_e| H_h |psi_e>, for n_evals (circuit, parameter vector) pairs laid out as in qsv_eval_circuits;
  * H_h is the Hermitian part of the operator (what qsv_set_operator keeps).  Zero exactly on eigenstates of H_h; the spread of a

@@ -15,8 +15,8 @@ PKG_DIR = Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = PKG_DIR / "libqsv.so"
 PYHELP_PATH = PKG_DIR / "_qsvpyhelp.so"  # CPython-API helper of the Python layer (csrc/pyhelp.c), optional
-SOURCES = ["kernels.hip", "qsv_api.hip", "plan.cpp", "split.cpp", "sort.hip", "gradient.hip", "value_cache.hip", "adjoint.hip", "adjoint_plan.cpp", "moments.hip", "covariance.hip", "overlap.hip", "reduced_density.hip", "operator_density.hip", "metric.hip", "deflation.hip", "cvar_gradient.hip"]
-HEADERS = ["kernels.hpp", "plan.hpp", "split.hpp", "gradient.hpp", "value_cache.hpp", "adjoint.hpp", "adjoint_plan.hpp", "moments.hpp", "covariance.hpp", "overlap.hpp", "reduced_density.hpp", "operator_density.hpp", "metric.hpp", "deflation.hpp", "cvar_gradient.hpp", "operator_row.hpp", "gate_loop_gen.inc", "../../include/qsv.h"]
+SOURCES = ["kernels.hip", "qsv_api.hip", "plan.cpp", "split.cpp", "sort.hip", "gradient.hip", "value_cache.hip", "adjoint.hip", "adjoint_plan.cpp", "moments.hip", "covariance.hip", "overlap.hip", "reduced_density.hip", "operator_density.hip", "metric.hip", "deflation.hip", "cvar_gradient.hip", "folded.hip"]
+HEADERS = ["kernels.hpp", "plan.hpp", "split.hpp", "gradient.hpp", "value_cache.hpp", "adjoint.hpp", "adjoint_plan.hpp", "moments.hpp", "covariance.hpp", "overlap.hpp", "reduced_density.hpp", "operator_density.hpp", "metric.hpp", "deflation.hpp", "cvar_gradient.hpp", "folded.hpp", "operator_row.hpp", "gate_loop_gen.inc", "../../include/qsv.h"]
 ARCH = "gfx950"
 
 

@@ -303,6 +303,8 @@ SIGNATURES = {
     "qsv_deflated_gradient_device": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
     "qsv_cvar_gradient_circuits": (C.c_int, [_P, C.c_double, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "qsv_cvar_gradient_device": (C.c_int, [_P, C.c_double, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
+    "qsv_folded_gradient_circuits": (C.c_int, [_P, C.c_int, C.c_double, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "qsv_folded_gradient_device": (C.c_int, [_P, C.c_int, C.c_double, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
     "qsv_variance_circuits":(C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
     "qsv_observables_covariance": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "qsv_overlap_circuits": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),

@@ -8,6 +8,7 @@ from queasars_amd.circuit_evaluation.circuit_evaluation import (  # noqa: F401
     DeflatedOperatorCircuitEvaluator,
     DeviceValueCache,
     ExactCVaRCircuitEvaluator,
+    FoldedSpectrumCircuitEvaluator,
     KeptState,
     OperatorCircuitEvaluator,
     OperatorSamplerCircuitEvaluator,

@@ -1349,6 +1349,59 @@ class StatevectorDevice:
         self.last_gradient_evaluations = len(circuits)
         return self.last_gradient_evaluations
 
+    # -- folded-spectrum and variance costs ---------------------------------------------------------
+    def folded_gradients(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]],
+                         target: Optional[float] = None, wrt=None, with_values: bool = False, with_energies: bool = False):
+        """Gradients of the folded-spectrum cost ``F_i = <psi_i|(H - c_i)^2|psi_i>`` of the operator's Hermitian part, from the
+        adjoint sweep with the seed ``(H - c)(H - c) psi`` (``qsv_folded_gradient_circuits``): one 1-D array per
+        circuit, ``wrt`` as in :meth:`gradients` -- an empty ``wrt`` is the value-only call, which sweeps nothing.  ``target``:
+        the centre c of every circuit, a finite number -- the cost is least at the eigenstate whose eigenvalue lies nearest --,
+        or None for each circuit's own ``<H>``: the variance, whose gradient this then is.  ``with_values``: also the costs in
+        their centred form ``|H psi - c psi|^2``, never negative; ``with_energies``: also ``<H>``; both float64 arrays.  The
+        result is the gradients alone, or a tuple ``(gradients[, values][, energies])``."""
+        centre, target = self._folded_centre(target)
+        n = len(circuits)
+        values = np.zeros(n, dtype=np.float64)
+        energies = np.zeros(n, dtype=np.float64)
+        entry = self._lib.qsv_folded_gradient_circuits
+
+        def function(handle, *rest):
+            return entry(handle, centre, target, *rest[:-1], *rest[-1])
+
+        trailing = (_lib.as_ptr(values), _lib.as_ptr(energies) if with_energies else None)
+        gradients = self._host_gradients(function, circuits, parameter_values, wrt, trailing)
+        self.last_gradient_evaluations = len(gradients)
+        out = (gradients,) + ((values,) if with_values else ()) + ((energies,) if with_energies else ())
+        return out if len(out) > 1 else gradients
+
+    def folded_gradients_of_device_parameters(self, circuits: Sequence[CircuitIR], matrix_ptr: int, width: int, event: int,
+                                              out_ptr: int, out_width: int, target: Optional[float] = None, wrt=None,
+                                              values_ptr: int = 0, energies_ptr: int = 0) -> int:
+        """:meth:`folded_gradients` with the layout and the contract of :meth:`gradients_of_device_parameters`
+        (``qsv_folded_gradient_device``): points read from and gradients left in device memory, queued on the handle's stream,
+        not waited for.  ``values_ptr`` / ``energies_ptr``: device memory for ``len(circuits)`` doubles each, or 0.  Returns
+        ``len(circuits)``, the evaluations counted."""
+        centre, target = self._folded_centre(target)
+        entry = self._lib.qsv_folded_gradient_device
+
+        def function(handle, *rest):
+            return entry(handle, centre, target, *rest[:-1], *rest[-1])
+
+        self._device_gradients(function, circuits, matrix_ptr, width, event, out_ptr, out_width, wrt,
+                               (_pointer(values_ptr), _pointer(energies_ptr)))
+        self.last_gradient_evaluations = len(circuits)
+        return self.last_gradient_evaluations
+
+    @staticmethod
+    def _folded_centre(target: Optional[float]) -> tuple[int, float]:
+        """(centre, target) as the library takes them: None is each evaluation's own mean."""
+        if target is None:
+            return 1, 0.0
+        target = float(target)
+        if not np.isfinite(target):
+            raise ValueError("target must be finite (None: each circuit's own mean, the variance)")
+        return 0, target
+
     # -- the operator's variance ------------------------------------------------------------------
     def variances(self, circuits: Sequence[CircuitIR], parameter_values: Sequence[Sequence[float]]) -> tuple[np.ndarray, np.ndarray]:
         """``(values, variances)`` of the operator set on the device, two float64 arrays with one entry per (circuit, parameter
@@ -2374,6 +2427,96 @@ class DeflatedOperatorCircuitEvaluator(_OperatorEvaluator):
         return energies, overlaps
 
     #: a search on the deflated cost runs the host drivers (not built)
+    device_resident_search_by_default = False
+
+    def device_resident_search_possible(self) -> bool:
+        return False
+
+
+class FoldedSpectrumCircuitEvaluator(_OperatorEvaluator):
+    """The folded-spectrum cost ``F = <psi|(H - target)^2|psi>`` of ``operator``, exact, on the GPU.  Its
+    minimum over states is the eigenstate whose eigenvalue lies nearest ``target``, so a search on it reaches an interior
+    eigenvalue directly (:func:`queasars_amd.evqe.spectrum.compute_eigenvalue_near`).  With ``target=None`` the centre is each
+    circuit's own ``<H>``: the cost is the variance ``<H^2> - <H>^2`` in its centred form, zero exactly on eigenstates
+    (:func:`queasars_amd.evqe.spectrum.minimize_variance`).
+
+    :param target: a finite number, or ``None`` for the variance
+    :param initial_state_circuit: as :class:`OperatorCircuitEvaluator`
+
+    ``evaluate_circuits`` gives the cost (a value-only call: nothing is swept), ``evaluate_gradients`` its exact gradient by
+    the adjoint sweep with the folded seed (there is no parameter-shift form), ``evaluate_energies`` ``<H>`` alone.  With a
+    fixed target the cost is an expectation value -- of ``(H - target)^2`` --, so every optimiser of the solver applies; the
+    variance is not one (it has a second harmonic in each angle): NFT's sinusoidal fit does not apply to it.  Circuits that
+    continue a kept state are refused."""
+
+    #: what the solver's host drivers read: every circuit is differentiated by one sweep
+    gradient_method = "adjoint"
+    last_gradient_evaluations = 0
+    last_gradient_evaluation_counts: list = []
+
+    def __init__(
+        self,
+        operator: PauliOperator,
+        target: Optional[float] = None,
+        initial_state_circuit: Optional[CircuitIR] = None,
+        dtype: str = "fp64",
+        device: int = 0,
+        statevector_device: Optional[StatevectorDevice] = None,
+    ):
+        if not isinstance(operator, PauliOperator):
+            raise ValueError("The operator must be a PauliOperator!")
+        _check_initial_state(initial_state_circuit, operator.num_qubits, "the amount of qubits in the given operator")
+        if initial_state_circuit is not None and initial_state_circuit.num_parameters:
+            raise ValueError("The initial state circuit must not have free parameters!")
+        if target is not None:
+            target = float(target)
+            if not np.isfinite(target):
+                raise ValueError("target must be finite (None: each circuit's own mean, the variance)")
+        if statevector_device is not None and statevector_device.n_qubits != operator.num_qubits:
+            raise ValueError("the device was created for a different number of qubits")
+        super().__init__(operator, initial_state_circuit, dtype, device, statevector_device)
+        self._target = target
+
+    @property
+    def target(self) -> Optional[float]:
+        return self._target
+
+    def _folded(self, circuits, parameter_values, wrt, **options):
+        """One :meth:`StatevectorDevice.folded_gradients` call: behind the initial state, the operator under the guard."""
+        if _has_none(circuits) or _has_none(parameter_values):
+            circuits, parameter_values = _present_pairs(circuits, parameter_values)
+        _same_length(len(circuits), len(parameter_values))
+        circuits = self._behind_initial_state(circuits)
+        with self._own_operator():
+            return self._device.folded_gradients(circuits, parameter_values, self._target, wrt, **options)
+
+    def _counted(self, gradients: list) -> list:
+        self.last_gradient_evaluations = len(gradients)
+        self.last_gradient_evaluation_counts = [1] * len(gradients)
+        return gradients
+
+    def evaluate_circuits(self, circuits: list[CircuitIR], parameter_values: list[list[float]]) -> list[float]:
+        """The cost of every circuit: the forward run, H psi and the residual's norm -- no gate is swept."""
+        _gradients, costs = self._folded(circuits, parameter_values, [], with_values=True)
+        return costs.tolist()
+
+    def evaluate_gradients(self, circuits: list[CircuitIR], parameter_values: list[list[float]], wrt=None) -> list[np.ndarray]:
+        """Exact gradients of :meth:`evaluate_circuits`: one 1-D array per circuit, ``wrt`` as in
+        :meth:`OperatorCircuitEvaluator.evaluate_gradients`.  :attr:`last_gradient_evaluations` counts one per circuit."""
+        return self._counted(self._folded(circuits, parameter_values, wrt))
+
+    def evaluate_values_and_gradients(self, circuits: list[CircuitIR], parameter_values: list[list[float]], wrt=None):
+        """``(values, gradients)`` from ONE call: the costs as a float64 array, the bits :meth:`evaluate_circuits` returns,
+        and the gradients of :meth:`evaluate_gradients`."""
+        gradients, values = self._folded(circuits, parameter_values, wrt, with_values=True)
+        return values, self._counted(gradients)
+
+    def evaluate_energies(self, circuits: list[CircuitIR], parameter_values: list[list[float]]) -> np.ndarray:
+        """``<psi_i|H|psi_i>`` alone as a float64 array: a value-only call, no gate is swept."""
+        _gradients, energies = self._folded(circuits, parameter_values, [], with_energies=True)
+        return energies
+
+    #: a search on the folded cost runs the host drivers (DESIGN.md 4.21: not built)
     device_resident_search_by_default = False
 
     def device_resident_search_possible(self) -> bool:

@@ -28,6 +28,7 @@
 #include "metric.hpp"
 #include "deflation.hpp"
 #include "cvar_gradient.hpp"
+#include "folded.hpp"
 #include "gradient.hpp"
 #include "value_cache.hpp"
 #include "kernels.hpp"
@@ -506,6 +507,11 @@ struct qsv_handle {
     // position | its chunk masses.  The host form's thresholds are d_defl_out.  Counted with the adjoint scratch (adj_stats).
     DeviceBuffer d_cvar_grad;
     const void* cvar_grad_checked[4] = {nullptr, nullptr, nullptr, nullptr};  // qsv_cvar_gradient_device's pointers
+    // folded-spectrum and variance costs (qsv_folded_gradient_circuits / qsv_folded_gradient_device; folded.hpp): one launch group's
+    // (E, c) pairs by position | its shares of |r|^2, and -- an operator with x-mask groups, a gate to sweep -- the group's residuals.
+    // The host form's energies are d_defl_out.  Counted with the adjoint scratch (adj_stats).
+    DeviceBuffer d_fold, d_fold_r;
+    const void* fold_checked[4] = {nullptr, nullptr, nullptr, nullptr};  // qsv_folded_gradient_device's pointers
     // the operator's moments (qsv_variance_circuits; moments.hpp): the call's (E, Var) pairs by position | one launch group's partials
     DeviceBuffer d_moments;
     // an observable set's second moments (qsv_observables_covariance; covariance.hpp): the call's values | covariances by position |
@@ -3243,7 +3249,7 @@ void qsv_destroy(qsv_t* h) {
                             &h->d_states, &h->d_wtab, &h->d_side, &h->d_factor, &h->d_factor_count, &h->d_factor_big, &h->d_factor_big_count, &h->d_quad, &h->d_fterms, &h->d_fpart, &h->d_batch, &h->d_mats, &h->d_partials, &h->d_out, &h->d_scratch, &h->d_prefix, &h->d_sdiag,
                             &h->d_obs_partials, &h->d_obs_values, &h->d_grad_tab, &h->d_grad_rows, &h->d_grad_values, &h->d_grad_base,
                             &h->d_grad_out, &h->d_adj_lambda, &h->d_adj_tab, &h->d_adj_mats, &h->d_adj_partials, &h->d_adj_epart, &h->d_adj_base,
-                            &h->d_adj_out, &h->d_adj_values, &h->d_defl, &h->d_defl_out, &h->d_cvar_grad, &h->d_moments, &h->d_cov, &h->d_overlap, &h->d_rdm, &h->d_opdm,
+                            &h->d_adj_out, &h->d_adj_values, &h->d_defl, &h->d_defl_out, &h->d_cvar_grad, &h->d_fold, &h->d_fold_r, &h->d_moments, &h->d_cov, &h->d_overlap, &h->d_rdm, &h->d_opdm,
                             &h->d_met_scratch, &h->d_met_tab, &h->d_met_mats, &h->d_met_partials, &h->d_met_base, &h->d_met_out})
         if (b->ptr) (void)hipFree(b->ptr);
     for (auto& kv : h->obs_sets) free_observable_set(kv.second);
@@ -5013,6 +5019,10 @@ struct AdjSeed {
     bool cvar = false, clipped = false;
     double alpha = 1.0;
     double* out_thresholds = nullptr;
+    // The folded cost's seed instead (folded_seed's): lambda_G = (H_h - c) r - (E - c)^2 psi, r = H_h psi - c psi,
+    // c the call's `target` or (own_mean) the evaluation's own E.  AdjCall::out_values then receives |r|^2, out_energies E.
+    bool folded = false, own_mean = false;
+    double target = 0.0;
 };
 
 // What both entry points run with the lock held: the call's tables, the forward run group by group, and behind each group the H
@@ -5111,6 +5121,13 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
     const bool clipped = seed && seed->clipped;
     if (clipped && (rc = ensure_counted(h, h->d_cvar_grad, cvar_gradient_scratch_doubles(h->n, gc_max) * sizeof(double), allocations))) return rc;
     double* const cvar_scratch = static_cast<double*>(h->d_cvar_grad.ptr);
+    // the folded seed's scratch; the residuals only where the row gathers (x-mask groups) and some evaluation sweeps a gate
+    const bool folded = seed && seed->folded, folded_gathers = folded && h->n_groups > 0;
+    const bool any_run = std::any_of(eval_runs.begin(), eval_runs.end(), [](uint32_t r) { return r > 0; });
+    if (folded && ((rc = ensure_counted(h, h->d_fold, folded_scratch_doubles(h->n, gc_max) * sizeof(double), allocations)) ||
+                   (folded_gathers && any_run && (rc = ensure_counted(h, h->d_fold_r, gc_max * dim * h->amp_bytes, allocations)))))
+        return rc;
+    double* const fold_scratch = static_cast<double*>(h->d_fold.ptr);
     const double* const sorted = static_cast<const double*>(h->d_sorted.ptr);  // (a CVaR seed's: sorted_values_ready)
     const void* dt = h->d_adj_tab.ptr;
     const AdjGate* d_gates = TableBlob::at<AdjGate>(dt, off_gates);
@@ -5123,7 +5140,8 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
     double* d_ovl = static_cast<double*>(h->d_defl.ptr);
     double* ovl_partials = K ? reinterpret_cast<double*>(static_cast<char*>(h->d_defl.ptr) + ovl_bytes) : nullptr;
     // E goes where the caller wants it apart from the cost; the cost is written behind it by the seed's finishing kernel
-    double* const d_energies = seed && seed->out_energies ? seed->out_energies : call.out_values;
+    // (the folded seed's finishing kernel writes both itself)
+    double* const d_energies = folded ? nullptr : seed && seed->out_energies ? seed->out_energies : call.out_values;
     double* mats = static_cast<double*>(h->d_adj_mats.ptr);
     double* partials = static_cast<double*>(h->d_adj_partials.ptr);
     double* e_partials = static_cast<double*>(h->d_adj_epart.ptr);
@@ -5143,6 +5161,23 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
         } else {
             QSV_HIP(h, launch_adjoint_apply_operator(h->dtype, h->d_states.ptr, h->d_adj_lambda.ptr, h->n, int(gc), operator_view(h), streaming,
                                                      e_partials, h->stream));
+        }
+        if (folded) {
+            // E and the centre from the shares, r = lambda_1 - c psi with the shares of |r|^2, then -- where a gate is swept at all --
+            // lambda_G = (H_h - c) r - (E - c)^2 psi over lambda_1; an operator of its diagonal part alone: both in one pass
+            const bool sweeps = most_runs > 0;
+            QSV_HIP(h, launch_folded_centre(e_partials, op_blocks, int(gc), seed->own_mean, seed->target, fold_scratch, h->stream));
+            if (!folded_gathers) {
+                QSV_HIP(h, launch_folded_diagonal(h->dtype, h->d_states.ptr, sweeps ? h->d_adj_lambda.ptr : nullptr, h->n, int(gc),
+                                                  operator_view(h).diag, fold_scratch, streaming, h->stream));
+            } else {
+                QSV_HIP(h, launch_folded_residual(h->dtype, h->d_states.ptr, h->d_adj_lambda.ptr, sweeps ? h->d_fold_r.ptr : nullptr, h->n,
+                                                  int(gc), fold_scratch, streaming, h->stream));
+                if (sweeps)
+                    QSV_HIP(h, launch_folded_seed(h->dtype, h->d_states.ptr, h->d_fold_r.ptr, h->d_adj_lambda.ptr, h->n, int(gc), operator_view(h), fold_scratch,
+                                                  streaming, h->stream));
+            }
+            h->adj_stats.n_state_sweeps += int64_t(gc) * (folded_gathers && sweeps ? 2 : 1);
         }
         if (K) {
             // c = Phi^H Psi while the states are still the final ones (the runs rewrite them), then -- where a gate is swept at all --
@@ -5166,7 +5201,9 @@ static int adjoint_locked(qsv_t* h, BatchArgs& args, const int* circuit_ids, con
         }
         QSV_HIP(h, launch_adjoint_combine(d_evals + g0, int(gc), d_offsets, d_entries, d_slots, partials, max_gates, blocks, e_partials,
                                           op_blocks, call.out_width, call.out, d_energies, h->stream));
-        if (seed && (K || (seed->out_energies && call.out_values)))
+        if (folded)
+            QSV_HIP(h, launch_folded_finish(d_evals + g0, int(gc), h->n, fold_scratch, call.out_values, seed->out_energies, h->stream));
+        else if (seed && (K || (seed->out_energies && call.out_values)))
             QSV_HIP(h, launch_deflation_finish(d_evals + g0, int(gc), uint32_t(K), d_betas, d_ovl, d_energies, call.out_values,
                                                K ? seed->out_overlaps : nullptr, h->stream));
         if (seed && seed->cvar)
@@ -5343,13 +5380,59 @@ int qsv_cvar_gradient_device(qsv_t* h, double alpha, int n_evals, const int* cir
     return device_form_end(h, adjoint_locked(h, args, circuit_ids, wrt_offsets, wrt, call, &seed), true);
 }
 
+// ---- folded-spectrum and variance costs (qsv.h: FOLDED-SPECTRUM AND VARIANCE COSTS; folded.hpp) --------------------------------------
+
+// The centre of a folded call, checked, as adjoint_locked's seed.
+static int folded_seed(qsv_t* h, int centre, double target, int n_evals, AdjSeed& seed) {
+    if (centre != 0 && centre != 1) return fail(h, QSV_E_ARG, "centre must be 0 (the target) or 1 (each evaluation's own mean)");
+    if (!std::isfinite(target)) return fail(h, QSV_E_ARG, "target is not finite");
+    seed.folded = true;
+    seed.own_mean = centre == 1;
+    seed.target = target;
+    if (n_evals == 0) return QSV_OK;
+    // (the register's size is asked first: such a handle need not hold an operator's tables)
+    if (const int rc = qubit_guard(h, "folded-spectrum costs are available up to 28 qubits", true)) return rc;
+    if (h->n_terms == 0) return fail(h, QSV_E_STATE, "no operator set (call qsv_set_operator first)");
+    return QSV_OK;
+}
+
+int qsv_folded_gradient_circuits(qsv_t* h, int centre, double target, int n_evals, const int* circuit_ids, const int64_t* param_offsets,
+                                 const double* params, const int64_t* wrt_offsets, const int32_t* wrt, double* out, double* out_values,
+                                 double* out_energies) {
+    QSV_OPEN(h, "qsv_folded_gradient_circuits", kDevice);
+    if (n_evals < 0 || (n_evals > 0 && (!circuit_ids || !param_offsets))) return fail(h, QSV_E_ARG, "bad arguments");
+    AdjSeed seed;
+    int rc = folded_seed(h, centre, target, n_evals, seed);
+    if (rc || n_evals == 0) return rc;
+    return adjoint_host_form(h, n_evals, circuit_ids, param_offsets, params, wrt_offsets, wrt, out, out_values,
+                             "folded-spectrum costs of a circuit on a kept state are not built", &seed, out_energies);
+}
+
+int qsv_folded_gradient_device(qsv_t* h, int centre, double target, int n_evals, const int* circuit_ids, int width,
+                               const double* device_values, void* ready_event, const int64_t* wrt_offsets, const int32_t* wrt, int out_width,
+                               double* device_out, double* device_out_values, double* device_out_energies) {
+    QSV_OPEN(h, "qsv_folded_gradient_device", kDevice);
+    const DeviceForm form{n_evals, circuit_ids, width, device_values, ready_event, out_width, device_out};
+    int rc = device_form_guard(h, form);
+    if (rc) return rc;
+    AdjSeed seed;
+    if ((rc = folded_seed(h, centre, target, n_evals, seed)) || n_evals == 0) return rc;
+    seed.out_energies = device_out_energies;
+    BatchArgs args;
+    if ((rc = device_form_open(h, form, {{"device_out_values", device_out_values}, {"device_out_energies", device_out_energies}},
+                               h->fold_checked, "folded-spectrum costs of a circuit on a kept state are not built", args)))
+        return rc;
+    const AdjCall call{device_values, width, device_out, out_width, device_out_values};
+    return device_form_end(h, adjoint_locked(h, args, circuit_ids, wrt_offsets, wrt, call, &seed), true);
+}
+
 int qsv_adjoint_stats(const qsv_t* h, qsv_adjoint_stats_t* out) {
     if (!out) return QSV_E_ARG;
     QSV_OPEN(h, "qsv_adjoint_stats", kHostOnly);
     *out = h->adj_stats;
     out->scratch_bytes = int64_t(h->d_adj_lambda.bytes + h->d_adj_tab.bytes + h->d_adj_mats.bytes + h->d_adj_partials.bytes + h->d_adj_epart.bytes +
                                  h->d_adj_base.bytes + h->d_adj_out.bytes + h->d_adj_values.bytes + h->d_defl.bytes + h->d_defl_out.bytes +
-                                 h->d_cvar_grad.bytes);
+                                 h->d_cvar_grad.bytes + h->d_fold.bytes + h->d_fold_r.bytes);
     return QSV_OK;
 }
 
